@@ -2,7 +2,7 @@
 """bench.py -- Mray/s (primary + shadow) on BASELINE.json configs[1]: Sponza-class scene, 1920x1080, one directional
 light, one shadow ray per lit pixel.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one frame of the hot path (primary rays + closest hit, hit reconstruction + PBR direct light, shadow rays,
@@ -10,6 +10,12 @@ accumulation; for N > 1 also the RCCL gather of the HDR tiles to rank 0 and the 
 lights are resident in HBM before the timed region.  N > 1 shards the frame by 32x32 screen tile (strong scaling) through
 libart's art_mgpu_* entry points: the whole sharded frame -- trace, ncclGather, un-tile -- is C ABI, this file is its caller.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, settles, warms up, times the K steps and prints the line.  --full adds everything else: the extra legs of
+one GPU (steady state, single frames, camera path and jumps, a moving model), the CPU baseline, the check of the ray counts
+against the oracle's, the roofline, and for N > 1 the second placement and the check of the gathered frame; --full --plain
+leaves out the extra legs and the CPU baseline again.
+--dump-outputs DIR writes the outputs of the last timed frame as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -53,7 +59,12 @@ def parse():
     ap.add_argument("--settle-seconds", type=float, default=1.0, help="untimed set-up before the warm-up: frames are traced for at least this long (and at least 3 ring depths), so the wave plan "
                     "has settled and the GPU has left its idle clocks; 0 = the 3 ring depths only")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall clock the CPU baseline repeats the frame for (the contract: a bounded sample, ~10-30 s of CPU work)")
-    ap.add_argument("--plain", action="store_true", help="only the contract's timed region (profiling passes: no single-frame spans, no steady-state / camera-path legs, no CPU baseline)")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline figure: the extra legs of one GPU (steady state, single-frame spans, camera path / jumps, "
+                                                        "moving model), the CPU baseline, the ray counts against the oracle's, the roofline; N > 1: both placements and the gathered frame's check")
+    ap.add_argument("--plain", action="store_true", help="with --full: no single-frame spans, no steady-state / camera-path / moving-model legs, no CPU baseline (profiling passes; "
+                                                         "the ray-count check and the roofline stay); a run without --full leaves all of these out anyway")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the last timed frame's outputs (colour, depth, normal; AO with --ao) "
+                                                                        "as DIR/<name>.npy in float32, at most 60 MB in all (one GPU only)")
     ap.add_argument("--tuning", default="", help="A/B sweeps: ArtTuning fields for the benchmarked context, key=value[,key=value...] (include/art.h: frame_form, tree_builder, frame_waves, "
                                                  "block_order, split_alpha ...); the default -- none -- is the product")
     ap.add_argument("--camera-walk", type=int, default=64, help="N = 1 extra leg `camera_path`: the camera moves every frame the way the reference's does (main.rs:69-131: a key held down, a hand on the "
@@ -97,6 +108,28 @@ def host_cores():
     return n
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs writes at most this many bytes
+
+
+def dump_outputs(r, out_dir, B, ao):
+    """--dump-outputs: what a caller of the timed path receives for its last frame -- art_read_color / art_read_depth / art_read_normal (fp32), and
+    art_read_ao (0..255, as float32) with --ao -- as <out_dir>/<name>.npy.  Whole frames if together they fit in DUMP_BYTES; else the same fixed,
+    seeded sample of pixels (sorted row-major indices) from each, shape [n] / [n, 4].  Every frame of a run is the same frame, so two runs with the
+    same arguments write the same files."""
+    import numpy as np
+    if B > 1:
+        r.set_read_frame(B - 1)       # the last frame of the last launch
+    outs = dict(color=r.read_color(), depth=r.read_depth(), normal=r.read_normal())
+    if ao:
+        outs["ao"] = r.read_ao().astype(np.float32)
+    w, h = r.extent
+    per_pixel = sum(a.nbytes for a in outs.values()) // (w * h)
+    pick = None if per_pixel * w * h <= DUMP_BYTES else np.sort(np.random.default_rng(0x5A0A).choice(w * h, DUMP_BYTES // per_pixel, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if pick is None else a.reshape(w * h, *a.shape[2:])[pick])
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` started plainly (no launcher, no WORLD_SIZE): this process -- which has not touched the GPU and never will -- starts the N ranks the way the
     driver does (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`) as a CHILD process, relays its output
@@ -113,6 +146,9 @@ def spawn_ranks(args):
 
 def main():
     args = parse()
+    full = args.full
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs writes a one-GPU run's outputs: with --gpus N > 1 the frames are assembled on several ranks")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args))
     watchdog = args.watchdog_seconds if args.watchdog_seconds >= 0 else (300.0 if int(os.environ.get("WORLD_SIZE", "1")) > 1 else 0.0)
@@ -131,6 +167,13 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus} (or plainly: bench.py starts its own ranks)")
     if not torch.cuda.is_available():
+        if world > 1:   # every rank says so before any of them leaves: the launcher stops the other ranks as soon as one has exited
+            from datetime import timedelta
+            print("bench.py needs an MI355X: libart has no CPU fallback", file=sys.stderr, flush=True)
+            dist.init_process_group("gloo", timeout=timedelta(seconds=60))
+            dist.barrier()
+            dist.destroy_process_group()
+            raise SystemExit(1)
         raise SystemExit("bench.py needs an MI355X: libart has no CPU fallback")
     if args.backend == "gloo":
         local_rank = local_rank % torch.cuda.device_count()   # rehearsal: ranks may share one GPU
@@ -269,10 +312,12 @@ def main():
         fence()
         wall = time.perf_counter() - t0
         stage, n_timed = r.collect_timings()  # HIP events on the frames' own streams, over the timed frames (last <= 128)
+        if args.dump_outputs:             # (one GPU: checked at the start)
+            dump_outputs(r, args.dump_outputs, B, args.ao)
 
-        # ---- outside the timed region: the gathered frame must equal an unsharded render of the same frame, bit for bit ---------------------------
+        # ---- outside the timed region (--full): the gathered frame must equal an unsharded render of the same frame, bit for bit ---------------------
         frame_ok = None
-        if world > 1 and (rank == 0 or spread):          # every rank that assembles frames checks the newest one it holds
+        if full and world > 1 and (rank == 0 or spread):          # every rank that assembles frames checks the newest one it holds
             got = mg.read_frame()
             whole = make_renderer(device=local_rank)
             whole.render_frame()
@@ -282,7 +327,7 @@ def main():
             else:
                 frame_ok = bool(np.array_equal(got.view(np.uint32), whole.read_color().view(np.uint32)))
             whole.close()
-        if world > 1 and spread:
+        if full and world > 1 and spread:
             control_plane("the frame check's all_gather")
             oks = [None] * world
             dist.all_gather_object(oks, frame_ok)
@@ -310,7 +355,7 @@ def main():
                     relief=relief, spread=spread, settle_launches=settle_launches, step=step, fence=fence, value=rays_total / (wall / args.steps) / 1e6, ms_per_step=wall * 1e3 / args.steps)
 
     if world > 1:
-        placements = [args.roots] if (dedicated or args.one_placement) else [args.roots, "rank0" if args.roots == "spread" else "spread"]
+        placements = [args.roots] if (dedicated or args.one_placement or not full) else [args.roots, "rank0" if args.roots == "spread" else "spread"]
         if dedicated:
             placements = ["rank0"]
     else:
@@ -321,7 +366,7 @@ def main():
             "r", "wall", "stage", "n_timed", "frame_ok", "counts", "st", "rays_total", "shadow_total", "B", "transport", "relief", "spread", "settle_launches", "step", "fence"))
         mg = None
 
-        extras = world == 1 and not args.plain
+        extras = world == 1 and full and not args.plain
         # ---- steady state: the same K frames with the ring kept full on both sides (device timestamps behind the last priming frame and behind frame K) ----
         steady = None
         if extras and not args.ao and args.steps >= 4 * F:   # (a run of fewer than four ring depths is all fill and drain: nothing steady to report)
@@ -508,12 +553,12 @@ def main():
         value = rays_total / (wall / args.steps) / 1e6
 
         # ---- the oracle's counters for this exact frame (canonical LBVH: per ray = SURVEY.md 8d's contract figure, per 8x8 packet) ------------------
-        fx = os.path.join(ROOT, "tests", "golden", f"{tag}.stats.json") if tag and not args.ao else None
+        fx = os.path.join(ROOT, "tests", "golden", f"{tag}.stats.json") if full and tag and not args.ao else None
         ost = json.load(open(fx)) if fx and os.path.exists(fx) else None
 
         # ---- CPU baseline: the scalar C oracle on this host's cores, on a bounded sample of the same frame ---------------------------------------
         cpu = None
-        if not args.no_cpu_baseline and not args.plain and not args.ao and world == 1:   # rank 0 at N = 1 only (the contract)
+        if full and not args.no_cpu_baseline and not args.plain and not args.ao and world == 1:   # rank 0 at N = 1 only (the contract)
             from oracle import orc
             ncores = host_cores()
             S = orc.Scene(sc.primitives, morton_bits=30)
@@ -556,7 +601,7 @@ def main():
         cur = json.load(open(cur_path)) if os.path.exists(cur_path) else {}
         entry = (cur.get("workloads") or {}).get(workload) if world == 1 else None
         pmc = entry["pmc"] if entry else {}
-        if args.ao and world == 1 and st.get("frame_launches") == 1:
+        if full and args.ao and world == 1 and st.get("frame_launches") == 1:
             # config 5: the dominant kernel is the AO launch's persistent tracer.  Its share of the machine's time per step = the step minus the same frames without
             # their AO pass, timed here the same way (fenced on both sides)
             for _ in range(2 * F):

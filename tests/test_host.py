@@ -206,7 +206,7 @@ def test_bench_and_tools_parse_and_bench_refuses_to_run_without_a_gpu():
     import glob, py_compile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "--frames-per-launch" in out.stdout and "--root-relief" in out.stdout
+    assert out.returncode == 0 and "--frames-per-launch" in out.stdout and "--root-relief" in out.stdout and "--full" in out.stdout and "--dump-outputs" in out.stdout
     for f in glob.glob(os.path.join(root, "tools", "*.py")) + [os.path.join(root, "__graft_entry__.py")]:
         py_compile.compile(f, doraise=True)
     import torch
