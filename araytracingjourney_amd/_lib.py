@@ -99,6 +99,7 @@ SYMBOLS = {
     "art_scene_set_primitive_enabled": (_I32, [_P, _U32, _I32]),
     "art_scene_needs_build": (_I32, [_P]),
     "art_scene_set_model_matrix": (_I32, [_P, _U32, _U32, _P]),
+    "art_scene_set_vertices": (_I32, [_P, _U32, _P, _U32]),
     "art_scene_build": (_I32, [_P]),
     "art_set_camera": (_I32, [_P, _P]),
     "art_camera_from_params": (_I32, [_P, _P, _F, _F, _F, _F, _P]),

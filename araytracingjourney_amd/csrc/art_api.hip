@@ -26,6 +26,7 @@ struct HostPrim {
     uint32_t tw, th;
     float o2w[12], w2o[12];
     bool enabled = true; // instanced in the acceleration structure (the reference's Device state, vk_model.rs:334-345); else kept on the host only
+    bool verts_stale = false; // art_scene_set_vertices replaced `verts` since they were uploaded: a build over the same set uploads them again
 };
 
 template <class T> struct DevBuf {
@@ -137,6 +138,11 @@ struct AsVersion {
     hipEvent_t ready = nullptr; bool ready_known = true; uint32_t ready_slot = 0; // the refit that wrote it: recorded on ring slot ready_slot's stream
     bool result_pending = false;         // h_result is that refit's once `ready` has fired
     uint64_t epoch = 0;                  // which refit wrote it (0: the build)
+    // Deformed meshes (art_scene_set_vertices): the version's own shading records (the build's array until the context first deforms a built primitive: version 0
+    // keeps aliasing it, the others get copies), and its staging of the replaced vertices -- pinned, written by the host once the version's previous refit is over,
+    // and device memory, filled by one copy on the refit's stream that the regather in the refit's leaf stage reads (ArtContext::deform_off: where each primitive's are)
+    DevShadeTri *shade = nullptr;
+    ArtVertex *h_stage = nullptr; float *d_stage = nullptr;
 };
 
 struct ArtContext {
@@ -177,6 +183,11 @@ struct ArtContext {
     hipStream_t refit_stream[4] = {nullptr, nullptr, nullptr, nullptr}; uint32_t n_refit_streams = 0;
     std::vector<DevPrim> h_dev_prims;          // host copy of d_prims (build order), matrices kept current
     std::vector<uint64_t> prim_moved;          // per primitive: the refit (as_epoch numbering) that first shows its latest move; 0: where the build put it
+    std::vector<uint64_t> prim_deformed;       // per primitive: the refit that first shows its latest vertices (art_scene_set_vertices); 0: the build's
+    std::vector<int64_t> deform_off;           // per primitive: first vertex of its slot in every version's staging (-1: never deformed since the build)
+    size_t deform_verts = 0;                   // vertices of a version's staging (the sum of the deformed primitives' counts)
+    void *shade_block = nullptr;               // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
+    void *stage_block = nullptr, *stage_pinned = nullptr;   // every version's staging of replaced vertices: device, pinned
     int64_t masked_tris = 0;                   // triangles of primitives disabled since the build (still in the arrays, written "nowhere")
     uint64_t as_epoch = 0, binary_epoch = 0;   // refits so far; the refit the binary trees / node records reflect
     double as_cost0 = 0.0; float refit_cost_ratio = 1.0f; uint32_t refits = 0, rebuilds = 0; float last_refit_ms = 0.f, first_move_ms = 0.f, versions_ms = 0.f;
@@ -278,11 +289,11 @@ int32_t sync_all(ArtContext *c) {
 }
 
 // ---- versions of the acceleration structure (moving models) ------------------------------------------------------------------------------
-struct AsPtrs { const DevTri *tris; const DevNodeW *widef; const DevNode4 *wide; const DevPrim *prims; };
+struct AsPtrs { const DevTri *tris; const DevNodeW *widef; const DevNode4 *wide; const DevPrim *prims; const DevShadeTri *shade; };
 AsPtrs as_ptrs(const ArtContext *c, uint32_t v) {
-    if (c->as.empty()) return AsPtrs{c->bvh.tris, c->bvh.widef, c->bvh.wide, c->d_prims.p};
+    if (c->as.empty()) return AsPtrs{c->bvh.tris, c->bvh.widef, c->bvh.wide, c->d_prims.p, c->bvh.shade_tris};
     const AsVersion &V = c->as[v];
-    return AsPtrs{V.tris, V.widef, V.wide, V.prims};
+    return AsPtrs{V.tris, V.widef, V.wide, V.prims, V.shade};
 }
 uint64_t as_epoch_of(const ArtContext *c, uint32_t v) { return c->as.empty() ? 0 : c->as[v].epoch; }
 // everything that reads them has finished (the caller synchronised)
@@ -292,6 +303,10 @@ void as_release(ArtContext *c) {
     }
     (void)hipFree(c->as_block); c->as_block = nullptr;                         // every version's device arrays
     if (c->as_pinned) (void)hipHostFree(c->as_pinned); c->as_pinned = nullptr; // every version's staging memory
+    if (c->shade_block) (void)hipFree(c->shade_block); c->shade_block = nullptr;           // the versions' shading records
+    if (c->stage_block) (void)hipFree(c->stage_block); c->stage_block = nullptr;           // the staging of replaced vertices
+    if (c->stage_pinned) (void)hipHostFree(c->stage_pinned); c->stage_pinned = nullptr;
+    c->deform_verts = 0; std::fill(c->deform_off.begin(), c->deform_off.end(), (int64_t)-1);
     c->as.clear(); c->as_cur = 0;
 }
 // the first move of a built scene: the ring of versions (ArtTuning.as_versions; default 4: one more than the reference's frames in flight, renderer.rs:135 -- measured on
@@ -341,6 +356,7 @@ int32_t as_create(ArtContext *c) {
         auto carve = [&](char *&p, size_t n) { char *q = p; p += pad(n); return q; };
         for (uint32_t v = 0; v < K; v++) { // (everything on the context's first stream, asynchronously: one wait at the end)
             AsVersion &V = c->as[v];
+            V.shade = c->bvh.shade_tris;   // (every version's own copy only once a built primitive is deformed: deform_prepare)
             if (v == 0) { V.tris = c->bvh.tris; V.widef = c->bvh.widef; V.wide = c->bvh.wide; V.prims = c->d_prims.p; }
             else {
                 V.owned = true;
@@ -425,8 +441,27 @@ int32_t scene_refresh(ArtContext *c, uint32_t k, hipStream_t s) {
     const size_t np = c->h_dev_prims.size();
     std::memcpy(V.h_prims, c->h_dev_prims.data(), np * sizeof(DevPrim));
     for (size_t p = 0; p < np; p++) V.h_touched[p] = (p < c->prim_moved.size() && c->prim_moved[p] > V.epoch) ? 1 : 0;   // what moved since THIS version was written (it may be several refits behind)
+    {   // what was deformed since this version was written: its current vertices into the version's staging (pinned, then ONE copy a run of slots on the refit's stream, in
+        // front of the refit that reads them from device memory), its table entry pointed there, and its shading records gathered again by the refit's leaf stage
+        size_t run_lo = 0, run_hi = 0;   // the run of staging slots the next copy covers (vertices)
+        auto flush = [&]() -> int32_t {
+            if (run_hi > run_lo) HIPC(hipMemcpyAsync(V.d_stage + run_lo * 12, V.h_stage + run_lo, (run_hi - run_lo) * sizeof(ArtVertex), hipMemcpyHostToDevice, s));
+            run_lo = run_hi = 0; return ART_OK;
+        };
+        for (size_t p = 0; p < np && p < c->prim_deformed.size(); p++) {
+            if (c->prim_deformed[p] <= V.epoch) continue;
+            const std::vector<ArtVertex> &vv = c->prims[p].verts;
+            const size_t off = (size_t)c->deform_off[p];
+            std::memcpy(V.h_stage + off, vv.data(), vv.size() * sizeof(ArtVertex));
+            V.h_prims[p].vertices = V.d_stage + off * 12;
+            V.h_touched[p] |= kTouchRegather;
+            if (off != run_hi) { r = flush(); if (r) return r; run_lo = off; }
+            run_hi = off + vv.size();
+        }
+        r = flush(); if (r) return r;
+    }
     RefitArgs ra{};
-    ra.T = c->T; ra.n_wide = c->bvh.n_wide; ra.n_prims = (uint32_t)np; ra.shade = c->bvh.shade_tris; ra.prims_host = V.dh_prims; ra.prims_dev = V.prims; ra.touched = V.dh_touched;
+    ra.T = c->T; ra.n_wide = c->bvh.n_wide; ra.n_prims = (uint32_t)np; ra.shade = V.shade; ra.prims_host = V.dh_prims; ra.prims_dev = V.prims; ra.touched = V.dh_touched;
     ra.sub_nodes = c->bvh.sub_nodes; ra.sub_leaves = c->bvh.sub_leaves; ra.sub_off = c->bvh.sub_off; ra.sub_batches = c->bvh.sub_batches; ra.sub_levels = c->bvh.sub_levels;
     ra.leaf_parent = c->bvh.leaf_parent; ra.node_parent = c->bvh.node_parent; ra.mark = V.mark; ra.tris = V.tris; ra.wide = V.wide; ra.widef = V.widef; ra.acc = V.acc; ra.result = V.dh_result;
     {   // the batches that hold a primitive that moved (since this version was written); the others keep their triangles, their boxes and -- in a large tree -- their
@@ -931,6 +966,65 @@ int32_t art_scene_set_model_matrix(ArtContext *c, uint32_t first, uint32_t n, co
     return ART_OK;
 }
 
+// The first deformation of a built primitive (art_scene_set_vertices): every version gets shading records of its own (a frame in flight must keep the normals it was
+// launched with), and the primitive a slot in every version's staging.  One synchronisation, here and never in front of a frame: an allocation that fails
+// comes back from the call that asked for it, with nothing changed.
+static int32_t deform_prepare(ArtContext *c, uint32_t id) {
+    const uint32_t K = (uint32_t)c->as.size();
+    const bool need_shade = K > 1 && !c->shade_block, need_stage = c->deform_off[id] < 0;
+    if (!need_shade && !need_stage) return ART_OK;   // (the steady state)
+    int32_t r = sync_all(c); if (r) return r;
+    auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    if (need_shade) {   // versions 1 .. K-1: copies of the build's records (nothing has written any version's yet); version 0 keeps aliasing them
+        const size_t each = pad((size_t)c->T * sizeof(DevShadeTri));
+        void *blk = nullptr;
+        hipError_t e = hipMalloc(&blk, (K - 1) * each);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(ART_E_NOMEM, std::string("art_scene_set_vertices: the versions' shading records: ") + hipGetErrorString(e)); }
+        hipStream_t s = c->main_stream();
+        for (uint32_t v = 1; v < K && e == hipSuccess; v++) e = hipMemcpyAsync((char *)blk + (v - 1) * each, c->bvh.shade_tris, (size_t)c->T * sizeof(DevShadeTri), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipFree(blk); return hipfail(e, "art_scene_set_vertices: copies of the shading records"); }
+        c->shade_block = blk;
+        for (uint32_t v = 1; v < K; v++) c->as[v].shade = (DevShadeTri *)((char *)blk + (v - 1) * each);
+    }
+    if (need_stage) {   // a larger staging for every version; what the old one held is not needed (a refit writes a version's staging in full for what it regathers)
+        const size_t nv = c->deform_verts + c->prims[id].verts.size(), each = pad(nv * sizeof(ArtVertex));
+        void *dblk = nullptr, *hblk = nullptr;
+        hipError_t e = hipMalloc(&dblk, K * each);
+        if (e == hipSuccess) { e = hipHostMalloc(&hblk, K * each, hipHostMallocDefault); if (e != hipSuccess) { (void)hipFree(dblk); dblk = nullptr; } }
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(ART_E_NOMEM, std::string("art_scene_set_vertices: staging of the vertices: ") + hipGetErrorString(e)); }
+        if (c->stage_block) (void)hipFree(c->stage_block);
+        if (c->stage_pinned) (void)hipHostFree(c->stage_pinned);
+        c->stage_block = dblk; c->stage_pinned = hblk;
+        for (uint32_t v = 0; v < K; v++) { c->as[v].d_stage = (float *)((char *)dblk + v * each); c->as[v].h_stage = (ArtVertex *)((char *)hblk + v * each); }
+        c->deform_off[id] = (int64_t)c->deform_verts; c->deform_verts = nv;
+    }
+    return ART_OK;
+}
+
+int32_t art_scene_set_vertices(ArtContext *c, uint32_t id, const ArtVertex *verts, uint32_t n_verts) {
+    if (!c || !verts) return fail(ART_E_INVALID, "art_scene_set_vertices: null argument");
+    if (id >= c->prims.size()) return fail(ART_E_INVALID, "art_scene_set_vertices: no such primitive");
+    HostPrim &p = c->prims[id];
+    if ((size_t)n_verts != p.verts.size()) return fail(ART_E_INVALID, "art_scene_set_vertices: the vertex count differs from the primitive's");
+    const bool in_tree = c->built && id < c->h_dev_prims.size() && c->h_dev_prims[id].n_tri > 0;   // its triangles are in the built structure (masked or not)
+    if (in_tree) {
+        int32_t r = use_device(c); if (r) return r;
+        if (c->as.empty()) {   // (the ring of versions: art_scene_build made it already when the host announced ART_FLAG_DYNAMIC_SCENE)
+            const auto t_begin = std::chrono::steady_clock::now();
+            r = as_create(c); if (r) return r;
+            c->first_move_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        }
+        r = deform_prepare(c, id); if (r) return r;
+    }
+    std::memcpy(p.verts.data(), verts, (size_t)n_verts * sizeof(ArtVertex));
+    p.verts_stale = true;                                            // the device's build copy is behind (a rebuild over the same set uploads them again)
+    if (!in_tree) return ART_OK;                                     // takes effect with the build
+    c->prim_deformed[id] = c->as_epoch + 1;                          // the next refit is the first to show them
+    if (p.enabled) c->xform_dirty = true;                            // instanced: the next art_trace (or query) refits first; a masked one is regathered when it comes back
+    return ART_OK;
+}
+
 int32_t art_scene_build(ArtContext *c) {
     if (!c) return fail(ART_E_INVALID, "art_scene_build: null context");
     if (c->prims.empty()) return fail(ART_E_STATE, "art_scene_build: no primitives");
@@ -965,8 +1059,9 @@ int32_t art_scene_build(ArtContext *c) {
         std::memcpy(d.o2w, p.o2w, 48); std::memcpy(d.w2o, p.w2o, 48);
         first[k] = T;
         if (!p.enabled) continue;
+        if (!resident || p.verts_stale) HIPC(hipMemcpy(c->d_verts.p + ov * 12, p.verts.data(), p.verts.size() * 48, hipMemcpyHostToDevice));   // (deformed since: art_scene_set_vertices)
+        p.verts_stale = false;
         if (!resident) {
-            HIPC(hipMemcpy(c->d_verts.p + ov * 12, p.verts.data(), p.verts.size() * 48, hipMemcpyHostToDevice));
             HIPC(hipMemcpy(c->d_indices.p + oi, p.indices.data(), p.indices.size(), hipMemcpyHostToDevice));
             HIPC(hipMemcpy(c->d_tex.p + ot, p.tex.data(), p.tex.size(), hipMemcpyHostToDevice));
         }
@@ -990,7 +1085,7 @@ int32_t art_scene_build(ArtContext *c) {
     c->uploaded = any ? now_set : std::vector<uint8_t>();
     c->h_first_tri = first;
     c->h_dev_prims = dp; c->masked_tris = 0;
-    c->prim_moved.assign(dp.size(), 0);
+    c->prim_moved.assign(dp.size(), 0); c->prim_deformed.assign(dp.size(), 0); c->deform_off.assign(dp.size(), -1);
     c->T = T;
     BuildInputs in{c->d_prims.p, (uint32_t)dp.size(), c->d_first_tri.p, T, c->cfg.morton_bits};
     hipEvent_t e0, e1;
@@ -1145,7 +1240,7 @@ static FrameArgs make_frame_args(ArtContext *c, FrameSlot &S, uint32_t version) 
     std::memcpy(&a.cam, &c->camera, sizeof(ArtCamera));
     a.W = c->W; a.H = c->H; a.tile_list = c->d_tile_list.p; a.n_tiles_owned = (uint32_t)c->tile_list.size(); a.tiles_x = c->tiles_x; a.n_local = c->n_local; a.block_order = c->d_block_order.p;
     const AsPtrs as = as_ptrs(c, version); // the version of the acceleration structure this launch reads
-    a.nodes = c->bvh.nodes; a.wide = as.wide; a.widef = as.widef; a.packet_wide = c->packet_wide; a.trace_kind[0] = c->kind_primary; a.trace_kind[1] = c->kind_shadow; a.trace_kind[2] = c->kind_ao; a.tune = TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}; a.pipelined = c->F > 1; a.tris = as.tris; a.shade_tris = c->bvh.shade_tris; a.prims = as.prims; a.tex_pool = c->d_tex.p;
+    a.nodes = c->bvh.nodes; a.wide = as.wide; a.widef = as.widef; a.packet_wide = c->packet_wide; a.trace_kind[0] = c->kind_primary; a.trace_kind[1] = c->kind_shadow; a.trace_kind[2] = c->kind_ao; a.tune = TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}; a.pipelined = c->F > 1; a.tris = as.tris; a.shade_tris = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p;
     a.n_lights = (uint32_t)c->lights.size();
     const uint32_t n_arg = std::min(a.n_lights, (uint32_t)kMaxLights);
     if (n_arg) std::memcpy(a.lights, c->lights.data(), (size_t)n_arg * sizeof(ArtLight));

@@ -514,9 +514,30 @@ hipError_t wide_build(Lbvh &l, uint32_t T, hipStream_t s, bool on_host) {
 // the touched bytes are read WHERE THE HOST WROTE THEM (pinned, device-visible memory: a few hundred bytes a wave touches once) -- round 3 uploaded both with two
 // copies in front of this launch; the launch also leaves the table's device copy for the frames behind it (their shading reads DevPrim).
 // A rewritten triangle marks the 4-wide node that holds it (mark[w] != 0: a box below w changes in this refit); the level passes below carry the marks upwards.
-__device__ __forceinline__ void retri_one(uint32_t p, const DevShadeTri *__restrict__ shade, const DevPrim *prims_host, const uint8_t *touched, const uint32_t *__restrict__ leaf_parent, uint32_t *mark, DevTri *tris) {
+// A primitive whose vertices were replaced since the version was written (art_scene_set_vertices: touched & kTouchRegather) first has the version's shading record
+// gathered again, by k_leaves' own fetches and stores, from the vertices the version's primitive table points at (the version's staging copy in device memory);
+// its positions are then transformed exactly like a moved primitive's: the bits a build over the new vertices writes.
+__device__ __forceinline__ void regather_one(uint32_t p, uint32_t prim, const DevPrim *prims_host, const DevTri *tris, DevShadeTri *__restrict__ shade) {
+    const DevPrim &P = prims_host[prim];
+    const uint32_t g = __float_as_uint(tris[p].f[15]);
+    uint32_t tl = g - P.first_tri, ix[3];
+    if (P.single_index_size == 2) { const uint16_t *q = (const uint16_t *)P.indices + 3 * (size_t)tl; ix[0] = q[0]; ix[1] = q[1]; ix[2] = q[2]; }
+    else { const uint32_t *q = (const uint32_t *)P.indices + 3 * (size_t)tl; ix[0] = q[0]; ix[1] = q[1]; ix[2] = q[2]; }
+    DevShadeTri st;
+    for (int k = 0; k < 3; k++) {
+        const float *v = P.vertices + (size_t)ix[k] * 12;
+        for (int j = 0; j < 3; j++) { st.f[3 * k + j] = v[j]; st.f[15 + 3 * k + j] = v[5 + j]; st.f[24 + 3 * k + j] = v[8 + j]; }
+        st.f[9 + 2 * k] = v[3]; st.f[10 + 2 * k] = v[4];
+        if (k == 0) st.f[33] = v[11];
+    }
+    st.f[34] = __uint_as_float(prim); st.f[35] = 0.f;
+    shade[p] = st;
+}
+__device__ __forceinline__ void retri_one(uint32_t p, DevShadeTri *__restrict__ shade, const DevPrim *prims_host, const uint8_t *touched, const uint32_t *__restrict__ leaf_parent, uint32_t *mark, DevTri *tris) {
     const uint32_t prim = __float_as_uint(shade[p].f[34]);
-    if (!touched[prim]) return;
+    const uint8_t how = touched[prim];
+    if (!how) return;
+    if (how & kTouchRegather) regather_one(p, prim, prims_host, tris, shade);   // (a masked primitive's too: it shows its new shape when it is enabled again)
     DevTri t;
     if (prims_host[prim].masked) {   // out of the structure until it is enabled again: a point nowhere, no extent
         for (int k = 0; k < 3; k++) { t.f[k] = kNowhere; t.f[3 + k] = 0.f; t.f[6 + k] = 0.f; t.f[9 + k] = kNowhere; t.f[12 + k] = kNowhere; }
@@ -608,7 +629,7 @@ __device__ __forceinline__ double wide_requant_node(uint32_t w, const DevNodeW *
 // sub_off: [0, nb + 1] node offsets of batches 0 .. nb (batch nb = the crown) | [nb + 2, 2 nb + 3] leaf offsets | then nb + 1 rows of (n_levels + 1) offsets into the batch's
 // node list, deepest level of the tree first.
 template <bool FOLD> __global__ void k_refit_sub(uint32_t batch0, uint32_t nb1 /*batches + the crown*/, uint32_t n_levels, const uint32_t *__restrict__ sub_nodes, const uint32_t *__restrict__ sub_leaves, const uint32_t *__restrict__ sub_off,
-                            const DevShadeTri *__restrict__ shade, const DevPrim *prims_host, DevPrim *prims_dev, uint32_t n_prim_words, const uint8_t *touched,
+                            DevShadeTri *__restrict__ shade, const DevPrim *prims_host, DevPrim *prims_dev, uint32_t n_prim_words, const uint8_t *touched,
                             const uint32_t *__restrict__ leaf_parent, const uint32_t *__restrict__ node_parent, uint32_t *mark, DevTri *tris, DevNodeW *widef, unsigned long long *stamp, bool first_launch,
                             DevNode4 *wide, double *acc, double *out /*null: not the refit's last launch*/, const uint32_t *__restrict__ dirty /*null: batch batch0 + blockIdx.x*/, double *batch_cost) {
     const uint32_t b = dirty ? dirty[blockIdx.x] : batch0 + blockIdx.x, tid = threadIdx.x, nt = blockDim.x;

@@ -146,18 +146,20 @@ void sah_prewarm(hipStream_t s);     // art_sahdev.hip
 // refit after a model moved (art_build.hip): the triangle records of a version of the acceleration structure from the shading records and that version's
 // primitive table; its 4-wide nodes bottom-up, level by level (l.wide_levels); the tree's surface-area cost (2 doubles: sum of child half-areas, root half-area);
 // the binary trees and node records from a version's triangles (on demand, synchronises)
-// prims_host / touched: PINNED host memory the kernels read in place (the version's staging copies: one byte per primitive -- whose triangles to make again); mark: one word
+// prims_host / touched: PINNED host memory the kernels read in place (the version's staging copies: one byte per primitive -- whose triangles to make again, 1 moved,
+// 2 vertices replaced: its shading records are gathered again first, from the vertices prims_host points at); shade: the version's shading records; mark: one word
 // per 4-wide node, all zero between refits; acc: 4 doubles of device scratch, zero between launches; result: 4 doubles, pinned host memory (cost sum, root half-area, start / end stamps)
 struct RefitArgs {
     uint32_t T, n_wide, n_prims;
     const uint32_t *sub_nodes, *sub_leaves, *sub_off; uint32_t sub_batches, sub_levels;
-    const DevShadeTri *shade; const DevPrim *prims_host; DevPrim *prims_dev; const uint8_t *touched;
+    DevShadeTri *shade; const DevPrim *prims_host; DevPrim *prims_dev; const uint8_t *touched;
     const uint32_t *leaf_parent, *node_parent; uint32_t *mark;
     DevTri *tris; DevNode4 *wide; DevNodeW *widef; double *acc, *result;
     const uint32_t *dirty; uint32_t n_dirty;   // the batches to run (device-visible list; null: all of them)
     double *batch_cost;                        // [sub_batches] this version's cost share of every batch (large trees: a batch that does not run keeps its share)
     bool fold;                                 // the quantised records and the cost in the refit's own workgroups (large trees: kFoldRequantNodes / ArtTuning.refit_fold_nodes)
 };
+constexpr uint8_t kTouchRegather = 2u;         // RefitArgs::touched: the primitive's vertices were replaced (bit 0: it moved)
 constexpr uint32_t kFoldRequantNodes = 400000;   // trees of this many 4-wide nodes and more: the refit's workgroups make the quantised records and the cost themselves (art_build.hip launch_refit)
 void launch_refit(const RefitArgs &r, hipStream_t s);
 void launch_wide_parents(uint32_t n_wide, const DevNodeW *widef, uint32_t *leaf_parent, uint32_t *node_parent, hipStream_t s);

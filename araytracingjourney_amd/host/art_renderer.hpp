@@ -125,6 +125,7 @@ enum class ModelState { Storage, Host, Device };
 struct Model { // VkModel: only Device models are instanced in the acceleration structure (renderer.rs:640-651)
     std::vector<uint32_t> primitive_ids; Sphere model_bounding_sphere; ModelState state = ModelState::Host; bool needs_cb_submit = false, instanced = true;
     ArtContext *ctx = nullptr; Matrix3x4 model_matrix{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; Sphere object_sphere; // the reader's sphere, before any model matrix
+    std::vector<std::vector<float>> positions; // object-space positions (x y z per vertex) of every primitive: set_vertices keeps the sphere from them
     // VkModel::set_model_matrix (vk_model.rs:461-466): the instance's object -> world matrix and the sphere that goes with it.  Fixed against the reference, which
     // transforms the sphere it HOLDS (already transformed) by the new matrix (:463-465) and so compounds the matrices of a model that moves every frame; the same for
     // the one call main.rs makes.  The reference rebuilds its TLAS every frame for this (renderer.rs:637-651); libart refits in front of the next frame.
@@ -132,6 +133,27 @@ struct Model { // VkModel: only Device models are instanced in the acceleration 
         model_matrix = m;
         model_bounding_sphere = object_sphere.transform(m);
         if (ctx && !primitive_ids.empty()) check(art_scene_set_model_matrix(ctx, primitive_ids.front(), (uint32_t)primitive_ids.size(), m.data())); // a model's ids are consecutive (art_scene_add_glb)
+    }
+    // BLAS update (a BLAS built with ALLOW_UPDATE, rebuilt in MODE_UPDATE; the reference never does this: its BLAS flags are PREFER_FAST_TRACE only, vk_model.rs:968):
+    // primitive primitive_ids[primitive_index] gets n new vertices, its count, indices, texture and matrix kept; the sphere follows the new positions (the centre of the
+    // model's box, the farthest position from it, before the model matrix).  On a built scene the next frame refits on the device (art_scene_set_vertices).
+    void set_vertices(size_t primitive_index, const ArtVertex *v, uint32_t n) {
+        if (primitive_index >= primitive_ids.size() || primitive_index >= positions.size()) throw Panic(ART_E_INVALID, "Model::set_vertices: no such primitive");
+        if (ctx) check(art_scene_set_vertices(ctx, primitive_ids[primitive_index], v, n));
+        std::vector<float> &q = positions[primitive_index];
+        q.resize((size_t)n * 3);
+        for (uint32_t i = 0; i < n; i++) for (int k = 0; k < 3; k++) q[3 * (size_t)i + k] = v[i].pos[k];
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto &p : positions) for (size_t i = 0; i + 2 < p.size(); i += 3) for (int k = 0; k < 3; k++) { lo[k] = std::fmin(lo[k], p[i + k]); hi[k] = std::fmax(hi[k], p[i + k]); }
+        Sphere sp; float r2 = 0;
+        for (int k = 0; k < 3; k++) sp.center[k] = 0.5f * (lo[k] + hi[k]);
+        for (const auto &p : positions) for (size_t i = 0; i + 2 < p.size(); i += 3) {
+            float dx = p[i] - sp.center[0], dy = p[i + 1] - sp.center[1], dz = p[i + 2] - sp.center[2];
+            r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
+        }
+        sp.radius = std::sqrt(r2);
+        object_sphere = sp;
+        model_bounding_sphere = object_sphere.transform(model_matrix);
     }
     const Matrix3x4 &get_transform_model_matrix() const { return model_matrix; } // vk_model.rs:358-363
     void update_model_status(const Vector3 &camera_pos) { // vk_model.rs:334-345
@@ -163,6 +185,17 @@ public:
         Model m; m.ctx = ctx_; m.model_matrix = model_matrix;
         for (uint32_t i = 0; i < n; i++) m.primitive_ids.push_back(first + i);
         auto cs = r.get_primitives_bounding_sphere();                      // vk_model.rs:501, then set_model_matrix (:461-466)
+        {   // the positions alone (12 B a vertex), for Model::set_vertices' sphere
+            std::vector<ArtGlbCopyInfo> infos(n ? n : 1); size_t total = 0;
+            check_glb(art_glb_copy_model_data(r.handle(), ART_ATTR_VERTICES, 0, nullptr, 0, infos.data(), n, &total));
+            std::vector<uint8_t> data(total ? total : 1);
+            check_glb(art_glb_copy_model_data(r.handle(), ART_ATTR_VERTICES, 0, data.data(), data.size(), infos.data(), n, &total));
+            for (uint32_t i = 0; i < n; i++) {
+                std::vector<float> q(infos[i].mesh_size / 4);
+                std::memcpy(q.data(), data.data() + infos[i].mesh_buffer_offset, q.size() * 4);
+                m.positions.push_back(std::move(q));
+            }
+        }
         Sphere sp; sp.center = cs.first; sp.radius = cs.second;
         m.object_sphere = sp;
         m.model_bounding_sphere = sp.transform(model_matrix);

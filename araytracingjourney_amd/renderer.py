@@ -181,6 +181,15 @@ class Sphere:
         return Sphere(m[:, :3] @ self.center + m[:, 3], scale * self.radius)
 
 
+def _positions_sphere(positions):
+    """a model's object-space bounding sphere from its primitives' positions: the centre of their box, the farthest position from it"""
+    lo = np.min([np.asarray(q)[:, :3].min(0) for q in positions], 0)
+    hi = np.max([np.asarray(q)[:, :3].max(0) for q in positions], 0)
+    c = 0.5 * (lo + hi)
+    rad = max(float(np.linalg.norm(np.asarray(q)[:, :3] - c, axis=1).max()) for q in positions)
+    return Sphere(c, rad)
+
+
 STORAGE, HOST, DEVICE = "Storage", "Host", "Device"
 
 
@@ -188,8 +197,9 @@ class Model:
     """VkModel's residency state machine (vk_model.rs:280-345, states :27-275): Storage <-> Host <-> Device by the distance between the
     camera and the model's bounding sphere.  Only Device models are instanced in the acceleration structure (renderer.rs:640-651)."""
 
-    def __init__(self, primitive_ids, sphere, reload=None, renderer=None, model_matrix=None, object_sphere=None):
+    def __init__(self, primitive_ids, sphere, reload=None, renderer=None, model_matrix=None, object_sphere=None, positions=None):
         self.primitive_ids = list(primitive_ids)
+        self._positions = None if positions is None else [np.array(q, np.float32).reshape(-1, 3) for q in positions]   # object-space positions per primitive (set_vertices keeps the sphere from them)
         self.model_bounding_sphere = sphere
         self._object_sphere = object_sphere     # the reader's sphere, before any model matrix (set_model_matrix transforms THIS one)
         self._renderer = renderer               # the libart context that instances the primitives
@@ -223,6 +233,25 @@ class Model:
                     runs.append((start, a - start + 1)); start = b
             for first, n in runs:
                 check(self._renderer._L.art_scene_set_model_matrix(self._renderer._ctx, first, n, _ptr(m)))
+
+    def set_vertices(self, primitive_index, vertices):
+        """BLAS update (a BLAS built with ALLOW_UPDATE, rebuilt in MODE_UPDATE; the reference never does this: its BLAS flags are PREFER_FAST_TRACE only,
+        vk_model.rs:968): primitive `primitive_ids[primitive_index]` gets new 48-byte vertices (float32 [n, 12]: position, uv, normal, tangent), its count,
+        indices, texture and matrix kept.  The bounding sphere follows the new positions, made as add_model makes it (over every primitive of the model, before
+        the model matrix).  On a built scene the next frame refits on the device (art_scene_set_vertices)."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        if v.ndim != 2 or v.shape[1] != 12:
+            raise ValueError("vertices must be float32 [n, 12] (position, uv, normal, tangent)")
+        if not 0 <= primitive_index < len(self.primitive_ids):
+            raise IndexError("primitive_index out of range")
+        if self._positions is None:
+            raise ValueError("the model's object-space positions are unknown")
+        if self._renderer is not None:
+            check(self._renderer._L.art_scene_set_vertices(self._renderer._ctx, self.primitive_ids[primitive_index], _ptr(v), v.shape[0]))
+        self._positions[primitive_index] = v[:, :3].copy()
+        self._object_sphere = _positions_sphere(self._positions)
+        m = self.model_matrix if self.model_matrix is not None else np.eye(3, 4, dtype=np.float32)
+        self.model_bounding_sphere = self._object_sphere.transform(m)
 
     def get_transform_model_matrix(self):           # vk_model.rs:358-363
         return None if self.model_matrix is None else self.model_matrix.copy()
@@ -284,12 +313,10 @@ class Renderer:
             check(self._L.art_scene_add_primitive(self._ctx, _ptr(verts), verts.shape[0], _ptr(idx), idx.size, idx.dtype.itemsize, _ptr(tex),
                                                   tex.shape[2], tex.shape[1], _ptr(m), C.byref(pid)))
             ids.append(pid.value)
-        lo = np.min([np.asarray(p.verts)[:, :3].min(0) for p in primitives], 0)
-        hi = np.max([np.asarray(p.verts)[:, :3].max(0) for p in primitives], 0)
-        c = 0.5 * (lo + hi)
-        rad = max(float(np.linalg.norm(np.asarray(p.verts)[:, :3] - c, axis=1).max()) for p in primitives)
+        positions = [np.asarray(p.verts)[:, :3] for p in primitives]
+        sp = _positions_sphere(positions)
         mm = model_matrix if model_matrix is not None else primitives[0].model
-        self._models.append(Model(ids, Sphere(c, rad).transform(mm), renderer=self, model_matrix=mm, object_sphere=Sphere(c, rad)))
+        self._models.append(Model(ids, sp.transform(mm), renderer=self, model_matrix=mm, object_sphere=sp, positions=positions))
         return ids
 
     def add_model_glb(self, reader, model_matrix):
@@ -301,7 +328,10 @@ class Renderer:
             raise _lib.ArtError(r, self._L.art_glb_last_error().decode("utf-8", "replace"))
         ids = list(range(first.value, first.value + n.value))
         c, rad = reader.get_primitives_bounding_sphere()   # vk_model.rs:501, then set_model_matrix (:461-466)
-        self._models.append(Model(ids, Sphere(c, rad).transform(model_matrix), renderer=self, model_matrix=model_matrix, object_sphere=Sphere(c, rad)))
+        from .model_reader import VERTICES
+        data, infos = reader.copy_model_data_to_ptr(VERTICES, 0)   # the positions alone (12 B a vertex), for Model.set_vertices' sphere
+        positions = [data[i.mesh_buffer_offset:i.mesh_buffer_offset + i.mesh_size].view(np.float32).reshape(-1, 3) for i in infos]
+        self._models.append(Model(ids, Sphere(c, rad).transform(model_matrix), renderer=self, model_matrix=model_matrix, object_sphere=Sphere(c, rad), positions=positions))
         return ids
 
     def models_mut(self):

@@ -1,6 +1,7 @@
 // host_mirror_demo.cpp -- the reference's main.rs:15-66 call sequence on the C++ host mirror.
 //   host_mirror_demo check            host-only checks (no GPU): light order, camera block, panic-on-error behaviour
 //   host_mirror_demo render <file.glb> [W H]   add_model + lights of main.rs + one frame; prints ray counts and a colour checksum
+//   host_mirror_demo deform <file.glb> [W H]   the same scene; then Model::set_vertices on its first primitive (grown from the origin) and back
 #include <cstdio>
 #include <cstring>
 #include "../araytracingjourney_amd/host/art_renderer.hpp"
@@ -77,7 +78,48 @@ int main(int argc, char **argv) {
                         st3.rebuilds, st3.refits, (int)(std::memcmp(again.data(), c.data(), c.size() * sizeof(float)) == 0));
             return 0;
         }
-        std::puts("usage: host_mirror_demo check | render <file.glb> [W H]");
+        if (argc >= 3 && !std::strcmp(argv[1], "deform")) {
+            uint32_t W = argc >= 5 ? (uint32_t)std::atoi(argv[3]) : 800, H = argc >= 5 ? (uint32_t)std::atoi(argv[4]) : 800;
+            // the first primitive's own 48-byte vertices, as art_scene_add_glb takes them
+            std::vector<ArtVertex> orig;
+            {
+                art::GltfModelReader r = art::GltfModelReader::open(argv[2], true, art::GltfModelReader::B8G8R8A8_UNORM);
+                uint32_t n = 0; art::check_glb(art_glb_primitive_count(r.handle(), &n));
+                const uint32_t attrs = ART_ATTR_VERTICES | ART_ATTR_TEX_COORDS | ART_ATTR_NORMALS | ART_ATTR_TANGENTS;
+                std::vector<ArtGlbCopyInfo> infos(n ? n : 1); size_t total = 0;
+                art::check_glb(art_glb_copy_model_data(r.handle(), attrs, 0, nullptr, 0, infos.data(), n, &total));
+                std::vector<uint8_t> data(total ? total : 1);
+                art::check_glb(art_glb_copy_model_data(r.handle(), attrs, 0, data.data(), data.size(), infos.data(), n, &total));
+                orig.resize(infos[0].mesh_size / sizeof(ArtVertex));
+                std::memcpy(orig.data(), data.data() + infos[0].mesh_buffer_offset, orig.size() * sizeof(ArtVertex));
+            }
+            art::Renderer renderer(W, H);
+            renderer.add_model(argv[2], {2, 0, 0, 0, 0, 2, 0, 0, 0, 0, 2, 0});
+            renderer.lights_mut().get_spot_lights_mut().push_back(art::SpotLight({0.0f, 1.5f, 0.0f}, {0.0f, -1.0f, 0.0f}, {13.6f, 1.6f, 22.2f}, 3.0f, {0.5236f, 0.7854f}, true));
+            renderer.lights_mut().get_point_lights_mut().push_back(art::PointLight({0.0f, 0.5f, -1.5f}, {8, 8, 8}, 6.0f, true));
+            renderer.camera_mut().set_pos({0.0f, 0.3f, -2.5f});
+            renderer.prepare_first_frame();
+            renderer.render_frame();
+            std::vector<float> c = renderer.color_output();
+            art::Model &m = renderer.models_mut()[0];
+            const float r0 = m.model_bounding_sphere.radius;
+            // the BLAS update: the first primitive grown from the origin, its normals turned -- the next frame refits, the one after the way back is the first frame again
+            std::vector<ArtVertex> def = orig;
+            for (ArtVertex &v : def) { for (int k = 0; k < 3; k++) v.pos[k] *= 1.5f; v.normal[0] = -v.normal[0]; }
+            m.set_vertices(0, def.data(), (uint32_t)def.size());
+            const float r1 = m.model_bounding_sphere.radius;
+            renderer.render_frame();
+            std::vector<float> deformed = renderer.color_output();
+            m.set_vertices(0, orig.data(), (uint32_t)orig.size());
+            const float r2 = m.model_bounding_sphere.radius;
+            renderer.render_frame();
+            std::vector<float> back = renderer.color_output();
+            ArtStats st = renderer.stats();
+            std::printf("DEFORM_OK verts=%zu refits=%u rebuilds=%u deformed_differs=%d back_equals_first=%d radius=%.6f,%.6f,%.6f\n", orig.size(), st.refits, st.rebuilds, (int)(deformed != c),
+                        (int)(std::memcmp(back.data(), c.data(), c.size() * sizeof(float)) == 0), r0, r1, r2);
+            return 0;
+        }
+        std::puts("usage: host_mirror_demo check | render <file.glb> [W H] | deform <file.glb> [W H]");
         return 2;
     } catch (const art::Panic &p) {
         std::printf("PANIC(%d): %s\n", p.code, p.what());

@@ -164,6 +164,20 @@ int32_t art_scene_needs_build(const ArtContext *ctx);
  * build, bit for bit (hits are structure-independent).  When the refitted tree's surface-area cost passes ArtTuning.refit_rebuild_ratio (default 2) times
  * the built tree's, art_trace builds again instead (ArtStats.rebuilds).  Every rank of an art_mgpu job must make the same calls. */
 int32_t art_scene_set_model_matrix(ArtContext *ctx, uint32_t first_primitive, uint32_t n_primitives, const float model3x4[12]);
+/* BLAS update (vkCmdBuildAccelerationStructuresKHR, mode UPDATE, on a BLAS built with ALLOW_UPDATE -- the reference never
+ * updates a BLAS: its flags are PREFER_FAST_TRACE only, vk_model.rs:968): primitive `primitive_id` gets n_verts new 48-byte
+ * vertices (position, uv, normal, tangent: all of them), its indices, texture and model matrix kept.  n_verts must equal the
+ * count it was added with.  Data are copied.  A null context or vertices, an unknown id or another count is ART_E_INVALID and
+ * changes nothing; values are accepted as art_scene_add_primitive accepts them.  On a primitive of the built structure this is
+ * a move (see art_scene_set_model_matrix): nothing is built, the NEXT art_trace (or query) refits first, on the same streams and
+ * with the same waits, into the next version of the structure -- its shading records too, which every version keeps a copy of
+ * from the first deformation on (that call synchronises once and allocates them: 144 B a triangle per version but the first,
+ * ART_E_NOMEM from this call if they do not fit).  Frames are those of a fresh build with the vertices current at their launch,
+ * bit for bit; moves and deformations between two frames make one refit, and the rebuild rule (ArtTuning.refit_rebuild_ratio)
+ * builds over the new vertices.  A primitive that left the structure by residency shows its new shape when it is enabled again;
+ * one the built structure does not hold (added since, or disabled at the build) with the next art_scene_build.  Every rank of an
+ * art_mgpu job must make the same calls. */
+int32_t art_scene_set_vertices(ArtContext *ctx, uint32_t primitive_id, const ArtVertex *verts, uint32_t n_verts);
 /* VkBlasBuilder::build_blas_from_geometry (vk_blas_builder.rs:88-170) + VkTlasBuilder::recreate_tlas
  * (vk_tlas_builder.rs:38-233): device LBVH over the world-space triangle soup. */
 int32_t art_scene_build(ArtContext *ctx);

@@ -1,0 +1,400 @@
+"""Deformed meshes (art_scene_set_vertices: a BLAS update, built with ALLOW_UPDATE and rebuilt in MODE_UPDATE in Vulkan terms): a built primitive gets new
+vertices, the next frame refits -- its shading records gathered again in the refit's leaf stage, into the version of the structure that frame reads -- and every
+frame is the oracle's frame of a scene built from scratch with the vertices current at its launch: depth and normal bit for bit, radiance within 1e-4."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from conftest import assert_radiance_close
+from helpers import device_to_host, oracle_camera, random_rays
+
+
+@pytest.fixture(scope="module")
+def R():
+    from araytracingjourney_amd import renderer
+    return renderer
+
+
+def _deformed(p, i, amp=0.02, shading_only=False):
+    """frame i's vertices of primitive p (float32 [n, 12]): positions pushed along their normals by a smooth function of the frame index, normals and tangents
+    turned, uvs slid; shading_only keeps the positions"""
+    v = np.array(p.verts, np.float32, copy=True)
+    pos, nrm = v[:, 0:3].copy(), v[:, 5:8].copy()
+    ph = np.float32(0.7 * i + 0.3)
+    f = (np.float32(amp) * np.sin(ph + np.float32(5.0) * pos[:, 0] + np.float32(3.0) * pos[:, 1] + np.float32(2.0) * pos[:, 2])).astype(np.float32)
+    if not shading_only:
+        v[:, 0:3] = pos + f[:, None] * nrm
+    tilt = np.array([np.sin(ph), np.float32(0.5) * np.cos(ph), np.float32(0.25)], np.float32) * np.float32(0.3)
+    n2 = nrm + tilt[None, :]
+    v[:, 5:8] = n2 / np.linalg.norm(n2, axis=1, keepdims=True).astype(np.float32)
+    t2 = v[:, 8:11] - tilt[None, ::-1]
+    v[:, 8:11] = t2 / np.maximum(np.linalg.norm(t2, axis=1, keepdims=True), np.float32(1e-6)).astype(np.float32)
+    v[:, 3:5] = v[:, 3:5] + np.float32(0.01 * (i + 1))
+    return np.ascontiguousarray(v, np.float32)
+
+
+def _setup(R, sc, movers, extent, lights, **kw):
+    """the scene as two models: everything else, and the primitives in `movers` (the model that deforms)"""
+    r = R.Renderer(extent, **kw)
+    r.add_model([p for j, p in enumerate(sc.primitives) if j not in movers])
+    r.add_model([sc.primitives[j] for j in movers])
+    cam = r.camera_mut()
+    cam.set_pos(sc.camera["pos"]); cam.set_dir(sc.camera["dir"]); cam.set_fovy(sc.camera["fovy"]); cam.set_znear(sc.camera["znear"]); cam.set_zfar(sc.camera["zfar"])
+    for d in lights:
+        r.lights_mut().push_dict(d)
+    r.prepare_first_frame()
+    r.upload_state()
+    return r, r.models_mut()[1]
+
+
+class _State:
+    """what the oracle must build: every mover's current vertices, the movers' matrix, whether they are in the structure"""
+
+    def __init__(self, sc, movers):
+        self.sc, self.movers = sc, list(movers)
+        self.verts = {j: sc.primitives[j].verts for j in movers}
+        self.model = None
+        self.enabled = True
+
+    def prims(self):
+        P = type(self.sc.primitives[0])
+        out = [p for j, p in enumerate(self.sc.primitives) if j not in self.movers]
+        if self.enabled:
+            out += [P(self.verts[j], self.sc.primitives[j].indices, self.sc.primitives[j].tex, self.sc.primitives[j].model if self.model is None else self.model)
+                    for j in self.movers]
+        return out
+
+
+def _deform(model, state, i, **kw):
+    for k, j in enumerate(state.movers):
+        v = _deformed(state.sc.primitives[j], i, **kw)
+        model.set_vertices(k, v)
+        state.verts[j] = v
+
+
+def _grab(r):
+    return (r.device_color(), r._dev("depth"), r._dev("normal"))
+
+
+def _check(orc, sc, prims, ptr, w, h, lights, what):
+    ref = orc.Scene(prims, morton_bits=30).render(oracle_camera(orc, sc, w, h), orc.make_lights(lights), len(lights), w, h, threads=8, debug=True)
+    (pc, nc), (pd, nd), (pn, nn) = ptr
+    color = device_to_host(pc, nc).view(np.float32).reshape(h, w, 4)
+    depth = device_to_host(pd, nd).view(np.float32).reshape(h, w)
+    normal = device_to_host(pn, nn).view(np.float32).reshape(h, w, 4)
+    assert np.array_equal(depth.view(np.uint32), ref["depth"].view(np.uint32)), f"{what}: depth"
+    assert np.array_equal(normal.view(np.uint32), ref["normal"].view(np.uint32)), f"{what}: normal"
+    assert_radiance_close(color, ref["color"], what=what)
+    return ref, color, depth
+
+
+def _frames(r, model, state, n):
+    """n frames back to back, the movers deformed before each; returns what the oracle needs for each and its buffers"""
+    out = []
+    for i in range(n):
+        _deform(model, state, i)
+        r.trace()
+        out.append((state.prims(), _grab(r)))
+    return out
+
+
+def _pose(base, i):
+    import math
+    a = 0.15 * i
+    ry = np.array([[math.cos(a), 0, math.sin(a), 0], [0, 1, 0, 0], [-math.sin(a), 0, math.cos(a), 0], [0, 0, 0, 1]])
+    t = np.eye(4); t[:3, 3] = (0.1 * math.sin(0.5 * i), 0.03 * i, 0.0)
+    return np.ascontiguousarray((t @ ry @ np.vstack([np.asarray(base, np.float64).reshape(3, 4), [0, 0, 0, 1]]))[:3], np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dynamic", [False, True], ids=["versions-at-first-deformation", "versions-at-build"])
+def test_cornell_last_primitive_deforms_every_frame(R, orc, get_scene, dynamic):
+    """the Cornell box (all crown: one workgroup refits it) with its last primitive deformed before each of four frames in flight"""
+    sc = get_scene("cornell")
+    w, h, F = 160, 160, 4
+    movers = [len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), sc.lights, frames_in_flight=F, dynamic_scene=dynamic)
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+    got = _frames(r, model, state, F)
+    r.sync()
+    assert r.stats()["refits"] == F and r.stats()["rebuilds"] == 0
+    for i, (prims, ptr) in enumerate(got):
+        _check(orc, sc, prims, ptr, w, h, sc.lights, f"frame {i}")
+    r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("versions", [3, 1, 8])
+def test_two_primitives_deform_with_sixteen_frames_in_flight(R, orc, get_scene, scenes, versions):
+    """sponza_like's two displaced spheres deformed before each of 16 frames launched without a host sync: every frame the oracle's, 16 refits, no rebuild"""
+    sc = get_scene("sponza_like", 0.12)
+    w, h, F = 320, 180, 16
+    lights = scenes.sponza_lights(4)
+    movers = [len(sc.primitives) - 2, len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), lights, frames_in_flight=F, tuning=dict(as_versions=versions, refit_rebuild_ratio=-1.0))
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+    got = _frames(r, model, state, F)
+    r.sync()
+    st = r.stats()
+    assert st["refits"] == F and st["rebuilds"] == 0 and st["refit_ms"] > 0
+    for i, (prims, ptr) in enumerate(got):
+        _check(orc, sc, prims, ptr, w, h, lights, f"frame {i}")
+    r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F,K", [(1, 4), (4, 4), (8, 0)])
+def test_lapping_the_ring_of_versions(R, orc, get_scene, scenes, F, K):
+    """F * K + 3 deformed frames back to back: every version's staging is rewritten several times; the last F frames are the oracle's"""
+    sc = get_scene("sponza_like", 0.12)
+    w, h = 240, 136
+    lights = scenes.sponza_lights(1)
+    movers = [len(sc.primitives) - 2, len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), lights, frames_in_flight=F, tuning=dict(as_versions=K, refit_rebuild_ratio=-1.0))
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+    n = F * (K if K else min(max(2 * F, 4), 24)) + 3
+    got = _frames(r, model, state, n)
+    r.sync()
+    assert r.stats()["refits"] == n
+    for i, (prims, ptr) in enumerate(got[-F:]):
+        _check(orc, sc, prims, ptr, w, h, lights, f"frame {n - F + i}")
+    r.close()
+
+
+@pytest.mark.gpu
+def test_deformation_move_and_residency_combined(R, orc, get_scene, scenes):
+    """frames that deform and move the model in one step, and the model taken out of the structure, deformed while it is out and put back (no build)"""
+    from araytracingjourney_amd._lib import check
+    sc = get_scene("sponza_like", 0.12)
+    plan = ["deform+move", "deform", "disable", "deform-out", "enable", "deform+move", "move", "deform+move"]
+    w, h, F = 320, 180, len(plan)   # (a ring slot per frame: every frame's outputs are read at the end)
+    lights = scenes.sponza_lights(4)
+    movers = [len(sc.primitives) - 2, len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), lights, frames_in_flight=F)
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+    base = sc.primitives[movers[0]].model
+
+    def enable(on):
+        for pid in model.primitive_ids:
+            check(r._L.art_scene_set_primitive_enabled(r._ctx, pid, 1 if on else 0))
+        state.enabled = on
+
+    got = []
+    for i, step in enumerate(plan):
+        if step.startswith("deform"):
+            _deform(model, state, i)
+        if step.endswith("move"):
+            m = _pose(base, i + 1); model.set_model_matrix(m); state.model = m
+        if step == "disable":
+            enable(False)
+        if step == "enable":
+            enable(True)
+        r.trace()
+        got.append((state.prims(), _grab(r), step))
+    r.sync()
+    st = r.stats()
+    assert st["rebuilds"] == 0 and st["refits"] == len(plan) - 1   # (the frame deformed while out refits nothing: nothing in the structure changed)
+    for i, (prims, ptr, step) in enumerate(got):
+        _check(orc, sc, prims, ptr, w, h, lights, f"frame {i} ({step})")
+    r.close()
+
+
+@pytest.mark.gpu
+def test_a_shading_only_change_shows(R, orc, get_scene, scenes):
+    """positions kept, normals and tangents turned: depth is the previous frame's bit for bit, colour changes, and both frames are the oracle's -- the shading
+    records are versioned and gathered again"""
+    sc = get_scene("sponza_like", 0.12)
+    w, h, F = 320, 180, 2
+    lights = scenes.sponza_lights(4)
+    movers = [len(sc.primitives) - 2, len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), lights, frames_in_flight=F)
+    state = _State(sc, movers)
+    r.trace()
+    first = (state.prims(), _grab(r))
+    _deform(model, state, 5, shading_only=True)
+    r.trace()
+    second = (state.prims(), _grab(r))
+    r.sync()
+    _, c0, d0 = _check(orc, sc, first[0], first[1], w, h, lights, "before")
+    ref, c1, d1 = _check(orc, sc, second[0], second[1], w, h, lights, "after")
+    assert np.array_equal(d0.view(np.uint32), d1.view(np.uint32))
+    on = (ref["hit_id"][..., 0] >= len(sc.primitives) - 2)   # the pixels of the two deformed primitives
+    assert on.sum() > 50 and not np.array_equal(c0[on], c1[on])
+    r.close()
+
+
+@pytest.mark.gpu
+def test_deformation_past_the_rebuild_rule_and_an_explicit_build(R, orc, get_scene, scenes):
+    """a deformation that inflates the tree (the movers' vertices spread far apart) crosses the default rebuild ratio: art_trace builds again over the deformed
+    vertices; and a deformation followed by art_scene_build (the same enabled set: the build's upload shortcut) is built over the new vertices too"""
+    sc = get_scene("sponza_like", 0.12)
+    w, h = 320, 180
+    lights = scenes.sponza_lights(1)
+    movers = [len(sc.primitives) - 2, len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), lights)
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+
+    def spread(i):
+        for k, j in enumerate(movers):
+            v = _deformed(sc.primitives[j], i)
+            c = v[:, 0:3].mean(0)
+            v[:, 0:3] = c + (v[:, 0:3] - c) * np.float32(12.0 + i)
+            model.set_vertices(k, v); state.verts[j] = v
+
+    spread(0); r.trace(); r.sync()
+    _check(orc, sc, state.prims(), _grab(r), w, h, lights, "inflated")
+    assert r.stats()["refit_cost_ratio"] > 2.0
+    spread(1); r.trace(); r.sync()
+    assert r.stats()["rebuilds"] >= 1
+    _check(orc, sc, state.prims(), _grab(r), w, h, lights, "after the rebuild")
+    _deform(model, state, 7)
+    r.prepare_first_frame()
+    r.trace(); r.sync()
+    _check(orc, sc, state.prims(), _grab(r), w, h, lights, "after art_scene_build")
+    r.close()
+
+
+@pytest.mark.gpu
+def test_config2_full_size_model_deforms(R, orc, get_scene, scenes):
+    """config 2 (262 816 triangles, 1920x1080, one directional light) with its 164 k-triangle model deformed for three frames; the refit's quantised records and cost
+    in its own workgroups (the large-tree form, forced: ArtTuning.refit_fold_nodes).  Hits bit for bit, the rest within 1e-4 as the still full-size frame is checked"""
+    sc = get_scene("sponza_like", 1.0)
+    w, h = 1920, 1080
+    lights = sc.lights[:1]
+    movers = [len(sc.primitives) - 1]
+    assert sc.primitives[movers[0]].n_tris > 150_000
+    r, model = _setup(R, sc, movers, (w, h), lights, keep_debug=True, tuning=dict(refit_fold_nodes=1))
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+    for i in range(3):
+        _deform(model, state, i, amp=0.01)
+        r.trace(); r.sync()
+        ref = orc.Scene(state.prims(), morton_bits=30).render(oracle_camera(orc, sc, w, h), orc.make_lights(lights), 1, w, h, threads=16, debug=True)
+        tuv, ids = r.read_hits()
+        assert np.array_equal(ids, ref["hit_id"]), f"frame {i}: {int((ids != ref['hit_id']).any(-1).sum())} hit ids differ"
+        assert np.array_equal(tuv.view(np.uint32)[..., :3], ref["hit_tuv"].view(np.uint32)[..., :3]), f"frame {i}: t/u/v"
+        assert_radiance_close(r.read_color(), ref["color"], what=f"frame {i}")
+        assert_radiance_close(r.read_depth(), ref["depth"], what=f"frame {i} depth")
+        assert_radiance_close(r.read_normal(), ref["normal"], rel=1e-4, floor=1e-5, what=f"frame {i} normal")
+    assert r.stats()["refits"] == 3 and r.stats()["rebuilds"] == 0
+    r.close()
+
+
+@pytest.mark.gpu
+def test_queries_and_ao_after_a_deformation(R, get_scene, scenes):
+    """after a deformed frame, the closest- and any-hit queries and the AO output equal those of a fresh context built with the deformed vertices"""
+    sc = get_scene("sponza_like", 0.12)
+    w, h = 320, 180
+    lights = scenes.sponza_lights(1)
+    movers = [len(sc.primitives) - 2, len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), lights, frames_in_flight=2)
+    r.trace(); r.sync()
+    state = _State(sc, movers)
+    for i in range(3):
+        _deform(model, state, i, amp=0.05)
+        r.trace()
+    r.sync()
+    fresh_sc = scenes.Scene(sc.name, state.prims(), sc.camera, lights)   # (the movers last, as in `r`)
+    fresh, _ = _setup(R, fresh_sc, movers, (w, h), lights)
+    fresh.trace(); fresh.sync()
+    rays = random_rays(20000, 11)
+    a_tuv, a_ids = r.query_closest(rays)
+    b_tuv, b_ids = fresh.query_closest(rays)
+    assert np.array_equal(a_ids, b_ids) and np.array_equal(a_tuv.view(np.uint32), b_tuv.view(np.uint32))
+    assert np.array_equal(r.query_any(rays), fresh.query_any(rays))
+    r.trace(); fresh.trace()
+    r.trace_ao(8); fresh.trace_ao(8)
+    a, b = r.read_ao(), fresh.read_ao()
+    assert np.array_equal(a, b) and a.min() < 255
+    r.close(); fresh.close()
+
+
+@pytest.mark.gpu
+def test_bad_calls_change_nothing_and_an_unbuilt_primitive_waits_for_the_build(R, orc, get_scene, scenes):
+    from araytracingjourney_amd import _lib
+    sc = get_scene("cornell")
+    w, h = 128, 128
+    movers = [len(sc.primitives) - 1]
+    r, model = _setup(R, sc, movers, (w, h), sc.lights)
+    r.trace(); r.sync()
+    before = r.read_color()
+    pid = model.primitive_ids[0]
+    v = _deformed(sc.primitives[pid], 3)
+    ptr = v.ctypes.data_as(C.c_void_p)
+    assert r._L.art_scene_set_vertices(r._ctx, pid, ptr, v.shape[0] - 1) == _lib.ART_E_INVALID
+    assert r._L.art_scene_set_vertices(r._ctx, pid, ptr, v.shape[0] + 1) == _lib.ART_E_INVALID
+    assert r._L.art_scene_set_vertices(r._ctx, 1000, ptr, v.shape[0]) == _lib.ART_E_INVALID
+    assert r._L.art_scene_set_vertices(r._ctx, pid, None, v.shape[0]) == _lib.ART_E_INVALID
+    assert r._L.art_scene_set_vertices(None, pid, ptr, v.shape[0]) == _lib.ART_E_INVALID
+    r.trace(); r.sync()
+    assert np.array_equal(r.read_color().view(np.uint32), before.view(np.uint32))
+    assert r.stats()["refits"] == 0
+    # a primitive added after the build: deformed, it shows (in its new shape) only once the scene is built again
+    extra = sc.primitives[0]
+    P = type(extra)
+    small = P(np.array(extra.verts, np.float32) * np.array([0.3] * 3 + [1] * 9, np.float32), extra.indices, extra.tex, extra.model)   # the room's box, shrunk
+    ids = r.add_model([small])
+    new = _deformed(small, 2, amp=0.05)
+    r.models_mut()[-1].set_vertices(0, new)
+    assert r.needs_build()
+    r.prepare_first_frame()
+    r.trace(); r.sync()
+    ref = orc.Scene(list(sc.primitives) + [P(new, small.indices, small.tex, small.model)], morton_bits=30).render(
+        oracle_camera(orc, sc, w, h), orc.make_lights(sc.lights), len(sc.lights), w, h, threads=8, debug=True)
+    assert ids == [len(sc.primitives)]
+    assert np.array_equal(r.read_depth().view(np.uint32), ref["depth"].view(np.uint32))
+    assert_radiance_close(r.read_color(), ref["color"])
+    r.close()
+
+
+@pytest.mark.gpu
+def test_cpp_host_mirror_deforms_a_glb(get_scene, tmp_path):
+    """Model::set_vertices on the C++ mirror: the first primitive of a GLB model grown and turned (one refit, the frame differs, the sphere grows), then given back
+    its own vertices (a second refit: the frame is the first one bit for bit)"""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    from glb_writer import write_glb
+    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "examples")])
+    sc = get_scene("cornell")
+    path = tmp_path / "cornell.glb"
+    write_glb(str(path), sc.primitives, png_modes=("RGBA", "RGBA", "RGBA"))
+    out = subprocess.run([os.path.join(root, "examples", "host_mirror_demo"), "deform", str(path), "160", "96"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "DEFORM_OK" in out.stdout, out.stdout + out.stderr
+    f = dict(kv.split("=") for kv in out.stdout.split("DEFORM_OK")[1].split("\n")[0].split())
+    assert int(f["verts"]) > 0
+    assert (int(f["refits"]), int(f["rebuilds"]), int(f["deformed_differs"]), int(f["back_equals_first"])) == (2, 0, 1, 1), out.stdout
+    r0, r1, r2 = (float(x) for x in f["radius"].split(","))
+    assert r1 > r2 > 0 and r0 > 0, out.stdout
+
+
+def test_model_set_vertices_keeps_the_bounding_sphere():
+    """Model.set_vertices without a context: the model's sphere is the one add_model would make over the new positions (the centre of the box of every
+    primitive's positions, the farthest position from it), placed by the model matrix; a bad shape or index changes nothing"""
+    from araytracingjourney_amd import renderer as R
+    rng = np.random.default_rng(3)
+    a = rng.uniform(-1, 1, (40, 12)).astype(np.float32)
+    b = rng.uniform(-0.5, 0.5, (25, 12)).astype(np.float32)
+    mm = np.array([2, 0, 0, 1, 0, 2, 0, 0, 0, 0, 2, -3], np.float32)
+    m = R.Model([0, 1], None, model_matrix=mm, positions=[a[:, :3], b[:, :3]])
+    nb = b.copy(); nb[:, 0:3] = nb[:, 0:3] * np.float32(4.0) + np.float32(1.0)
+    m.set_vertices(1, nb)
+    pts = np.concatenate([a[:, :3], nb[:, :3]])
+    lo, hi = pts.min(0), pts.max(0)
+    c = 0.5 * (lo + hi)
+    rad = float(np.linalg.norm(pts - c, axis=1).max())
+    want = R.Sphere(c, rad).transform(mm)
+    assert np.allclose(m.model_bounding_sphere.center, want.center, atol=1e-6) and abs(m.model_bounding_sphere.radius - want.radius) < 1e-6
+    assert abs(m.model_bounding_sphere.radius - 2 * rad) < 1e-5
+    before = (m.model_bounding_sphere.center.copy(), m.model_bounding_sphere.radius)
+    with pytest.raises(ValueError):
+        m.set_vertices(0, a[:, :11])
+    with pytest.raises(IndexError):
+        m.set_vertices(2, a)
+    assert np.array_equal(m.model_bounding_sphere.center, before[0]) and m.model_bounding_sphere.radius == before[1]
