@@ -100,6 +100,7 @@ SYMBOLS = {
     "art_scene_needs_build": (_I32, [_P]),
     "art_scene_set_model_matrix": (_I32, [_P, _U32, _U32, _P]),
     "art_scene_set_vertices": (_I32, [_P, _U32, _P, _U32]),
+    "art_scene_set_alpha_cutoff": (_I32, [_P, _U32, _F]),
     "art_scene_build": (_I32, [_P]),
     "art_set_camera": (_I32, [_P, _P]),
     "art_camera_from_params": (_I32, [_P, _P, _F, _F, _F, _F, _P]),
@@ -147,6 +148,7 @@ SYMBOLS = {
     "art_glb_open": (_I32, [C.c_char_p, _I32, _I32, _P]),
     "art_glb_close": (_I32, [_P]),
     "art_glb_primitive_count": (_I32, [_P, _P]),
+    "art_glb_primitive_alpha": (_I32, [_P, _U32, _P, _P, _P]),
     "art_glb_copy_model_data": (_I32, [_P, _U32, _U32, _P, _SZ, _P, _U32, _P]),
     "art_glb_bounding_sphere": (_I32, [_P, _P, _P]),
     "art_glb_permute_pixels": (_I32, [_P, _SZ, _U32, _P, _U32, _U32, _P, _SZ]),

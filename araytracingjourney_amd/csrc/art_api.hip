@@ -27,6 +27,7 @@ struct HostPrim {
     float o2w[12], w2o[12];
     bool enabled = true; // instanced in the acceleration structure (the reference's Device state, vk_model.rs:334-345); else kept on the host only
     bool verts_stale = false; // art_scene_set_vertices replaced `verts` since they were uploaded: a build over the same set uploads them again
+    float cutoff = 0.0f;      // alpha cutoff (art_scene_set_alpha_cutoff; 0: opaque)
 };
 
 template <class T> struct DevBuf {
@@ -71,6 +72,7 @@ struct FrameSlot {
     hipGraphExec_t graph = nullptr;  // the frame's launch sequence captured once (graph mode); dropped whenever an input changes
     void *wait_event = nullptr;      // external event the slot's next frame must wait for (art_wait_external_event)
     uint32_t as_version = 0;         // which version of the acceleration structure the slot's latest frame read (art_trace_ao and the read-backs follow it)
+    bool alpha = false;              // ... and whether it ran the instances with the alpha test (art_trace_ao follows it too)
     void release() {
         d_counters.release(); d_shadow_bits.release(); d_hits.release(); d_contrib.release(); d_shadow_rays.release();
         d_color.release(); d_normal.release(); d_color_tiles.release(); d_depth.release(); d_occl.release(); d_ao.release(); d_ao_pix.release(); d_wave_cost.release(); d_lights_more.release(); d_pix_more.release();
@@ -189,6 +191,12 @@ struct ArtContext {
     void *shade_block = nullptr;               // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
     void *stage_block = nullptr, *stage_pinned = nullptr;   // every version's staging of replaced vertices: device, pinned
     int64_t masked_tris = 0;                   // triangles of primitives disabled since the build (still in the arrays, written "nowhere")
+    // alpha-masked primitives: the cutoffs travel in the versioned primitive table (DevPrim::cutoff), so a change is a refit over no batch, like a
+    // primitive that is disabled; alpha_bits marks the leaves whose primitive may have a cutoff (made by the build, bits added in front of the refit that first shows a
+    // new cutoff, never cleared until the next build: a superset is safe, the cutoff itself decides)
+    DevBuf<uint32_t> d_alpha_bits;
+    bool alpha_live = false;                   // some enabled primitive has a cutoff > 0: frames and queries run the instances with the alpha test
+    bool alpha_bits_stale = false;             // a built primitive got a cutoff > 0 since the bits were last made
     uint64_t as_epoch = 0, binary_epoch = 0;   // refits so far; the refit the binary trees / node records reflect
     double as_cost0 = 0.0; float refit_cost_ratio = 1.0f; uint32_t refits = 0, rebuilds = 0; float last_refit_ms = 0.f, first_move_ms = 0.f, versions_ms = 0.f;
     ArtCamera camera{};
@@ -286,6 +294,12 @@ int32_t sync_all(ArtContext *c) {
     if (c->plan.plan_stream && c->plan.pending) { for (uint32_t k = 0; k < c->F; k++) HIPC(hipStreamSynchronize(c->stream_of(k))); HIPC(hipStreamSynchronize(c->plan.plan_stream)); }   // (a plan behind a sampled frame)
     for (uint32_t k = 0; k < c->F; k++) HIPC(hipStreamSynchronize(c->stream_of(k)));
     return ART_OK;
+}
+
+void alpha_refresh_live(ArtContext *c) {
+    bool any = false;
+    for (const HostPrim &p : c->prims) any = any || (p.enabled && p.cutoff > 0.0f && p.n_indices >= 3);
+    c->alpha_live = any;
 }
 
 // ---- versions of the acceleration structure (moving models) ------------------------------------------------------------------------------
@@ -477,6 +491,10 @@ int32_t scene_refresh(ArtContext *c, uint32_t k, hipStream_t s) {
         }
         ra.dirty = all ? nullptr : V.dh_dirty; ra.n_dirty = nd; ra.batch_cost = V.batch_cost;
         if (all) V.cost_cached = true;
+    }
+    if (c->alpha_bits_stale) {   // a primitive got a cutoff: its leaves' bits, from this version's table, in front of the refit whose event the frames wait for
+        launch_alpha_bits(c->T, c->bvh.leaf_gid, c->bvh.tri_prim, V.dh_prims, c->d_alpha_bits.p, s);
+        c->alpha_bits_stale = false;
     }
     launch_refit(ra, s);
     HIPC(hipEventRecord(V.ready, s)); V.ready_known = false; V.ready_slot = beside ? ~0u : k; V.result_pending = true;   // (~0: no frame stream is behind it by itself)
@@ -925,6 +943,7 @@ int32_t art_scene_set_primitive_enabled(ArtContext *c, uint32_t id, int32_t enab
     HostPrim &p = c->prims[id];
     if (p.enabled == (enabled != 0)) return ART_OK;
     p.enabled = enabled != 0;
+    alpha_refresh_live(c);
     if (!c->built) return ART_OK;                                // takes effect with the build
     if (p.n_indices < 3) return ART_OK;                          // no triangles: nothing to take out or bring back
     if (id < c->h_dev_prims.size() && c->h_dev_prims[id].n_tri > 0) {
@@ -940,6 +959,27 @@ int32_t art_scene_set_primitive_enabled(ArtContext *c, uint32_t id, int32_t enab
         return ART_OK;
     }
     c->built = false;                                            // not part of the built structure: art_scene_build
+    return ART_OK;
+}
+
+// An alpha cutoff: takes effect at the next art_trace or query without a build -- the value travels in the versioned primitive table, so the next frame
+// refits over no batch (as for a disabled primitive) and frames in flight keep the table they were launched with.
+int32_t art_scene_set_alpha_cutoff(ArtContext *c, uint32_t id, float cutoff) {
+    if (!c) return fail(ART_E_INVALID, "art_scene_set_alpha_cutoff: null context");
+    if (id >= c->prims.size()) return fail(ART_E_INVALID, "art_scene_set_alpha_cutoff: no such primitive");
+    if (!(cutoff >= 0.0f && cutoff <= 1.0f)) return fail(ART_E_INVALID, "art_scene_set_alpha_cutoff: the cutoff must lie in [0, 1]");   // (NaN too)
+    HostPrim &p = c->prims[id];
+    if (cutoff == 0.0f) cutoff = 0.0f;   // (-0 is 0: opaque)
+    if (p.cutoff == cutoff) return ART_OK;
+    const bool was_cut = p.cutoff > 0.0f;
+    p.cutoff = cutoff;
+    alpha_refresh_live(c);
+    if (!c->built || id >= c->h_dev_prims.size()) return ART_OK;   // takes effect with the build
+    DevPrim &d = c->h_dev_prims[id];
+    d.cutoff = cutoff;
+    if (d.n_tri == 0) return ART_OK;                                // no triangles in the structure (a build brings them, with the cutoff)
+    if (cutoff > 0.0f && !was_cut) c->alpha_bits_stale = true;      // its leaves get their bits in front of the refit
+    c->xform_dirty = true;                                          // the next art_trace (or query) writes the next version of the table
     return ART_OK;
 }
 
@@ -1055,7 +1095,7 @@ int32_t art_scene_build(ArtContext *c) {
         DevPrim &d = dp[k];
         std::memset(&d, 0, sizeof(d));
         d.vertices = c->d_verts.p + ov * 12; d.indices = c->d_indices.p + oi; d.texture_offset = (uint32_t)ot; d.single_index_size = p.idx_bytes;
-        d.tw = p.tw; d.th = p.th; d.first_tri = T; d.n_tri = p.enabled ? p.n_indices / 3 : 0;
+        d.tw = p.tw; d.th = p.th; d.first_tri = T; d.n_tri = p.enabled ? p.n_indices / 3 : 0; d.cutoff = p.cutoff;
         std::memcpy(d.o2w, p.o2w, 48); std::memcpy(d.w2o, p.w2o, 48);
         first[k] = T;
         if (!p.enabled) continue;
@@ -1111,6 +1151,17 @@ int32_t art_scene_build(ArtContext *c) {
     float ms = 0; HIPC(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     c->stats.build_ms = ms; c->stats.num_triangles = T; c->stats.num_primitives = (uint32_t)dp.size(); c->stats.num_nodes = c->kind_primary == 4 ? c->bvh.n_wide : (T > 1 ? T - 1 : 1);
+    {   // the leaf bits of the alpha test, from zero (on the first stream, then waited for: the frames run on every ring slot's stream)
+        const size_t nw = ((size_t)T + 31) / 32;
+        HIPC(c->d_alpha_bits.ensure(nw + 1));
+        HIPC(hipMemsetAsync(c->d_alpha_bits.p, 0, (nw + 1) * 4, c->main_stream()));
+        bool cut = false;
+        for (const DevPrim &d : dp) cut = cut || (d.n_tri > 0 && d.cutoff > 0.0f);
+        if (cut) { launch_alpha_bits(T, c->bvh.leaf_gid, c->bvh.tri_prim, c->d_prims.p, c->d_alpha_bits.p, c->main_stream()); HIPC(hipGetLastError()); }
+        HIPC(hipStreamSynchronize(c->main_stream()));
+        c->alpha_bits_stale = false;
+        alpha_refresh_live(c);
+    }
     c->built = true;
     c->plan.next_sample = c->frame_no; c->plan.interval = 1; // a new scene: the heavy blocks are elsewhere
     c->first_move_ms = 0.f; c->versions_ms = 0.f;
@@ -1255,6 +1306,7 @@ static FrameArgs make_frame_args(ArtContext *c, FrameSlot &S, uint32_t version) 
     a.batch = c->B; a.tiles_stride = c->padded_tiles * kTilePixels;
     for (uint32_t i = 0; i + 1 < kMaxBatch; i++) std::memcpy(&a.cam_more[i], &c->cam_more[i], sizeof(ArtCamera));
     a.tile_xy = c->d_tile_xy.p; a.wave_items = c->plan.d_items[c->plan.cur].p; a.n_wave_items = c->plan.n_items[c->plan.cur]; a.wave_cost = nullptr; // art_trace sets it for the frames the wave plan samples
+    a.alpha = c->alpha_live; a.alpha_bits = c->d_alpha_bits.p;   // (art_trace_ao: the frame's own choice, FrameSlot::alpha)
     return a;
 }
 
@@ -1306,6 +1358,7 @@ int32_t art_trace(ArtContext *c) {
     S.as_version = ver;
     r = lights_upload(c, S, s); if (r) return r;
     FrameArgs a = make_frame_args(c, S, ver);
+    S.alpha = a.alpha;
     if (c->tiled()) a.color_tiles = S.tiles_for(c->frame_no, c->F); // alternates when a pair of buffers is bound
     const bool fused = c->fused && c->kind_primary == 8 && c->kind_shadow == 8;
     if (c->B > 1 && !fused) return fail(ART_E_STATE, "art_trace: several frames per launch need the default fused frame");
@@ -1418,6 +1471,7 @@ int32_t art_trace_ao(ArtContext *c, uint32_t spp, float radius) {
     for (uint32_t k = 0; k <= spp; k++) lut[k] = (uint32_t)(std::pow(1.0 - (double)k / (double)spp, 2.2) * 255.0 + 0.5); // XE_GTAO_DEFAULT_FINAL_VALUE_POWER (vk_xe_gtao.rs:22)
     r = ensure_binary(c, c->kind_ao == 2); if (r) return r;
     FrameArgs a = make_frame_args(c, S, S.as_version); // the structure the frame itself was traced in
+    a.alpha = S.alpha;                                  // (and the cutoffs of that version's table)
     if (!c->as.empty()) c->as[S.as_version].aux[c->last] = true;
     HIPC(hipMemsetAsync(S.d_counters.p + 64 + 16 * 32, 0, 8 * 32 * 4, s)); // the AO launch's work cursors
     HIPC(hipEventRecord(S.ao_ev[0], s));
@@ -1794,7 +1848,7 @@ int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *t
     if (e == hipSuccess && (refresh_now(c) != ART_OK || ensure_wide(c, true) != ART_OK || ensure_binary(c, qkind == 2) != ART_OK)) e = hipErrorUnknown; // (a pending move is applied first)
     if (e == hipSuccess) e = c->slot[0].d_counters.ensure(kCounterWords);
     if (e == hipSuccess) e = hipMemsetAsync(c->slot[0].d_counters.p, 0, kCounterWords * 4, c->main_stream());
-    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_closest(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
+    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_closest(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(c->main_stream());
     if (e == hipSuccess) e = hipMemcpy(h.data(), d_h, (size_t)n * 16, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(tris.data(), c->bvh.tris, (size_t)c->T * sizeof(DevTri), hipMemcpyDeviceToHost);
@@ -1824,7 +1878,7 @@ int32_t art_query_any(ArtContext *c, const float *rays, uint32_t n, uint8_t *hit
     if (e == hipSuccess && (refresh_now(c) != ART_OK || ensure_wide(c, true) != ART_OK || ensure_binary(c, qkind == 2) != ART_OK)) e = hipErrorUnknown;
     if (e == hipSuccess) e = c->slot[0].d_counters.ensure(kCounterWords);
     if (e == hipSuccess) e = hipMemsetAsync(c->slot[0].d_counters.p, 0, kCounterWords * 4, c->main_stream());
-    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_any(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
+    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_any(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(c->main_stream());
     if (e == hipSuccess) e = hipMemcpy(h.data(), d_h, (size_t)n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d_r); (void)hipFree(d_h);

@@ -708,6 +708,20 @@ __global__ __launch_bounds__(256) void k_wide_requant(uint32_t n_wide, const Dev
     }
 }
 
+// the leaf bits of the alpha test (FrameArgs::alpha_bits): a thread per word of 32 leaf positions, set where the leaf's primitive has a cutoff > 0 in `prims`.  Bits are only ever
+// added (atomicOr): a frame in flight that reads a word while it changes sees its own bits either way, and a bit of a primitive whose cutoff went back to 0 costs that
+// frame a look at the cutoff, never a wrong answer.  The next build starts from zero.
+__global__ __launch_bounds__(256) void k_alpha_bits(uint32_t T, const uint32_t *__restrict__ leaf_gid, const uint32_t *__restrict__ tri_prim, const DevPrim *prims, uint32_t *bits) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= (T + 31u) / 32u) return;
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < 32u && w * 32u + j < T; j++) if (prims[tri_prim[leaf_gid[w * 32u + j]]].cutoff > 0.0f) m |= 1u << j;
+    if (m) atomicOr(&bits[w], m);
+}
+void launch_alpha_bits(uint32_t T, const uint32_t *leaf_gid, const uint32_t *tri_prim, const DevPrim *prims, uint32_t *bits, hipStream_t s) {
+    const uint32_t nw = (T + 31u) / 32u;
+    if (nw) k_alpha_bits<<<(nw + 255) / 256, 256, 0, s>>>(T, leaf_gid, tri_prim, prims, bits);
+}
 void launch_wide_parents(uint32_t n_wide, const DevNodeW *widef, uint32_t *leaf_parent, uint32_t *node_parent, hipStream_t s) {
     k_wide_parents<<<(n_wide + 255) / 256, 256, 0, s>>>(n_wide, widef, leaf_parent, node_parent);
 }

@@ -172,7 +172,10 @@ bool decode_png(const uint8_t *d, size_t n, Image &out, std::string &err) {
 enum { A_VERTICES = 1, A_TEX_COORDS = 2, A_NORMALS = 4, A_TANGENTS = 8, A_INDICES = 16 }; // MeshAttributeType, model_reader.rs:6-12
 enum { T_ALBEDO = 1, T_ORM = 2, T_NORMAL = 4, T_EMISSIVE = 8 };                            // TextureType, model_reader.rs:14-19
 struct Attr { uint64_t start = 0, len = 0; uint32_t elem_size = 0, stride = 0; uint64_t count() const { return stride ? len / stride : 0; } }; // :10-34
-struct Prim { std::map<int, Attr> attrs; std::map<int, int> textures; /* type -> image index */ };
+struct Prim {
+    std::map<int, Attr> attrs; std::map<int, int> textures; /* type -> image index */
+    int alpha_mode = 0; float alpha_cutoff = 0.5f; bool base_alpha = false;   // the material's alphaMode (0 OPAQUE, 1 MASK, 2 BLEND), alphaCutoff, base-colour image with an alpha channel
+};
 
 } // namespace
 
@@ -351,6 +354,17 @@ static int32_t glb_open_impl(const char *path, int32_t normalize_vectors, int32_
                     if (ii < 0 || (size_t)ii >= g->images.size()) return gfail(ART_E_INVALID, "Cannot open texture idx " + std::to_string(ii));
                     P.textures[sl.first] = ii;
                 }
+            // alphaMode / alphaCutoff (glTF 2.0 material defaults: OPAQUE, 0.5); whether the base-colour image as decoded -- before any coercion -- has alpha
+            if (const JV *am = m.get("alphaMode")) {
+                if (am->t != JV::Str || (am->s != "OPAQUE" && am->s != "MASK" && am->s != "BLEND")) return gfail(ART_E_INVALID, "material alphaMode must be OPAQUE, MASK or BLEND");
+                P.alpha_mode = am->s == "MASK" ? 1 : (am->s == "BLEND" ? 2 : 0);
+            }
+            if (const JV *ac = m.get("alphaCutoff")) {
+                if (ac->t != JV::Num || !(ac->n >= 0.0)) return gfail(ART_E_INVALID, "material alphaCutoff must be a number >= 0");
+                P.alpha_cutoff = (float)ac->n;
+            }
+            auto it = P.textures.find(T_ALBEDO);
+            if (it != P.textures.end()) { const int f = g->images[it->second].format; P.base_alpha = f == F_R8G8B8A8 || f == F_B8G8R8A8 || f == F_R16G16B16A16; }
         }
         g->prims.push_back(std::move(P));
     }
@@ -415,6 +429,14 @@ int32_t art_glb_open(const char *path, int32_t normalize_vectors, int32_t coerce
 int32_t art_glb_close(ArtGlb *g) { delete g; return ART_OK; }
 
 int32_t art_glb_primitive_count(ArtGlb *g, uint32_t *n) { if (!g || !n) return gfail(ART_E_INVALID, "art_glb_primitive_count: null argument"); *n = (uint32_t)g->prims.size(); return ART_OK; }
+
+int32_t art_glb_primitive_alpha(ArtGlb *g, uint32_t primitive, int32_t *mode, float *cutoff, int32_t *base_color_has_alpha) {
+    if (!g || !mode || !cutoff || !base_color_has_alpha) return gfail(ART_E_INVALID, "art_glb_primitive_alpha: null argument");
+    if (primitive >= g->prims.size()) return gfail(ART_E_INVALID, "art_glb_primitive_alpha: no such primitive");
+    const Prim &P = g->prims[primitive];
+    *mode = P.alpha_mode; *cutoff = P.alpha_cutoff; *base_color_has_alpha = P.base_alpha ? 1 : 0;
+    return ART_OK;
+}
 
 // copy_model_data_to_ptr (:156-281).  dst == NULL: sizing pass.  infos: one ArtGlbCopyInfo per primitive (may be NULL).
 static int32_t glb_copy_impl(ArtGlb *g, uint32_t attr_mask, uint32_t tex_mask, void *dst, size_t cap, ArtGlbCopyInfo *infos, uint32_t n_infos, size_t *total) {

@@ -24,8 +24,10 @@ struct DevPrim {
     uint32_t first_tri, n_tri;
     float o2w[12];              // row-major 3x4
     float w2o[12];
-    uint32_t masked, pad_;      // a primitive that left the structure without a build (art_scene_set_primitive_enabled): its triangles are written "nowhere" by the next refit
+    uint32_t masked;            // a primitive that left the structure without a build (art_scene_set_primitive_enabled): its triangles are written "nowhere" by the next refit
+    float cutoff;               // alpha cutoff (art_scene_set_alpha_cutoff): > 0 discards a candidate whose layer-0 alpha is below it; 0 = opaque
 };
+static_assert(sizeof(DevPrim) == 144, "DevPrim layout");
 // "Nowhere": the point box at 3e38 that absent children of a 4-wide node have carried since round 1 -- no ray passes it in any form of the slab test (|t| >= 3e38 on
 // every axis).  A masked triangle's record is one, and a union skips such boxes (a node with nothing else below it is nowhere itself).
 constexpr float kNowhere = 3.0e38f;
@@ -236,6 +238,9 @@ struct FrameArgs {
     // cam_more[b - 1], and writes its outputs b * (W * H) pixels (color, depth, normal), b * n_local (pix_bits, hits) and
     // b * tiles_stride (color_tiles) further on.  A launch costs ~7 us of machine time whatever it traces (profiles/README.md r1o).
     uint32_t batch; uint32_t tiles_stride; CameraArg cam_more[3];   // tiles_stride: TEXELS between two frames' tiles
+    // alpha-masked primitives: alpha set = the instances with the alpha test (some enabled primitive has a cutoff > 0); alpha_bits: one bit per leaf
+    // position, set where the triangle's primitive may have a cutoff > 0 (a superset: the cutoff itself comes from `prims`, the frame's version of the table)
+    bool alpha; const uint32_t *alpha_bits;
 };
 constexpr uint32_t kMaxBatch = 4;
 void launch_primary(const FrameArgs &a, hipStream_t s);
@@ -262,7 +267,10 @@ constexpr uint32_t kAoTableEntriesPerSample = 64 * 64;
 void launch_ao_table(uint32_t spp, float4 *tab, hipStream_t s); // tab: spp * kAoTableEntriesPerSample float4
 // pix: 2 * n_local float4 of scratch (per-pixel origin | start node, normal | noise index); tab: launch_ao_table's; entry_search: start the rays below the root
 void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, float4 *pix, const float4 *tab, bool entry_search, uint32_t *ao, const uint32_t *lut, hipStream_t s);
-struct BvhView { const DevNode *nodes; const DevNode4 *wide; const DevTri *tris; int kind; TraceTune tune; }; // kind: 2 | 4
+struct BvhView { const DevNode *nodes; const DevNode4 *wide; const DevTri *tris; int kind; TraceTune tune;   // kind: 2 | 4
+                 bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool; };   // alpha: FrameArgs' (the queries' alpha test)
+// the bits of FrameArgs::alpha_bits: bit p of word p / 32 |= (prims[primitive of leaf p].cutoff > 0); never cleared between builds (art_build.hip)
+void launch_alpha_bits(uint32_t T, const uint32_t *leaf_gid, const uint32_t *tri_prim, const DevPrim *prims, uint32_t *bits, hipStream_t s);
 void launch_query_closest(const BvhView &b, const float4 *rays, uint32_t n, float4 *hits, uint32_t *cursors, hipStream_t s);
 void launch_query_any(const BvhView &b, const float4 *rays, uint32_t n, uint32_t *hit, uint32_t *cursors, hipStream_t s);
 // per-frame counter block (zeroed every frame): [64..] primary cursors, [64+256..] shadow cursors, [64+512..] query cursors,

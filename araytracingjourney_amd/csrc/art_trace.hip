@@ -45,6 +45,75 @@ __device__ __forceinline__ V3 xform_vec(const float *m, V3 p) {
     return mk((m[0] * p.x + m[1] * p.y) + m[2] * p.z, (m[4] * p.x + m[5] * p.y) + m[6] * p.z, (m[8] * p.x + m[9] * p.y) + m[10] * p.z);
 }
 
+// ------------------------------------------------------------------------------------------------ textures
+// sampler2DArray, linear / REPEAT, LOD 0 (no derivatives in a raygen stage): vk_rt_descriptor_set.rs:42-56
+__device__ __forceinline__ int wrapi(int i, int n) { int m = i % n; return m < 0 ? m + n : m; }
+// the four taps of a bilinear sample and its weights (texture_offset, tw, th: the primitive's texture in the pool) -- sample_tex's first lines, restated for the alpha
+// test: shared by a call, the default k_frame instances' register allocation moved (k_frame<true, true, false, false> 63 -> 64 VGPRs)
+__device__ __forceinline__ void tex_taps(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw_, uint32_t th_, int layer, float u, float v,
+                                         uint32_t &t00, uint32_t &t10, uint32_t &t01, uint32_t &t11, float &fx, float &fy) {
+    int tw = (int)tw_, th = (int)th_;
+    float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
+    float x0f = floorf(x), y0f = floorf(y);
+    fx = x - x0f; fy = y - y0f;
+    int x0 = wrapi((int)x0f, tw), y0 = wrapi((int)y0f, th);
+    int x1 = wrapi(x0 + 1, tw), y1 = wrapi(y0 + 1, th);
+    const uint32_t *base = pool + texture_offset + (size_t)layer * tw * th;
+    t00 = base[(size_t)y0 * tw + x0]; t10 = base[(size_t)y0 * tw + x1]; t01 = base[(size_t)y1 * tw + x0]; t11 = base[(size_t)y1 * tw + x1];
+}
+// channel c (byte c of the RGBA8 texels) of the bilinear sample
+__device__ __forceinline__ float tex_channel(uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11, float fx, float fy, int c) {
+    const float k = 1.0f / 255.0f;
+    float A = (float)((t00 >> (8 * c)) & 255u) * k, B = (float)((t10 >> (8 * c)) & 255u) * k;
+    float Cc = (float)((t01 >> (8 * c)) & 255u) * k, D = (float)((t11 >> (8 * c)) & 255u) * k;
+    float top = A * (1.0f - fx) + B * fx, bot = Cc * (1.0f - fx) + D * fx;
+    return top * (1.0f - fy) + bot * fy;
+}
+__device__ float4 sample_tex(const uint32_t *__restrict__ pool, const DevPrim &P, int layer, float u, float v) {
+    int tw = (int)P.tw, th = (int)P.th;
+    float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
+    float x0f = floorf(x), y0f = floorf(y);
+    float fx = x - x0f, fy = y - y0f;
+    int x0 = wrapi((int)x0f, tw), y0 = wrapi((int)y0f, th);
+    int x1 = wrapi(x0 + 1, tw), y1 = wrapi(y0 + 1, th);
+    const uint32_t *base = pool + P.texture_offset + (size_t)layer * tw * th;
+    uint32_t t00 = base[(size_t)y0 * tw + x0], t10 = base[(size_t)y0 * tw + x1], t01 = base[(size_t)y1 * tw + x0], t11 = base[(size_t)y1 * tw + x1];
+    float o[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) o[c] = tex_channel(t00, t10, t01, t11, fx, fy, c);
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+
+// ------------------------------------------------------------------------------------------------ alpha-masked primitives
+// A candidate that accept() takes is discarded when its primitive's cutoff c > 0 and alpha < c: alpha = byte 3 of texture layer 0, bilinear / REPEAT / LOD 0 at the
+// hit's texture coordinate, made with shade_surface's operations (a visible pixel's shading and its alpha test see the same uv).  Only the instances built with the
+// test (template parameter ALPHA) read any of this; the host picks them while some enabled primitive has c > 0.
+struct AlphaView {
+    const uint32_t *bits;        // one bit per leaf position: its primitive may have c > 0 (FrameArgs::alpha_bits)
+    const DevShadeTri *shade;    // the frame's version of the shading records (uv, primitive id) and of the primitive table (c)
+    const DevPrim *prims;
+    const uint32_t *tex;
+};
+// the alpha of the candidate (pos, u, v) of primitive prim_tex = {texture_offset, tw, th}; uv0..uv2 of its shading record
+__device__ __forceinline__ float alpha_at(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw, uint32_t th, float4 s2, float4 s3, float u, float v) {
+    float bx = 1.0f - u - v, by = u, bz = v;
+    float tu = (s2.y * bx + s2.w * by) + s3.y * bz, tv = (s2.z * bx + s3.x * by) + s3.z * bz;   // shade_surface's tu / tv
+    uint32_t t00, t10, t01, t11; float fx, fy;
+    tex_taps(pool, texture_offset, tw, th, 0, tu, tv, t00, t10, t01, t11, fx, fy);
+    return tex_channel(t00, t10, t01, t11, fx, fy, 3);
+}
+// per-ray walks: true = the candidate at leaf position pos is cut (its lane fetches the record, the cutoff and four texels only if the leaf's bit is set)
+__device__ __forceinline__ bool alpha_cut(const AlphaView &av, uint32_t pos, float u, float v) {
+    if (!((av.bits[pos >> 5] >> (pos & 31u)) & 1u)) return false;
+    const float4 *sq = reinterpret_cast<const float4 *>(av.shade + pos);
+    const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+    const DevPrim &P = av.prims[__float_as_uint(s8.z)];
+    const float c = P.cutoff;
+    if (!(c > 0.0f)) return false;
+    return alpha_at(av.tex, P.texture_offset, P.tw, P.th, s2, s3, u, v) < c;
+}
+
 // ------------------------------------------------------------------------------------------------ traversal
 struct Ray {
     V3 o, d;
@@ -153,7 +222,7 @@ __device__ __forceinline__ bool local_to_xy(uint32_t p, const uint32_t *__restri
 // Moeller-Trumbore block is ~150 instructions and, run whenever any single lane reaches a leaf, it was 60 % of all
 // issued instructions at ~2 % lane utilisation.
 constexpr int kOvfStack4 = 288; // 16 + 288 >= 3 pending siblings per level * 95 levels + 1
-template <bool ANY, int OVF, int LDSN = kLdsStack> struct TravBase {   // LDSN: entries of the per-lane stack that live in LDS
+template <bool ANY, int OVF, int LDSN = kLdsStack, bool ALPHA = false> struct TravBase {   // LDSN: entries of the per-lane stack that live in LDS; ALPHA: the alpha test
     Ray r;
     float tbest, bu, bv;
     uint32_t bpos, bgid;
@@ -175,8 +244,8 @@ template <bool ANY, int OVF, int LDSN = kLdsStack> struct TravBase {   // LDSN: 
         if (sp < LDSN) cur = lds[sp * kTraceBlock]; else cur = *(volatile int *)&ovf[sp - LDSN];
         return false;
     }
-    // accept() of DESIGN.md 1.1 for the triangle in `cur`: exact triangle-AABB slab, then Moeller-Trumbore
-    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf) {
+    // accept() of DESIGN.md 1.1 for the triangle in `cur`: exact triangle-AABB slab, then Moeller-Trumbore (and with ALPHA the alpha test of DESIGN.md 3.2)
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
         uint32_t pos = (uint32_t)~cur;
         // the reference of an ABSENT child of a 4-wide node (kAbsentChild: no leaf sits at position 2^31 - 1).  Its inverted box is left before it is entered by every
         // ray with a sign on every axis -- but a node scaled down to a point (a one-triangle tree, a node whose children were all masked) gives near == far on all three
@@ -190,10 +259,13 @@ template <bool ANY, int OVF, int LDSN = kLdsStack> struct TravBase {   // LDSN: 
         // the conjunction) would nearly always run; after the triangle test it runs for the few hits only.  Same accept().
         if (moller_trumbore(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v)) {
             if (slab(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te)) {
-                if (ANY) { bpos = pos; tbest = t; return true; }
-                float teff = fmaxf(t, te);
-                uint32_t gid = __float_as_uint(td.w);
-                if (teff < tbest || (teff == tbest && gid < bgid)) { tbest = teff; bu = u; bv = v; bpos = pos; bgid = gid; }
+                if (ANY) { if (!ALPHA || !alpha_cut(av, pos, u, v)) { bpos = pos; tbest = t; return true; } }
+                else {
+                    float teff = fmaxf(t, te);
+                    uint32_t gid = __float_as_uint(td.w);
+                    // (only a candidate that would win is tested: a cut one that would lose changes nothing)
+                    if ((teff < tbest || (teff == tbest && gid < bgid)) && (!ALPHA || !alpha_cut(av, pos, u, v))) { tbest = teff; bu = u; bv = v; bpos = pos; bgid = gid; }
+                }
             }
         }
         return pop(lds, ovf);
@@ -213,7 +285,7 @@ template <bool ANY, int OVF, int LDSN = kLdsStack> struct TravBase {   // LDSN: 
 };
 
 // 64-byte binary nodes (DevNode): both child boxes in full precision
-template <bool ANY> struct Trav : TravBase<ANY, kOvfStack> {
+template <bool ANY, bool ALPHA = false> struct Trav : TravBase<ANY, kOvfStack, kLdsStack, ALPHA> {
     using Nodes = const DevNode *;
     __device__ __forceinline__ bool step_internal(Nodes nodes, int *lds, int *ovf) {
         const float4 *nq = reinterpret_cast<const float4 *>(nodes + this->cur);
@@ -226,7 +298,7 @@ template <bool ANY> struct Trav : TravBase<ANY, kOvfStack> {
 };
 
 // 64-byte 4-wide quantised nodes (DevNode4)
-template <bool ANY, int LDSN = kLdsStack> struct Trav4 : TravBase<ANY, kOvfStack4 + (kLdsStack - LDSN), LDSN> {
+template <bool ANY, int LDSN = kLdsStack, bool ALPHA = false> struct Trav4 : TravBase<ANY, kOvfStack4 + (kLdsStack - LDSN), LDSN, ALPHA> {
     using Nodes = const DevNode4 *;
     __device__ __forceinline__ bool step_internal(Nodes wide, int *lds, int *ovf) {
         const uint4 *nq = reinterpret_cast<const uint4 *>(wide + this->cur);
@@ -335,7 +407,7 @@ __device__ unsigned long long g_packet_prof[24];   // + [8] shader-clock cycles 
 #else
 #define PPROF(i, n)
 #endif
-template <bool ANY, bool WIDE, int OCT, bool COUNT = false>
+template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false>
 __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps) {
     int cur = 0, sp = 0; // wave-uniform
     constexpr int kPop = kAbsentChild;
@@ -414,13 +486,29 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
             // tested this very box for the packet, so nearly every wave would pay for the slab, while few lanes survive the triangle test
             bool acc = moller_trumbore_flat(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v) && on;
             if (acc) acc = slab_oct<OCT>(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te);
+            // the alpha test: the triangle is wave-uniform, so its leaf bit, its shading record's uv and primitive id and that primitive's cutoff
+            // are scalar loads, made only when the bit is set and some lane took the candidate; then the lanes that did fetch their four texels
+            const auto alpha_keep = [&](bool cand) -> bool {
+                if (!ALPHA || ballot64(cand) == 0ull) return cand;
+                typedef __attribute__((address_space(4))) const uint32_t *Words;
+                if (!((((Words)(uintptr_t)a.alpha_bits)[pos >> 5] >> (pos & 31u)) & 1u)) return cand;
+                ConstQuads sq = const_quads(a.shade_tris + pos);
+                const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+                const Words P = (Words)(uintptr_t)(a.prims + __float_as_uint(s8.z));
+                const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
+                if (!(c > 0.0f)) return cand;
+                const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
+                if (cand) cand = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
+                return cand;
+            };
             // the ray state changes through selects, outside the divergent branches (no register copies around them)
-            if (ANY) { bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest; } // first accepted triangle: this lane is done
+            if (ANY) { if (ALPHA) acc = alpha_keep(acc); bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest; } // first accepted triangle: this lane is done
             else {
                 float teff;   // = fmaxf(t, te): one v_max_f32 (fmaxf first quiets both operands, which are the results of arithmetic here: two more instructions a step)
                 asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
                 uint32_t gid = __float_as_uint(td.w);
                 bool better = acc & ((teff < tbest) | ((teff == tbest) & (gid < bgid))); // (bitwise: three compares and three mask operations, no nested exec regions)
+                if (ALPHA) better = alpha_keep(better);   // (only a candidate that would win is tested: a cut one that would lose changes nothing)
                 tbest = better ? teff : tbest; bu = better ? u : bu; bv = better ? v : bv; bpos = better ? pos : bpos; bgid = better ? gid : bgid;
             }
 #ifdef ART_PACKET_PROF
@@ -447,7 +535,7 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
 }
 
 // one packet through the walk that fits its rays' direction signs
-template <bool ANY, bool WIDE, bool COUNT = false>
+template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false>
 __device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps) {
     uint64_t act = ballot64(on);
     if (act == 0ull) return;
@@ -456,15 +544,15 @@ __device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, 
     bool uniform = (nx == 0ull || nx == act) && (ny == 0ull || ny == act) && (nz == 0ull || nz == act);
     int oct = !uniform ? 8 : (nx ? 1 : 0) | (ny ? 2 : 0) | (nz ? 4 : 0);
     switch (oct) {
-    case 0: packet_walk<ANY, WIDE, 0, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 1: packet_walk<ANY, WIDE, 1, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 2: packet_walk<ANY, WIDE, 2, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 3: packet_walk<ANY, WIDE, 3, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 4: packet_walk<ANY, WIDE, 4, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 5: packet_walk<ANY, WIDE, 5, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 6: packet_walk<ANY, WIDE, 6, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 7: packet_walk<ANY, WIDE, 7, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    default: packet_walk<ANY, WIDE, 8, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 0: packet_walk<ANY, WIDE, 0, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 1: packet_walk<ANY, WIDE, 1, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 2: packet_walk<ANY, WIDE, 2, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 3: packet_walk<ANY, WIDE, 3, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 4: packet_walk<ANY, WIDE, 4, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 5: packet_walk<ANY, WIDE, 5, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 6: packet_walk<ANY, WIDE, 6, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 7: packet_walk<ANY, WIDE, 7, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    default: packet_walk<ANY, WIDE, 8, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
     }
 }
 
@@ -635,6 +723,7 @@ struct TraceArgs {
     const float *depth; const float4 *normal; uint32_t spp; float ao_radius; uint8_t *occl;
     const float4 *ao_pix;     // MODE_AO: per local pixel, origin | start node and world normal | Hilbert index (k_ao_pixels)
     const float4 *ao_tab;     // MODE_AO: [sample][Hilbert index] tangent-frame direction (k_ao_table)
+    AlphaView alpha;          // the instances with the alpha test only
 };
 
 #ifdef ART_TRACE_PROF
@@ -650,7 +739,7 @@ __device__ unsigned long long g_trace_prof[8];
 // finished it compacts the idle lanes with __ballot / mbcnt and hands them the next candidates of its chunk; chunks
 // come from eight per-XCD work cursors (one returning atomic per chunk), so neighbouring rays stay on one XCD's L2.
 // Every wave exits once all cursors are exhausted and its lanes are idle.
-template <int MODE, int WIDTH>
+template <int MODE, int WIDTH, bool ALPHA = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MODE == MODE_AO ? 8 : 4, 8))) void k_trace(TraceArgs a) {
     constexpr bool ANY = MODE == MODE_SHADOW || MODE == MODE_QUERY_ANY || MODE == MODE_AO;
     __shared__ int stack[kLdsStack * kTraceBlock];
@@ -664,7 +753,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
     uint32_t shards_left = 8;
     uint32_t cur = 0, end = 0; // wave-uniform: the unread part of this wave's chunk
     bool exhausted = false, active = false;
-    typename std::conditional<WIDTH == 4, Trav4<ANY>, Trav<ANY>>::type tr;
+    typename std::conditional<WIDTH == 4, Trav4<ANY, kLdsStack, ALPHA>, Trav<ANY, ALPHA>>::type tr;
     uint32_t slot = 0, traced = 0;
 #ifdef ART_TRACE_PROF
     unsigned long long prof_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -760,7 +849,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
         uint64_t lm = __ballot(on_leaf);
         if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || __ballot(active && !done && tr.cur >= 0) == 0ull)) {
             TPROF(3, 1); TPROF(4, __popcll(lm));
-            if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf);
+            if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf, a.alpha);
         }
         if (done) {
             active = false;
@@ -791,6 +880,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
 constexpr int kAoLds = 8;           // per-lane stack entries in LDS (AO rays start deep in the tree and are short: the walk rarely holds more; the rest spills)
 constexpr int kAoPoolFields = 11;   // o.xyz d.xyz inv.xyz entry slot
 constexpr uint32_t kAoPoolTake = 8; // idle lanes at which the wave turns to the pool (ArtTuning.trace_refill overrides)
+template <bool ALPHA = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_trace_ao(TraceArgs a) {
     __shared__ int stack[kAoLds * kTraceBlock];
     __shared__ float pool[kAoPoolFields][kTraceBlock];
@@ -804,7 +894,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
     uint32_t pool_n = 0;         // wave-uniform: rays in the pool
     bool exhausted = false, active = false;
-    Trav4<true, kAoLds> tr;
+    Trav4<true, kAoLds, ALPHA> tr;
     tr.r.tmin = a.ao_radius * 0.01f; tr.r.tmax = a.ao_radius;
     uint32_t slot = 0;
     for (;;) {
@@ -877,7 +967,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
             if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
         const bool on_leaf = active && !done && tr.cur < 0;
         const uint64_t lm = ballot64(on_leaf);
-        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf); }
+        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf, a.alpha); }
         if (done) { active = false; a.occl[slot] = tr.bpos != kNoHit ? 1 : 0; }
     }
 }
@@ -958,30 +1048,6 @@ __device__ float Burley_diffuse_local_sss(float a_, float NdotV, float nc_NdotV,
     float f90 = 0.5f + 2.0f * F_SS90;
     float diffuse = (1.0f - ratio) * F_Schlick1(1.0f, f90, nc_NdotL) * F_Schlick1(1.0f, f90, nc_NdotV);
     return NdotV * (diffuse + local_sss) * ART_INV_PI;
-}
-
-// ------------------------------------------------------------------------------------------------ textures
-// sampler2DArray, linear / REPEAT, LOD 0 (no derivatives in a raygen stage): vk_rt_descriptor_set.rs:42-56
-__device__ __forceinline__ int wrapi(int i, int n) { int m = i % n; return m < 0 ? m + n : m; }
-__device__ float4 sample_tex(const uint32_t *__restrict__ pool, const DevPrim &P, int layer, float u, float v) {
-    int tw = (int)P.tw, th = (int)P.th;
-    float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
-    float x0f = floorf(x), y0f = floorf(y);
-    float fx = x - x0f, fy = y - y0f;
-    int x0 = wrapi((int)x0f, tw), y0 = wrapi((int)y0f, th);
-    int x1 = wrapi(x0 + 1, tw), y1 = wrapi(y0 + 1, th);
-    const uint32_t *base = pool + P.texture_offset + (size_t)layer * tw * th;
-    uint32_t t00 = base[(size_t)y0 * tw + x0], t10 = base[(size_t)y0 * tw + x1], t01 = base[(size_t)y1 * tw + x0], t11 = base[(size_t)y1 * tw + x1];
-    const float k = 1.0f / 255.0f;
-    float o[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        float A = (float)((t00 >> (8 * c)) & 255u) * k, B = (float)((t10 >> (8 * c)) & 255u) * k;
-        float Cc = (float)((t01 >> (8 * c)) & 255u) * k, D = (float)((t11 >> (8 * c)) & 255u) * k;
-        float top = A * (1.0f - fx) + B * fx, bot = Cc * (1.0f - fx) + D * fx;
-        o[c] = top * (1.0f - fy) + bot * fy;
-    }
-    return make_float4(o[0], o[1], o[2], o[3]);
 }
 
 // ---- shading (raytrace.rgen.glsl:103-199), shared by the staged frame (k_shade) and the fused frame (k_frame) ---------
@@ -1149,7 +1215,7 @@ __device__ __forceinline__ uint64_t tick(float &dep) { uint64_t t; asm volatile(
 #else
 #define PHASE(i, dep)
 #endif
-template <bool WIDE, bool ONE_LIGHT, bool COUNT = false, bool BATCH = false>   // WIDE: the 128-byte 4-wide nodes (the default) | the 64-byte binary nodes
+template <bool WIDE, bool ONE_LIGHT, bool COUNT = false, bool BATCH = false, bool ALPHA = false>   // WIDE: the 128-byte 4-wide nodes (the default) | the 64-byte binary nodes; ALPHA: the alpha test
 __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_frame(FrameArgs a) {
     // One wave per workgroup: the waves of a frame are independent (nothing is shared, no barrier), and a workgroup of four held its LDS and its place
     // in the dispatcher's books until its slowest wave was done -- packets differ 25x in steps.  Single-wave groups: +2.5 % rays/s (profiles/README.md r2).
@@ -1182,7 +1248,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     PHASE(0, r.inv.x)
     float tbest = on ? r.tmax : -1.0f, bu = 0.f, bv = 0.f;
     uint32_t bpos = kNoHit, bgid = kNoHit;
-    walk_dispatch<false, WIDE, COUNT>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps);
+    walk_dispatch<false, WIDE, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps);
     PHASE(1, tbest)
     uint32_t p, x, y; bool mine;
     frame_pixel(a, wid, p, x, y, mine);
@@ -1216,7 +1282,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         PHASE(3, sr.inv.x)
         float st = son ? sr.tmax : -1.0f, su = 0.f, sv = 0.f;
         uint32_t spos = kNoHit, sgid = kNoHit;
-        walk_dispatch<true, WIDE, COUNT>(a, sr, son, stk, st, su, sv, spos, sgid, steps);
+        walk_dispatch<true, WIDE, COUNT, ALPHA>(a, sr, son, stk, st, su, sv, spos, sgid, steps);
         PHASE(4, st)
         if (want && spos != kNoHit) { // shadowed: the light keeps 0.05 of its contribution (raytrace.rgen.glsl:179-181)
             c4 = make_float4(c4.x * 0.05f, c4.y * 0.05f, c4.z * 0.05f, c4.w);
@@ -1411,18 +1477,22 @@ static inline uint32_t persistent_blocks(uint32_t total, const Tune &t) {
     uint32_t need = (total + kTraceBlock - 1) / kTraceBlock, cap = t.blocks * (kBlock / kTraceBlock);   // the presets count 256-thread blocks
     return need < cap ? (need ? need : 1u) : cap;
 }
-template <int MODE> static void launch_trace(TraceArgs &a, int kind, bool pipelined, const TraceTune &o, hipStream_t s) {
+// alpha: the instances with the alpha test (a.alpha set up by the caller)
+template <int MODE> static void launch_trace(TraceArgs &a, int kind, bool pipelined, const TraceTune &o, bool alpha, hipStream_t s) {
     const Tune t = tune(pipelined, MODE == MODE_AO, o);
     uint32_t nb = persistent_blocks(a.total, t);
     a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch;
-    if (kind == 4) k_trace<MODE, 4><<<nb, kTraceBlock, 0, s>>>(a);
+    if (alpha) { if (kind == 4) k_trace<MODE, 4, true><<<nb, kTraceBlock, 0, s>>>(a); else k_trace<MODE, 2, true><<<nb, kTraceBlock, 0, s>>>(a); }
+    else if (kind == 4) k_trace<MODE, 4><<<nb, kTraceBlock, 0, s>>>(a);
     else k_trace<MODE, 2><<<nb, kTraceBlock, 0, s>>>(a);
 }
+static AlphaView alpha_view(const FrameArgs &f) { return AlphaView{f.alpha_bits, f.shade_tris, f.prims, f.tex_pool}; }
 void launch_primary(const FrameArgs &f, hipStream_t s) {   // staged frames: the persistent per-ray tracer
     TraceArgs a{};
     a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = f.n_local; a.cursors = f.counters + 64; a.cam = f.cam; a.W = f.W; a.H = f.H;
     a.tile_list = f.tile_list; a.tiles_x = f.tiles_x; a.hits = f.hits;
-    launch_trace<MODE_PRIMARY>(a, f.trace_kind[0], f.pipelined, f.tune, s);
+    a.alpha = alpha_view(f);
+    launch_trace<MODE_PRIMARY>(a, f.trace_kind[0], f.pipelined, f.tune, f.alpha, s);
 }
 void launch_shade(const FrameArgs &a, hipStream_t s) { k_shade<<<blocks_for(a.n_local), kBlock, 0, s>>>(a); }
 void launch_shadow(const FrameArgs &f, hipStream_t s) {
@@ -1430,21 +1500,25 @@ void launch_shadow(const FrameArgs &f, hipStream_t s) {
     TraceArgs a{};
     a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = f.n_local * f.n_lights; a.cursors = f.counters + 64 + 8 * kCursorStride; a.count = f.counters + kShadowSlots;
     a.rays = f.shadow_rays; a.contrib = f.contrib; a.n_local = f.n_local; a.shadow_bits = f.shadow_bits;
-    launch_trace<MODE_SHADOW>(a, f.trace_kind[1], f.pipelined, f.tune, s);
+    a.alpha = alpha_view(f);
+    launch_trace<MODE_SHADOW>(a, f.trace_kind[1], f.pipelined, f.tune, f.alpha, s);
 }
-template <bool WIDE, bool ONE_LIGHT> static void launch_frame_form(const FrameArgs &a, uint32_t g, bool count, hipStream_t s) {
+template <bool WIDE, bool ONE_LIGHT, bool ALPHA = false> static void launch_frame_form(const FrameArgs &a, uint32_t g, bool count, hipStream_t s) {
     if (a.batch > 1) { // several frames per launch
         const dim3 gb(g, a.batch);
-        if (count) k_frame<WIDE, ONE_LIGHT, true, true><<<gb, kFrameBlock, 0, s>>>(a); else k_frame<WIDE, ONE_LIGHT, false, true><<<gb, kFrameBlock, 0, s>>>(a);
-    } else if (count) k_frame<WIDE, ONE_LIGHT, true><<<g, kFrameBlock, 0, s>>>(a);
-    else k_frame<WIDE, ONE_LIGHT><<<g, kFrameBlock, 0, s>>>(a);
+        if (count) k_frame<WIDE, ONE_LIGHT, true, true, ALPHA><<<gb, kFrameBlock, 0, s>>>(a); else k_frame<WIDE, ONE_LIGHT, false, true, ALPHA><<<gb, kFrameBlock, 0, s>>>(a);
+    } else if (count) k_frame<WIDE, ONE_LIGHT, true, false, ALPHA><<<g, kFrameBlock, 0, s>>>(a);
+    else k_frame<WIDE, ONE_LIGHT, false, false, ALPHA><<<g, kFrameBlock, 0, s>>>(a);
 }
 bool launch_frame(const FrameArgs &a, hipStream_t s) { // returns whether the launch wrote a.wave_cost
     const uint32_t g = a.n_wave_items;   // one workgroup per wave item
     if (g == 0) return false;
     const bool one = a.n_lights == 1;
     const bool count = a.wave_cost != nullptr && a.n_lights > 0; // a sampled frame of the wave plan: the step-counting instances
-    if (a.packet_wide) { if (one) launch_frame_form<true, true>(a, g, count, s); else launch_frame_form<true, false>(a, g, count, s); }
+    if (a.alpha) {   // some enabled primitive has an alpha cutoff: the instances with the alpha test
+        if (a.packet_wide) { if (one) launch_frame_form<true, true, true>(a, g, count, s); else launch_frame_form<true, false, true>(a, g, count, s); }
+        else { if (one) launch_frame_form<false, true, true>(a, g, count, s); else launch_frame_form<false, false, true>(a, g, count, s); }
+    } else if (a.packet_wide) { if (one) launch_frame_form<true, true>(a, g, count, s); else launch_frame_form<true, false>(a, g, count, s); }
     else { if (one) launch_frame_form<false, true>(a, g, count, s); else launch_frame_form<false, false>(a, g, count, s); }
     return count;
 }
@@ -1455,13 +1529,15 @@ void launch_query_closest(const BvhView &b, const float4 *rays, uint32_t n, floa
     if (!n) return;
     TraceArgs a{};
     a.nodes = b.nodes; a.wide = b.wide; a.tris = b.tris; a.total = n; a.cursors = cursors; a.rays = rays; a.hits = hits;
-    launch_trace<MODE_QUERY_CLOSEST>(a, b.kind, false, b.tune, s);
+    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool};
+    launch_trace<MODE_QUERY_CLOSEST>(a, b.kind, false, b.tune, b.alpha, s);
 }
 void launch_query_any(const BvhView &b, const float4 *rays, uint32_t n, uint32_t *hit, uint32_t *cursors, hipStream_t s) {
     if (!n) return;
     TraceArgs a{};
     a.nodes = b.nodes; a.wide = b.wide; a.tris = b.tris; a.total = n; a.cursors = cursors; a.rays = rays; a.any_out = hit;
-    launch_trace<MODE_QUERY_ANY>(a, b.kind, false, b.tune, s);
+    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool};
+    launch_trace<MODE_QUERY_ANY>(a, b.kind, false, b.tune, b.alpha, s);
 }
 // AO resolve: occluded count -> uint(pow(visibility, 2.2) * 255 + 0.5) through a host-built table; 255 where nothing was hit
 #ifdef ART_PACKET_PROF
@@ -1507,13 +1583,14 @@ void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, fl
     TraceArgs a{};
     a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = n_slots; a.cursors = f.counters + 64 + 16 * kCursorStride; a.cam = f.cam; a.W = f.W; a.H = f.H;
     a.tile_list = f.tile_list; a.tiles_x = f.tiles_x; a.depth = f.depth; a.normal = f.normal; a.spp = spp; a.ao_radius = radius; a.occl = occl;
-    a.ao_pix = pix; a.ao_tab = tab;
+    a.ao_pix = pix; a.ao_tab = tab; a.alpha = alpha_view(f);
     if (f.trace_kind[2] == 4) {   // the default: the AO launch's own tracer (rays made by the whole wave into a pool); 6 = the same walk through the generic tracer (round 3's form), 2 = binary nodes
         Tune t = tune(f.pipelined, true, f.tune);
         if (!(f.tune.refill >= 1 && f.tune.refill <= 64)) t.refill = kAoPoolTake;
         a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch;
-        k_trace_ao<<<persistent_blocks(a.total, t), kTraceBlock, 0, s>>>(a);
-    } else launch_trace<MODE_AO>(a, f.trace_kind[2] == 6 ? 4 : f.trace_kind[2], f.pipelined, f.tune, s);
+        if (f.alpha) k_trace_ao<true><<<persistent_blocks(a.total, t), kTraceBlock, 0, s>>>(a);
+        else k_trace_ao<<<persistent_blocks(a.total, t), kTraceBlock, 0, s>>>(a);
+    } else launch_trace<MODE_AO>(a, f.trace_kind[2] == 6 ? 4 : f.trace_kind[2], f.pipelined, f.tune, f.alpha, s);
     k_ao_resolve<<<blocks_for(f.n_local), kBlock, 0, s>>>(f, occl, spp, l, ao);
 }
 void launch_untile(const float4 *gathered, const uint32_t *tile_slot, uint32_t shard_stride, uint32_t n_frames, uint32_t frame_stride, uint32_t W, uint32_t H, float4 *frame, hipStream_t s) {

@@ -155,6 +155,14 @@ struct Model { // VkModel: only Device models are instanced in the acceleration 
         object_sphere = sp;
         model_bounding_sphere = object_sphere.transform(model_matrix);
     }
+    // Alpha-masked primitive (glTF alphaMode MASK; Vulkan: non-opaque geometry whose any-hit shader ignores the intersection when alpha < cutoff; the reference
+    // marks all its geometry opaque, vk_model.rs:927): a hit on primitive primitive_ids[primitive_index] is discarded for every ray where the alpha of its texture
+    // layer 0 is below `cutoff`; 0 is opaque, cutoff must lie in [0, 1].  Nothing is built: the next frame takes it up (art_scene_set_alpha_cutoff).
+    void set_alpha_cutoff(size_t primitive_index, float cutoff) {
+        if (primitive_index >= primitive_ids.size()) throw Panic(ART_E_INVALID, "Model::set_alpha_cutoff: no such primitive");
+        if (!(cutoff >= 0.0f && cutoff <= 1.0f)) throw Panic(ART_E_INVALID, "Model::set_alpha_cutoff: the cutoff must lie in [0, 1]");
+        if (ctx) check(art_scene_set_alpha_cutoff(ctx, primitive_ids[primitive_index], cutoff));
+    }
     const Matrix3x4 &get_transform_model_matrix() const { return model_matrix; } // vk_model.rs:358-363
     void update_model_status(const Vector3 &camera_pos) { // vk_model.rs:334-345
         float d = model_bounding_sphere.get_distance_from_point(camera_pos);
@@ -178,7 +186,9 @@ public:
     }
     Renderer(const Renderer &) = delete;
     ~Renderer() { if (ctx_) art_destroy(ctx_); }
-    void add_model(const std::string &file_path, const Matrix3x4 &model_matrix) { // renderer.rs:346 -> vk_model.rs:494-528
+    // alpha_mask (opt-in; the reference draws every material opaque): every primitive whose material is alphaMode MASK and whose base-colour image has an alpha
+    // channel gets its alphaCutoff (Model::set_alpha_cutoff).  An RGB image is coerced with alpha 0 and is never masked; BLEND is drawn opaque.
+    void add_model(const std::string &file_path, const Matrix3x4 &model_matrix, bool alpha_mask = false) { // renderer.rs:346 -> vk_model.rs:494-528
         GltfModelReader r = GltfModelReader::open(file_path, true, GltfModelReader::B8G8R8A8_UNORM);
         uint32_t first = 0, n = 0;
         check_glb(art_scene_add_glb(ctx_, r.handle(), model_matrix.data(), &first, &n));
@@ -199,6 +209,12 @@ public:
         Sphere sp; sp.center = cs.first; sp.radius = cs.second;
         m.object_sphere = sp;
         m.model_bounding_sphere = sp.transform(model_matrix);
+        if (alpha_mask)
+            for (uint32_t i = 0; i < n; i++) {
+                int32_t mode = 0, has_alpha = 0; float cutoff = 0.5f;
+                check_glb(art_glb_primitive_alpha(r.handle(), i, &mode, &cutoff, &has_alpha));
+                if (mode == 1 && has_alpha) m.set_alpha_cutoff(i, std::fmin(std::fmax(cutoff, 0.0f), 1.0f));
+            }
         models_.push_back(m);
     }
     std::vector<Model> &models_mut() { return models_; }

@@ -37,6 +37,13 @@ class GltfModelReader:
         _check(self._L.art_glb_primitive_count(self._h, C.byref(n)))
         return n.value
 
+    def primitive_alpha(self, primitive):
+        """(mode, cutoff, base_color_has_alpha) of a primitive's material: mode 0 OPAQUE, 1 MASK, 2 BLEND (alphaMode); cutoff = alphaCutoff (0.5 by default);
+        whether the base-colour image as decoded had an alpha channel (art_glb_primitive_alpha)"""
+        mode, cutoff, has = C.c_int32(), C.c_float(), C.c_int32()
+        _check(self._L.art_glb_primitive_alpha(self._h, primitive, C.byref(mode), C.byref(cutoff), C.byref(has)))
+        return mode.value, cutoff.value, bool(has.value)
+
     def copy_model_data_to_ptr(self, mesh_attributes, textures, copy=True):  # gltf_model_reader.rs:156-281
         n = self.primitive_count()
         infos = (ArtGlbCopyInfo * max(1, n))()

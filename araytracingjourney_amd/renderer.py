@@ -253,6 +253,23 @@ class Model:
         m = self.model_matrix if self.model_matrix is not None else np.eye(3, 4, dtype=np.float32)
         self.model_bounding_sphere = self._object_sphere.transform(m)
 
+    def set_alpha_cutoff(self, primitive_index, cutoff):
+        """Alpha-masked primitive (glTF alphaMode MASK; Vulkan: non-opaque geometry whose any-hit shader ignores the intersection when alpha < cutoff; the
+        reference marks all its geometry opaque, vk_model.rs:927): a hit on primitive `primitive_ids[primitive_index]` is discarded for every ray -- primary,
+        shadow, AO, queries -- where the alpha of its texture layer 0 is below `cutoff`.  0 is opaque (the default); cutoff must lie in [0, 1].  Nothing is
+        built: the next frame takes it up (art_scene_set_alpha_cutoff)."""
+        if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float, np.floating, np.integer)):
+            raise TypeError("cutoff must be a number")
+        c = float(cutoff)
+        if not 0.0 <= c <= 1.0:   # (NaN too)
+            raise ValueError("cutoff must lie in [0, 1]")
+        if isinstance(primitive_index, bool) or not isinstance(primitive_index, (int, np.integer)):
+            raise TypeError("primitive_index must be an integer")
+        if not 0 <= primitive_index < len(self.primitive_ids):
+            raise IndexError("primitive_index out of range")
+        if self._renderer is not None:
+            check(self._renderer._L.art_scene_set_alpha_cutoff(self._renderer._ctx, self.primitive_ids[primitive_index], c))
+
     def get_transform_model_matrix(self):           # vk_model.rs:358-363
         return None if self.model_matrix is None else self.model_matrix.copy()
 
@@ -319,8 +336,10 @@ class Renderer:
         self._models.append(Model(ids, sp.transform(mm), renderer=self, model_matrix=mm, object_sphere=sp, positions=positions))
         return ids
 
-    def add_model_glb(self, reader, model_matrix):
-        """renderer.rs:346 with a GltfModelReader (opened with normalize + B8G8R8A8 coercion like vk_model.rs:498-504)"""
+    def add_model_glb(self, reader, model_matrix, alpha_mask=False):
+        """renderer.rs:346 with a GltfModelReader (opened with normalize + B8G8R8A8 coercion like vk_model.rs:498-504).
+        alpha_mask=True (opt-in; the reference draws every material opaque): every primitive whose material is alphaMode MASK and whose base-colour image has
+        an alpha channel gets its alphaCutoff (Model.set_alpha_cutoff).  An RGB image is coerced with alpha 0 and is never masked; BLEND is drawn opaque."""
         first, n = C.c_uint32(), C.c_uint32()
         m = np.ascontiguousarray(model_matrix, dtype=np.float32)
         r = self._L.art_scene_add_glb(self._ctx, reader._h, _ptr(m), C.byref(first), C.byref(n))
@@ -331,7 +350,13 @@ class Renderer:
         from .model_reader import VERTICES
         data, infos = reader.copy_model_data_to_ptr(VERTICES, 0)   # the positions alone (12 B a vertex), for Model.set_vertices' sphere
         positions = [data[i.mesh_buffer_offset:i.mesh_buffer_offset + i.mesh_size].view(np.float32).reshape(-1, 3) for i in infos]
-        self._models.append(Model(ids, Sphere(c, rad).transform(model_matrix), renderer=self, model_matrix=model_matrix, object_sphere=Sphere(c, rad), positions=positions))
+        model = Model(ids, Sphere(c, rad).transform(model_matrix), renderer=self, model_matrix=model_matrix, object_sphere=Sphere(c, rad), positions=positions)
+        self._models.append(model)
+        if alpha_mask:
+            for i in range(len(ids)):
+                mode, cutoff, has_alpha = reader.primitive_alpha(i)
+                if mode == 1 and has_alpha:
+                    model.set_alpha_cutoff(i, min(max(cutoff, 0.0), 1.0))
         return ids
 
     def models_mut(self):

@@ -2,6 +2,7 @@
 //   host_mirror_demo check            host-only checks (no GPU): light order, camera block, panic-on-error behaviour
 //   host_mirror_demo render <file.glb> [W H]   add_model + lights of main.rs + one frame; prints ray counts and a colour checksum
 //   host_mirror_demo deform <file.glb> [W H]   the same scene; then Model::set_vertices on its first primitive (grown from the origin) and back
+//   host_mirror_demo alpha <file.glb> [W H]    the same scene with add_model(..., alpha_mask = true), with the cutoffs set by hand, and opaque
 #include <cstdio>
 #include <cstring>
 #include "../araytracingjourney_amd/host/art_renderer.hpp"
@@ -119,7 +120,45 @@ int main(int argc, char **argv) {
                         (int)(std::memcmp(back.data(), c.data(), c.size() * sizeof(float)) == 0), r0, r1, r2);
             return 0;
         }
-        std::puts("usage: host_mirror_demo check | render <file.glb> [W H] | deform <file.glb> [W H]");
+        if (argc >= 3 && !std::strcmp(argv[1], "alpha")) {
+            // alpha-masked primitives: the model added with alpha_mask (MASK materials whose base colour has alpha get their alphaCutoff), the same model with the
+            // cutoffs set by hand from the reader, and the model as the reference draws it (opaque): the first two frames are equal bit for bit, the third differs
+            uint32_t W = argc >= 5 ? (uint32_t)std::atoi(argv[3]) : 800, H = argc >= 5 ? (uint32_t)std::atoi(argv[4]) : 800;
+            std::vector<std::pair<uint32_t, float>> by_hand;
+            {
+                art::GltfModelReader r = art::GltfModelReader::open(argv[2], true, art::GltfModelReader::B8G8R8A8_UNORM);
+                uint32_t n = 0; art::check_glb(art_glb_primitive_count(r.handle(), &n));
+                for (uint32_t i = 0; i < n; i++) {
+                    int32_t mode = 0, has = 0; float c = 0.f;
+                    art::check_glb(art_glb_primitive_alpha(r.handle(), i, &mode, &c, &has));
+                    if (mode == 1 && has) by_hand.push_back({i, c});
+                }
+            }
+            auto frame = [&](int how, ArtStats &st) {   // 0: alpha_mask, 1: by hand, 2: opaque
+                art::Renderer renderer(W, H);
+                renderer.add_model(argv[2], {2, 0, 0, 0, 0, 2, 0, 0, 0, 0, 2, 0}, how == 0);
+                renderer.lights_mut().get_spot_lights_mut().push_back(art::SpotLight({0.0f, 1.5f, 0.0f}, {0.0f, -1.0f, 0.0f}, {13.6f, 1.6f, 22.2f}, 3.0f, {0.5236f, 0.7854f}, true));
+                renderer.lights_mut().get_point_lights_mut().push_back(art::PointLight({0.0f, 0.5f, -1.5f}, {8, 8, 8}, 6.0f, true));
+                renderer.camera_mut().set_pos({0.0f, 0.3f, -2.5f});
+                renderer.prepare_first_frame();
+                if (how == 1) for (auto &bh : by_hand) renderer.models_mut()[0].set_alpha_cutoff(bh.first, bh.second);
+                renderer.render_frame();
+                renderer.compute_ao();
+                st = renderer.stats();
+                std::vector<float> c = renderer.color_output(), d = renderer.depth_output();
+                std::vector<uint32_t> ao = renderer.ao_output();
+                std::vector<uint8_t> all(c.size() * 4 + d.size() * 4 + ao.size() * 4);
+                std::memcpy(all.data(), c.data(), c.size() * 4); std::memcpy(all.data() + c.size() * 4, d.data(), d.size() * 4); std::memcpy(all.data() + c.size() * 4 + d.size() * 4, ao.data(), ao.size() * 4);
+                return all;
+            };
+            ArtStats s0, s1, s2;
+            std::vector<uint8_t> masked = frame(0, s0), hand = frame(1, s1), opaque = frame(2, s2);
+            std::printf("ALPHA_OK masked_prims=%zu masked_equals_by_hand=%d differs_from_opaque=%d hit_masked=%llu hit_opaque=%llu shadow_masked=%llu shadow_opaque=%llu rebuilds=%u\n", by_hand.size(),
+                        (int)(masked == hand), (int)(masked != opaque), (unsigned long long)s0.hit_pixels, (unsigned long long)s2.hit_pixels, (unsigned long long)s0.shadow_rays,
+                        (unsigned long long)s2.shadow_rays, s1.rebuilds);
+            return 0;
+        }
+        std::puts("usage: host_mirror_demo check | render <file.glb> [W H] | deform <file.glb> [W H] | alpha <file.glb> [W H]");
         return 2;
     } catch (const art::Panic &p) {
         std::printf("PANIC(%d): %s\n", p.code, p.what());

@@ -153,6 +153,13 @@ int32_t art_scene_clear(ArtContext *ctx);
  * of a scene built without / with it, bit for bit; its device arrays stay until the next art_scene_build.  A primitive that was disabled when the scene was built
  * (never uploaded) needs art_scene_build to appear: art_scene_needs_build says which case the context is in. */
 int32_t art_scene_set_primitive_enabled(ArtContext *ctx, uint32_t primitive_id, int32_t enabled);
+/* Alpha-masked primitives (glTF alphaMode MASK; in Vulkan terms non-opaque geometry whose any-hit shader ignores the intersection when alpha < cutoff): a candidate
+ * hit on primitive `primitive_id` is discarded when cutoff > 0 and the alpha of its texture layer 0 (byte 3, bilinear / REPEAT / LOD 0 at the hit's texture coordinate,
+ * the sampler of the shading) is below cutoff -- for every ray: primary, shadow (a cut texel lets the light through), AO and both queries.  0 (the default) is opaque.
+ * May be called at any time; on a built scene nothing is built: the NEXT art_trace (or query) takes it up, as for art_scene_set_primitive_enabled, and frames in flight
+ * keep the cutoffs they were launched with.  NaN, a value outside [0, 1], an unknown id or a null context is ART_E_INVALID and changes nothing.  Scenes in which no
+ * enabled primitive has a cutoff > 0 run the kernels without the test.  Every rank of an art_mgpu job must make the same calls.  DESIGN.md 3.2. */
+int32_t art_scene_set_alpha_cutoff(ArtContext *ctx, uint32_t primitive_id, float cutoff);
 /* 1: the next art_trace would fail with ART_E_STATE until art_scene_build has run (primitives added, or enabled that the last build did not contain); 0: it would not */
 int32_t art_scene_needs_build(const ArtContext *ctx);
 /* VkModel::set_model_matrix (vk_model.rs:461-466) -> get_transform_model_matrix (:358-363) -> the instance record of the per-frame TLAS
@@ -345,6 +352,9 @@ const char *art_glb_last_error(void);
 int32_t art_glb_open(const char *path, int32_t normalize_vectors, int32_t coerce_format, ArtGlb **out);
 int32_t art_glb_close(ArtGlb *glb);
 int32_t art_glb_primitive_count(ArtGlb *glb, uint32_t *n);
+/* the material of a primitive: mode 0 OPAQUE, 1 MASK, 2 BLEND (alphaMode); cutoff = alphaCutoff (0.5 by default); base_color_has_alpha = the base-colour image as
+ * decoded has an alpha channel (1) or not (0: a coerced image gets alpha 0 in every texel).  art_scene_add_glb applies none of it (art_scene_set_alpha_cutoff does). */
+int32_t art_glb_primitive_alpha(ArtGlb *glb, uint32_t primitive, int32_t *mode, float *cutoff, int32_t *base_color_has_alpha);
 /* copy_model_data_to_ptr (:156-281): dst NULL = sizing pass; *total = bytes the copy needs */
 int32_t art_glb_copy_model_data(ArtGlb *glb, uint32_t attr_mask, uint32_t tex_mask, void *dst, size_t cap, ArtGlbCopyInfo *infos,
                                 uint32_t n_infos, size_t *total);
