@@ -210,6 +210,13 @@ struct ArtContext {
     DevBuf<uint32_t> d_tile_slot;   // un-tile table: tile -> owner << 24 | index among the owner's tiles (every shard's layout, setup_frame)
     DevBuf<uint32_t> d_block_order; // launch block -> 256-pixel block of the frame: one L2 (XCD) per screen region (setup_frame)
     WavePlan plan;                  // fused frame: wave -> (8x8 block, cells)
+    // Shadow-occluder hints of the fused frame's any-hit packet walks (FrameArgs::hints): ONE table for the context -- not one per ring slot: the frames in
+    // flight feed each other -- of (n_local / 64) * kHintLights entries of four leaf positions.  All 0xFF (empty) after setup_frame (allocation, resize) and after every
+    // art_scene_build (leaf positions change; the build the refit's cost rule starts is one); both run with nothing in flight.  Refits, moves, deformations, enable / disable,
+    // cameras and lights leave it alone: leaf positions survive them and every hint is tested against the frame's own triangles.
+    DevBuf<uint32_t> d_hints;
+    bool shadow_hints = true;       // ArtTuning.shadow_hints = 1 turns them off: the frames get a null table
+    size_t hint_words() const { return (size_t)(n_local / 64u) * kHintLights * 4u; }
     static constexpr int kRing = 128;          // per-frame stage events kept for art_collect_timings
     hipEvent_t ev[kRing][5] = {};
     bool ev_fused[kRing] = {};                 // the frame was one launch: only ev[0] and ev[4] were recorded
@@ -709,6 +716,7 @@ int32_t setup_frame(ArtContext *c) {
     {
         int32_t pr = plan_reset(c); if (pr) return pr;
     }
+    HIPC(c->d_hints.ensure(c->hint_words())); HIPC(hipMemset(c->d_hints.p, 0xFF, c->d_hints.n * 4));   // the blocks are other pixels now: every entry empty
     for (uint32_t k = 0; k < c->F; k++) {
         FrameSlot &S = c->slot[k];
         HIPC(S.d_wave_cost.ensure(c->plan.cap ? c->plan.cap : 1));
@@ -856,7 +864,7 @@ int32_t art_destroy(ArtContext *c) {
     as_release(c);
     lbvh_free(c->bvh); c->arena.release();
     c->d_verts.release(); c->d_indices.release(); c->d_tex.release(); c->d_prims.release(); c->d_first_tri.release(); c->d_ao_tab.release();
-    c->d_tile_list.release(); c->d_tile_xy.release(); c->d_tile_slot.release(); c->d_block_order.release(); c->plan.release();
+    c->d_tile_list.release(); c->d_tile_xy.release(); c->d_tile_slot.release(); c->d_block_order.release(); c->d_hints.release(); c->plan.release();
     for (uint32_t k = 0; k < kMaxFrames; k++) {
         c->slot[k].release();
         if (c->slot[k].done) (void)hipEventDestroy(c->slot[k].done);
@@ -889,6 +897,7 @@ int32_t art_set_tuning(ArtContext *c, const ArtTuning *t) {
     c->fast_trace = !(c->cfg.flags & ART_FLAG_FAST_BUILD);
     c->tree_builder = t->tree_builder == 1 ? 1 : 3;
     c->packet_wide = t->packet_wide != 2;   // 0: the default (4-wide), 1: 4-wide, 2: binary
+    c->shadow_hints = t->shadow_hints == 0;
     c->macro = t->block_order == 0 ? 2u : (t->block_order == 1 ? 0u : t->block_order);
     c->ao_entry = t->ao_entry_off == 0;
     c->wide_on_host = t->wide_builder == 1;
@@ -1158,6 +1167,8 @@ int32_t art_scene_build(ArtContext *c) {
         bool cut = false;
         for (const DevPrim &d : dp) cut = cut || (d.n_tri > 0 && d.cutoff > 0.0f);
         if (cut) { launch_alpha_bits(T, c->bvh.leaf_gid, c->bvh.tri_prim, c->d_prims.p, c->d_alpha_bits.p, c->main_stream()); HIPC(hipGetLastError()); }
+        // the shadow-occluder hints are leaf positions of the tree that just went away: all empty (nothing is in flight -- sync_all above -- and the wait below is in front of every later frame)
+        if (c->d_hints.p) HIPC(hipMemsetAsync(c->d_hints.p, 0xFF, c->d_hints.n * 4, c->main_stream()));
         HIPC(hipStreamSynchronize(c->main_stream()));
         c->alpha_bits_stale = false;
         alpha_refresh_live(c);
@@ -1307,6 +1318,7 @@ static FrameArgs make_frame_args(ArtContext *c, FrameSlot &S, uint32_t version) 
     for (uint32_t i = 0; i + 1 < kMaxBatch; i++) std::memcpy(&a.cam_more[i], &c->cam_more[i], sizeof(ArtCamera));
     a.tile_xy = c->d_tile_xy.p; a.wave_items = c->plan.d_items[c->plan.cur].p; a.n_wave_items = c->plan.n_items[c->plan.cur]; a.wave_cost = nullptr; // art_trace sets it for the frames the wave plan samples
     a.alpha = c->alpha_live; a.alpha_bits = c->d_alpha_bits.p;   // (art_trace_ao: the frame's own choice, FrameSlot::alpha)
+    a.hints = c->shadow_hints ? c->d_hints.p : nullptr; a.hint_leaves = c->T;
     return a;
 }
 
@@ -1829,6 +1841,27 @@ int32_t art_read_shadow_bits(ArtContext *c, uint32_t *bits, size_t n_pixels) {
         if (x >= c->W || y >= c->H) continue;
         bits[(size_t)y * c->W + x] = sb[p];
     }
+    return ART_OK;
+}
+
+// the context's table of shadow-occluder hints (FrameArgs::hints): words = 4 * kHintLights * (local pixels / 64), entry (block b, light slot l) at 16 * b + 4 * l
+int32_t art_read_shadow_hints(ArtContext *c, uint32_t *words, size_t n_words) {
+    if (!c || !words) return fail(ART_E_INVALID, "art_read_shadow_hints: null argument");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    if (!c->frame_ready) return fail(ART_E_STATE, "art_read_shadow_hints: no frame layout yet (art_trace)");
+    if (n_words != c->hint_words()) return fail(ART_E_INVALID, "art_read_shadow_hints: size mismatch");
+    if (n_words) HIPC(hipMemcpy(words, c->d_hints.p, n_words * 4, hipMemcpyDeviceToHost));
+    return ART_OK;
+}
+int32_t art_write_shadow_hints(ArtContext *c, const uint32_t *words, size_t n_words) {   // tests only: any content is a legal table
+    if (!c || !words) return fail(ART_E_INVALID, "art_write_shadow_hints: null argument");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    if (!c->frame_ready) return fail(ART_E_STATE, "art_write_shadow_hints: no frame layout yet (art_trace)");
+    if (n_words != c->hint_words()) return fail(ART_E_INVALID, "art_write_shadow_hints: size mismatch");
+    if (n_words) HIPC(hipMemcpy(c->d_hints.p, words, n_words * 4, hipMemcpyHostToDevice));
+    HIPC(hipDeviceSynchronize());
     return ART_OK;
 }
 

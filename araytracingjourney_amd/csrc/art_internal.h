@@ -241,7 +241,16 @@ struct FrameArgs {
     // alpha-masked primitives: alpha set = the instances with the alpha test (some enabled primitive has a cutoff > 0); alpha_bits: one bit per leaf
     // position, set where the triangle's primitive may have a cutoff > 0 (a superset: the cutoff itself comes from `prims`, the frame's version of the table)
     bool alpha; const uint32_t *alpha_bits;
+    // Shadow-occluder hints: per (8x8 block of the context's local pixels, light slot i % kHintLights) four leaf positions whose triangles occluded rays of that
+    // block's shadow packet a frame ago (0xFFFFFFFF: none).  The any-hit packet walks of k_frame visit them as ordinary triangle steps before the root and write back the ones
+    // that accepted a ray.  ONE table per context, shared by all frames in flight, read and written without atomics or fences: RACES ON IT ARE BENIGN BY CONSTRUCTION.  A reader
+    // may see any mix of old, new or stale (scalar cache) words; each word by itself is either a leaf position of the current tree (< hint_leaves), which is then tested against
+    // the frame's own triangle array like any leaf the walk would reach -- an any-hit answer is "some triangle accepts the ray", whatever the order -- or it is ignored; so no
+    // output bit depends on which one it was.  Written with plain vector stores only.  Null: the kernel neither loads nor stores it (ArtTuning.shadow_hints = 1).
+    uint32_t *hints; uint32_t hint_leaves;   // [n_local / 64][kHintLights][4]; leaf positions of the tree (T): what a word must be below to be visited
 };
+constexpr uint32_t kHintLights = 4;
+constexpr uint32_t kHintEmpty = 0xFFFFFFFFu;
 constexpr uint32_t kMaxBatch = 4;
 void launch_primary(const FrameArgs &a, hipStream_t s);
 void launch_shade(const FrameArgs &a, hipStream_t s);

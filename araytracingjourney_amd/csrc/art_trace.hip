@@ -402,18 +402,41 @@ template <class T> __device__ __forceinline__ ConstQuads const_quads(const T *p)
 // profiling build only (make EXTRA=-DART_PACKET_PROF; tools/packet_prof.py): what the packet walks of k_frame are made of, summed over all waves since the last reset.
 // [0..11] closest-hit (primary) walks, [12..23] any-hit (shadow) walks: walks, node steps, triangle steps, triangle steps that came off the stack, triangle steps in
 // which some lane accepted the triangle, lanes that accepted, child boxes hit by some lane (of 4 per node step), mixed-octant walks
-__device__ unsigned long long g_packet_prof[24];   // + [8] shader-clock cycles in node steps, [9] in triangle steps, [10] in the beam's set-up (each with the pop behind it)
+__device__ unsigned long long g_packet_prof[24];   // + [8] shader-clock cycles in node steps, [9] in triangle steps (each with the pop behind it), [10] triangle steps that were hints, [11] walks that ended inside their hint steps
 #define PPROF(i, n) do { if ((threadIdx.x & 63u) == 0) atomicAdd(&g_packet_prof[(ANY ? 12 : 0) + (i)], (unsigned long long)(n)); } while (0)
 #else
 #define PPROF(i, n)
 #endif
-template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false>
-__device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps) {
-    int cur = 0, sp = 0; // wave-uniform
+// Shadow-occluder hints of one any-hit walk (FrameArgs::hints), wave-uniform.  In: where the walk starts -- cur / sp as hints_seed left them: the block's valid
+// hints are visited as ordinary triangle steps BEFORE the root, which waits below them on the stack (no hints: cur 0, sp 0, the walk as it always was).  Lanes a hint occludes
+// are off for the rest of the walk; if all are, the walk ends in its triangle step like any other.  Out: n, how many triangle steps of this walk accepted a ray; the leaf
+// position of accepting step j is in stk[kPacketStack + j % 4] (four words behind the stack: a ring, so the four most recent survive).  A leaf accepts in at most one step of
+// a walk -- what it would accept it accepts the first time it is visited -- so the ring holds no position twice.
+struct PacketHints { int cur, sp; uint32_t n; };
+// The stack of the next any-hit walk, seeded from a hint entry (any four words): a word is visited only if it is a leaf position of this tree (< n_leaves); what it holds is
+// then tested against this frame's triangles like any leaf the walk reaches, so a stale or a made-up word costs a step and changes nothing.  w0 is visited first.
+// (Called in front of the shadow ray's set-up: the two registers of lane 0's stack writes are not to be had once the ray is live -- seeded inside the walk, the multi-light
+// instances spilled up to seven registers more.)
+__device__ __forceinline__ PacketHints hints_seed(int *stk, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t n_leaves) {
+    PacketHints h{0, 0, 0u};
+    if ((w0 & w1 & w2 & w3) == kHintEmpty) return h;   // (a fully lit block's entry: nothing but this compare)
+    const bool lane0 = (threadIdx.x & 63u) == 0;
+    if (w3 < n_leaves) { if (lane0) stk[h.sp] = h.cur; h.sp++; h.cur = (int)~w3; }
+    if (w2 < n_leaves) { if (lane0) stk[h.sp] = h.cur; h.sp++; h.cur = (int)~w2; }
+    if (w1 < n_leaves) { if (lane0) stk[h.sp] = h.cur; h.sp++; h.cur = (int)~w1; }
+    if (w0 < n_leaves) { if (lane0) stk[h.sp] = h.cur; h.sp++; h.cur = (int)~w0; }
+    return h;
+}
+template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false, bool HINTS = false>   // HINTS: an any-hit walk that takes and leaves hints
+__device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
+    int cur = HINTS ? h.cur : 0, sp = HINTS ? h.sp : 0; // wave-uniform
     constexpr int kPop = kAbsentChild;
 #ifdef ART_PACKET_PROF
-    unsigned long long pp_[10] = {1, 0, 0, 0, 0, 0, 0, OCT == 8, 0, 0}; bool from_stack_ = false;
+    unsigned long long pp_[12] = {1, 0, 0, 0, 0, 0, 0, OCT == 8, 0, 0, 0, 0}; bool from_stack_ = false; int hints_left_ = 0;
 #endif // "take the next node from the stack" (no leaf has position 2^31 - 1); also what an absent child of a 4-wide node refers to
+#ifdef ART_PACKET_PROF
+    if (HINTS) hints_left_ = sp;   // (every seeded hint put one reference on the stack)
+#endif
     for (;;) {
 #ifdef ART_PACKET_PROF
         const unsigned long long tk0_ = __builtin_amdgcn_s_memtime(); const bool was_node_ = cur >= 0;
@@ -502,7 +525,12 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
                 return cand;
             };
             // the ray state changes through selects, outside the divergent branches (no register copies around them)
-            if (ANY) { if (ALPHA) acc = alpha_keep(acc); bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest; } // first accepted triangle: this lane is done
+            if (ANY) { // first accepted triangle: this lane is done
+                if (ALPHA) acc = alpha_keep(acc);
+                bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest;
+                // a triangle that occluded some ray is next frame's hint (only accepting triangles are kept, so a hint that accepted nothing is forgotten after one frame)
+                if (HINTS && ballot64(acc) != 0ull) { if ((threadIdx.x & 63u) == 0) stk[kPacketStack + (h.n & 3u)] = (int)pos; h.n++; }
+            }
             else {
                 float teff;   // = fmaxf(t, te): one v_max_f32 (fmaxf first quiets both operands, which are the results of arithmetic here: two more instructions a step)
                 asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
@@ -513,6 +541,7 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
             }
 #ifdef ART_PACKET_PROF
             { uint64_t am_ = ballot64(acc); pp_[2]++; pp_[3] += from_stack_; pp_[4] += am_ != 0ull; pp_[5] += __popcll(am_); }
+            if (ANY && hints_left_ > 0) { pp_[10]++; pp_[11] += ballot64(on) == 0ull; hints_left_--; }
 #endif
             cur = kPop;
             if (ANY && ballot64(on) == 0ull) break; // every ray of the packet is occluded
@@ -530,13 +559,13 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
 #endif
     }
 #ifdef ART_PACKET_PROF
-    for (int i = 0; i < 10; i++) PPROF(i, pp_[i]);
+    for (int i = 0; i < 12; i++) PPROF(i, pp_[i]);
 #endif
 }
 
 // one packet through the walk that fits its rays' direction signs
-template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false>
-__device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps) {
+template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false, bool HINTS = false>
+__device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
     uint64_t act = ballot64(on);
     if (act == 0ull) return;
     // direction signs per axis: all set, none set, or mixed over the packet's rays
@@ -544,15 +573,15 @@ __device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, 
     bool uniform = (nx == 0ull || nx == act) && (ny == 0ull || ny == act) && (nz == 0ull || nz == act);
     int oct = !uniform ? 8 : (nx ? 1 : 0) | (ny ? 2 : 0) | (nz ? 4 : 0);
     switch (oct) {
-    case 0: packet_walk<ANY, WIDE, 0, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 1: packet_walk<ANY, WIDE, 1, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 2: packet_walk<ANY, WIDE, 2, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 3: packet_walk<ANY, WIDE, 3, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 4: packet_walk<ANY, WIDE, 4, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 5: packet_walk<ANY, WIDE, 5, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 6: packet_walk<ANY, WIDE, 6, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    case 7: packet_walk<ANY, WIDE, 7, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
-    default: packet_walk<ANY, WIDE, 8, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps); break;
+    case 0: packet_walk<ANY, WIDE, 0, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 1: packet_walk<ANY, WIDE, 1, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 2: packet_walk<ANY, WIDE, 2, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 3: packet_walk<ANY, WIDE, 3, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 4: packet_walk<ANY, WIDE, 4, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 5: packet_walk<ANY, WIDE, 5, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 6: packet_walk<ANY, WIDE, 6, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 7: packet_walk<ANY, WIDE, 7, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    default: packet_walk<ANY, WIDE, 8, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
     }
 }
 
@@ -1215,11 +1244,16 @@ __device__ __forceinline__ uint64_t tick(float &dep) { uint64_t t; asm volatile(
 #else
 #define PHASE(i, dep)
 #endif
+// The instances of k_frame that take shadow-occluder hints: all but those whose register allocation the hint code moved past what the same instance had without it -- the
+// binary-node walk with several frames per launch (one VGPR more in four of its instances) and the plain multi-light instance with the alpha test (two spilled registers);
+// these ignore the table and walk from the root as before (tools/kres.sh; profiles/README.md, "shadow-occluder hints").  Any subset is a correct frame: hints change no bit.
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr bool kFrameHints = !(!WIDE && BATCH) && !(ALPHA && !ONE_LIGHT && !COUNT && !BATCH);
 template <bool WIDE, bool ONE_LIGHT, bool COUNT = false, bool BATCH = false, bool ALPHA = false>   // WIDE: the 128-byte 4-wide nodes (the default) | the 64-byte binary nodes; ALPHA: the alpha test
 __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_frame(FrameArgs a) {
     // One wave per workgroup: the waves of a frame are independent (nothing is shared, no barrier), and a workgroup of four held its LDS and its place
     // in the dispatcher's books until its slowest wave was done -- packets differ 25x in steps.  Single-wave groups: +2.5 % rays/s (profiles/README.md r2).
-    __shared__ int wstack[kPacketStack];
+    __shared__ int wstack[kPacketStack + 4];   // + the ring of a shadow walk's accepting leaf positions (PacketHints)
+    constexpr bool HINTS = kFrameHints<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     int *stk = wstack;
     const uint32_t wid = blockIdx.x;
     if (wid >= a.n_wave_items) return;
@@ -1248,7 +1282,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     PHASE(0, r.inv.x)
     float tbest = on ? r.tmax : -1.0f, bu = 0.f, bv = 0.f;
     uint32_t bpos = kNoHit, bgid = kNoHit;
-    walk_dispatch<false, WIDE, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps);
+    { PacketHints none{0, 0, 0u}; walk_dispatch<false, WIDE, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, none); }   // (closest-hit walks take no hints)
     PHASE(1, tbest)
     uint32_t p, x, y; bool mine;
     frame_pixel(a, wid, p, x, y, mine);
@@ -1270,6 +1304,15 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     uint32_t sbits = 0, more = 0;
     // (until the walks fetched their nodes into SGPRs the multi-light instance parked the surface record in LDS across each shadow walk; it fits now)
     for (uint32_t i = 0; i < (ONE_LIGHT ? 1u : a.n_lights); i++) { // uniform loop: the shadow packet needs the whole wave
+        // the block's shadow-occluder hints for this light slot (FrameArgs::hints): one wave-uniform 16-byte load through the constant address space; the parts of a split
+        // block share their block's entry.  Hints off (null table): the walk starts at the root with nothing in front of it, and nothing is stored.
+        PacketHints hn{0, 0, 0u};
+        typedef uint32_t U4 __attribute__((ext_vector_type(4)));
+        if (HINTS && a.hints) {
+            const uint32_t blk = ((__attribute__((address_space(4))) const uint32_t *)(uintptr_t)a.wave_items)[2u * wid];
+            const U4 e = ((__attribute__((address_space(4))) const U4 *)(uintptr_t)a.hints)[blk * kHintLights + (i & (kHintLights - 1u))];
+            hn = hints_seed(stk, e.x, e.y, e.z, e.w, a.hint_leaves);
+        }
         float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f), ro = make_float4(0.f, 0.f, 0.f, 1.0f), rd = make_float4(0.f, 0.f, 1.f, 0.f);
         bool want = false;
         const ArtLight L = ONE_LIGHT ? a.lights[0] : frame_light(a, i);
@@ -1282,7 +1325,19 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         PHASE(3, sr.inv.x)
         float st = son ? sr.tmax : -1.0f, su = 0.f, sv = 0.f;
         uint32_t spos = kNoHit, sgid = kNoHit;
-        walk_dispatch<true, WIDE, COUNT, ALPHA>(a, sr, son, stk, st, su, sv, spos, sgid, steps);
+        const uint64_t traced = HINTS ? ballot64(son) : 0ull;
+        walk_dispatch<true, WIDE, COUNT, ALPHA, HINTS>(a, sr, son, stk, st, su, sv, spos, sgid, steps, hn);
+        if (HINTS && a.hints && traced != 0ull) { // (no shadow ray: the entry is left alone -- the idle wave of a split block shares the entry of the block's working parts)
+            // the walk's occluders, the most recent first; the entry's address and what it holds now are looked up again (launder: like the pixel, nothing of this is carried
+            // through the walk in registers); lane 0 writes them with one plain vector store unless the entry already says so
+            uint32_t o[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) o[k] = k < hn.n ? (uint32_t)stk[kPacketStack + ((hn.n - 1u - k) & 3u)] : kHintEmpty;
+            const uint32_t blk = ((__attribute__((address_space(4))) const uint32_t *)(uintptr_t)a.wave_items)[2u * launder(wid)];
+            const size_t at = blk * kHintLights + (i & (kHintLights - 1u));
+            const U4 e = ((__attribute__((address_space(4))) const U4 *)(uintptr_t)a.hints)[at];
+            if (((e.x ^ o[0]) | (e.y ^ o[1]) | (e.z ^ o[2]) | (e.w ^ o[3])) != 0u && __lane_id() == 0) reinterpret_cast<uint4 *>(a.hints)[at] = make_uint4(o[0], o[1], o[2], o[3]);
+        }
         PHASE(4, st)
         if (want && spos != kNoHit) { // shadowed: the light keeps 0.05 of its contribution (raytrace.rgen.glsl:179-181)
             c4 = make_float4(c4.x * 0.05f, c4.y * 0.05f, c4.z * 0.05f, c4.w);

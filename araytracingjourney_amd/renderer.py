@@ -608,6 +608,17 @@ class Renderer:
         check(self._L.art_read_shadow_bits(self._ctx, _ptr(b), w * h))
         return b
 
+    def read_shadow_hints(self):
+        """the context's table of shadow-occluder hints (art_read_shadow_hints): uint32 [8x8 blocks of the local pixels, 4 light slots, 4 leaf positions], 0xFFFFFFFF = none"""
+        a = np.empty((self.layout()["tiles_owned"] * 16, 4, 4), np.uint32)
+        check(self._L.art_read_shadow_hints(self._ctx, _ptr(a), a.size))
+        return a
+
+    def write_shadow_hints(self, table):
+        """overwrite that table (art_write_shadow_hints; tests only: any content leaves every frame what it is)"""
+        a = np.ascontiguousarray(table, dtype=np.uint32)
+        check(self._L.art_write_shadow_hints(self._ctx, _ptr(a), a.size))
+
     def query_closest(self, rays):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]

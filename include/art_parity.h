@@ -45,12 +45,18 @@ typedef struct ArtTuning {
     uint32_t plan_moving_interval; /* wave plan: frames between two looks at the waves while the camera / the lights change every frame (0 = 32) */
     uint32_t refit_streams;     /* moving models: streams of their own the refits run on, beside the frames of the ring slot they precede (0 = min(frames in flight, 4); 0xFFFFFFFF: none -- every refit on its frame's stream, in front of it) */
     uint32_t refit_fold_nodes;  /* moving models: trees of this many 4-wide nodes and more make the quantised records and the cost inside the refit's own workgroups, with a cached share of the cost per batch (0 = 400 000; 1 = every tree: the tests' way to that form on small scenes) */
+    uint32_t shadow_hints;      /* the fused frame's shadow packets test the triangles that occluded their 8x8 block a frame ago before they walk the tree from the root: 0 = on (the product) | 1 = off: the frame kernel neither reads nor writes the context's hint table */
 } ArtTuning;
 int32_t art_set_tuning(ArtContext *ctx, const ArtTuning *tuning);
 /* per-pixel primary hit record, row-major: tuv[4*i] = t,u,v,0 ; ids[2*i] = primitive index (-1 miss), triangle id */
 int32_t art_read_hits(ArtContext *ctx, float *tuv, int32_t *ids, size_t n_pixels);
 /* per pixel: bit i = light i shadowed, bit 16+i = shadow ray for light i traced (i < 16) */
 int32_t art_read_shadow_bits(ArtContext *ctx, uint32_t *bits, size_t n_pixels);
+/* the context's table of shadow-occluder hints: for every 8x8 block b of the context's local pixels (local pixel id / 64) and light slot l = light % 4, four leaf positions
+ * (~child of art_get_traversal_tree / art_get_wide_nodes; 0xFFFFFFFF: none) at words[16 * b + 4 * l ..]; n_words = 16 * local pixels / 64.  Both calls synchronise and need
+ * the frame layout of a first art_trace.  art_write_shadow_hints overwrites the table (tests only: ANY content leaves every frame bit for bit what it is). */
+int32_t art_read_shadow_hints(ArtContext *ctx, uint32_t *words, size_t n_words);
+int32_t art_write_shadow_hints(ArtContext *ctx, const uint32_t *words, size_t n_words);
 /* arbitrary ray queries on the built scene.  rays: n x 8 floats (o.xyz, tmin, d.xyz, tmax), host memory. */
 int32_t art_query_closest(ArtContext *ctx, const float *rays, uint32_t n, float *tuv, int32_t *ids);
 int32_t art_query_any(ArtContext *ctx, const float *rays, uint32_t n, uint8_t *hit);
