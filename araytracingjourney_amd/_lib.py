@@ -101,6 +101,8 @@ SYMBOLS = {
     "art_scene_set_model_matrix": (_I32, [_P, _U32, _U32, _P]),
     "art_scene_set_vertices": (_I32, [_P, _U32, _P, _U32]),
     "art_scene_set_alpha_cutoff": (_I32, [_P, _U32, _F]),
+    "art_scene_set_primitive_mask": (_I32, [_P, _U32, _U32]),
+    "art_set_ray_masks": (_I32, [_P, _U32, _U32, _U32]),
     "art_scene_build": (_I32, [_P]),
     "art_set_camera": (_I32, [_P, _P]),
     "art_camera_from_params": (_I32, [_P, _P, _F, _F, _F, _F, _P]),
@@ -177,6 +179,8 @@ PARITY_SYMBOLS = {
     "art_write_shadow_hints": (_I32, [_P, _P, _SZ]),
     "art_query_closest": (_I32, [_P, _P, _U32, _P, _P]),
     "art_query_any": (_I32, [_P, _P, _U32, _P]),
+    "art_query_closest_masked": (_I32, [_P, _P, _U32, _U32, _P, _P]),
+    "art_query_any_masked": (_I32, [_P, _P, _U32, _U32, _P]),
     "art_get_lbvh": (_I32, [_P] + [_P] * 7),
     "art_get_traversal_tree": (_I32, [_P, _P, _P, _P]),
     "art_get_wide_nodes": (_I32, [_P, _P, _P, _SZ, _P]),

@@ -28,6 +28,7 @@ struct HostPrim {
     bool enabled = true; // instanced in the acceleration structure (the reference's Device state, vk_model.rs:334-345); else kept on the host only
     bool verts_stale = false; // art_scene_set_vertices replaced `verts` since they were uploaded: a build over the same set uploads them again
     float cutoff = 0.0f;      // alpha cutoff (art_scene_set_alpha_cutoff; 0: opaque)
+    uint32_t vis = 0xFFu;     // visibility mask (art_scene_set_primitive_mask; 0xFF: every ray sees it)
 };
 
 template <class T> struct DevBuf {
@@ -73,6 +74,7 @@ struct FrameSlot {
     void *wait_event = nullptr;      // external event the slot's next frame must wait for (art_wait_external_event)
     uint32_t as_version = 0;         // which version of the acceleration structure the slot's latest frame read (art_trace_ao and the read-backs follow it)
     bool alpha = false;              // ... and whether it ran the instances with the alpha test (art_trace_ao follows it too)
+    uint32_t ray_masks = kRayMasksAll; // ... and the cull masks of its rays (art_set_ray_masks; art_trace_ao casts its rays with the frame's AO mask)
     void release() {
         d_counters.release(); d_shadow_bits.release(); d_hits.release(); d_contrib.release(); d_shadow_rays.release();
         d_color.release(); d_normal.release(); d_color_tiles.release(); d_depth.release(); d_occl.release(); d_ao.release(); d_ao_pix.release(); d_wave_cost.release(); d_lights_more.release(); d_pix_more.release();
@@ -195,7 +197,8 @@ struct ArtContext {
     // primitive that is disabled; alpha_bits marks the leaves whose primitive may have a cutoff (made by the build, bits added in front of the refit that first shows a
     // new cutoff, never cleared until the next build: a superset is safe, the cutoff itself decides)
     DevBuf<uint32_t> d_alpha_bits;
-    bool alpha_live = false;                   // some enabled primitive has a cutoff > 0: frames and queries run the instances with the alpha test
+    bool alpha_live = false;                   // some enabled primitive has a cutoff > 0 or a visibility mask other than 0xFF: frames and queries run the instances with the alpha test
+    uint32_t ray_masks = kRayMasksAll;         // art_set_ray_masks: primary | shadow << 8 | ao << 16; per-launch state like the camera
     bool alpha_bits_stale = false;             // a built primitive got a cutoff > 0 since the bits were last made
     uint64_t as_epoch = 0, binary_epoch = 0;   // refits so far; the refit the binary trees / node records reflect
     double as_cost0 = 0.0; float refit_cost_ratio = 1.0f; uint32_t refits = 0, rebuilds = 0; float last_refit_ms = 0.f, first_move_ms = 0.f, versions_ms = 0.f;
@@ -305,7 +308,7 @@ int32_t sync_all(ArtContext *c) {
 
 void alpha_refresh_live(ArtContext *c) {
     bool any = false;
-    for (const HostPrim &p : c->prims) any = any || (p.enabled && p.cutoff > 0.0f && p.n_indices >= 3);
+    for (const HostPrim &p : c->prims) any = any || (p.enabled && (p.cutoff > 0.0f || p.vis != 0xFFu) && p.n_indices >= 3);
     c->alpha_live = any;
 }
 
@@ -960,7 +963,7 @@ int32_t art_scene_set_primitive_enabled(ArtContext *c, uint32_t id, int32_t enab
         // next frame, like a move -- a model that crosses the residency radius (vk_model.rs:334-345) costs a fraction of a millisecond, not a build; its
         // device arrays stay where they are until the next art_scene_build (288 GB of HBM: the way back is as cheap).
         DevPrim &d = c->h_dev_prims[id];
-        d.masked = p.enabled ? 0u : 1u;
+        d.masked = (d.masked & ~kPrimOut) | (p.enabled ? 0u : kPrimOut);   // (the visibility bits stay)
         c->masked_tris += p.enabled ? -(int64_t)d.n_tri : (int64_t)d.n_tri;
         c->prim_moved[id] = c->as_epoch + 1;
         c->xform_dirty = true;
@@ -989,6 +992,39 @@ int32_t art_scene_set_alpha_cutoff(ArtContext *c, uint32_t id, float cutoff) {
     if (d.n_tri == 0) return ART_OK;                                // no triangles in the structure (a build brings them, with the cutoff)
     if (cutoff > 0.0f && !was_cut) c->alpha_bits_stale = true;      // its leaves get their bits in front of the refit
     c->xform_dirty = true;                                          // the next art_trace (or query) writes the next version of the table
+    return ART_OK;
+}
+
+// A visibility mask: the same path as a cutoff -- the value travels in the versioned primitive table (the complement, in DevPrim::masked), the next
+// art_trace or query refits over no batch, frames in flight keep theirs.  Nothing is built.
+int32_t art_scene_set_primitive_mask(ArtContext *c, uint32_t id, uint32_t mask) {
+    if (!c) return fail(ART_E_INVALID, "art_scene_set_primitive_mask: null context");
+    if (id >= c->prims.size()) return fail(ART_E_INVALID, "art_scene_set_primitive_mask: primitive_id: no such primitive");
+    if (mask > 0xFFu) return fail(ART_E_INVALID, "art_scene_set_primitive_mask: mask: above 0xFF");
+    HostPrim &p = c->prims[id];
+    if (p.vis == mask) return ART_OK;
+    p.vis = mask;
+    alpha_refresh_live(c);
+    if (!c->built || id >= c->h_dev_prims.size()) return ART_OK;   // takes effect with the build
+    DevPrim &d = c->h_dev_prims[id];
+    d.masked = (d.masked & kPrimOut) | ((~mask & 0xFFu) << kPrimVisShift);
+    if (d.n_tri == 0) return ART_OK;                                // no triangles in the structure (a build brings them, with the mask)
+    if (mask != 0xFFu) c->alpha_bits_stale = true;                  // its leaves get their bits in front of the refit (bits that are there already stay)
+    c->xform_dirty = true;                                          // the next art_trace (or query) writes the next version of the table
+    return ART_OK;
+}
+
+// The cull masks of the rays art_trace and art_trace_ao cast: kernel arguments, so a frame in flight keeps the ones it was launched with.
+int32_t art_set_ray_masks(ArtContext *c, uint32_t primary, uint32_t shadow, uint32_t ao) {
+    if (!c) return fail(ART_E_INVALID, "art_set_ray_masks: null context");
+    if (primary > 0xFFu) return fail(ART_E_INVALID, "art_set_ray_masks: primary: above 0xFF");
+    if (shadow > 0xFFu) return fail(ART_E_INVALID, "art_set_ray_masks: shadow: above 0xFF");
+    if (ao > 0xFFu) return fail(ART_E_INVALID, "art_set_ray_masks: ao: above 0xFF");
+    const uint32_t m = primary | (shadow << 8) | (ao << 16);
+    if (m == c->ray_masks) return ART_OK;
+    int32_t r = use_device(c); if (r) return r;
+    drop_graphs(c);   // a captured frame holds the old masks
+    c->ray_masks = m;
     return ART_OK;
 }
 
@@ -1104,7 +1140,7 @@ int32_t art_scene_build(ArtContext *c) {
         DevPrim &d = dp[k];
         std::memset(&d, 0, sizeof(d));
         d.vertices = c->d_verts.p + ov * 12; d.indices = c->d_indices.p + oi; d.texture_offset = (uint32_t)ot; d.single_index_size = p.idx_bytes;
-        d.tw = p.tw; d.th = p.th; d.first_tri = T; d.n_tri = p.enabled ? p.n_indices / 3 : 0; d.cutoff = p.cutoff;
+        d.tw = p.tw; d.th = p.th; d.first_tri = T; d.n_tri = p.enabled ? p.n_indices / 3 : 0; d.cutoff = p.cutoff; d.masked = (~p.vis & 0xFFu) << kPrimVisShift;
         std::memcpy(d.o2w, p.o2w, 48); std::memcpy(d.w2o, p.w2o, 48);
         first[k] = T;
         if (!p.enabled) continue;
@@ -1165,7 +1201,7 @@ int32_t art_scene_build(ArtContext *c) {
         HIPC(c->d_alpha_bits.ensure(nw + 1));
         HIPC(hipMemsetAsync(c->d_alpha_bits.p, 0, (nw + 1) * 4, c->main_stream()));
         bool cut = false;
-        for (const DevPrim &d : dp) cut = cut || (d.n_tri > 0 && d.cutoff > 0.0f);
+        for (const DevPrim &d : dp) cut = cut || (d.n_tri > 0 && (d.cutoff > 0.0f || (d.masked >> kPrimVisShift) != 0u));
         if (cut) { launch_alpha_bits(T, c->bvh.leaf_gid, c->bvh.tri_prim, c->d_prims.p, c->d_alpha_bits.p, c->main_stream()); HIPC(hipGetLastError()); }
         // the shadow-occluder hints are leaf positions of the tree that just went away: all empty (nothing is in flight -- sync_all above -- and the wait below is in front of every later frame)
         if (c->d_hints.p) HIPC(hipMemsetAsync(c->d_hints.p, 0xFF, c->d_hints.n * 4, c->main_stream()));
@@ -1317,7 +1353,11 @@ static FrameArgs make_frame_args(ArtContext *c, FrameSlot &S, uint32_t version) 
     a.batch = c->B; a.tiles_stride = c->padded_tiles * kTilePixels;
     for (uint32_t i = 0; i + 1 < kMaxBatch; i++) std::memcpy(&a.cam_more[i], &c->cam_more[i], sizeof(ArtCamera));
     a.tile_xy = c->d_tile_xy.p; a.wave_items = c->plan.d_items[c->plan.cur].p; a.n_wave_items = c->plan.n_items[c->plan.cur]; a.wave_cost = nullptr; // art_trace sets it for the frames the wave plan samples
-    a.alpha = c->alpha_live; a.alpha_bits = c->d_alpha_bits.p;   // (art_trace_ao: the frame's own choice, FrameSlot::alpha)
+    // the filtered instances run while the scene needs them (alpha_live) or some ray type's cull mask is 0 (such rays see nothing, and no leaf bit says so)
+    const uint32_t rm = c->ray_masks;
+    a.ray_masks = rm;
+    a.alpha = c->alpha_live || (rm & 0xFFu) == 0u || ((rm >> 8) & 0xFFu) == 0u || ((rm >> 16) & 0xFFu) == 0u;
+    a.alpha_bits = c->d_alpha_bits.p;   // (art_trace_ao: the frame's own choice, FrameSlot::alpha and ::ray_masks)
     a.hints = c->shadow_hints ? c->d_hints.p : nullptr; a.hint_leaves = c->T;
     return a;
 }
@@ -1370,7 +1410,7 @@ int32_t art_trace(ArtContext *c) {
     S.as_version = ver;
     r = lights_upload(c, S, s); if (r) return r;
     FrameArgs a = make_frame_args(c, S, ver);
-    S.alpha = a.alpha;
+    S.alpha = a.alpha; S.ray_masks = a.ray_masks;
     if (c->tiled()) a.color_tiles = S.tiles_for(c->frame_no, c->F); // alternates when a pair of buffers is bound
     const bool fused = c->fused && c->kind_primary == 8 && c->kind_shadow == 8;
     if (c->B > 1 && !fused) return fail(ART_E_STATE, "art_trace: several frames per launch need the default fused frame");
@@ -1483,7 +1523,7 @@ int32_t art_trace_ao(ArtContext *c, uint32_t spp, float radius) {
     for (uint32_t k = 0; k <= spp; k++) lut[k] = (uint32_t)(std::pow(1.0 - (double)k / (double)spp, 2.2) * 255.0 + 0.5); // XE_GTAO_DEFAULT_FINAL_VALUE_POWER (vk_xe_gtao.rs:22)
     r = ensure_binary(c, c->kind_ao == 2); if (r) return r;
     FrameArgs a = make_frame_args(c, S, S.as_version); // the structure the frame itself was traced in
-    a.alpha = S.alpha;                                  // (and the cutoffs of that version's table)
+    a.alpha = S.alpha; a.ray_masks = S.ray_masks;       // (and the cutoffs and masks of that version's table, and the cull masks that were current at the frame's art_trace)
     if (!c->as.empty()) c->as[S.as_version].aux[c->last] = true;
     HIPC(hipMemsetAsync(S.d_counters.p + 64 + 16 * 32, 0, 8 * 32 * 4, s)); // the AO launch's work cursors
     HIPC(hipEventRecord(S.ao_ev[0], s));
@@ -1865,8 +1905,11 @@ int32_t art_write_shadow_hints(ArtContext *c, const uint32_t *words, size_t n_wo
     return ART_OK;
 }
 
-int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *tuv, int32_t *ids) {
+int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *tuv, int32_t *ids) { return art_query_closest_masked(c, rays, n, 0xFFu, tuv, ids); }
+// (the rays' cull mask, DESIGN.md 3.4: 0xFF is art_query_closest; the filtered tracer instances run while the scene needs them or the mask is 0)
+int32_t art_query_closest_masked(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, float *tuv, int32_t *ids) {
     if (!c || (n && (!rays || !tuv || !ids))) return fail(ART_E_INVALID, "art_query_closest: null argument");
+    if (cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_query_closest_masked: cull_mask: above 0xFF");
     if (!c->built) return fail(ART_E_STATE, "art_query_closest: scene not built");
     if (n == 0) return ART_OK;
     int32_t r = use_device(c); if (r) return r;
@@ -1881,7 +1924,7 @@ int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *t
     if (e == hipSuccess && (refresh_now(c) != ART_OK || ensure_wide(c, true) != ART_OK || ensure_binary(c, qkind == 2) != ART_OK)) e = hipErrorUnknown; // (a pending move is applied first)
     if (e == hipSuccess) e = c->slot[0].d_counters.ensure(kCounterWords);
     if (e == hipSuccess) e = hipMemsetAsync(c->slot[0].d_counters.p, 0, kCounterWords * 4, c->main_stream());
-    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_closest(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
+    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_closest(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live || cull_mask == 0u, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p, cull_mask}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(c->main_stream());
     if (e == hipSuccess) e = hipMemcpy(h.data(), d_h, (size_t)n * 16, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(tris.data(), c->bvh.tris, (size_t)c->T * sizeof(DevTri), hipMemcpyDeviceToHost);
@@ -1896,8 +1939,10 @@ int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *t
     return ART_OK;
 }
 
-int32_t art_query_any(ArtContext *c, const float *rays, uint32_t n, uint8_t *hit) {
+int32_t art_query_any(ArtContext *c, const float *rays, uint32_t n, uint8_t *hit) { return art_query_any_masked(c, rays, n, 0xFFu, hit); }
+int32_t art_query_any_masked(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, uint8_t *hit) {
     if (!c || (n && (!rays || !hit))) return fail(ART_E_INVALID, "art_query_any: null argument");
+    if (cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_query_any_masked: cull_mask: above 0xFF");
     if (!c->built) return fail(ART_E_STATE, "art_query_any: scene not built");
     if (n == 0) return ART_OK;
     int32_t r = use_device(c); if (r) return r;
@@ -1911,7 +1956,7 @@ int32_t art_query_any(ArtContext *c, const float *rays, uint32_t n, uint8_t *hit
     if (e == hipSuccess && (refresh_now(c) != ART_OK || ensure_wide(c, true) != ART_OK || ensure_binary(c, qkind == 2) != ART_OK)) e = hipErrorUnknown;
     if (e == hipSuccess) e = c->slot[0].d_counters.ensure(kCounterWords);
     if (e == hipSuccess) e = hipMemsetAsync(c->slot[0].d_counters.p, 0, kCounterWords * 4, c->main_stream());
-    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_any(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
+    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_any(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live || cull_mask == 0u, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p, cull_mask}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(c->main_stream());
     if (e == hipSuccess) e = hipMemcpy(h.data(), d_h, (size_t)n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d_r); (void)hipFree(d_h);

@@ -539,7 +539,7 @@ __device__ __forceinline__ void retri_one(uint32_t p, DevShadeTri *__restrict__ 
     if (!how) return;
     if (how & kTouchRegather) regather_one(p, prim, prims_host, tris, shade);   // (a masked primitive's too: it shows its new shape when it is enabled again)
     DevTri t;
-    if (prims_host[prim].masked) {   // out of the structure until it is enabled again: a point nowhere, no extent
+    if (prims_host[prim].masked & kPrimOut) {   // out of the structure until it is enabled again: a point nowhere, no extent
         for (int k = 0; k < 3; k++) { t.f[k] = kNowhere; t.f[3 + k] = 0.f; t.f[6 + k] = 0.f; t.f[9 + k] = kNowhere; t.f[12 + k] = kNowhere; }
     } else {
         const float4 *sq = reinterpret_cast<const float4 *>(shade + p);
@@ -708,14 +708,14 @@ __global__ __launch_bounds__(256) void k_wide_requant(uint32_t n_wide, const Dev
     }
 }
 
-// the leaf bits of the alpha test (FrameArgs::alpha_bits): a thread per word of 32 leaf positions, set where the leaf's primitive has a cutoff > 0 in `prims`.  Bits are only ever
+// the leaf bits of the alpha test (FrameArgs::alpha_bits): a thread per word of 32 leaf positions, set where the leaf's primitive has a cutoff > 0 or a visibility mask other than 0xFF in `prims`.  Bits are only ever
 // added (atomicOr): a frame in flight that reads a word while it changes sees its own bits either way, and a bit of a primitive whose cutoff went back to 0 costs that
 // frame a look at the cutoff, never a wrong answer.  The next build starts from zero.
 __global__ __launch_bounds__(256) void k_alpha_bits(uint32_t T, const uint32_t *__restrict__ leaf_gid, const uint32_t *__restrict__ tri_prim, const DevPrim *prims, uint32_t *bits) {
     const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= (T + 31u) / 32u) return;
     uint32_t m = 0;
-    for (uint32_t j = 0; j < 32u && w * 32u + j < T; j++) if (prims[tri_prim[leaf_gid[w * 32u + j]]].cutoff > 0.0f) m |= 1u << j;
+    for (uint32_t j = 0; j < 32u && w * 32u + j < T; j++) { const DevPrim &P = prims[tri_prim[leaf_gid[w * 32u + j]]]; if (P.cutoff > 0.0f || (P.masked >> kPrimVisShift) != 0u) m |= 1u << j; }
     if (m) atomicOr(&bits[w], m);
 }
 void launch_alpha_bits(uint32_t T, const uint32_t *leaf_gid, const uint32_t *tri_prim, const DevPrim *prims, uint32_t *bits, hipStream_t s) {

@@ -24,10 +24,14 @@ struct DevPrim {
     uint32_t first_tri, n_tri;
     float o2w[12];              // row-major 3x4
     float w2o[12];
-    uint32_t masked;            // a primitive that left the structure without a build (art_scene_set_primitive_enabled): its triangles are written "nowhere" by the next refit
+    uint32_t masked;            // bit 0: a primitive that left the structure without a build (art_scene_set_primitive_enabled): its triangles are written "nowhere" by the next refit;
+                                // bits 8..15: the COMPLEMENT of its visibility mask (art_scene_set_primitive_mask), so that all zero is the default 0xFF
     float cutoff;               // alpha cutoff (art_scene_set_alpha_cutoff): > 0 discards a candidate whose layer-0 alpha is below it; 0 = opaque
 };
 static_assert(sizeof(DevPrim) == 144, "DevPrim layout");
+constexpr uint32_t kPrimOut = 1u;             // DevPrim::masked: out of the structure
+constexpr uint32_t kPrimVisShift = 8u;        // DevPrim::masked: ~vis & 0xFF sits here
+__host__ __device__ inline uint32_t prim_vis(uint32_t masked) { return ~(masked >> kPrimVisShift) & 0xFFu; }
 // "Nowhere": the point box at 3e38 that absent children of a 4-wide node have carried since round 1 -- no ray passes it in any form of the slab test (|t| >= 3e38 on
 // every axis).  A masked triangle's record is one, and a union skips such boxes (a node with nothing else below it is nowhere itself).
 constexpr float kNowhere = 3.0e38f;
@@ -248,7 +252,11 @@ struct FrameArgs {
     // the frame's own triangle array like any leaf the walk would reach -- an any-hit answer is "some triangle accepts the ray", whatever the order -- or it is ignored; so no
     // output bit depends on which one it was.  Written with plain vector stores only.  Null: the kernel neither loads nor stores it (ArtTuning.shadow_hints = 1).
     uint32_t *hints; uint32_t hint_leaves;   // [n_local / 64][kHintLights][4]; leaf positions of the tree (T): what a word must be below to be visited
+    // Ray visibility masks: the cull masks of this launch's rays, primary | shadow << 8 | ao << 16.  Read by the instances with the alpha test only (`alpha` is
+    // also set while a primitive has a visibility mask other than 0xFF or one of these is 0); alpha_bits marks the leaves of such primitives too.
+    uint32_t ray_masks;
 };
+constexpr uint32_t kRayMasksAll = 0xFFFFFFu;
 constexpr uint32_t kHintLights = 4;
 constexpr uint32_t kHintEmpty = 0xFFFFFFFFu;
 constexpr uint32_t kMaxBatch = 4;
@@ -277,8 +285,9 @@ void launch_ao_table(uint32_t spp, float4 *tab, hipStream_t s); // tab: spp * kA
 // pix: 2 * n_local float4 of scratch (per-pixel origin | start node, normal | noise index); tab: launch_ao_table's; entry_search: start the rays below the root
 void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, float4 *pix, const float4 *tab, bool entry_search, uint32_t *ao, const uint32_t *lut, hipStream_t s);
 struct BvhView { const DevNode *nodes; const DevNode4 *wide; const DevTri *tris; int kind; TraceTune tune;   // kind: 2 | 4
-                 bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool; };   // alpha: FrameArgs' (the queries' alpha test)
-// the bits of FrameArgs::alpha_bits: bit p of word p / 32 |= (prims[primitive of leaf p].cutoff > 0); never cleared between builds (art_build.hip)
+                 bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool;   // alpha: FrameArgs' (the queries' alpha test)
+                 uint32_t cull = 0xFFu; };   // the queries' cull mask
+// the bits of FrameArgs::alpha_bits: bit p of word p / 32 |= (prims[primitive of leaf p] has a cutoff > 0 or a visibility mask other than 0xFF); never cleared between builds (art_build.hip)
 void launch_alpha_bits(uint32_t T, const uint32_t *leaf_gid, const uint32_t *tri_prim, const DevPrim *prims, uint32_t *bits, hipStream_t s);
 void launch_query_closest(const BvhView &b, const float4 *rays, uint32_t n, float4 *hits, uint32_t *cursors, hipStream_t s);
 void launch_query_any(const BvhView &b, const float4 *rays, uint32_t n, uint32_t *hit, uint32_t *cursors, hipStream_t s);

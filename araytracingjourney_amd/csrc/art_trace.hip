@@ -94,6 +94,7 @@ struct AlphaView {
     const DevShadeTri *shade;    // the frame's version of the shading records (uv, primitive id) and of the primitive table (c)
     const DevPrim *prims;
     const uint32_t *tex;
+    uint32_t cull;               // ray visibility masks: the cull mask of this launch's rays
 };
 // the alpha of the candidate (pos, u, v) of primitive prim_tex = {texture_offset, tw, th}; uv0..uv2 of its shading record
 __device__ __forceinline__ float alpha_at(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw, uint32_t th, float4 s2, float4 s3, float u, float v) {
@@ -104,11 +105,16 @@ __device__ __forceinline__ float alpha_at(const uint32_t *__restrict__ pool, uin
     return tex_channel(t00, t10, t01, t11, fx, fy, 3);
 }
 // per-ray walks: true = the candidate at leaf position pos is cut (its lane fetches the record, the cutoff and four texels only if the leaf's bit is set)
+// The visibility rule of DESIGN.md 3.4 comes first: a candidate whose primitive's mask shares no bit with the rays' cull mask is discarded before any texel is fetched
+// (a cull mask of 0 sees nothing, whatever the leaf bits say: they only mark masks other than 0xFF).
 __device__ __forceinline__ bool alpha_cut(const AlphaView &av, uint32_t pos, float u, float v) {
+    if (av.cull == 0u) return true;
     if (!((av.bits[pos >> 5] >> (pos & 31u)) & 1u)) return false;
     const float4 *sq = reinterpret_cast<const float4 *>(av.shade + pos);
-    const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+    const float4 s8 = sq[8];
     const DevPrim &P = av.prims[__float_as_uint(s8.z)];
+    if ((prim_vis(P.masked) & av.cull) == 0u) return true;
+    const float4 s2 = sq[2], s3 = sq[3];
     const float c = P.cutoff;
     if (!(c > 0.0f)) return false;
     return alpha_at(av.tex, P.texture_offset, P.tw, P.th, s2, s3, u, v) < c;
@@ -431,6 +437,10 @@ template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false, 
 __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
     int cur = HINTS ? h.cur : 0, sp = HINTS ? h.sp : 0; // wave-uniform
     constexpr int kPop = kAbsentChild;
+    // ray visibility masks: the cull mask of this walk's rays, a kernel argument; rays with a cull mask of 0 see nothing
+    // (read from the arguments where it is used: a value kept through the walk costs the multi-light instances a scalar register they do not have)
+    const auto cull = [&]() -> uint32_t { return ANY ? (a.ray_masks >> 8) & 0xFFu : a.ray_masks & 0xFFu; };
+    if (ALPHA && cull() == 0u) return;
 #ifdef ART_PACKET_PROF
     unsigned long long pp_[12] = {1, 0, 0, 0, 0, 0, 0, OCT == 8, 0, 0, 0, 0}; bool from_stack_ = false; int hints_left_ = 0;
 #endif // "take the next node from the stack" (no leaf has position 2^31 - 1); also what an absent child of a 4-wide node refers to
@@ -502,49 +512,60 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
             else cur = kPop;
         } else {
             uint32_t pos = (uint32_t)~cur;
-            ConstQuads tq = const_quads(a.tris + pos);
-            float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid: one 64-byte scalar load (DevTri)
-            float te = 0.f, t = 0.f, u = 0.f, v = 0.f;
-            // accept() = slab(AABB(tri)) AND Moeller-Trumbore: the conjunction is evaluated triangle test first -- the parent already
-            // tested this very box for the packet, so nearly every wave would pay for the slab, while few lanes survive the triangle test
-            bool acc = moller_trumbore_flat(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v) && on;
-            if (acc) acc = slab_oct<OCT>(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te);
-            // the alpha test: the triangle is wave-uniform, so its leaf bit, its shading record's uv and primitive id and that primitive's cutoff
-            // are scalar loads, made only when the bit is set and some lane took the candidate; then the lanes that did fetch their four texels
-            const auto alpha_keep = [&](bool cand) -> bool {
-                if (!ALPHA || ballot64(cand) == 0ull) return cand;
-                typedef __attribute__((address_space(4))) const uint32_t *Words;
-                if (!((((Words)(uintptr_t)a.alpha_bits)[pos >> 5] >> (pos & 31u)) & 1u)) return cand;
-                ConstQuads sq = const_quads(a.shade_tris + pos);
-                const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+            typedef __attribute__((address_space(4))) const uint32_t *Words;
+            // the filtered instances: does this leaf's primitive need a look at its record (a cutoff > 0 or a visibility mask other than 0xFF)?  One scalar bit test.
+            bool unseen = false;
+            const auto flagged = [&]() -> bool { return ((((Words)(uintptr_t)a.alpha_bits)[pos >> 5] >> (pos & 31u)) & 1u) != 0u; };
+            // the visibility rule, before anything else of the step: the triangle is wave-uniform, so its primitive id and that primitive's mask are scalar
+            // loads and the decision a scalar branch -- a leaf no ray of this walk may see costs the wave no vector work.  (A hint step comes through here as well.)
+            if (ALPHA && flagged()) {
+                const float4 s8 = const_quads(a.shade_tris + pos)[8];
                 const Words P = (Words)(uintptr_t)(a.prims + __float_as_uint(s8.z));
-                const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
-                if (!(c > 0.0f)) return cand;
-                const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
-                if (cand) cand = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
-                return cand;
-            };
-            // the ray state changes through selects, outside the divergent branches (no register copies around them)
-            if (ANY) { // first accepted triangle: this lane is done
-                if (ALPHA) acc = alpha_keep(acc);
-                bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest;
-                // a triangle that occluded some ray is next frame's hint (only accepting triangles are kept, so a hint that accepted nothing is forgotten after one frame)
-                if (HINTS && ballot64(acc) != 0ull) { if ((threadIdx.x & 63u) == 0) stk[kPacketStack + (h.n & 3u)] = (int)pos; h.n++; }
+                unseen = (prim_vis(P[offsetof(DevPrim, masked) / 4]) & cull()) == 0u;
             }
-            else {
-                float teff;   // = fmaxf(t, te): one v_max_f32 (fmaxf first quiets both operands, which are the results of arithmetic here: two more instructions a step)
-                asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
-                uint32_t gid = __float_as_uint(td.w);
-                bool better = acc & ((teff < tbest) | ((teff == tbest) & (gid < bgid))); // (bitwise: three compares and three mask operations, no nested exec regions)
-                if (ALPHA) better = alpha_keep(better);   // (only a candidate that would win is tested: a cut one that would lose changes nothing)
-                tbest = better ? teff : tbest; bu = better ? u : bu; bv = better ? v : bv; bpos = better ? pos : bpos; bgid = better ? gid : bgid;
-            }
+            if (!unseen) {
+                ConstQuads tq = const_quads(a.tris + pos);
+                float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid: one 64-byte scalar load (DevTri)
+                float te = 0.f, t = 0.f, u = 0.f, v = 0.f;
+                // accept() = slab(AABB(tri)) AND Moeller-Trumbore: the conjunction is evaluated triangle test first -- the parent already
+                // tested this very box for the packet, so nearly every wave would pay for the slab, while few lanes survive the triangle test
+                bool acc = moller_trumbore_flat(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v) && on;
+                if (acc) acc = slab_oct<OCT>(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te);
+                // the alpha test: the triangle is wave-uniform, so its leaf bit, its shading record's uv and primitive id and that primitive's cutoff
+                // are scalar loads, made only when the bit is set and some lane took the candidate; then the lanes that did fetch their four texels
+                const auto alpha_keep = [&](bool cand) -> bool {
+                    if (!ALPHA || ballot64(cand) == 0ull || !flagged()) return cand;
+                    ConstQuads sq = const_quads(a.shade_tris + pos);
+                    const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+                    const Words P = (Words)(uintptr_t)(a.prims + __float_as_uint(s8.z));
+                    const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
+                    if (!(c > 0.0f)) return cand;
+                    const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
+                    if (cand) cand = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
+                    return cand;
+                };
+                // the ray state changes through selects, outside the divergent branches (no register copies around them)
+                if (ANY) { // first accepted triangle: this lane is done
+                    if (ALPHA) acc = alpha_keep(acc);
+                    bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest;
+                    // a triangle that occluded some ray is next frame's hint (only accepting triangles are kept, so a hint that accepted nothing is forgotten after one frame)
+                    if (HINTS && ballot64(acc) != 0ull) { if ((threadIdx.x & 63u) == 0) stk[kPacketStack + (h.n & 3u)] = (int)pos; h.n++; }
+                }
+                else {
+                    float teff;   // = fmaxf(t, te): one v_max_f32 (fmaxf first quiets both operands, which are the results of arithmetic here: two more instructions a step)
+                    asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
+                    uint32_t gid = __float_as_uint(td.w);
+                    bool better = acc & ((teff < tbest) | ((teff == tbest) & (gid < bgid))); // (bitwise: three compares and three mask operations, no nested exec regions)
+                    if (ALPHA) better = alpha_keep(better);   // (only a candidate that would win is tested: a cut one that would lose changes nothing)
+                    tbest = better ? teff : tbest; bu = better ? u : bu; bv = better ? v : bv; bpos = better ? pos : bpos; bgid = better ? gid : bgid;
+                }
 #ifdef ART_PACKET_PROF
-            { uint64_t am_ = ballot64(acc); pp_[2]++; pp_[3] += from_stack_; pp_[4] += am_ != 0ull; pp_[5] += __popcll(am_); }
-            if (ANY && hints_left_ > 0) { pp_[10]++; pp_[11] += ballot64(on) == 0ull; hints_left_--; }
+                { uint64_t am_ = ballot64(acc); pp_[2]++; pp_[3] += from_stack_; pp_[4] += am_ != 0ull; pp_[5] += __popcll(am_); }
+                if (ANY && hints_left_ > 0) { pp_[10]++; pp_[11] += ballot64(on) == 0ull; hints_left_--; }
 #endif
+                if (ANY && ballot64(on) == 0ull) break; // every ray of the packet is occluded
+            }
             cur = kPop;
-            if (ANY && ballot64(on) == 0ull) break; // every ray of the packet is occluded
         }
         if (cur == kPop) {
             if (sp == 0) break;
@@ -1247,7 +1268,9 @@ __device__ __forceinline__ uint64_t tick(float &dep) { uint64_t t; asm volatile(
 // The instances of k_frame that take shadow-occluder hints: all but those whose register allocation the hint code moved past what the same instance had without it -- the
 // binary-node walk with several frames per launch (one VGPR more in four of its instances) and the plain multi-light instance with the alpha test (two spilled registers);
 // these ignore the table and walk from the root as before (tools/kres.sh; profiles/README.md, "shadow-occluder hints").  Any subset is a correct frame: hints change no bit.
-template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr bool kFrameHints = !(!WIDE && BATCH) && !(ALPHA && !ONE_LIGHT && !COUNT && !BATCH);
+// With the visibility rule in the triangle step the step-counting sibling of the latter over binary nodes went the same way (one spilled VGPR) and joined them.
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr bool kFrameHints = !(!WIDE && BATCH) && !(ALPHA && !ONE_LIGHT && !COUNT && !BATCH) &&
+                                                                                                      !(ALPHA && !WIDE && !ONE_LIGHT && COUNT && !BATCH);
 template <bool WIDE, bool ONE_LIGHT, bool COUNT = false, bool BATCH = false, bool ALPHA = false>   // WIDE: the 128-byte 4-wide nodes (the default) | the 64-byte binary nodes; ALPHA: the alpha test
 __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_frame(FrameArgs a) {
     // One wave per workgroup: the waves of a frame are independent (nothing is shared, no barrier), and a workgroup of four held its LDS and its place
@@ -1541,12 +1564,13 @@ template <int MODE> static void launch_trace(TraceArgs &a, int kind, bool pipeli
     else if (kind == 4) k_trace<MODE, 4><<<nb, kTraceBlock, 0, s>>>(a);
     else k_trace<MODE, 2><<<nb, kTraceBlock, 0, s>>>(a);
 }
-static AlphaView alpha_view(const FrameArgs &f) { return AlphaView{f.alpha_bits, f.shade_tris, f.prims, f.tex_pool}; }
+// which: 0 primary | 1 shadow | 2 AO rays (their cull mask out of FrameArgs::ray_masks)
+static AlphaView alpha_view(const FrameArgs &f, int which) { return AlphaView{f.alpha_bits, f.shade_tris, f.prims, f.tex_pool, (f.ray_masks >> (8 * which)) & 0xFFu}; }
 void launch_primary(const FrameArgs &f, hipStream_t s) {   // staged frames: the persistent per-ray tracer
     TraceArgs a{};
     a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = f.n_local; a.cursors = f.counters + 64; a.cam = f.cam; a.W = f.W; a.H = f.H;
     a.tile_list = f.tile_list; a.tiles_x = f.tiles_x; a.hits = f.hits;
-    a.alpha = alpha_view(f);
+    a.alpha = alpha_view(f, 0);
     launch_trace<MODE_PRIMARY>(a, f.trace_kind[0], f.pipelined, f.tune, f.alpha, s);
 }
 void launch_shade(const FrameArgs &a, hipStream_t s) { k_shade<<<blocks_for(a.n_local), kBlock, 0, s>>>(a); }
@@ -1555,7 +1579,7 @@ void launch_shadow(const FrameArgs &f, hipStream_t s) {
     TraceArgs a{};
     a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = f.n_local * f.n_lights; a.cursors = f.counters + 64 + 8 * kCursorStride; a.count = f.counters + kShadowSlots;
     a.rays = f.shadow_rays; a.contrib = f.contrib; a.n_local = f.n_local; a.shadow_bits = f.shadow_bits;
-    a.alpha = alpha_view(f);
+    a.alpha = alpha_view(f, 1);
     launch_trace<MODE_SHADOW>(a, f.trace_kind[1], f.pipelined, f.tune, f.alpha, s);
 }
 template <bool WIDE, bool ONE_LIGHT, bool ALPHA = false> static void launch_frame_form(const FrameArgs &a, uint32_t g, bool count, hipStream_t s) {
@@ -1584,14 +1608,14 @@ void launch_query_closest(const BvhView &b, const float4 *rays, uint32_t n, floa
     if (!n) return;
     TraceArgs a{};
     a.nodes = b.nodes; a.wide = b.wide; a.tris = b.tris; a.total = n; a.cursors = cursors; a.rays = rays; a.hits = hits;
-    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool};
+    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool, b.cull};
     launch_trace<MODE_QUERY_CLOSEST>(a, b.kind, false, b.tune, b.alpha, s);
 }
 void launch_query_any(const BvhView &b, const float4 *rays, uint32_t n, uint32_t *hit, uint32_t *cursors, hipStream_t s) {
     if (!n) return;
     TraceArgs a{};
     a.nodes = b.nodes; a.wide = b.wide; a.tris = b.tris; a.total = n; a.cursors = cursors; a.rays = rays; a.any_out = hit;
-    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool};
+    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool, b.cull};
     launch_trace<MODE_QUERY_ANY>(a, b.kind, false, b.tune, b.alpha, s);
 }
 // AO resolve: occluded count -> uint(pow(visibility, 2.2) * 255 + 0.5) through a host-built table; 255 where nothing was hit
@@ -1638,7 +1662,7 @@ void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, fl
     TraceArgs a{};
     a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = n_slots; a.cursors = f.counters + 64 + 16 * kCursorStride; a.cam = f.cam; a.W = f.W; a.H = f.H;
     a.tile_list = f.tile_list; a.tiles_x = f.tiles_x; a.depth = f.depth; a.normal = f.normal; a.spp = spp; a.ao_radius = radius; a.occl = occl;
-    a.ao_pix = pix; a.ao_tab = tab; a.alpha = alpha_view(f);
+    a.ao_pix = pix; a.ao_tab = tab; a.alpha = alpha_view(f, 2);
     if (f.trace_kind[2] == 4) {   // the default: the AO launch's own tracer (rays made by the whole wave into a pool); 6 = the same walk through the generic tracer (round 3's form), 2 = binary nodes
         Tune t = tune(f.pipelined, true, f.tune);
         if (!(f.tune.refill >= 1 && f.tune.refill <= 64)) t.refill = kAoPoolTake;

@@ -163,6 +163,14 @@ struct Model { // VkModel: only Device models are instanced in the acceleration 
         if (!(cutoff >= 0.0f && cutoff <= 1.0f)) throw Panic(ART_E_INVALID, "Model::set_alpha_cutoff: the cutoff must lie in [0, 1]");
         if (ctx) check(art_scene_set_alpha_cutoff(ctx, primitive_ids[primitive_index], cutoff));
     }
+    // Visibility mask (Vulkan: VkAccelerationStructureInstanceKHR.mask; the reference hard-codes 0xFF, vk_model.rs:373): a hit on primitive primitive_ids[primitive_index]
+    // is discarded for every ray whose cull mask shares no bit with `mask` (Renderer::set_ray_masks).  0xFF is the default; mask must lie in 0..0xFF.  Nothing is built:
+    // the next frame takes it up (art_scene_set_primitive_mask).
+    void set_mask(size_t primitive_index, uint32_t mask) {
+        if (primitive_index >= primitive_ids.size()) throw Panic(ART_E_INVALID, "Model::set_mask: no such primitive");
+        if (mask > 0xFFu) throw Panic(ART_E_INVALID, "Model::set_mask: the mask must lie in 0..0xFF");
+        if (ctx) check(art_scene_set_primitive_mask(ctx, primitive_ids[primitive_index], mask));
+    }
     const Matrix3x4 &get_transform_model_matrix() const { return model_matrix; } // vk_model.rs:358-363
     void update_model_status(const Vector3 &camera_pos) { // vk_model.rs:334-345
         float d = model_bounding_sphere.get_distance_from_point(camera_pos);
@@ -178,10 +186,10 @@ class Renderer {
     ArtContext *ctx_ = nullptr; uint32_t w_, h_; Camera camera_; Lights lights_; std::vector<Model> models_;
 public:
     // VulkanTempleRayTracedRenderer::new (renderer.rs:140); camera defaults of renderer.rs:222-231
-    Renderer(uint32_t width, uint32_t height, int device = -1, uint32_t frames_in_flight = 1)
+    Renderer(uint32_t width, uint32_t height, int device = -1, uint32_t frames_in_flight = 1, uint32_t extra_flags = 0)   // extra_flags: ART_FLAG_* besides the host's own
         : w_(width), h_(height), camera_({0, 0, 0}, {0, 0, 1}, (float)width / (float)height, 1.57079632679f, 0.1f, 1000.0f) {
         ArtConfig cfg{}; cfg.device = device; cfg.width = width; cfg.height = height; cfg.frames_in_flight = frames_in_flight;
-        cfg.flags = ART_FLAG_DYNAMIC_SCENE;   // this host moves its models (set_model_matrix) and switches them in and out by residency: the ring of structure versions is made by the build, not by the first moved frame
+        cfg.flags = ART_FLAG_DYNAMIC_SCENE | extra_flags;   // this host moves its models (set_model_matrix) and switches them in and out by residency: the ring of structure versions is made by the build, not by the first moved frame
         check(art_create(&cfg, &ctx_));
     }
     Renderer(const Renderer &) = delete;
@@ -243,6 +251,12 @@ public:
         check(art_set_lights(ctx_, ls.data(), (uint32_t)ls.size()));
         check(art_trace(ctx_));
         if (wait) check(art_sync(ctx_));
+    }
+    // the cull masks of the rays render_frame (primary, shadow) and compute_ao (ao) cast (Vulkan: traceRayEXT's cullMask; the reference hard-codes 0xFF,
+    // raytrace.rgen.glsl:92,169): per-launch state like the camera; 0 is legal, such a ray sees nothing (art_set_ray_masks)
+    void set_ray_masks(uint32_t primary = 0xFFu, uint32_t shadow = 0xFFu, uint32_t ao = 0xFFu) {
+        if (primary > 0xFFu || shadow > 0xFFu || ao > 0xFFu) throw Panic(ART_E_INVALID, "Renderer::set_ray_masks: a mask must lie in 0..0xFF");
+        check(art_set_ray_masks(ctx_, primary, shadow, ao));
     }
     void compute_ao(uint32_t spp = 16, float radius = 0.2f * 1.457f) { check(art_trace_ao(ctx_, spp, radius)); } // ao_layer.compute_ao, renderer.rs:688
     void resize(uint32_t w, uint32_t h) { check(art_resize(ctx_, w, h)); w_ = w; h_ = h; camera_.set_aspect((float)w / (float)h); } // renderer.rs:523-564

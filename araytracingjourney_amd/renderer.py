@@ -270,6 +270,18 @@ class Model:
         if self._renderer is not None:
             check(self._renderer._L.art_scene_set_alpha_cutoff(self._renderer._ctx, self.primitive_ids[primitive_index], c))
 
+    def set_mask(self, primitive_index, mask):
+        """Visibility mask (Vulkan: VkAccelerationStructureInstanceKHR.mask; the reference hard-codes 0xFF, vk_model.rs:373): a hit on primitive
+        `primitive_ids[primitive_index]` is discarded for every ray whose cull mask shares no bit with `mask` (Renderer.set_ray_masks, the queries' cull_mask).
+        0xFF is the default, 0 hides it from every ray; mask must lie in 0..0xFF.  Nothing is built: the next frame takes it up (art_scene_set_primitive_mask)."""
+        v = _mask_value("mask", mask)
+        if isinstance(primitive_index, bool) or not isinstance(primitive_index, (int, np.integer)):
+            raise TypeError("primitive_index must be an integer")
+        if not 0 <= primitive_index < len(self.primitive_ids):
+            raise IndexError("primitive_index out of range")
+        if self._renderer is not None:
+            check(self._renderer._L.art_scene_set_primitive_mask(self._renderer._ctx, self.primitive_ids[primitive_index], v))
+
     def get_transform_model_matrix(self):           # vk_model.rs:358-363
         return None if self.model_matrix is None else self.model_matrix.copy()
 
@@ -278,6 +290,19 @@ class Model:
 
     def reset_command_buffer_submission_status(self):
         self.needs_cb_submit = False
+
+
+# the named bits of include/art.h: a convention only, the library gives bits no meaning
+MASK_ALL, VIS_CAMERA, VIS_SHADOW, VIS_AO, VIS_QUERY = 0xFF, 1, 2, 4, 8
+
+
+def _mask_value(name, v):
+    """an 8-bit visibility / cull mask: an integer in 0..0xFF"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer")
+    if not 0 <= int(v) <= 0xFF:
+        raise ValueError(f"{name} must lie in 0..0xFF")
+    return int(v)
 
 
 class Renderer:
@@ -619,19 +644,28 @@ class Renderer:
         a = np.ascontiguousarray(table, dtype=np.uint32)
         check(self._L.art_write_shadow_hints(self._ctx, _ptr(a), a.size))
 
-    def query_closest(self, rays):
+    def set_ray_masks(self, primary=0xFF, shadow=0xFF, ao=0xFF):
+        """the cull masks of the rays trace() (primary, shadow) and trace_ao() (ao) cast (Vulkan: traceRayEXT's cullMask; the reference hard-codes 0xFF,
+        raytrace.rgen.glsl:92,169): a ray sees a primitive iff its mask (Model.set_mask) shares a bit with the ray's.  Per-launch state like the camera: a
+        frame keeps what was current at its trace().  0 is legal: such a ray sees nothing (art_set_ray_masks)."""
+        p, s, a = _mask_value("primary", primary), _mask_value("shadow", shadow), _mask_value("ao", ao)
+        check(self._L.art_set_ray_masks(self._ctx, p, s, a))
+
+    def query_closest(self, rays, cull_mask=0xFF):
+        m = _mask_value("cull_mask", cull_mask)
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]
         tuv = np.zeros((n, 4), np.float32)
         ids = np.zeros((n, 2), np.int32)
-        check(self._L.art_query_closest(self._ctx, _ptr(rays), n, _ptr(tuv), _ptr(ids)))
+        check(self._L.art_query_closest_masked(self._ctx, _ptr(rays), n, m, _ptr(tuv), _ptr(ids)))   # (0xFF is art_query_closest)
         return tuv, ids
 
-    def query_any(self, rays):
+    def query_any(self, rays, cull_mask=0xFF):
+        m = _mask_value("cull_mask", cull_mask)
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]
         hit = np.zeros(n, np.uint8)
-        check(self._L.art_query_any(self._ctx, _ptr(rays), n, _ptr(hit)))
+        check(self._L.art_query_any_masked(self._ctx, _ptr(rays), n, m, _ptr(hit)))   # (0xFF is art_query_any)
         return hit
 
     def get_lbvh(self):

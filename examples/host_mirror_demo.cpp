@@ -3,9 +3,11 @@
 //   host_mirror_demo render <file.glb> [W H]   add_model + lights of main.rs + one frame; prints ray counts and a colour checksum
 //   host_mirror_demo deform <file.glb> [W H]   the same scene; then Model::set_vertices on its first primitive (grown from the origin) and back
 //   host_mirror_demo alpha <file.glb> [W H]    the same scene with add_model(..., alpha_mask = true), with the cutoffs set by hand, and opaque
+//   host_mirror_demo masks <file.glb> [W H]    the same scene with its LAST primitive (a planar one) seen but casting no shadow (Model::set_mask, Renderer::set_ray_masks)
 #include <cstdio>
 #include <cstring>
 #include "../araytracingjourney_amd/host/art_renderer.hpp"
+#include "../include/art_parity.h"
 
 static int host_checks() {
     using namespace art;
@@ -158,7 +160,40 @@ int main(int argc, char **argv) {
                         (unsigned long long)s2.shadow_rays, s1.rebuilds);
             return 0;
         }
-        std::puts("usage: host_mirror_demo check | render <file.glb> [W H] | deform <file.glb> [W H] | alpha <file.glb> [W H]");
+        if (argc >= 3 && !std::strcmp(argv[1], "masks")) {
+            // ray visibility masks: the model's last primitive (planar, so it cannot occlude rays that start on itself) gets the mask CAMERA | AO while primary / shadow / AO
+            // rays carry CAMERA / SHADOW / AO: it is seen but casts no shadow.  That frame is a composite of two others, bit for bit: the plain frame where the primary hit is
+            // that primitive, the frame without it (disabled) everywhere else.
+            uint32_t W = argc >= 5 ? (uint32_t)std::atoi(argv[3]) : 800, H = argc >= 5 ? (uint32_t)std::atoi(argv[4]) : 800;
+            std::vector<int32_t> ids((size_t)W * H * 2);
+            auto frame = [&](int how, ArtStats &st, int32_t &last) {   // 0: plain, 1: the last primitive disabled, 2: seen but shadowless
+                art::Renderer renderer(W, H, -1, 1, ART_FLAG_KEEP_DEBUG);
+                renderer.add_model(argv[2], {2, 0, 0, 0, 0, 2, 0, 0, 0, 0, 2, 0});
+                renderer.lights_mut().get_spot_lights_mut().push_back(art::SpotLight({0.0f, 1.5f, 0.0f}, {0.0f, -1.0f, 0.0f}, {13.6f, 1.6f, 22.2f}, 3.0f, {0.5236f, 0.7854f}, true));
+                renderer.lights_mut().get_point_lights_mut().push_back(art::PointLight({0.0f, 0.5f, -1.5f}, {8, 8, 8}, 6.0f, true));
+                renderer.camera_mut().set_pos({0.0f, 0.3f, -2.5f});
+                renderer.prepare_first_frame();
+                art::Model &m = renderer.models_mut()[0];
+                last = (int32_t)m.primitive_ids.back();
+                if (how == 1) art::check(art_scene_set_primitive_enabled(renderer.handle(), m.primitive_ids.back(), 0));
+                if (how == 2) { m.set_mask(m.primitive_ids.size() - 1, ART_VIS_CAMERA | ART_VIS_AO); renderer.set_ray_masks(ART_VIS_CAMERA, ART_VIS_SHADOW, ART_VIS_AO); }
+                renderer.render_frame();
+                st = renderer.stats();
+                if (how == 0) { std::vector<float> tuv((size_t)W * H * 4); art::check(art_read_hits(renderer.handle(), tuv.data(), ids.data(), (size_t)W * H)); }
+                return renderer.color_output();
+            };
+            ArtStats s0, s1, s2; int32_t last = -1;
+            std::vector<float> plain = frame(0, s0, last), off = frame(1, s1, last), shadowless = frame(2, s2, last);
+            bool composite = true; size_t seen = 0;
+            for (size_t p = 0; p < (size_t)W * H; p++) {
+                const bool on_it = ids[2 * p] == last; seen += on_it;
+                composite = composite && std::memcmp(&shadowless[4 * p], on_it ? &plain[4 * p] : &off[4 * p], 16) == 0;
+            }
+            std::printf("MASKS_OK primitive=%d seen_pixels=%zu shadowless_equals_composite=%d differs_from_plain=%d differs_from_off=%d shadow_rays=%llu shadow_rays_plain=%llu rebuilds=%u\n", last, seen,
+                        (int)composite, (int)(shadowless != plain), (int)(shadowless != off), (unsigned long long)s2.shadow_rays, (unsigned long long)s0.shadow_rays, s2.rebuilds);
+            return 0;
+        }
+        std::puts("usage: host_mirror_demo check | render <file.glb> [W H] | deform <file.glb> [W H] | alpha <file.glb> [W H] | masks <file.glb> [W H]");
         return 2;
     } catch (const art::Panic &p) {
         std::printf("PANIC(%d): %s\n", p.code, p.what());

@@ -160,6 +160,26 @@ int32_t art_scene_set_primitive_enabled(ArtContext *ctx, uint32_t primitive_id, 
  * keep the cutoffs they were launched with.  NaN, a value outside [0, 1], an unknown id or a null context is ART_E_INVALID and changes nothing.  Scenes in which no
  * enabled primitive has a cutoff > 0 run the kernels without the test.  Every rank of an art_mgpu job must make the same calls.  DESIGN.md 3.2. */
 int32_t art_scene_set_alpha_cutoff(ArtContext *ctx, uint32_t primitive_id, float cutoff);
+/* Ray visibility masks (Vulkan: VkAccelerationStructureInstanceKHR.mask against traceRayEXT's cullMask; the reference hard-codes both to 0xFF, vk_model.rs:373,
+ * raytrace.rgen.glsl:92,169): every primitive has an 8-bit visibility mask and every ray an 8-bit cull mask, 0xFF each by default.  A candidate hit on a primitive is
+ * discarded iff (mask of the primitive & cull mask of the ray) == 0 -- per candidate, before the alpha test (an invisible candidate fetches no texel), for primary,
+ * shadow and AO rays and the masked queries of art_parity.h.  The library gives the bits no meaning; the names below are a convention only. */
+#define ART_MASK_ALL 255u /* 0xFF */
+#define ART_VIS_CAMERA 1u
+#define ART_VIS_SHADOW 2u
+#define ART_VIS_AO 4u
+#define ART_VIS_QUERY 8u
+/* The visibility mask of primitive `primitive_id`.  May be called at any time; on a built scene nothing is built: the NEXT art_trace (or query) takes it up, as for
+ * art_scene_set_alpha_cutoff, and frames in flight keep the masks they were launched with; a rebuild takes the masks along.  ArtStats.rebuilds and
+ * art_scene_needs_build are untouched.  A mask above 0xFF, an unknown id or a null context is ART_E_INVALID and changes nothing.  Every rank of an art_mgpu job
+ * must make the same calls.  DESIGN.md 3.4. */
+int32_t art_scene_set_primitive_mask(ArtContext *ctx, uint32_t primitive_id, uint32_t mask);
+/* The cull masks of the rays art_trace (primary, shadow) and art_trace_ao (ao) cast.  Per-launch state like the camera: a frame keeps what was current at its
+ * art_trace -- art_trace_ao casts its rays with the AO mask of the frame it follows -- and all frames of a launch (art_set_frames_per_launch) share them.  0 is
+ * legal: such a ray sees nothing.  A shadow ray is traced, and counted in ArtStats.shadow_rays, whether or not it can see anything; hit_pixels follows what the
+ * primary rays see.  A value above 0xFF or a null context is ART_E_INVALID and changes nothing.  Scenes in which every enabled primitive has the mask 0xFF and no
+ * cutoff, traced with no cull mask of 0, run the kernels without the test. */
+int32_t art_set_ray_masks(ArtContext *ctx, uint32_t primary, uint32_t shadow, uint32_t ao);
 /* 1: the next art_trace would fail with ART_E_STATE until art_scene_build has run (primitives added, or enabled that the last build did not contain); 0: it would not */
 int32_t art_scene_needs_build(const ArtContext *ctx);
 /* VkModel::set_model_matrix (vk_model.rs:461-466) -> get_transform_model_matrix (:358-363) -> the instance record of the per-frame TLAS

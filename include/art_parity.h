@@ -60,6 +60,10 @@ int32_t art_write_shadow_hints(ArtContext *ctx, const uint32_t *words, size_t n_
 /* arbitrary ray queries on the built scene.  rays: n x 8 floats (o.xyz, tmin, d.xyz, tmax), host memory. */
 int32_t art_query_closest(ArtContext *ctx, const float *rays, uint32_t n, float *tuv, int32_t *ids);
 int32_t art_query_any(ArtContext *ctx, const float *rays, uint32_t n, uint8_t *hit);
+/* the same queries with a cull mask for their rays (art.h, ray visibility masks: a candidate on a primitive whose mask shares no bit with cull_mask is discarded;
+ * 0 sees nothing, above 0xFF is ART_E_INVALID); art_query_closest / art_query_any are the 0xFF case */
+int32_t art_query_closest_masked(ArtContext *ctx, const float *rays, uint32_t n, uint32_t cull_mask, float *tuv, int32_t *ids);
+int32_t art_query_any_masked(ArtContext *ctx, const float *rays, uint32_t n, uint32_t cull_mask, uint8_t *hit);
 /* the device-built binary LBVH, in the oracle's canonical form (any pointer may be NULL):
  * leaf_gid[T], keys[T], child[2*(T-1)], node_lo/hi[(T-1)*3], leaf_lo/hi[T*3] */
 int32_t art_get_lbvh(ArtContext *ctx, uint32_t *leaf_gid, uint64_t *keys, int32_t *child, float *node_lo,
