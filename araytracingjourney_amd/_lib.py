@@ -66,6 +66,17 @@ class ArtTuning(C.Structure):
                [(n, C.c_uint32) for n in ("ao_entry_off", "trace_chunk", "trace_refill", "trace_blocks", "hw_queues", "log", "wide_builder", "as_versions")] + [("refit_rebuild_ratio", C.c_float), ("trace_leaf_batch", C.c_uint32), ("plan_moving_interval", C.c_uint32), ("refit_streams", C.c_uint32), ("refit_fold_nodes", C.c_uint32), ("shadow_hints", C.c_uint32)]
 
 
+ART_CAST_CLOSEST, ART_CAST_ANY = 0, 1
+ART_CAST_MAX_RAYS = 2147418112   # 2^31 - 65536 (include/art.h)
+ART_CAST_POOL = 32               # casts in flight before art_cast_rays waits for the oldest
+
+
+class ArtRayCast(C.Structure):
+    """one art_cast_rays: device pointers, the stream, and what to trace"""
+    _fields_ = [("rays_dev", C.c_void_p), ("tuv_dev", C.c_void_p), ("ids_dev", C.c_void_p), ("hit_dev", C.c_void_p), ("hip_stream", C.c_void_p),
+                ("n", C.c_uint32), ("kind", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class ArtLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "frames_in_flight", "frames_per_launch", "shard_rank", "shard_count", "tiles_owned", "tiles_padded",
                                           "tile_bytes", "reserved")]
@@ -114,6 +125,9 @@ SYMBOLS = {
     "art_resize": (_I32, [_P, _U32, _U32]),
     "art_trace": (_I32, [_P]),
     "art_sync": (_I32, [_P]),
+    "art_cast_rays": (_I32, [_P, _P]),
+    "art_cast_sync": (_I32, [_P]),
+    "art_cast_counts": (_I32, [_P, _P, _P, _P]),
     "art_present": (_I32, [_P]),
     "art_read_present": (_I32, [_P, _P, _SZ]),
     "art_read_packed": (_I32, [_P, _P, _P, _P]),

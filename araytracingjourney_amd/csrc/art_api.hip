@@ -149,6 +149,20 @@ struct AsVersion {
     ArtVertex *h_stage = nullptr; float *d_stage = nullptr;
 };
 
+// Rays in device buffers (art_cast_rays).  Every cast takes the next of a ring of ART_CAST_POOL blocks: the block's work cursors (zeroed on the cast's stream in
+// front of the launch), and an event recorded behind the launch on that stream.  The event is all the host ever needs of a cast, whichever stream the caller gave: the block is
+// free again once it has fired (a ring that is lapped waits for it on the host: CastState::host_waits), the version of the structure the cast reads may be rewritten once it
+// has fired (scene_refresh), and art_cast_sync / sync_all wait for the events of all blocks.  (One event per VERSION behind "the latest cast that reads it" would not do: casts
+// on two callers' streams are not ordered, so the latest says nothing about the one before.)
+struct CastBlock { hipEvent_t ev = nullptr; bool set = false; uint32_t version = 0; };
+struct CastState {
+    hipStream_t stream = nullptr;              // made by the first cast: casts with hip_stream NULL, the queries, and the refit a cast finds pending when the context has no refit streams
+    uint32_t *cursors = nullptr;               // ART_CAST_POOL * kCastCursorWords words, one allocation
+    CastBlock block[ART_CAST_POOL]; uint32_t next = 0;
+    uint64_t casts = 0, rays = 0, host_waits = 0;
+    DevBuf<float4> q_rays; DevBuf<uint8_t> q_out;   // art_query_*: the rays and the records of one query at a time on the device; they only grow
+};
+
 struct ArtContext {
     ArtConfig cfg{};
     int device = 0;
@@ -213,6 +227,7 @@ struct ArtContext {
     DevBuf<uint32_t> d_tile_slot;   // un-tile table: tile -> owner << 24 | index among the owner's tiles (every shard's layout, setup_frame)
     DevBuf<uint32_t> d_block_order; // launch block -> 256-pixel block of the frame: one L2 (XCD) per screen region (setup_frame)
     WavePlan plan;                  // fused frame: wave -> (8x8 block, cells)
+    CastState cast;                 // rays in device buffers
     // Shadow-occluder hints of the fused frame's any-hit packet walks (FrameArgs::hints): ONE table for the context -- not one per ring slot: the frames in
     // flight feed each other -- of (n_local / 64) * kHintLights entries of four leaf positions.  All 0xFF (empty) after setup_frame (allocation, resize) and after every
     // art_scene_build (leaf positions change; the build the refit's cost rule starts is one); both run with nothing in flight.  Refits, moves, deformations, enable / disable,
@@ -299,7 +314,14 @@ int32_t ensure_wide(ArtContext *c, bool needed) {
     return ART_OK;
 }
 
+// every cast enqueued so far has finished, on whichever stream it runs
+int32_t cast_wait_all(ArtContext *c) {
+    for (CastBlock &b : c->cast.block) if (b.set) { HIPC(hipEventSynchronize(b.ev)); b.set = false; }
+    return ART_OK;
+}
 int32_t sync_all(ArtContext *c) {
+    { int32_t r = cast_wait_all(c); if (r) return r; }   // (first: a cast may stand behind a refit below, never the other way round)
+    if (c->cast.stream) HIPC(hipStreamSynchronize(c->cast.stream));   // (a refit a cast put there, the zeroing of a block)
     for (uint32_t i = 0; i < c->n_refit_streams; i++) HIPC(hipStreamSynchronize(c->refit_stream[i]));   // (a refit no frame has waited for yet)
     if (c->plan.plan_stream && c->plan.pending) { for (uint32_t k = 0; k < c->F; k++) HIPC(hipStreamSynchronize(c->stream_of(k))); HIPC(hipStreamSynchronize(c->plan.plan_stream)); }   // (a plan behind a sampled frame)
     for (uint32_t k = 0; k < c->F; k++) HIPC(hipStreamSynchronize(c->stream_of(k)));
@@ -425,6 +447,7 @@ void harvest_cost(ArtContext *c) {
 // written are waited for on the host, like the reference's per-frame fence (renderer.rs:451-466).
 // What the stream sees: three launches and one event record (round 3: two uploads, a launch per tree level, a clear, the cost's read-back and four event records --
 // twenty operations, 0.3 ms of issue in front of a 0.1 ms refit).
+// (k = ~0u: in front of a cast, s a stream of the context that no frame runs on: every ring slot's frames are waited for, every later launch waits for V.ready)
 int32_t scene_refresh(ArtContext *c, uint32_t k, hipStream_t s) {
     if (!c->xform_dirty) return ART_OK;
     int32_t r;
@@ -456,6 +479,14 @@ int32_t scene_refresh(ArtContext *c, uint32_t k, hipStream_t s) {
             }
         }
         V.used[j] = 0; V.aux[j] = false;
+    }
+    {   // casts still reading it (art_cast_rays: a cast holds the version it was launched on): the same wait, counted
+        bool waited = false;
+        for (CastBlock &b : c->cast.block) if (b.set && b.version == next) {
+            if (hipEventQuery(b.ev) != hipSuccess) { (void)hipGetLastError(); HIPC(hipEventSynchronize(b.ev)); waited = true; }
+            b.set = false;
+        }
+        if (waited) c->cast.host_waits++;
     }
     // the staging memory below is read by the kernels of the refit that wrote this version last: that refit has to be over before the host writes it again (it is, whenever the
     // frames above were waited for -- they ran behind it -- but nothing else says so: a version no frame ever read, a ring slot that skipped its turn)
@@ -863,7 +894,12 @@ int32_t art_destroy(ArtContext *c) {
     (void)hipSetDevice(c->device);
     for (uint32_t k = 0; k < c->F; k++) if (c->stream_of(k)) (void)hipStreamSynchronize(c->stream_of(k));
     drop_graphs(c);
+    (void)cast_wait_all(c);   // casts on callers' streams too
     for (uint32_t i = 0; i < c->n_refit_streams; i++) if (c->refit_stream[i]) { (void)hipStreamSynchronize(c->refit_stream[i]); (void)hipStreamDestroy(c->refit_stream[i]); }
+    for (CastBlock &b : c->cast.block) if (b.ev) (void)hipEventDestroy(b.ev);
+    if (c->cast.cursors) (void)hipFree(c->cast.cursors);
+    c->cast.q_rays.release(); c->cast.q_out.release();
+    if (c->cast.stream) release_stream(c->device, c->cast.stream);
     as_release(c);
     lbvh_free(c->bvh); c->arena.release();
     c->d_verts.release(); c->d_indices.release(); c->d_tex.release(); c->d_prims.release(); c->d_first_tri.release(); c->d_ao_tab.release();
@@ -945,6 +981,7 @@ int32_t art_scene_add_primitive(ArtContext *c, const ArtVertex *verts, uint32_t 
 
 int32_t art_scene_clear(ArtContext *c) {
     if (!c) return fail(ART_E_INVALID, "art_scene_clear: null context");
+    if (c->cast.stream) { int32_t r = use_device(c); if (r) return r; r = cast_wait_all(c); if (r) return r; }   // outstanding casts read the scene that goes away
     c->prims.clear(); c->uploaded.clear(); c->built = false;
     return ART_OK;
 }
@@ -1905,6 +1942,114 @@ int32_t art_write_shadow_hints(ArtContext *c, const uint32_t *words, size_t n_wo
     return ART_OK;
 }
 
+// ---- rays in device buffers (include/art.h: art_cast_rays) ------------------------------------------------------------------------------------
+// the first cast of a context: its stream (counted against the budget beside kMaxFrameSlots), the cursor blocks and their events
+static int32_t cast_setup(ArtContext *c) {
+    CastState &K = c->cast;
+    if (K.stream) return ART_OK;
+    uint32_t *cur = nullptr;
+    HIPC(hipMalloc(&cur, (size_t)ART_CAST_POOL * kCastCursorWords * 4));
+    hipError_t e = hipSuccess;
+    for (CastBlock &b : K.block) if (e == hipSuccess && !b.ev) e = hipEventCreateWithFlags(&b.ev, hipEventDisableTiming);
+    hipStream_t s = nullptr;
+    if (e == hipSuccess) e = acquire_stream(c->device, &s);
+    if (e != hipSuccess) { (void)hipFree(cur); return hipfail(e, "art_cast_rays: the cast stream, cursor blocks and events"); }   // (events made so far stay: art_destroy)
+    K.cursors = cur; K.stream = s;
+    return ART_OK;
+}
+// Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
+static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block) {
+    int32_t r = use_device(c); if (r) return r;
+    r = cast_setup(c); if (r) return r;
+    CastState &K = c->cast;
+    if (c->xform_dirty) { r = scene_refresh(c, ~0u, K.stream); if (r) return r; }   // the scene as of the call: the refit in front of the cast (past the cost threshold: a rebuild)
+    r = ensure_wide(c, true); if (r) return r;
+    hipStream_t s = user ? user : K.stream;
+    const uint32_t ver = c->as_cur;
+    if (!c->as.empty()) {
+        AsVersion &V = c->as[ver];
+        if (!V.ready_known) {   // the refit that wrote this version may still run: an event wait on the cast's stream, nothing on the host
+            if (hipEventQuery(V.ready) == hipSuccess) V.ready_known = true;
+            else { (void)hipGetLastError(); HIPC(hipStreamWaitEvent(s, V.ready, 0)); }
+        }
+    }
+    const uint32_t bi = K.next % ART_CAST_POOL;
+    CastBlock &B = K.block[bi];
+    if (B.set) {   // the ring of cursor blocks is lapped: its oldest cast has to be over
+        if (hipEventQuery(B.ev) != hipSuccess) { (void)hipGetLastError(); HIPC(hipEventSynchronize(B.ev)); K.host_waits++; }
+        B.set = false;
+    }
+    uint32_t *cursors = K.cursors + (size_t)bi * kCastCursorWords;
+    HIPC(hipMemsetAsync(cursors, 0, kCastCursorWords * 4, s));
+    const AsPtrs as = as_ptrs(c, ver);
+    CastArgs a{};
+    a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
+    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = (uint8_t *)hit; a.cursors = cursors;
+    a.tune = TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch};
+    a.alpha = c->alpha_live || cull == 0u;   // the filtered instances run while the scene needs them or the mask is 0 (such rays see nothing, and no leaf bit says so)
+    a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p; a.cull = cull;
+    launch_cast(a, s);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(B.ev, s));
+    B.set = true; B.version = ver; K.next++; K.casts++; K.rays += n;
+    if (block) *block = bi;
+    return ART_OK;
+}
+
+int32_t art_cast_rays(ArtContext *c, const ArtRayCast *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_cast_rays: null argument");
+    if (d->kind != ART_CAST_CLOSEST && d->kind != ART_CAST_ANY) return fail(ART_E_INVALID, "art_cast_rays: kind: ART_CAST_CLOSEST or ART_CAST_ANY");
+    if (d->flags != 0u) return fail(ART_E_INVALID, "art_cast_rays: flags: must be 0");
+    if (d->cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_cast_rays: cull_mask: above 0xFF");
+    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_cast_rays: n: above ART_CAST_MAX_RAYS");
+    const bool any = d->kind == ART_CAST_ANY;
+    auto bad = [&](const void *p, size_t align) { return (p == nullptr && d->n != 0u) || ((uintptr_t)p & (align - 1)) != 0; };   // (n = 0 touches nothing: a null buffer is one of no rays)
+    if (bad(d->rays_dev, 16)) return fail(ART_E_INVALID, "art_cast_rays: rays_dev: null or not 16-byte aligned");
+    if (any) {
+        if (d->tuv_dev || d->ids_dev) return fail(ART_E_INVALID, "art_cast_rays: tuv_dev / ids_dev: must be NULL for ART_CAST_ANY");
+        if (bad(d->hit_dev, 1)) return fail(ART_E_INVALID, "art_cast_rays: hit_dev: null");
+    } else {
+        if (d->hit_dev) return fail(ART_E_INVALID, "art_cast_rays: hit_dev: must be NULL for ART_CAST_CLOSEST");
+        if (bad(d->tuv_dev, 16)) return fail(ART_E_INVALID, "art_cast_rays: tuv_dev: null or not 16-byte aligned");
+        if (bad(d->ids_dev, 8)) return fail(ART_E_INVALID, "art_cast_rays: ids_dev: null or not 8-byte aligned");
+    }
+    if (!c->built) return fail(ART_E_STATE, "art_cast_rays: scene not built (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    return cast_enqueue(c, d->rays_dev, d->n, any, d->cull_mask, d->tuv_dev, d->ids_dev, d->hit_dev, (hipStream_t)d->hip_stream, nullptr);
+}
+
+int32_t art_cast_sync(ArtContext *c) {
+    if (!c) return fail(ART_E_INVALID, "art_cast_sync: null context");
+    if (!c->cast.stream) return ART_OK;   // nothing was ever cast
+    int32_t r = use_device(c); if (r) return r;
+    return cast_wait_all(c);
+}
+
+int32_t art_cast_counts(ArtContext *c, uint64_t *casts, uint64_t *rays, uint64_t *host_waits) {
+    if (!c) return fail(ART_E_INVALID, "art_cast_counts: null context");
+    if (casts) *casts = c->cast.casts;
+    if (rays) *rays = c->cast.rays;
+    if (host_waits) *host_waits = c->cast.host_waits;
+    return ART_OK;
+}
+
+// The queries of include/art_parity.h: host wrappers over the cast -- the rays into a device buffer the context keeps (it only grows), one cast on the context's cast stream,
+// that cast's event as the fence, the records back.  Frames in flight are not waited for.
+static int32_t query_by_cast(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, bool any, float *tuv, int32_t *ids, uint8_t *hit, const char *who) {
+    if (n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, std::string(who) + ": more than ART_CAST_MAX_RAYS rays");
+    int32_t r = use_device(c); if (r) return r;
+    CastState &K = c->cast;
+    const size_t out_bytes = any ? (size_t)n : (size_t)n * 24;   // t,u,v,0 of every ray, then the id pairs
+    HIPC(K.q_rays.ensure((size_t)n * 2)); HIPC(K.q_out.ensure(out_bytes));   // (the cast that read them last was fenced by its query)
+    HIPC(hipMemcpy(K.q_rays.p, rays, (size_t)n * 32, hipMemcpyHostToDevice));
+    uint32_t bi = 0;
+    r = cast_enqueue(c, K.q_rays.p, n, any, cull_mask, any ? nullptr : K.q_out.p, any ? nullptr : K.q_out.p + (size_t)n * 16, any ? K.q_out.p : nullptr, nullptr, &bi);
+    if (r) return r;
+    HIPC(hipEventSynchronize(K.block[bi].ev)); K.block[bi].set = false;
+    if (any) HIPC(hipMemcpy(hit, K.q_out.p, n, hipMemcpyDeviceToHost));
+    else { HIPC(hipMemcpy(tuv, K.q_out.p, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(ids, K.q_out.p + (size_t)n * 16, (size_t)n * 8, hipMemcpyDeviceToHost)); }
+    return ART_OK;
+}
 int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *tuv, int32_t *ids) { return art_query_closest_masked(c, rays, n, 0xFFu, tuv, ids); }
 // (the rays' cull mask, DESIGN.md 3.4: 0xFF is art_query_closest; the filtered tracer instances run while the scene needs them or the mask is 0)
 int32_t art_query_closest_masked(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, float *tuv, int32_t *ids) {
@@ -1912,31 +2057,7 @@ int32_t art_query_closest_masked(ArtContext *c, const float *rays, uint32_t n, u
     if (cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_query_closest_masked: cull_mask: above 0xFF");
     if (!c->built) return fail(ART_E_STATE, "art_query_closest: scene not built");
     if (n == 0) return ART_OK;
-    int32_t r = use_device(c); if (r) return r;
-    float4 *d_r = nullptr, *d_h = nullptr;
-    HIPC(hipMalloc(&d_r, (size_t)n * 32));
-    hipError_t e = hipMalloc(&d_h, (size_t)n * 16);
-    if (e != hipSuccess) { (void)hipFree(d_r); return hipfail(e, "hipMalloc"); }
-    std::vector<float4> h(n);
-    std::vector<DevTri> tris(c->T);
-    e = hipMemcpy(d_r, rays, (size_t)n * 32, hipMemcpyHostToDevice);
-    const int qkind = c->kind_primary == 8 ? 2 : c->kind_primary;
-    if (e == hipSuccess && (refresh_now(c) != ART_OK || ensure_wide(c, true) != ART_OK || ensure_binary(c, qkind == 2) != ART_OK)) e = hipErrorUnknown; // (a pending move is applied first)
-    if (e == hipSuccess) e = c->slot[0].d_counters.ensure(kCounterWords);
-    if (e == hipSuccess) e = hipMemsetAsync(c->slot[0].d_counters.p, 0, kCounterWords * 4, c->main_stream());
-    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_closest(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live || cull_mask == 0u, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p, cull_mask}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->main_stream());
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d_h, (size_t)n * 16, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(tris.data(), c->bvh.tris, (size_t)c->T * sizeof(DevTri), hipMemcpyDeviceToHost);
-    (void)hipFree(d_r); (void)hipFree(d_h);
-    if (e != hipSuccess) return hipfail(e, "art_query_closest");
-    for (uint32_t i = 0; i < n; i++) {
-        uint32_t pos; std::memcpy(&pos, &h[i].w, 4);
-        tuv[4 * i] = h[i].x; tuv[4 * i + 1] = h[i].y; tuv[4 * i + 2] = h[i].z; tuv[4 * i + 3] = 0;
-        if (pos == kNoHit) { ids[2 * i] = -1; ids[2 * i + 1] = -1; }
-        else { uint32_t gid; std::memcpy(&gid, &tris[pos].f[15], 4); gid_to_ids(c, gid, ids + 2 * i); }
-    }
-    return ART_OK;
+    return query_by_cast(c, rays, n, cull_mask, false, tuv, ids, nullptr, "art_query_closest");
 }
 
 int32_t art_query_any(ArtContext *c, const float *rays, uint32_t n, uint8_t *hit) { return art_query_any_masked(c, rays, n, 0xFFu, hit); }
@@ -1945,24 +2066,7 @@ int32_t art_query_any_masked(ArtContext *c, const float *rays, uint32_t n, uint3
     if (cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_query_any_masked: cull_mask: above 0xFF");
     if (!c->built) return fail(ART_E_STATE, "art_query_any: scene not built");
     if (n == 0) return ART_OK;
-    int32_t r = use_device(c); if (r) return r;
-    float4 *d_r = nullptr; uint32_t *d_h = nullptr;
-    HIPC(hipMalloc(&d_r, (size_t)n * 32));
-    hipError_t e = hipMalloc(&d_h, (size_t)n * 4);
-    if (e != hipSuccess) { (void)hipFree(d_r); return hipfail(e, "hipMalloc"); }
-    std::vector<uint32_t> h(n);
-    e = hipMemcpy(d_r, rays, (size_t)n * 32, hipMemcpyHostToDevice);
-    const int qkind = c->kind_shadow == 8 ? 4 : c->kind_shadow;
-    if (e == hipSuccess && (refresh_now(c) != ART_OK || ensure_wide(c, true) != ART_OK || ensure_binary(c, qkind == 2) != ART_OK)) e = hipErrorUnknown;
-    if (e == hipSuccess) e = c->slot[0].d_counters.ensure(kCounterWords);
-    if (e == hipSuccess) e = hipMemsetAsync(c->slot[0].d_counters.p, 0, kCounterWords * 4, c->main_stream());
-    if (e == hipSuccess) { const AsPtrs as = as_ptrs(c, c->as_cur); launch_query_any(BvhView{c->bvh.nodes, as.wide, as.tris, qkind, TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch}, c->alpha_live || cull_mask == 0u, c->d_alpha_bits.p, as.shade, as.prims, c->d_tex.p, cull_mask}, d_r, n, d_h, c->slot[0].d_counters.p + 64 + 512, c->main_stream()); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->main_stream());
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d_h, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_r); (void)hipFree(d_h);
-    if (e != hipSuccess) return hipfail(e, "art_query_any");
-    for (uint32_t i = 0; i < n; i++) hit[i] = (uint8_t)h[i];
-    return ART_OK;
+    return query_by_cast(c, rays, n, cull_mask, true, nullptr, nullptr, hit, "art_query_any");
 }
 
 int32_t art_get_lbvh(ArtContext *c, uint32_t *leaf_gid, uint64_t *keys, int32_t *child, float *node_lo, float *node_hi, float *leaf_lo, float *leaf_hi) {

@@ -75,6 +75,7 @@ constexpr uint32_t kNoHit = 0xFFFFFFFFu;
 constexpr int kMaxLights = 16;        // light records that travel in the kernel arguments
 constexpr uint32_t kMaxLightsTotal = 1024; // art_set_lights' bound (records 16.. live in a device table per ring slot)
 constexpr uint32_t kMaxFrameSlots = 24; // ring slots of a context (more than ~22 streams in use stall the command processor)
+                                        // (the budget: the frame streams, up to four refit streams, the wave plan's stream and -- from the first art_cast_rays on -- the cast stream)
 constexpr uint32_t kTileRingMax = 8;    // caller-owned compact tile buffers per ring slot (art_bind_color_tiles_ring)
 int32_t ring_rewind(ArtContext *ctx);   // art_api.hip: waits for every frame in flight, then the next art_trace is launch 0 again (ring slot 0, first tile buffer)
 void set_last_error(const char *msg);   // art_api.hip: the thread's art_last_error() string, for entry points that live in other files
@@ -279,19 +280,28 @@ struct PlanArgs {
     uint32_t *result;
 };
 void launch_plan(const PlanArgs &p, hipStream_t s);
-// ambient occlusion on the frame's depth/normal outputs; occl: n_local*spp bytes; lut: spp+1 output values; cursors at counters[64+512..] are reused (queries never overlap a frame)
+// ambient occlusion on the frame's depth/normal outputs; occl: n_local*spp bytes; lut: spp+1 output values; its cursors are counters[64+512..]
 constexpr uint32_t kAoTableEntriesPerSample = 64 * 64;
 void launch_ao_table(uint32_t spp, float4 *tab, hipStream_t s); // tab: spp * kAoTableEntriesPerSample float4
 // pix: 2 * n_local float4 of scratch (per-pixel origin | start node, normal | noise index); tab: launch_ao_table's; entry_search: start the rays below the root
 void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, float4 *pix, const float4 *tab, bool entry_search, uint32_t *ao, const uint32_t *lut, hipStream_t s);
-struct BvhView { const DevNode *nodes; const DevNode4 *wide; const DevTri *tris; int kind; TraceTune tune;   // kind: 2 | 4
-                 bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool;   // alpha: FrameArgs' (the queries' alpha test)
-                 uint32_t cull = 0xFFu; };   // the queries' cull mask
+// One cast of rays that sit in a device buffer (art_cast_rays; art_query_* are host wrappers over it): rays[2i] = o.xyz,tmin | rays[2i+1] = d.xyz,tmax.
+// Closest (any false): tuv[i] = t,u,v,0 and ids[i] = primitive, triangle in the primitive -- a miss is tmax,0,0,0 and -1,-1; any: hit[i] = 0 | 1.
+struct CastArgs {
+    const DevNode4 *wide; const DevTri *tris;           // the version of the structure the cast reads
+    const uint32_t *tri_prim, *first_tri;               // gid -> primitive (Lbvh::tri_prim); primitive -> its first gid (the build's table): the ids, on the device
+    const float4 *rays; uint32_t n; bool any;
+    float4 *tuv; int2 *ids; uint8_t *hit;
+    uint32_t *cursors;                                  // kCastCursorWords words, zeroed on the cast's stream in front of the launch
+    TraceTune tune;
+    bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool;   // alpha: FrameArgs' (the mask / alpha test)
+    uint32_t cull;                                      // the rays' cull mask
+};
+constexpr uint32_t kCastCursorWords = 8 * 32;           // eight per-XCD cursors, a 128-byte line each
+void launch_cast(const CastArgs &c, hipStream_t s);
 // the bits of FrameArgs::alpha_bits: bit p of word p / 32 |= (prims[primitive of leaf p] has a cutoff > 0 or a visibility mask other than 0xFF); never cleared between builds (art_build.hip)
 void launch_alpha_bits(uint32_t T, const uint32_t *leaf_gid, const uint32_t *tri_prim, const DevPrim *prims, uint32_t *bits, hipStream_t s);
-void launch_query_closest(const BvhView &b, const float4 *rays, uint32_t n, float4 *hits, uint32_t *cursors, hipStream_t s);
-void launch_query_any(const BvhView &b, const float4 *rays, uint32_t n, uint32_t *hit, uint32_t *cursors, hipStream_t s);
-// per-frame counter block (zeroed every frame): [64..] primary cursors, [64+256..] shadow cursors, [64+512..] query cursors,
+// per-frame counter block (zeroed every frame): [64..] primary cursors, [64+256..] shadow cursors, [64+512..] AO cursors,
 // then 64 hit-pixel slots and 64 shadow-ray slots, each on its own 128-byte line: one word would serialise ~11 ns per atomic
 // (32 640 waves on one address cost the shading kernel 0.3 ms)
 constexpr uint32_t kCounterWords = 8192;

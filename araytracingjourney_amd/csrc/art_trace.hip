@@ -195,7 +195,7 @@ constexpr int kTraceBlock = 64;  // the persistent per-ray tracer: likewise (its
 // are throughput-bound -> fewer cursor atomics, fewer resident waves.  A context's ArtTuning (trace_chunk / trace_refill / trace_blocks / trace_leaf_batch)
 // overrides the presets of ITS launches, for sweeps.
 struct Tune { uint32_t chunk, refill, blocks, leaf_batch; };
-// [0] / [1]: primary, shadow and query rays, one frame at a time / several in flight; [2] / [3]: AO rays likewise -- sixteen consecutive slots are one
+// [0] / [1]: primary and shadow rays, one frame at a time / several in flight; [2] / [3]: AO rays likewise -- sixteen consecutive slots are one
 // pixel's rays, a refill is cheap (k_ao_pixels + k_ao_table), and the kernel fits 8 waves per SIMD: larger chunks (a wave stays on 64 neighbouring
 // pixels), all 8 192 wave slots (config 5: 13 700 -> 14 280 Mray/s over the presets of the other rays).  leaf_batch: lanes that must stand on a triangle
 // before the wave runs the triangle test.  1 for the other rays (one frame of them at a time is bound by its slowest wave: waiting lanes lengthen it,
@@ -203,14 +203,14 @@ struct Tune { uint32_t chunk, refill, blocks, leaf_batch; };
 // lanes: 2 / 4 / 8 / 12 / 16 lanes -> 14 510 / 14 930 / 15 370 / 15 330 / 15 070 Mray/s on config 5
 static const Tune kPreset[4] = {{64, 12, 1536, 1}, {128, 24, 1024, 1}, {256, 16, 2048, 8}, {1024, 24, 2048, 8}};
 // the preset for a launch, with the context's overrides (they travel with the launch: nothing process-wide)
-static Tune tune(bool pipelined, bool ao, const TraceTune &o) {
-    Tune t = kPreset[(ao ? 2 : 0) + (pipelined ? 1 : 0)];
+static Tune tune_over(Tune t, const TraceTune &o) {
     if (o.chunk >= 64 && o.chunk <= 65536) t.chunk = o.chunk;
     if (o.refill >= 1 && o.refill <= 64) t.refill = o.refill;
     if (o.blocks >= 1 && o.blocks <= 16384) t.blocks = o.blocks;
     if (o.leaf_batch >= 1 && o.leaf_batch <= 64) t.leaf_batch = o.leaf_batch;
     return t;
 }
+static Tune tune(bool pipelined, bool ao, const TraceTune &o) { return tune_over(kPreset[(ao ? 2 : 0) + (pipelined ? 1 : 0)], o); }
 constexpr int kCursorStride = 32; // one 128-byte line per XCD cursor
 
 // local pixel id -> frame coordinates.  p = tile*1024 + sub*64 + lane; a wave covers an 8x8 pixel block.
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(kBlock) void k_ao_pixels(FrameArgs a, const DevNode
 }
 
 // what a persistent tracing wave reads its rays from and writes its results to
-enum { MODE_PRIMARY = 0, MODE_SHADOW = 1, MODE_QUERY_CLOSEST = 2, MODE_QUERY_ANY = 3, MODE_AO = 4 };
+enum { MODE_PRIMARY = 0, MODE_SHADOW = 1, MODE_QUERY_CLOSEST = 2, MODE_QUERY_ANY = 3, MODE_AO = 4 };   // (2 and 3: the queries' former instances -- see below k_trace: nothing launches them, rays in device buffers have a tracer of their own, k_cast)
 struct TraceArgs {
     const DevNode *nodes; const DevNode4 *wide; const DevTri *tris;
     uint32_t total;          // candidate slots
@@ -924,6 +924,14 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
     }
 }
 
+// The queries' instances of k_trace (MODE_QUERY_CLOSEST / MODE_QUERY_ANY) are launched by nothing any more: art_query_* go through k_cast like every ray in a device buffer, and
+// their launchers are gone.  The instances themselves stay in the code object for one reason: tests/test_alpha.py and tests/test_ray_masks.py pin the presence, registers and
+// scratch of k_trace<2 | 3, 2 | 4, *> by name.  Once those two tests let go of them, these eight lines and the two modes go.
+template __global__ void k_trace<MODE_QUERY_CLOSEST, 2, false>(TraceArgs); template __global__ void k_trace<MODE_QUERY_CLOSEST, 4, false>(TraceArgs);
+template __global__ void k_trace<MODE_QUERY_CLOSEST, 2, true>(TraceArgs);  template __global__ void k_trace<MODE_QUERY_CLOSEST, 4, true>(TraceArgs);
+template __global__ void k_trace<MODE_QUERY_ANY, 2, false>(TraceArgs);     template __global__ void k_trace<MODE_QUERY_ANY, 4, false>(TraceArgs);
+template __global__ void k_trace<MODE_QUERY_ANY, 2, true>(TraceArgs);      template __global__ void k_trace<MODE_QUERY_ANY, 4, true>(TraceArgs);
+
 // The AO launch's own persistent tracer (round 4): rays are MADE by the whole wave, sixty-four at a time, into a pool in LDS, and a lane that finishes TAKES its next ray from
 // the pool at once (a dozen LDS reads) -- in k_trace a finished lane waits until two dozen lanes are idle, because a refill there is ~80 instructions whoever runs it: 48 of
 // 64 lanes held a ray (profiles/README.md round 3).  Same slots, same rays, same walks (Trav4, any hit): the occlusion bytes cannot change.
@@ -1019,6 +1027,118 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
         const uint64_t lm = ballot64(on_leaf);
         if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf, a.alpha); }
         if (done) { active = false; a.occl[slot] = tr.bpos != kNoHit ? 1 : 0; }
+    }
+}
+
+// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT): k_trace_ao's shape with the rays read instead of made.  The whole
+// wave reads the next (up to) 64 rays of its chunk -- two 16-byte loads a lane, 2 KB a wave in one piece -- and writes the live ones into the pool with everything ray_init makes
+// of them; a dead ray (non-finite origin or direction, NaN tmax: TravBase::start's rule) gets its miss record there and then and never enters the pool.  A lane that finishes
+// takes its next ray from the pool at once.  One walk for every context, whatever ArtTuning says: Trav4 over the quantised 4-wide nodes (hits are structure-independent,
+// DESIGN.md 1.1).  Closest hits leave as t,u,v,0 and (primitive, triangle in the primitive): the walk carries the best candidate's gid, tri_prim names its primitive and
+// first_tri that primitive's first gid -- no triangle record, no host.  Any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's record depends on
+// the ray alone.
+struct CastK {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *rays; float4 *tuv; int2 *ids; uint8_t *hit;
+    uint32_t total, chunk, refill, leaf_batch;
+    uint32_t *cursors;        // 8 per-XCD chunk cursors, kCursorStride words apart (zeroed in front of the launch)
+    AlphaView alpha;          // the instances with the mask / alpha test only
+};
+static_assert(kCastCursorWords == 8u * kCursorStride, "a cast's cursor block");
+constexpr int kCastLds = 8;           // per-lane stack entries in LDS: 2 KB + the pool's 3 KB a wave = 32 waves in a CU's 160 KB
+constexpr int kCastPoolFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
+constexpr uint32_t kCastPoolTake = 8; // idle lanes at which the wave turns to the pool (ArtTuning.trace_refill overrides)
+template <bool ANY, bool ALPHA>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) {
+    __shared__ int stack[kCastLds * kTraceBlock];
+    __shared__ float pool[kCastPoolFields][kTraceBlock];
+    int ovf[kOvfStack4 + (kLdsStack - kCastLds)];
+    const uint32_t leaf_batch = a.leaf_batch;
+    int *lds = &stack[threadIdx.x];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // total <= ART_CAST_MAX_RAYS = 2^31 - 65536 and 64 <= chunk <= 65536: total + chunk, chunk ends and n_chunks * 8 fit 32 bits
+    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u; // HW_REG_XCC_ID: speed only
+    uint32_t shards_left = 8;
+    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
+    uint32_t pool_n = 0;         // wave-uniform: rays in the pool
+    bool exhausted = false, active = false;
+    Trav4<ANY, kCastLds, ALPHA> tr;
+    uint32_t slot = 0;
+    for (;;) {
+        const uint64_t idle = ballot64(!active);
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        if (n_idle >= a.refill) {
+            if (pool_n == 0 && !exhausted) {      // the pool is empty: the WHOLE wave reads the next (up to) 64 rays of its chunk
+                if (cur == end) {
+                    uint32_t got = 0xFFFFFFFFu;
+                    if (lane == 0) {
+                        while (shards_left) {
+                            uint32_t lo = (n_chunks * shard) >> 3, hi = (n_chunks * (shard + 1u)) >> 3;
+                            uint32_t c = hi > lo ? atomicAdd(&a.cursors[shard * kCursorStride], 1u) : 0u;
+                            if (hi > lo && c < hi - lo) { got = lo + c; break; }
+                            shard = (shard + 1u) & 7u; shards_left--;
+                        }
+                    }
+                    got = __builtin_amdgcn_readfirstlane(got);
+                    shard = __builtin_amdgcn_readfirstlane(shard);
+                    shards_left = __builtin_amdgcn_readfirstlane(shards_left);
+                    if (got >= n_chunks) exhausted = true;   // (also the never-expected out-of-range pop: no record beyond total is touched)
+                    else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
+                }
+                if (!exhausted) {
+                    const uint32_t take = min(64u, end - cur), sidx = cur + lane;
+                    bool has = false;
+                    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, 0.f);
+                    if (lane < take) {
+                        r0 = a.rays[2 * (size_t)sidx]; r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
+                        has = ray_finite(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z)) && r1.w == r1.w;
+                        if (!has) {                // a dead ray accepts nothing: its miss record, without a walk
+                            if (ANY) a.hit[sidx] = 0;
+                            else { a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1); }
+                        }
+                    }
+                    const uint64_t hm = ballot64(has);
+                    if (has) {
+                        const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+                        const V3 inv = mk(1.0f / safe_dir(r1.x), 1.0f / safe_dir(r1.y), 1.0f / safe_dir(r1.z));   // ray_init's operations
+                        pool[0][at] = r0.x; pool[1][at] = r0.y; pool[2][at] = r0.z; pool[3][at] = r1.x; pool[4][at] = r1.y; pool[5][at] = r1.z;
+                        pool[6][at] = inv.x; pool[7][at] = inv.y; pool[8][at] = inv.z; pool[9][at] = r0.w; pool[10][at] = r1.w; pool[11][at] = __uint_as_float(sidx);
+                    }
+                    pool_n = (uint32_t)__popcll(hm);
+                    cur += take;
+                }
+            }
+            if (pool_n) {                             // idle lanes take rays from the top of the pool
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (!active && rank < pool_n) {
+                    const uint32_t at = pool_n - 1u - rank;
+                    tr.r.o = mk(pool[0][at], pool[1][at], pool[2][at]); tr.r.d = mk(pool[3][at], pool[4][at], pool[5][at]); tr.r.inv = mk(pool[6][at], pool[7][at], pool[8][at]);
+                    tr.r.ood = mk(tr.r.o.x * tr.r.inv.x, tr.r.o.y * tr.r.inv.y, tr.r.o.z * tr.r.inv.z);
+                    tr.r.tmin = pool[9][at]; tr.r.tmax = pool[10][at];
+                    tr.tbest = tr.r.tmax; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.sp = 0; tr.cur = 0;
+                    slot = __float_as_uint(pool[11][at]);
+                    active = true;
+                }
+                pool_n -= min(n_idle, pool_n);
+            } else if (exhausted) { if (n_idle == 64u) break; }
+            if (ballot64(active) == 0ull) continue;   // nothing to trace yet (64 dead rays): read more
+        }
+        bool done = false;
+#pragma unroll
+        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
+            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
+        const bool on_leaf = active && !done && tr.cur < 0;
+        const uint64_t lm = ballot64(on_leaf);
+        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf, a.alpha); }
+        if (done) {
+            active = false;
+            if (ANY) a.hit[slot] = tr.bpos != kNoHit ? 1 : 0;
+            else if (tr.bgid != kNoHit) {             // the ids, on the device: gid -> primitive (k_soup's table) -> triangle in the primitive
+                const uint32_t prim = a.tri_prim[tr.bgid];
+                a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
+                a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+            } else { a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1); }
+        }
     }
 }
 
@@ -1603,20 +1723,20 @@ bool launch_frame(const FrameArgs &a, hipStream_t s) { // returns whether the la
 }
 void launch_frame_stats(const FrameArgs &a, uint32_t *out, hipStream_t s) { k_frame_stats<<<blocks_for(a.n_local), kBlock, 0, s>>>(a, out); }
 void launch_accumulate(const FrameArgs &a, hipStream_t s) { k_accumulate<<<blocks_for(a.n_local), kBlock, 0, s>>>(a); }
-// queries: rays[2i] = o.xyz,tmin | rays[2i+1] = d.xyz,tmax;  cursors: 8 * kCursorStride zeroed words
-void launch_query_closest(const BvhView &b, const float4 *rays, uint32_t n, float4 *hits, uint32_t *cursors, hipStream_t s) {
-    if (!n) return;
-    TraceArgs a{};
-    a.nodes = b.nodes; a.wide = b.wide; a.tris = b.tris; a.total = n; a.cursors = cursors; a.rays = rays; a.hits = hits;
-    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool, b.cull};
-    launch_trace<MODE_QUERY_CLOSEST>(a, b.kind, false, b.tune, b.alpha, s);
-}
-void launch_query_any(const BvhView &b, const float4 *rays, uint32_t n, uint32_t *hit, uint32_t *cursors, hipStream_t s) {
-    if (!n) return;
-    TraceArgs a{};
-    a.nodes = b.nodes; a.wide = b.wide; a.tris = b.tris; a.total = n; a.cursors = cursors; a.rays = rays; a.any_out = hit;
-    a.alpha = AlphaView{b.alpha_bits, b.shade, b.prims, b.tex_pool, b.cull};
-    launch_trace<MODE_QUERY_ANY>(a, b.kind, false, b.tune, b.alpha, s);
+// rays in device buffers (art_cast_rays and, through it, the queries): {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernel has -- a cast is
+// throughput-bound like it -- with the context's ArtTuning overrides
+static const Tune kCastPreset = {256, kCastPoolTake, 2048, 8};
+void launch_cast(const CastArgs &c, hipStream_t s) {
+    if (!c.n) return;
+    const Tune t = tune_over(kCastPreset, c.tune);
+    CastK a{};
+    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.rays = c.rays; a.tuv = c.tuv; a.ids = c.ids; a.hit = c.hit;
+    a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
+    a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
+    const uint32_t nb = persistent_blocks(c.n, t);
+    if (c.any) { if (c.alpha) k_cast<true, true><<<nb, kTraceBlock, 0, s>>>(a); else k_cast<true, false><<<nb, kTraceBlock, 0, s>>>(a); }
+    else if (c.alpha) k_cast<false, true><<<nb, kTraceBlock, 0, s>>>(a);
+    else k_cast<false, false><<<nb, kTraceBlock, 0, s>>>(a);
 }
 // AO resolve: occluded count -> uint(pow(visibility, 2.2) * 255 + 0.5) through a host-built table; 255 where nothing was hit
 #ifdef ART_PACKET_PROF

@@ -259,6 +259,22 @@ public:
         check(art_set_ray_masks(ctx_, primary, shadow, ao));
     }
     void compute_ao(uint32_t spp = 16, float radius = 0.2f * 1.457f) { check(art_trace_ao(ctx_, spp, radius)); } // ao_layer.compute_ao, renderer.rs:688
+    // Rays of the application's own (Vulkan: traceRayEXT from its own ray-generation shader, VK_KHR_ray_query; the reference has no call for it): n rays of 8 floats -- o.xyz,
+    // tmin, d.xyz, tmax -- in DEVICE memory, traced asynchronously on hip_stream (nullptr: a stream the context owns, fenced by cast_sync).  Closest hits: n x 4 floats
+    // t,u,v,0 and n x 2 int32 (primitive, triangle); any hit: n bytes.  The scene is the one of the call: a pending move or mask is taken up first (art_cast_rays).
+    static ArtRayCast closest_cast(const void *rays_dev, uint32_t n, void *tuv_dev, void *ids_dev, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtRayCast d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.hip_stream = hip_stream; d.n = n; d.kind = ART_CAST_CLOSEST; d.cull_mask = cull_mask;
+        return d;
+    }
+    static ArtRayCast any_cast(const void *rays_dev, uint32_t n, void *hit_dev, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtRayCast d{}; d.rays_dev = rays_dev; d.hit_dev = hit_dev; d.hip_stream = hip_stream; d.n = n; d.kind = ART_CAST_ANY; d.cull_mask = cull_mask;
+        return d;
+    }
+    static void cast_rays(ArtContext *ctx, const ArtRayCast &d) { check(art_cast_rays(ctx, &d)); }   // panics like every other call of the mirror
+    void cast_rays(const ArtRayCast &d) { cast_rays(ctx_, d); }
+    void cast_sync() { check(art_cast_sync(ctx_)); }
+    struct CastCounts { uint64_t casts, rays, host_waits; };
+    CastCounts cast_counts() { CastCounts c{}; check(art_cast_counts(ctx_, &c.casts, &c.rays, &c.host_waits)); return c; }
     void resize(uint32_t w, uint32_t h) { check(art_resize(ctx_, w, h)); w_ = w; h_ = h; camera_.set_aspect((float)w / (float)h); } // renderer.rs:523-564
     std::vector<float> color_output() { std::vector<float> o((size_t)w_ * h_ * 4); check(art_read_color(ctx_, o.data(), o.size() * 4)); return o; }
     std::vector<float> depth_output() { std::vector<float> o((size_t)w_ * h_); check(art_read_depth(ctx_, o.data(), o.size() * 4)); return o; }

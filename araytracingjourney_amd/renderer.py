@@ -323,6 +323,7 @@ class Renderer:
             t.hw_queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0)
         check(self._L.art_set_tuning(self._ctx, C.byref(t)))
         self.extent = (w, h)
+        self._device = device
         self.shard = shard
         self.packed_tiles = packed_tiles
         # defaults of renderer.rs:222-231
@@ -650,6 +651,57 @@ class Renderer:
         frame keeps what was current at its trace().  0 is legal: such a ray sees nothing (art_set_ray_masks)."""
         p, s, a = _mask_value("primary", primary), _mask_value("shadow", shadow), _mask_value("ao", ao)
         check(self._L.art_set_ray_masks(self._ctx, p, s, a))
+
+    def cast_rays(self, rays, kind="closest", cull_mask=0xFF, out=None, stream=None):
+        """Trace rays that sit on the device (art_cast_rays: the application's own traceRayEXT).  rays: a torch tensor on this context's device, float32, shape (n, 8) --
+        o.xyz, tmin, d.xyz, tmax -- contiguous and 16-byte aligned.  kind "closest" returns (tuv, ids): (n, 4) float32 t,u,v,0 -- a miss is (tmax, 0, 0, 0) -- and (n, 2) int32
+        (primitive, triangle in the primitive), -1,-1 for a miss; kind "any" returns hit: (n,) uint8.  out: the tensor(s) to write -- (tuv, ids) or hit, of at least n records,
+        which must not overlap the rays -- instead of new ones.  The cast is enqueued on `stream` (a torch stream or a raw hipStream_t; default: torch's current stream) and
+        the call returns: no host synchronisation, the results are ordered behind the cast on that stream like those of any torch operation."""
+        import torch
+        m = _mask_value("cull_mask", cull_mask)
+        if kind not in ("closest", "any"):
+            raise ValueError("kind must be 'closest' or 'any'")
+        if self._device < 0:   # created on "the current device": the one torch calls current (the same HIP runtime state), looked up once
+            self._device = torch.cuda.current_device()
+        dev = self._device
+        if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device.index != dev:
+            raise ValueError(f"rays must be a torch tensor on cuda:{dev}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.data_ptr() % 16:
+            raise ValueError("rays must be float32 of shape (n, 8), contiguous and 16-byte aligned")
+        n = rays.shape[0]
+
+        def _out(t, name, dtype, width, align):
+            ok = isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and \
+                t.shape[0] >= n and tuple(t.shape[1:]) == width
+            if not ok:
+                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n,{' ' + str(width[0]) if width else ''}), {align}-byte aligned")
+            return t
+        d = _lib.ArtRayCast(rays_dev=rays.data_ptr() or None, n=n, cull_mask=m, flags=0)
+        if kind == "closest":
+            tuv, ids = out if out is not None else (torch.empty((n, 4), dtype=torch.float32, device=rays.device), torch.empty((n, 2), dtype=torch.int32, device=rays.device))
+            _out(tuv, "tuv", torch.float32, (4,), 16), _out(ids, "ids", torch.int32, (2,), 8)
+            d.kind, d.tuv_dev, d.ids_dev, res = _lib.ART_CAST_CLOSEST, tuv.data_ptr() or None, ids.data_ptr() or None, (tuv, ids)
+        else:
+            hit = out if out is not None else torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            _out(hit, "hit", torch.uint8, (), 1)
+            d.kind, d.hit_dev, res = _lib.ART_CAST_ANY, hit.data_ptr() or None, hit
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        # torch's default stream is HIP's null stream, handle 0 -- which art_cast_rays reads as "the context's cast stream": hipStreamLegacy (1) names the null stream itself
+        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1
+        check(self._L.art_cast_rays(self._ctx, C.byref(d)))
+        return res
+
+    def cast_sync(self):
+        """every cast enqueued so far has finished, on whichever stream (art_cast_sync)"""
+        check(self._L.art_cast_sync(self._ctx))
+
+    def cast_counts(self) -> dict:
+        """casts enqueued, their rays, and the host waits casts caused (art_cast_counts)"""
+        a, b, w = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self._L.art_cast_counts(self._ctx, C.byref(a), C.byref(b), C.byref(w)))
+        return dict(casts=a.value, rays=b.value, host_waits=w.value)
 
     def query_closest(self, rays, cull_mask=0xFF):
         m = _mask_value("cull_mask", cull_mask)

@@ -35,6 +35,12 @@ static int host_checks() {
     Sphere sp; sp.center = {1, 0, 0}; sp.radius = 2.0f;
     Sphere st = sp.transform({2, 0, 0, 5, 0, 3, 0, 0, 0, 0, 1, 0});                                              // model_reader.rs:128-141
     if (std::fabs(st.center[0] - 7.0f) > 1e-6f || std::fabs(st.radius - 6.0f) > 1e-6f) { std::puts("FAIL sphere transform"); return 1; }
+    // a cast whose answer is known without a device: a descriptor that is well-formed, through no context -- ART_E_INVALID, nothing touched (art_cast_rays)
+    int cast_code = 0; float fake[8] = {0};
+    try { Renderer::cast_rays(nullptr, Renderer::any_cast(fake, 0, nullptr)); } catch (const Panic &p) { cast_code = p.code; }
+    if (cast_code != ART_E_INVALID) { std::puts("FAIL a cast without a context must panic with ART_E_INVALID"); return 1; }
+    const ArtRayCast cd = Renderer::closest_cast(fake, 1, fake, fake, nullptr, 0x0Fu);
+    if (cd.kind != ART_CAST_CLOSEST || cd.hit_dev != nullptr || cd.flags != 0u || cd.cull_mask != 0x0Fu || sizeof(ArtRayCast) != 56) { std::puts("FAIL cast descriptor"); return 1; }
     std::puts("HOST_MIRROR_OK");
     return 0;
 }

@@ -253,6 +253,53 @@ int32_t art_lpm_control_block(int32_t shoulder, float soft_gap, float hdr_max, f
 /* the fence (renderer.rs:451-466) */
 int32_t art_sync(ArtContext *ctx);
 
+/* ---- rays of the application's own (new functionality: in Vulkan terms traceRayEXT from a ray-generation shader the APPLICATION wrote, or VK_KHR_ray_query --
+ * the reference has no call for it: its only rays are the pixels of raytrace.rgen.glsl and their shadow rays) -----------------------------------------------
+ * One cast traces n rays that sit in a DEVICE buffer (a torch tensor, any hipMalloc'ed memory) through the built structure and leaves one record per ray in
+ * device buffers, on a stream: lidar and sensor models, visibility and light probes, picking, collision rays, anything the caller shades itself.
+ *  - Results: those of art_query_closest_masked / art_query_any_masked (include/art_parity.h, now host wrappers over the same path) for the same rays, bit for
+ *    bit -- accept() and t_eff of DESIGN.md 1.1, the closest hit the argmin of (t_eff, global triangle id); u, v the barycentrics of vertices 1 and 2; ids the
+ *    primitive id art_scene_add_primitive gave and the triangle's index in that primitive; a miss is (tmax, 0, 0, 0) and (-1, -1); a ray with a non-finite origin
+ *    or direction or a NaN tmax is a miss; a candidate is first tested against the visibility masks (primitive's mask & cull_mask == 0: discarded, no texel
+ *    fetched), then against its primitive's alpha cutoff.  A ray's record depends on that ray alone: the order of the rays in the buffer cannot matter.
+ *  - Asynchronous: the call enqueues and returns.  It makes no hipMalloc / hipFree, synchronises with nothing and does not wait for frames in flight (the first
+ *    cast of a context creates its cast stream, cursor blocks and events, and the first cast of a freshly built scene may complete the structure -- the 4-wide
+ *    nodes, the ring of versions of a scene that moved -- as the first art_trace would).  The records are ordered behind the cast on hip_stream; with hip_stream
+ *    NULL, on a stream the context owns for casts, whose fence is art_cast_sync.  Casts on one stream run in call order.  Casts and frames are unordered against
+ *    each other and neither changes the other's results.
+ *  - Scene: a cast sees the scene as of the call, like a frame: a pending move, deformation, residency switch, alpha cutoff or primitive mask is taken up first
+ *    (the refit runs on a stream of the context in front of the cast; only events cross over to a caller's stream), and the cast holds the version of the
+ *    structure it was launched on until it finishes: a refit that would rewrite that version waits for it on the host first, as it does for frames.
+ *  - Host waits, counted by art_cast_counts: that wait, and the pool of per-cast work-cursor blocks running dry -- it is ART_CAST_POOL deep: the 33rd cast in
+ *    flight waits for the oldest.  art_scene_build (the rebuild art_trace or a cast starts by itself included), art_set_tuning, art_resize, art_scene_clear,
+ *    art_sync and art_destroy wait for outstanding casts.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null, superfluous or misaligned pointer for the kind; an unknown
+ *    kind; cull_mask above 0xFF; flags other than 0; n above ART_CAST_MAX_RAYS.  ART_E_STATE: the scene is not built, or art_scene_needs_build.  The output
+ *    buffers must not overlap the rays: the caller's contract, not checked.
+ *  - Sharded contexts and several frames per launch cast like any other: a cast depends on neither the extent nor the shard.  (Not through art_mgpu_*.) */
+#define ART_CAST_CLOSEST 0u
+#define ART_CAST_ANY 1u
+/* the tracer's slot arithmetic is 32-bit: it hands out chunks of 64 .. 65536 rays, and n + the largest chunk (hence every chunk end, and 8 x the number of
+ * chunks, which its per-XCD cursors are cut by) must fit -- 2^31 - 65536 */
+#define ART_CAST_MAX_RAYS 2147418112u
+#define ART_CAST_POOL 32u
+typedef struct ArtRayCast {
+    const void *rays_dev;  /* n x 8 floats: o.xyz, tmin, d.xyz, tmax (the layout of the queries); 16-byte aligned */
+    void *tuv_dev;         /* CLOSEST: n x 4 floats t,u,v,0 -- a miss is (tmax,0,0,0); 16-byte aligned.  ANY: must be NULL */
+    void *ids_dev;         /* CLOSEST: n x 2 int32 (primitive id as art_scene_add_primitive gave it, triangle in the primitive), -1,-1 for a miss; 8-byte aligned.  ANY: must be NULL */
+    void *hit_dev;         /* ANY: n x uint8, 1 = something within [tmin, tmax].  CLOSEST: must be NULL */
+    void *hip_stream;      /* hipStream_t the cast is enqueued on (e.g. torch's current stream); NULL = a stream the context owns for casts */
+    uint32_t n;            /* 0 is legal: nothing is enqueued */
+    uint32_t kind;         /* ART_CAST_* */
+    uint32_t cull_mask;    /* 0..0xFF, as art_set_ray_masks; 0 sees nothing */
+    uint32_t flags;        /* must be 0 */
+} ArtRayCast;
+int32_t art_cast_rays(ArtContext *ctx, const ArtRayCast *cast);
+/* every cast enqueued so far has finished (those on callers' streams included) */
+int32_t art_cast_sync(ArtContext *ctx);
+/* since art_create: casts enqueued (n > 0), their rays, and the times art_cast_rays (or a refit in front of a frame) waited on the host for a cast.  Any pointer may be NULL. */
+int32_t art_cast_counts(ArtContext *ctx, uint64_t *casts, uint64_t *rays, uint64_t *host_waits);
+
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
  * fp32 RGBA normal; row-major full frame, of the most recently traced frame.  Host copies (synchronising) and raw device
