@@ -63,7 +63,7 @@ class ArtGlbCopyInfo(C.Structure):
 class ArtTuning(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("frame_form", "tree_builder", "packet_wide", "primary_walk", "shadow_walk", "ao_walk", "block_order", "fixed_waves",
                                           "split_fixed_steps", "split_min_steps")] + [("split_alpha", C.c_float)] + \
-               [(n, C.c_uint32) for n in ("ao_entry_off", "trace_chunk", "trace_refill", "trace_blocks", "hw_queues", "log", "wide_builder", "as_versions")] + [("refit_rebuild_ratio", C.c_float), ("trace_leaf_batch", C.c_uint32), ("plan_moving_interval", C.c_uint32), ("refit_streams", C.c_uint32), ("refit_fold_nodes", C.c_uint32), ("shadow_hints", C.c_uint32)]
+               [(n, C.c_uint32) for n in ("ao_entry_off", "trace_chunk", "trace_refill", "trace_blocks", "hw_queues", "log", "wide_builder", "as_versions")] + [("refit_rebuild_ratio", C.c_float), ("trace_leaf_batch", C.c_uint32), ("plan_moving_interval", C.c_uint32), ("refit_streams", C.c_uint32), ("refit_fold_nodes", C.c_uint32), ("shadow_hints", C.c_uint32), ("plain_math", C.c_uint32)]
 
 
 ART_CAST_CLOSEST, ART_CAST_ANY = 0, 1
@@ -198,6 +198,7 @@ PARITY_SYMBOLS = {
     "art_get_lbvh": (_I32, [_P] + [_P] * 7),
     "art_get_traversal_tree": (_I32, [_P, _P, _P, _P]),
     "art_get_wide_nodes": (_I32, [_P, _P, _P, _SZ, _P]),
+    "art_parity_math_sweep": (_I32, [_P, _U32, _U32, C.c_uint64, _U32, _P, _P, _P, _P]),
     "art_mgpu_pending": (_I32, [_P, _P, _P]),
 }
 

@@ -1396,6 +1396,7 @@ static FrameArgs make_frame_args(ArtContext *c, FrameSlot &S, uint32_t version) 
     a.alpha = c->alpha_live || (rm & 0xFFu) == 0u || ((rm >> 8) & 0xFFu) == 0u || ((rm >> 16) & 0xFFu) == 0u;
     a.alpha_bits = c->d_alpha_bits.p;   // (art_trace_ao: the frame's own choice, FrameSlot::alpha and ::ray_masks)
     a.hints = c->shadow_hints ? c->d_hints.p : nullptr; a.hint_leaves = c->T;
+    a.plain_math = c->tuning.plain_math != 0;
     return a;
 }
 
@@ -1939,6 +1940,26 @@ int32_t art_write_shadow_hints(ArtContext *c, const uint32_t *words, size_t n_wo
     if (n_words != c->hint_words()) return fail(ART_E_INVALID, "art_write_shadow_hints: size mismatch");
     if (n_words) HIPC(hipMemcpy(c->d_hints.p, words, n_words * 4, hipMemcpyHostToDevice));
     HIPC(hipDeviceSynchronize());
+    return ART_OK;
+}
+
+// the guarded fast paths of art_trace.hip (inv_sqrt_exact / sqrt_exact) against the plain expressions over a set of bit patterns (include/art_parity.h)
+int32_t art_parity_math_sweep(ArtContext *c, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint64_t *mismatches, uint32_t *first_bad_bits,
+                              uint64_t *fast_lanes, float guard[2]) {
+    if (!c || !mismatches || !first_bad_bits || !fast_lanes || !guard) return fail(ART_E_INVALID, "art_parity_math_sweep: null argument");
+    if (which > 4 || count > (1ull << 32)) return fail(ART_E_INVALID, "art_parity_math_sweep: which 0..4, at most 2^32 patterns");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    math_sweep_guard(guard);
+    unsigned long long *d = nullptr, h[3] = {0ull, ~0ull, 0ull};
+    HIPC(hipMalloc(&d, sizeof h));
+    hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { launch_math_sweep(which, first_bits, count, stride, d, nullptr); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
+    hipFree(d);
+    HIPC(e);
+    *mismatches = h[0]; *fast_lanes = h[2];
+    if (h[0]) *first_bad_bits = first_bits + (uint32_t)h[1] * stride;
     return ART_OK;
 }
 

@@ -256,6 +256,7 @@ struct FrameArgs {
     // Ray visibility masks: the cull masks of this launch's rays, primary | shadow << 8 | ao << 16.  Read by the instances with the alpha test only (`alpha` is
     // also set while a primitive has a visibility mask other than 0xFF or one of these is 0); alpha_bits marks the leaves of such primitives too.
     uint32_t ray_masks;
+    bool plain_math;           // ArtTuning.plain_math: the frame's square roots take the plain expressions (art_trace.hip inv_sqrt_exact / sqrt_exact: the fallback, in every wave)
 };
 constexpr uint32_t kRayMasksAll = 0xFFFFFFu;
 constexpr uint32_t kHintLights = 4;
@@ -267,6 +268,9 @@ void launch_shadow(const FrameArgs &a, hipStream_t s);
 void launch_accumulate(const FrameArgs &a, hipStream_t s);
 bool launch_frame(const FrameArgs &a, hipStream_t s);      // the fused frame: primary + shade + shadow + accumulate in one launch; true: it also wrote a.wave_cost (a.wave_cost set and a counting instance exists)
 void launch_frame_stats(const FrameArgs &a, uint32_t *out, hipStream_t s); // out[0] += shadow rays, out[1] += hit pixels
+// art_parity_math_sweep (include/art_parity.h): out = three device words, [0] += mismatches, [1] = min(index of a mismatch), [2] += lanes on the fast path; guard = the fast path's range
+void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, unsigned long long *out, hipStream_t s);
+void math_sweep_guard(float guard[2]);
 // The wave plan of the fused frame, made ON THE DEVICE behind a sampled frame (k_plan, art_trace.hip): from the steps every wave of that launch counted, every 8x8 block's level
 // (0 one wave | 1 four quadrant waves | 2 sixteen cell waves) and, if a level changed that matters, the next table of wave items.  result (pinned host memory, read once the
 // event behind the launch has fired): [0] items of the new table, [1] 1 = a new table was written, [2] blocks in four, [3] blocks in sixteen, [4] the step target, [5] slowest wave

@@ -27,8 +27,53 @@ __device__ __forceinline__ float dot3(V3 a, V3 b) { return fmaf(a.z, b.z, fmaf(a
 __device__ __forceinline__ V3 cross3(V3 a, V3 b) {
     return mk(fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)));
 }
-__device__ __forceinline__ float len3(V3 a) { return sqrtf(dot3(a, a)); }
-__device__ __forceinline__ V3 nrm3(V3 a) { float inv = 1.0f / sqrtf(dot3(a, a)); return a * inv; }
+// ---- sqrtf(x) and 1.0f / sqrtf(x), bit for bit, without the range handling their inputs never need ("the guarded fast path") ----
+// hipcc compiles either expression correctly rounded and denormal-safe: a 2^32 pre-scale below 2^-96, a class fix-up for 0 / inf, two v_div_scale and a v_div_fixup
+// around one core -- v_sqrt_f32 moved by at most one ulp after two FMA residuals; v_rcp_f32 and the division's FMA chain.  Squared lengths of shading vectors sit
+// near 1, where none of that wrapping does anything.  A wave whose active lanes all hold x in [kExactLo, kExactHi] (one ballot, one scalar branch) runs the core
+// alone: the same hardware instructions and the same FMAs in the same order, so the same bits (28 -> 18 vector instructions for 1 / sqrt).  Any lane outside (a zero
+// or denormal normal, inf, NaN, a negative) sends the WHOLE wave through the plain expression: those keep today's bits by construction.  kExactLo is the compiler's
+// own scaling threshold; below kExactHi the root stays under 2^48, far from where v_div_scale begins to act.  tests/test_exact_math.py sweeps all 2^32 inputs.
+constexpr float kExactLo = 0x1p-96f, kExactHi = 0x1p96f;
+__device__ __forceinline__ float sqrt_core(float x) {
+    float s = __builtin_amdgcn_sqrtf(x);
+    float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
+    float vp = fmaf(-dn, s, x), vs = fmaf(-up, s, x);
+    s = vp <= 0.0f ? dn : s;
+    return vs > 0.0f ? up : s;
+}
+__device__ __forceinline__ float rcp_core(float d) {   // 1.0f / d: the quotient's first estimate 1.0f * r is r itself
+    float r = __builtin_amdgcn_rcpf(d);
+    r = fmaf(fmaf(-d, r, 1.0f), r, r);
+    float q = fmaf(fmaf(-d, r, 1.0f), r, r);
+    return fmaf(fmaf(-d, q, 1.0f), r, q);
+}
+// plain: wave-uniform, forces the plain expression (ArtTuning.plain_math); fast: whether this wave took the core (the sweep counts it); FAST = false: the plain expression
+// and nothing else, for the k_frame instances whose register allocation the guard's branches would move (kFrameFastMath)
+__device__ __forceinline__ bool exact_in_range(float x, bool plain) {
+    return !plain && __builtin_amdgcn_ballot_w64(!(x >= kExactLo && x <= kExactHi)) == 0ull;
+}
+template <bool FAST = true> __device__ __forceinline__ float inv_sqrt_exact(float x, bool plain, bool &fast) {
+    fast = FAST && exact_in_range(x, plain);
+    if (fast) return rcp_core(sqrt_core(x));
+    return 1.0f / sqrtf(x);
+}
+template <bool FAST = true> __device__ __forceinline__ float sqrt_exact(float x, bool plain, bool &fast) {
+    fast = FAST && exact_in_range(x, plain);
+    if (fast) return sqrt_core(x);
+    return sqrtf(x);
+}
+// the guard of a whole block of calls (shade_surface): every call notes how far above kExactLo its x lies -- as integers, where the non-negative floats are in order and a
+// zero, a denormal, a negative or a NaN wraps or lands above the range's width -- and the block tests the largest note once
+__device__ __forceinline__ void exact_note(float x, uint32_t &far) { far = max(far, __float_as_uint(x) - __float_as_uint(kExactLo)); }
+__device__ __forceinline__ bool exact_noted_in_range(uint32_t far) { return __builtin_amdgcn_ballot_w64(far > __float_as_uint(kExactHi) - __float_as_uint(kExactLo)) == 0ull; }
+template <bool FAST = true> __device__ __forceinline__ float len3(V3 a, bool plain = false) { bool f; return sqrt_exact<FAST>(dot3(a, a), plain, f); }
+template <bool FAST = true> __device__ __forceinline__ V3 nrm3(V3 a, bool plain = false) { bool f; float inv = inv_sqrt_exact<FAST>(dot3(a, a), plain, f); return a * inv; }
+__device__ __forceinline__ float inv_sqrt_noting(float x, uint32_t &far) { exact_note(x, far); return rcp_core(sqrt_core(x)); }   // the core, unguarded, and its note
+template <bool CORE> __device__ __forceinline__ V3 nrm3_noting(V3 a, uint32_t &far) {   // CORE: that | the plain expression
+    float x = dot3(a, a);
+    return a * (CORE ? inv_sqrt_noting(x, far) : 1.0f / sqrtf(x));
+}
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 __device__ __forceinline__ float mixf(float x, float y, float a) { return x * (1.0f - a) + y * a; }
 __device__ __forceinline__ V3 ld3(const float *p) { return mk(p[0], p[1], p[2]); }
@@ -841,7 +886,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
                             float ux = px / (float)a.W, uy = py / (float)a.H;
                             float dx = ux * 2.0f - 1.0f, dy = uy * 2.0f - 1.0f;
                             V3 org = mat4_mul(a.cam.view_inv, 0.f, 0.f, 0.f, 1.f);
-                            V3 tgt = nrm3(mat4_mul(a.cam.proj_inv, dx, dy, 1.f, 1.f));
+                            V3 tgt = nrm3<false>(mat4_mul(a.cam.proj_inv, dx, dy, 1.f, 1.f));   // (plain: with the guard the filtered binary-node instance takes a 72nd register)
                             V3 dir = mat4_mul(a.cam.view_inv, tgt.x, tgt.y, tgt.z, 0.f);
                             tr.start(org, dir, 0.001f, 10000.0f);
                             active = true;
@@ -1182,7 +1227,7 @@ __device__ V3 get_unnormalized_L_vec(const ArtLight &l, V3 pos) { // light.glsl:
     }
     return mk(1.0f, 1.0f, 1.0f);
 }
-__device__ V3 get_light_radiance(const ArtLight &l, V3 pos, V3 L) { // light.glsl:34-48
+template <bool FAST> __device__ V3 get_light_radiance(const ArtLight &l, V3 pos, V3 L, bool plain) { // light.glsl:34-48
     V3 rad = ld3(l.color);
     if (l.type == 1u || l.type == 3u) {
         float theta_s = acosf(clampf(dot3(ld3(l.dir), neg(L)), -1.0f, 1.0f));
@@ -1190,7 +1235,7 @@ __device__ V3 get_light_radiance(const ArtLight &l, V3 pos, V3 L) { // light.gls
         rad = rad * (t * t);
     }
     if (l.falloff_distance > 0.0f) {
-        float q = __fdividef(len3(ld3(l.pos) - pos), l.falloff_distance);
+        float q = __fdividef(len3<FAST>(ld3(l.pos) - pos, plain), l.falloff_distance);
         float w = fmaxf(1.0f - q * q, 0.0f);
         rad = rad * (w * w);
     }
@@ -1224,7 +1269,7 @@ __device__ float Burley_diffuse_local_sss(float a_, float NdotV, float nc_NdotV,
 struct Surface { V3 world_pos, N, Vv, albedo; float metallic, alpha, nc_NdotV, NdotV; };
 
 // rgen:107-150: the hit triangle's attributes, normal mapping, material; also the frame's depth / view-space normal outputs
-__device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal) {
+template <bool CORE> __device__ __forceinline__ void shade_surface_body(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal, uint32_t &far) {
     // one dependent fetch: the shading record holds what get_indices + three vertex reads would return (rgen:107-114)
     const float4 *sq = reinterpret_cast<const float4 *>(a.shade_tris + pos);
     float4 s0 = sq[0], s1 = sq[1], s2 = sq[2], s3 = sq[3], s4 = sq[4], s5 = sq[5], s6 = sq[6], s7 = sq[7], s8 = sq[8];
@@ -1233,22 +1278,22 @@ __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraAr
     V3 posv = (mk(s0.x, s0.y, s0.z) * bx + mk(s0.w, s1.x, s1.y) * by) + mk(s1.z, s1.w, s2.x) * bz;
     V3 world_pos = xform_point(P.o2w, posv);
     float tu = (s2.y * bx + s2.w * by) + s3.y * bz, tv = (s2.z * bx + s3.x * by) + s3.z * bz;
-    V3 nrm = nrm3((mk(s3.w, s4.x, s4.y) * bx + mk(s4.z, s4.w, s5.x) * by) + mk(s5.y, s5.z, s5.w) * bz);
+    V3 nrm = nrm3_noting<CORE>((mk(s3.w, s4.x, s4.y) * bx + mk(s4.z, s4.w, s5.x) * by) + mk(s5.y, s5.z, s5.w) * bz, far);
     const float *Wm = P.w2o;
-    V3 world_normal = nrm3(mk(dot3(nrm, mk(Wm[0], Wm[4], Wm[8])), dot3(nrm, mk(Wm[1], Wm[5], Wm[9])), dot3(nrm, mk(Wm[2], Wm[6], Wm[10]))));
-    V3 tan = nrm3((mk(s6.x, s6.y, s6.z) * bx + mk(s6.w, s7.x, s7.y) * by) + mk(s7.z, s7.w, s8.x) * bz);
-    V3 world_tangent = nrm3(xform_vec(P.o2w, tan));
-    world_tangent = nrm3(world_tangent - world_normal * dot3(world_tangent, world_normal));
+    V3 world_normal = nrm3_noting<CORE>(mk(dot3(nrm, mk(Wm[0], Wm[4], Wm[8])), dot3(nrm, mk(Wm[1], Wm[5], Wm[9])), dot3(nrm, mk(Wm[2], Wm[6], Wm[10]))), far);
+    V3 tan = nrm3_noting<CORE>((mk(s6.x, s6.y, s6.z) * bx + mk(s6.w, s7.x, s7.y) * by) + mk(s7.z, s7.w, s8.x) * bz, far);
+    V3 world_tangent = nrm3_noting<CORE>(xform_vec(P.o2w, tan), far);
+    world_tangent = nrm3_noting<CORE>(world_tangent - world_normal * dot3(world_tangent, world_normal), far);
     V3 world_binormal = cross3(world_normal, world_tangent) * s8.y;
     float4 tx = sample_tex(a.tex_pool, P, 2, tu, tv);
-    V3 N = nrm3(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f));
-    N = nrm3((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z);
+    V3 N = nrm3_noting<CORE>(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f), far);
+    N = nrm3_noting<CORE>((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z, far);
     tx = sample_tex(a.tex_pool, P, 0, tu, tv);
     V3 albedo = mk(__powf(tx.x, 2.2f), __powf(tx.y, 2.2f), __powf(tx.z, 2.2f)); // radiance-only from here: fast intrinsics
     tx = sample_tex(a.tex_pool, P, 1, tu, tv);
     float roughness = tx.y, metallic = tx.z;
     S.world_pos = world_pos; S.N = N; S.albedo = albedo; S.metallic = metallic;
-    S.Vv = nrm3(ld3(cam.camera_pos) - world_pos); // exact: V + L cancels at grazing angles and would amplify a 1-ulp rsq
+    S.Vv = nrm3_noting<CORE>(ld3(cam.camera_pos) - world_pos, far); // exact: V + L cancels at grazing angles and would amplify a 1-ulp rsq
     S.alpha = roughness * roughness;
     S.nc_NdotV = dot3(N, S.Vv);
     S.NdotV = clampf(S.nc_NdotV, 1e-5f, 1.0f);
@@ -1257,17 +1302,26 @@ __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraAr
     const float *VI = cam.view_inv;
     V3 on = mk((VI[0] * N.x + VI[1] * N.y) + VI[2] * N.z, (VI[4] * N.x + VI[5] * N.y) + VI[6] * N.z, (VI[8] * N.x + VI[9] * N.y) + VI[10] * N.z);
     on.y = -on.y; on.z = -on.z;
-    on = nrm3(on);
+    on = nrm3_noting<CORE>(on, far);
     out_normal = mk(on.x * 0.5f + 0.5f, on.y * 0.5f + 0.5f, on.z * 0.5f + 0.5f);
 }
 
+// The surface block's nine normalisations under ONE guard: a branch in front of each (inv_sqrt_exact) cuts the block into ten scheduling regions and moves the register
+// allocation of every k_frame instance; here the block runs the core straight through, notes the range of what it was given, and a wave in which any lane's note is out
+// of range runs the block again with the plain expressions (a normal of length zero, a NaN vertex: nothing a frame has many of).  What the first pass computed from such a
+// value is discarded whole: no address depends on a normalised vector, so it is arithmetic on garbage and nothing else.
+template <bool FAST> __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal) {
+    uint32_t far = 0u;
+    if (FAST) { if (!a.plain_math) { shade_surface_body<true>(a, cam, pos, hu, hv, S, out_depth, out_normal, far); if (exact_noted_in_range(far)) return; } }
+    shade_surface_body<false>(a, cam, pos, hu, hv, S, out_depth, out_normal, far);
+}
 // rgen:152-185 up to the shadow ray: c = (rho_s + rho_d) * radiance, c.w = NdotL; the shadow ray (origin, tmax | direction) if one is due
-__device__ __forceinline__ bool shade_light(const ArtLight &l, const Surface &S, float4 &c4, float4 &ro, float4 &rd) {
+template <bool FAST> __device__ __forceinline__ bool shade_light(const ArtLight &l, const Surface &S, bool plain, float4 &c4, float4 &ro, float4 &rd) {
     // a directional light's L and |nn_L| do not depend on the pixel: the host made them (art_api.hip directional_constants, the same operations)
     const bool directional = l.type == 2u;
     V3 nn_L = directional ? mk(0.f, 0.f, 0.f) : get_unnormalized_L_vec(l, S.world_pos);
-    V3 L = directional ? ld3(l.area_pos2) : nrm3(nn_L);
-    V3 Hh = nrm3(S.Vv + L);
+    V3 L = directional ? ld3(l.area_pos2) : nrm3<FAST>(nn_L, plain);
+    V3 Hh = nrm3<FAST>(S.Vv + L, plain);
     float nc_NdotL = dot3(S.N, L);
     float NdotL = clampf(nc_NdotL, 0.0f, 1.0f);
     float NdotH = clampf(dot3(S.N, Hh), 0.0f, 1.0f);
@@ -1279,11 +1333,11 @@ __device__ __forceinline__ bool shade_light(const ArtLight &l, const Surface &S,
     float DG = D_GGX(S.alpha, NdotH) * V_SmithGGXCorrelated_fast(S.alpha, S.NdotV, NdotL);
     V3 rho_s = Ks * DG;
     V3 rho_d = Kd * Burley_diffuse_local_sss(S.alpha, S.NdotV, S.nc_NdotV, nc_NdotL, LdotH, 0.4f);
-    V3 rad = get_light_radiance(l, S.world_pos, L);
+    V3 rad = get_light_radiance<FAST>(l, S.world_pos, L, plain);
     V3 c = (rho_s + rho_d) * rad;
     c4 = make_float4(c.x, c.y, c.z, NdotL);
     if (l.casts_shadows && nc_NdotL > 0.0f) { // raytrace.rgen.glsl:165: origin world_pos, dir L, tmax length(nn_L)
-        ro = make_float4(S.world_pos.x, S.world_pos.y, S.world_pos.z, directional ? l.penumbra_angle : len3(nn_L));
+        ro = make_float4(S.world_pos.x, S.world_pos.y, S.world_pos.z, directional ? l.penumbra_angle : len3<FAST>(nn_L, plain));
         rd = make_float4(L.x, L.y, L.z, 0.f);
         return true;
     }
@@ -1329,11 +1383,11 @@ __global__ __launch_bounds__(kBlock) void k_shade(FrameArgs a) {
         }
     } else {
         Surface S;
-        shade_surface(a, a.cam, pos, h.y, h.z, S, out_depth, out_normal);
+        shade_surface<true>(a, a.cam, pos, h.y, h.z, S, out_depth, out_normal);
         for (uint32_t i = 0; i < a.n_lights; i++) {
             float4 c4, ro, rd;
             const ArtLight L = frame_light(a, i);
-            bool want = shade_light(L, S, c4, ro, rd);
+            bool want = shade_light<true>(L, S, a.plain_math, c4, ro, rd);
             size_t slot = (size_t)i * a.n_local + p;
             st_nt(&a.contrib[slot], c4);
             if (want) {
@@ -1391,12 +1445,20 @@ __device__ __forceinline__ uint64_t tick(float &dep) { uint64_t t; asm volatile(
 // With the visibility rule in the triangle step the step-counting sibling of the latter over binary nodes went the same way (one spilled VGPR) and joined them.
 template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr bool kFrameHints = !(!WIDE && BATCH) && !(ALPHA && !ONE_LIGHT && !COUNT && !BATCH) &&
                                                                                                       !(ALPHA && !WIDE && !ONE_LIGHT && COUNT && !BATCH);
+// The instances of k_frame whose normalisations take the guarded fast paths (shade_surface's block guard, inv_sqrt_exact / sqrt_exact in the camera ray and shade_light): the
+// one-light instances with one frame per launch and no alpha test -- the default instance, its step-counting sibling and the two over binary nodes.  These keep the register
+// allocation they had with the plain expressions to the register (63 VGPRs, no scratch: tests/test_alpha.py and tests/test_ray_masks.py pin it).  Every other instance moved:
+// one to three VGPRs more in the one-light ones, 2 to 10 spilled registers in the multi-light ones, which have no register to spare for the guard's note (tools/kres.sh;
+// profiles/exact_math_kres_{parent,new}.txt, profiles/README.md "exact 1/sqrt").  Those compile the plain expressions, as before.  Any subset is the same frame: the fast
+// paths change no bit.
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr bool kFrameFastMath = ONE_LIGHT && !BATCH && !ALPHA;
 template <bool WIDE, bool ONE_LIGHT, bool COUNT = false, bool BATCH = false, bool ALPHA = false>   // WIDE: the 128-byte 4-wide nodes (the default) | the 64-byte binary nodes; ALPHA: the alpha test
 __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_frame(FrameArgs a) {
     // One wave per workgroup: the waves of a frame are independent (nothing is shared, no barrier), and a workgroup of four held its LDS and its place
     // in the dispatcher's books until its slowest wave was done -- packets differ 25x in steps.  Single-wave groups: +2.5 % rays/s (profiles/README.md r2).
     __shared__ int wstack[kPacketStack + 4];   // + the ring of a shadow walk's accepting leaf positions (PacketHints)
     constexpr bool HINTS = kFrameHints<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
+    constexpr bool FASTM = kFrameFastMath<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     int *stk = wstack;
     const uint32_t wid = blockIdx.x;
     if (wid >= a.n_wave_items) return;
@@ -1417,7 +1479,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
         float dx = (fx / (float)a.W) * 2.0f - 1.0f, dy = (fy / (float)a.H) * 2.0f - 1.0f;
         V3 org = mat4_mul(cam.view_inv, 0.f, 0.f, 0.f, 1.f);
-        V3 tgt = nrm3(mat4_mul(cam.proj_inv, dx, dy, 1.f, 1.f));
+        V3 tgt = nrm3<FASTM>(mat4_mul(cam.proj_inv, dx, dy, 1.f, 1.f), a.plain_math);
         V3 dir = mat4_mul(cam.view_inv, tgt.x, tgt.y, tgt.z, 0.f);
         ray_init(r, org, dir, 0.001f, 10000.0f);
     }
@@ -1436,7 +1498,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     Surface S;
     S.world_pos = mk(0.f, 0.f, 0.f); S.N = mk(0.f, 0.f, 1.f); S.Vv = mk(0.f, 0.f, 1.f); S.albedo = mk(0.f, 0.f, 0.f);
     S.metallic = 0.f; S.alpha = 0.f; S.nc_NdotV = 0.f; S.NdotV = 0.f;
-    if (hit) shade_surface(a, cam, bpos, bu, bv, S, out_depth, out_normal);
+    if (hit) shade_surface<FASTM>(a, cam, bpos, bu, bv, S, out_depth, out_normal);
     if (in) {
         const size_t pix = frame_px + (size_t)y * a.W + x;
         st_nt(&a.depth[pix], out_depth);
@@ -1459,7 +1521,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f), ro = make_float4(0.f, 0.f, 0.f, 1.0f), rd = make_float4(0.f, 0.f, 1.f, 0.f);
         bool want = false;
         const ArtLight L = ONE_LIGHT ? a.lights[0] : frame_light(a, i);
-        if (hit) want = shade_light(L, S, c4, ro, rd);
+        if (hit) want = shade_light<FASTM>(L, S, a.plain_math, c4, ro, rd);
         if (want) { if (i < 16u) sbits |= 1u << (16u + i); else more++; }   // (lights 16.. have no bits of their own: their shadow rays are counted)
         Ray sr;
         if (L.type == 2u) ray_init_inv(sr, mk(ro.x, ro.y, ro.z), ld3(L.area_pos2), ld3(L.area_pos3), 0.01f, L.penumbra_angle); // (wave-uniform branch)
@@ -1723,6 +1785,65 @@ bool launch_frame(const FrameArgs &a, hipStream_t s) { // returns whether the la
 }
 void launch_frame_stats(const FrameArgs &a, uint32_t *out, hipStream_t s) { k_frame_stats<<<blocks_for(a.n_local), kBlock, 0, s>>>(a, out); }
 void launch_accumulate(const FrameArgs &a, hipStream_t s) { k_accumulate<<<blocks_for(a.n_local), kBlock, 0, s>>>(a); }
+
+// ---- art_parity_math_sweep: inv_sqrt_exact / sqrt_exact against the plain expressions, any set of the 2^32 inputs (tests/test_exact_math.py) ----
+__device__ __attribute__((noinline)) float plain_inv_sqrt(float x) { return 1.0f / sqrtf(x); }
+__device__ __attribute__((noinline)) float plain_sqrt(float x) { return sqrtf(x); }
+// The shorter candidate: v_rsq_f32, a Markstein step to the root, v_rcp_f32 and one Newton step -- 10 vector instructions instead of 16.  The sweep finds it exact over
+// the whole guard range too (profiles/README.md, "exact 1/sqrt"), but no placement of it left the default k_frame instance its 63 registers (61 or 64: the figure is
+// pinned), so the frame kernels run the compiler's core; kept here so that the sweep keeps proving it for the day the allocation has room.
+__device__ __forceinline__ float inv_sqrt_short(float x) {
+    float y = __builtin_amdgcn_rsqf(x);
+    float s = x * y, h = 0.5f * y;
+    s = fmaf(s, fmaf(-h, s, 0.5f), s);
+    s = fmaf(fmaf(-s, s, x), h, s);
+    float q = __builtin_amdgcn_rcpf(s);
+    return fmaf(fmaf(-s, q, 1.0f), q, q);
+}
+constexpr uint32_t kSweepBlocks = 4096;
+template <int WHICH> __global__ __launch_bounds__(kBlock) void k_math_sweep(uint32_t first_bits, uint64_t count, uint32_t stride, unsigned long long *__restrict__ out) {
+    unsigned long long bad = 0, fast_n = 0, bad_at = ~0ull;
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    // a wave's lanes take 64 consecutive i: the loop is wave-uniform, the lanes past `count` sit out (the helpers' ballots see the active lanes only)
+    for (uint64_t base = (uint64_t)blockIdx.x * kBlock + (threadIdx.x & ~63u); base < count; base += step) {
+        const uint64_t i = base + (threadIdx.x & 63u);
+        if (i < count) {
+            const float x = __uint_as_float(first_bits + (uint32_t)i * stride);
+            bool fast = false;
+            float got, ref;
+            if (WHICH == 0) { got = inv_sqrt_exact(x, false, fast); ref = plain_inv_sqrt(x); }
+            else if (WHICH == 1) { got = sqrt_exact(x, false, fast); ref = plain_sqrt(x); }
+            else if (WHICH == 2) {   // shade_surface's form: the core unguarded and a note, the guard behind it, the plain expression where it fails
+                uint32_t far = 0u;
+                got = inv_sqrt_noting(x, far);
+                fast = exact_noted_in_range(far);
+                if (!fast) got = 1.0f / sqrtf(x);
+                ref = plain_inv_sqrt(x);
+            } else if (WHICH == 3) { fast = exact_in_range(x, false); got = fast ? inv_sqrt_short(x) : 1.0f / sqrtf(x); ref = plain_inv_sqrt(x); }
+            else { fast = exact_in_range(x, false); got = fast ? __builtin_amdgcn_rsqf(x) : 1.0f / sqrtf(x); ref = plain_inv_sqrt(x); }   // the sweep's own control: v_rsq_f32 alone is NOT exact
+            if (__float_as_uint(got) != __float_as_uint(ref)) { bad++; if (i < bad_at) bad_at = i; }
+            fast_n += fast ? 1u : 0u;
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        bad += __shfl_xor(bad, off); fast_n += __shfl_xor(fast_n, off);
+        const unsigned long long o = __shfl_xor(bad_at, off); bad_at = o < bad_at ? o : bad_at;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], bad_at); }
+        if (fast_n) atomicAdd(&out[2], fast_n);
+    }
+}
+void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, unsigned long long *out, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kSweepBlocks, (count + kBlock - 1) / kBlock);
+    if (!blocks) return;
+    if (which == 0) k_math_sweep<0><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
+    else if (which == 1) k_math_sweep<1><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
+    else if (which == 2) k_math_sweep<2><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
+    else if (which == 3) k_math_sweep<3><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
+    else k_math_sweep<4><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
+}
+void math_sweep_guard(float guard[2]) { guard[0] = kExactLo; guard[1] = kExactHi; }
 // rays in device buffers (art_cast_rays and, through it, the queries): {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernel has -- a cast is
 // throughput-bound like it -- with the context's ArtTuning overrides
 static const Tune kCastPreset = {256, kCastPoolTake, 2048, 8};

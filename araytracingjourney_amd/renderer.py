@@ -645,6 +645,13 @@ class Renderer:
         a = np.ascontiguousarray(table, dtype=np.uint32)
         check(self._L.art_write_shadow_hints(self._ctx, _ptr(a), a.size))
 
+    def math_sweep(self, which, first_bits=0, count=1 << 32, stride=1):
+        """art_parity_math_sweep: the shading kernels' fast paths for 1 / sqrt(x) (which 0, 2; 3 the shorter candidate, 4 the control that must fail) and sqrt(x) (1) against the plain expressions on the bit patterns
+        first_bits + i * stride, i < count -> dict(mismatches, first_bad_bits (None without a mismatch), fast_lanes, guard=(lo, hi))"""
+        bad, fast, first, guard = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), (C.c_float * 2)()
+        check(self._L.art_parity_math_sweep(self._ctx, which, first_bits, count, stride, C.byref(bad), C.byref(first), C.byref(fast), guard))
+        return dict(mismatches=bad.value, first_bad_bits=first.value if bad.value else None, fast_lanes=fast.value, guard=(guard[0], guard[1]))
+
     def set_ray_masks(self, primary=0xFF, shadow=0xFF, ao=0xFF):
         """the cull masks of the rays trace() (primary, shadow) and trace_ao() (ao) cast (Vulkan: traceRayEXT's cullMask; the reference hard-codes 0xFF,
         raytrace.rgen.glsl:92,169): a ray sees a primitive iff its mask (Model.set_mask) shares a bit with the ray's.  Per-launch state like the camera: a

@@ -46,6 +46,8 @@ typedef struct ArtTuning {
     uint32_t refit_streams;     /* moving models: streams of their own the refits run on, beside the frames of the ring slot they precede (0 = min(frames in flight, 4); 0xFFFFFFFF: none -- every refit on its frame's stream, in front of it) */
     uint32_t refit_fold_nodes;  /* moving models: trees of this many 4-wide nodes and more make the quantised records and the cost inside the refit's own workgroups, with a cached share of the cost per batch (0 = 400 000; 1 = every tree: the tests' way to that form on small scenes) */
     uint32_t shadow_hints;      /* the fused frame's shadow packets test the triangles that occluded their 8x8 block a frame ago before they walk the tree from the root: 0 = on (the product) | 1 = off: the frame kernel neither reads nor writes the context's hint table */
+    uint32_t plain_math;        /* the frame's normalisations and lengths (ray generation and shading of the fused and the staged frame): 0 = the guarded fast path for sqrtf(x) and 1.0f / sqrtf(x) (the product;
+                                 * art_parity_math_sweep) | 1 = the plain expressions in every wave: the same frame bit for bit */
 } ArtTuning;
 int32_t art_set_tuning(ArtContext *ctx, const ArtTuning *tuning);
 /* per-pixel primary hit record, row-major: tuv[4*i] = t,u,v,0 ; ids[2*i] = primitive index (-1 miss), triangle id */
@@ -75,6 +77,15 @@ int32_t art_get_traversal_tree(ArtContext *ctx, int32_t *child, float *node_lo, 
  * n_nodes records of 64 B (8-bit quantised child boxes: the per-ray walks) and of 128 B (float child boxes, children sorted along one axis: the packet
  * walks); node 0 is the root, child >= 0: node index, < 0: ~leaf position, INT32_MIN: absent (bit i of the records' valid masks clear).  Either pointer may be NULL; *n_nodes is always set. */
 int32_t art_get_wide_nodes(ArtContext *ctx, void *quantised, void *floats, size_t capacity_nodes, uint32_t *n_nodes);
+/* proof that the shading kernels' guarded fast paths return the plain expressions' bits: which = 0: 1.0f / sqrtf(x) behind its own guard (inv_sqrt_exact), 1: sqrtf(x)
+ * likewise (sqrt_exact), 2: 1.0f / sqrtf(x) in the form of the surface block (the unguarded core and its note, the block's guard behind it).  A kernel feeds the bit
+ * patterns first_bits + i * stride (mod 2^32), i < count, lane l of a wave taking i = 64 k + l, to the helper the frame kernels call and to a non-inlined copy of the plain
+ * expression in the same translation unit, and compares the two results as uint32.  *mismatches = patterns that differ, *first_bad_bits = the pattern of the lowest such i
+ * (untouched when there is none), *fast_lanes = patterns whose wave took the fast path (a wave takes it only when all its lanes are inside guard[0] <= x <= guard[1]).
+ * which = 3: the shorter v_rsq_f32-based candidate for 1.0f / sqrtf(x) that the frame kernels do not run yet (profiles/README.md, "exact 1/sqrt"), under the same guard;
+ * which = 4: v_rsq_f32 alone under that guard -- a 1-ulp approximation, the sweep's own control: it must report mismatches.  Synchronises. */
+int32_t art_parity_math_sweep(ArtContext *ctx, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint64_t *mismatches, uint32_t *first_bad_bits,
+                              uint64_t *fast_lanes, float guard[2]);
 
 
 /* ---- building blocks of art_mgpu_* (rehearsals of other exchange loops) ---- */

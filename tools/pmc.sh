@@ -1,9 +1,9 @@
 #!/bin/bash
-# usage: tools/pmc.sh <tag> [bench.py arguments ...] -- collects PMC counters for bench.py (separate passes; kernel-trace only, as gpurun requires)
+# usage: [PMC_SHORT=1] [ART_LIB_PATH=<another build>] tools/pmc.sh <tag> [bench.py arguments ...] -- collects PMC counters for bench.py (separate passes; kernel-trace only: counters are never combined with any other tracing)
 set -e
 TAG=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 i=0
@@ -14,7 +14,8 @@ if [ -z "$PMC_SHORT" ]; then SETS+=("TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "TCP_
 SETS+=("FETCH_SIZE" "WRITE_SIZE")
 for C in "${SETS[@]}"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/p$i -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --plain --settle-seconds 0 --frames-in-flight 8 "$@" > $OUT/p$i.log 2>&1 || echo "pass $i failed"
+  # every pass under its own time limit; a pass that fails or hangs ends the script (nothing more is started on a card that may have faulted)
+  timeout -k 10 ${PMC_PASS_SECONDS:-300} rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/p$i -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --plain --settle-seconds 0 --frames-in-flight 8 "$@" > $OUT/p$i.log 2>&1 || { echo "pass $i failed: stopping" >&2; tail -5 $OUT/p$i.log >&2; exit 1; }
 done
 python3 - <<PY
 import csv, glob, collections
