@@ -921,7 +921,7 @@ int32_t art_set_tuning(ArtContext *c, const ArtTuning *t) {
     if (!c || !t) return fail(ART_E_INVALID, "art_set_tuning: null argument");
     auto walk_ok = [](uint32_t k) { return k == 0 || k == 2 || k == 4; };
     if ((t->frame_form != 0 && t->frame_form != 2) || t->tree_builder > 1 || t->packet_wide > 2 || !walk_ok(t->primary_walk) || !walk_ok(t->shadow_walk) || !(walk_ok(t->ao_walk) || t->ao_walk == 6))
-        return fail(ART_E_INVALID, "art_set_tuning: frame_form 0|2, tree_builder 0..1, packet_wide 0..2, walks 0|2|4");
+        return fail(ART_E_INVALID, "art_set_tuning: frame_form 0|2, tree_builder 0..1, packet_wide 0..2, primary_walk / shadow_walk 0|2|4, ao_walk 0|2|4|6");
     if (t->frame_form == 0 && (t->primary_walk || t->shadow_walk)) return fail(ART_E_INVALID, "art_set_tuning: the fused frame's rays are packets (primary_walk / shadow_walk choose the per-ray walks of frame_form 2)");
     if (t->as_versions > kMaxAsVersions || !(t->refit_rebuild_ratio == t->refit_rebuild_ratio)) return fail(ART_E_INVALID, "art_set_tuning: as_versions 0..24, refit_rebuild_ratio a number");
     int32_t r = use_device(c); if (r) return r;

@@ -305,6 +305,17 @@ def _mask_value(name, v):
     return int(v)
 
 
+def tuning_from_dict(tuning) -> "_lib.ArtTuning":
+    """an ArtTuning from a dict of its fields.  ctypes takes an unknown keyword as a plain attribute, so a misspelt or removed key would select nothing and the
+    caller -- a test's form table, a sweep -- would run the default without a word: any key that is no field of ArtTuning is a ValueError that names it"""
+    tuning = dict(tuning or {})
+    fields = [n for n, _ in _lib.ArtTuning._fields_]
+    bad = sorted(k for k in tuning if k not in fields)
+    if bad:
+        raise ValueError(f"tuning: unknown key{'s' if len(bad) > 1 else ''} {', '.join(repr(k) for k in bad)} (ArtTuning has {', '.join(fields)})")
+    return _lib.ArtTuning(**tuning)
+
+
 class Renderer:
     """VulkanTempleRayTracedRenderer (renderer.rs:121-137) on libart: same call order, no window/swapchain."""
 
@@ -318,7 +329,7 @@ class Renderer:
         check(self._L.art_create(C.byref(cfg), C.byref(self._ctx)))
         # The host tells the library how many hardware queues it asked HIP for (libart itself reads no environment variable); `tuning` picks one of the
         # equivalent forms of the path (ArtTuning: staged / per-ray frames, host-built tree, wave-plan targets ...) -- tests and sweeps only.
-        t = _lib.ArtTuning(**dict(tuning or {}))
+        t = tuning_from_dict(tuning)
         if not t.hw_queues:
             t.hw_queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0)
         check(self._L.art_set_tuning(self._ctx, C.byref(t)))

@@ -28,7 +28,8 @@ typedef struct ArtTuning {
                                  * packet walks -- went in round 4 with the other forms that had lost: the packet's beam as node step, PLOC trees, 6- / 7-wave instances) */
     uint32_t tree_builder;      /* 0 the context's default (binned SAH on the device; ART_FLAG_FAST_BUILD: LBVH topology) | 1 binned SAH on the host threads */
     uint32_t packet_wide;       /* the fused frame's packet walks: 0 = default (the 128-byte 4-wide float nodes), 1 = 4-wide, 2 = the 64-byte binary nodes */
-    uint32_t primary_walk, shadow_walk, ao_walk; /* frame_form 2 (and the AO rays of any frame): one ray type's per-ray walk: 0 default | 2 binary nodes | 4 quantised 4-wide nodes */
+    uint32_t primary_walk, shadow_walk, ao_walk; /* frame_form 2 (and the AO rays of any frame): one ray type's per-ray walk: 0 default | 2 binary nodes | 4 quantised 4-wide nodes;
+                                 * ao_walk alone also takes 6: the quantised 4-wide walk through the generic persistent tracer (k_trace) instead of the AO launch's own tracer (k_trace_ao, which is what 0 and 4 run) */
     uint32_t block_order;       /* launch order of the 256-pixel blocks: 0 XCD-aware macro-blocks of 2x2 tiles | 1 identity | n: macro-blocks of n x n tiles */
     uint32_t fixed_waves;       /* 1: no adaptive wave plan (like ART_FLAG_FIXED_WAVES) */
     uint32_t split_fixed_steps; /* wave plan: a fixed packet-step target instead of the adaptive one (0: adaptive) */
