@@ -799,7 +799,7 @@ __global__ __launch_bounds__(kBlock) void k_ao_pixels(FrameArgs a, const DevNode
 }
 
 // what a persistent tracing wave reads its rays from and writes its results to
-enum { MODE_PRIMARY = 0, MODE_SHADOW = 1, MODE_QUERY_CLOSEST = 2, MODE_QUERY_ANY = 3, MODE_AO = 4 };   // (2 and 3: the queries' former instances -- see below k_trace: nothing launches them, rays in device buffers have a tracer of their own, k_cast)
+enum { MODE_PRIMARY = 0, MODE_SHADOW = 1, MODE_AO = 4 };   // (2 and 3 were the queries': rays in device buffers have a tracer of their own, k_cast.  Not renumbered: tools and profiles name k_trace<4, ..>)
 struct TraceArgs {
     const DevNode *nodes; const DevNode4 *wide; const DevTri *tris;
     uint32_t total;          // candidate slots
@@ -810,12 +810,11 @@ struct TraceArgs {
     // MODE_PRIMARY
     CameraArg cam; uint32_t W, H; const uint32_t *tile_list; uint32_t tiles_x;
     float4 *hits;
-    // MODE_SHADOW / MODE_QUERY_*: rays[2*slot] = o.xyz,tmax(<=0: no ray) | rays[2*slot+1] = d.xyz,tmin (queries) / unused
+    // MODE_SHADOW: rays[2*slot] = o.xyz,tmax(<=0: no ray) | rays[2*slot+1] = d.xyz,unused
     const float4 *rays;
     float4 *contrib; uint32_t n_local; uint32_t *shadow_bits;
-    uint32_t *any_out;
-    // MODE_AO: rays are generated from the frame's depth + view-space normal outputs (XeGTAO's inputs); slot -> (local pixel, sample): ao_slot_decode
-    const float *depth; const float4 *normal; uint32_t spp; float ao_radius; uint8_t *occl;
+    // MODE_AO: rays are generated from the frame's depth + view-space normal outputs (XeGTAO's inputs) by way of k_ao_pixels; slot -> (local pixel, sample): ao_slot_decode
+    uint32_t spp; float ao_radius; uint8_t *occl;
     const float4 *ao_pix;     // MODE_AO: per local pixel, origin | start node and world normal | Hilbert index (k_ao_pixels)
     const float4 *ao_tab;     // MODE_AO: [sample][Hilbert index] tangent-frame direction (k_ao_table)
     AlphaView alpha;          // the instances with the alpha test only
@@ -830,13 +829,33 @@ __device__ unsigned long long g_trace_prof[8];
 #else
 #define TPROF(i, n)
 #endif
+// A persistent wave takes its next chunk: lane 0 pops from the eight per-XCD cursors, its own XCD's first, and everyone learns the result.  Returns the chunk's index,
+// 0xFFFFFFFF when every cursor is exhausted.  (The caller keeps exhausted / cur / end: handing them through here by reference costs k_trace up to 9 VGPRs.)
+__device__ __forceinline__ uint32_t pop_chunk(uint32_t *cursors, uint32_t n_chunks, uint32_t lane, uint32_t &shard, uint32_t &shards_left) {
+    uint32_t got = 0xFFFFFFFFu;
+    if (lane == 0) {
+        while (shards_left) { // shard s owns chunks [n*s/8, n*(s+1)/8): contiguous, so an XCD keeps a screen region
+            uint32_t lo = (n_chunks * shard) >> 3, hi = (n_chunks * (shard + 1u)) >> 3;
+            uint32_t c = hi > lo ? atomicAdd(&cursors[shard * kCursorStride], 1u) : 0u;
+            if (hi > lo && c < hi - lo) { got = lo + c; break; }
+            shard = (shard + 1u) & 7u; shards_left--;
+        }
+    }
+    got = __builtin_amdgcn_readfirstlane(got);
+    shard = __builtin_amdgcn_readfirstlane(shard);
+    shards_left = __builtin_amdgcn_readfirstlane(shards_left);
+    return got;
+}
+#ifndef ART_NODE_REPS
+#define ART_NODE_REPS 3   // node steps a lane may take per turn of the loop (the turn's ballots, refill test and branches are scalar work the wave pays per turn: config 5 19 000 -> 20 000 Mray/s at 3, 19 900 at 2, 19 000 at 6)
+#endif
 // Persistent-threads wavefront tracer.  Each wave keeps up to 64 rays in flight; when kRefill or more lanes have
 // finished it compacts the idle lanes with __ballot / mbcnt and hands them the next candidates of its chunk; chunks
 // come from eight per-XCD work cursors (one returning atomic per chunk), so neighbouring rays stay on one XCD's L2.
 // Every wave exits once all cursors are exhausted and its lanes are idle.
 template <int MODE, int WIDTH, bool ALPHA = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MODE == MODE_AO ? 8 : 4, 8))) void k_trace(TraceArgs a) {
-    constexpr bool ANY = MODE == MODE_SHADOW || MODE == MODE_QUERY_ANY || MODE == MODE_AO;
+    constexpr bool ANY = MODE == MODE_SHADOW || MODE == MODE_AO;
     __shared__ int stack[kLdsStack * kTraceBlock];
     int ovf[WIDTH == 4 ? kOvfStack4 : kOvfStack];
     const uint32_t leaf_batch = a.leaf_batch;
@@ -858,19 +877,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
         TPROF(0, 1); TPROF(7, 64 - __popcll(idle));
         uint32_t n_idle = (uint32_t)__popcll(idle);
         if (!exhausted && n_idle >= a.refill) {
-            if (cur == end) { // take the next chunk: lane 0 pops, everyone learns the result
-                uint32_t got = 0xFFFFFFFFu;
-                if (lane == 0) {
-                    while (shards_left) { // shard s owns chunks [n*s/8, n*(s+1)/8): contiguous, so an XCD keeps a screen region
-                        uint32_t lo = (n_chunks * shard) >> 3, hi = (n_chunks * (shard + 1u)) >> 3;
-                        uint32_t c = hi > lo ? atomicAdd(&a.cursors[shard * kCursorStride], 1u) : 0u;
-                        if (hi > lo && c < hi - lo) { got = lo + c; break; }
-                        shard = (shard + 1u) & 7u; shards_left--;
-                    }
-                }
-                got = __builtin_amdgcn_readfirstlane(got);
-                shard = __builtin_amdgcn_readfirstlane(shard);
-                shards_left = __builtin_amdgcn_readfirstlane(shards_left);
+            if (cur == end) {
+                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
                 if (got >= n_chunks) exhausted = true; // (also the never-expected out-of-range pop: no slot beyond total is touched)
                 else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
             }
@@ -909,11 +917,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
                         }
                     } else {
                         float4 r0 = a.rays[2 * (size_t)sidx];
-                        if (MODE != MODE_SHADOW || r0.w > 0.0f) {
+                        if (r0.w > 0.0f) {
                             float4 r1 = a.rays[2 * (size_t)sidx + 1];
-                            // shadow rays: tmin 0.01 (raytrace.rgen.glsl:174); queries carry their own tmin
-                            if (MODE == MODE_SHADOW) tr.start(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), 0.01f, r0.w);
-                            else tr.start(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), r0.w, r1.w);
+                            tr.start(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), 0.01f, r0.w);   // shadow rays: tmin 0.01 (raytrace.rgen.glsl:174)
                             active = true;
                         }
                     }
@@ -927,12 +933,10 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
             if (exhausted) break;
             continue;
         }
-        // one internal step for every lane standing on a node ...
+        // up to ART_NODE_REPS internal steps for every lane standing on a node ...  (this block and pooled_trace's are the same steps in two texts: one helper for both gave
+        // k_trace<0, 4, true> a 78th register, and the pooled loop alone lost 0.2 to 1.3 % of its rate through it -- profiles/README.md, "one pooled loop")
         bool done = false;
         { uint64_t nm_ = __ballot(active && tr.cur >= 0); if (nm_) { TPROF(1, 1); TPROF(2, __popcll(nm_)); } }
-#ifndef ART_NODE_REPS
-#define ART_NODE_REPS 3   // node steps a lane may take per turn of the loop (the turn's ballots, refill test and branches are scalar work the wave pays per turn: config 5 19 000 -> 20 000 Mray/s at 3, 19 900 at 2, 19 000 at 6)
-#endif
 #pragma unroll
         for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
         if (active && !done && tr.cur >= 0) {
@@ -948,10 +952,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
         }
         if (done) {
             active = false;
-            if (MODE == MODE_PRIMARY || MODE == MODE_QUERY_CLOSEST)
-                a.hits[slot] = tr.bpos != kNoHit ? make_float4(tr.tbest, tr.bu, tr.bv, __uint_as_float(tr.bpos))
-                                                 : make_float4(MODE == MODE_PRIMARY ? 10000.0f : tr.r.tmax, 0.f, 0.f, __uint_as_float(kNoHit));
-            else if (MODE == MODE_QUERY_ANY) a.any_out[slot] = tr.bpos != kNoHit ? 1u : 0u;
+            if (MODE == MODE_PRIMARY)
+                a.hits[slot] = tr.bpos != kNoHit ? make_float4(tr.tbest, tr.bu, tr.bv, __uint_as_float(tr.bpos)) : make_float4(10000.0f, 0.f, 0.f, __uint_as_float(kNoHit));
             else if (MODE == MODE_AO) a.occl[slot] = tr.bpos != kNoHit ? 1 : 0;
             else if (tr.bpos != kNoHit) { // shadowed: the light keeps 0.05 of its contribution (raytrace.rgen.glsl:179-181)
                 float4 c = a.contrib[slot];
@@ -969,135 +971,24 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
     }
 }
 
-// The queries' instances of k_trace (MODE_QUERY_CLOSEST / MODE_QUERY_ANY) are launched by nothing any more: art_query_* go through k_cast like every ray in a device buffer, and
-// their launchers are gone.  The instances themselves stay in the code object for one reason: tests/test_alpha.py and tests/test_ray_masks.py pin the presence, registers and
-// scratch of k_trace<2 | 3, 2 | 4, *> by name.  Once those two tests let go of them, these eight lines and the two modes go.
-template __global__ void k_trace<MODE_QUERY_CLOSEST, 2, false>(TraceArgs); template __global__ void k_trace<MODE_QUERY_CLOSEST, 4, false>(TraceArgs);
-template __global__ void k_trace<MODE_QUERY_CLOSEST, 2, true>(TraceArgs);  template __global__ void k_trace<MODE_QUERY_CLOSEST, 4, true>(TraceArgs);
-template __global__ void k_trace<MODE_QUERY_ANY, 2, false>(TraceArgs);     template __global__ void k_trace<MODE_QUERY_ANY, 4, false>(TraceArgs);
-template __global__ void k_trace<MODE_QUERY_ANY, 2, true>(TraceArgs);      template __global__ void k_trace<MODE_QUERY_ANY, 4, true>(TraceArgs);
-
-// The AO launch's own persistent tracer (round 4): rays are MADE by the whole wave, sixty-four at a time, into a pool in LDS, and a lane that finishes TAKES its next ray from
-// the pool at once (a dozen LDS reads) -- in k_trace a finished lane waits until two dozen lanes are idle, because a refill there is ~80 instructions whoever runs it: 48 of
-// 64 lanes held a ray (profiles/README.md round 3).  Same slots, same rays, same walks (Trav4, any hit): the occlusion bytes cannot change.
-constexpr int kAoLds = 8;           // per-lane stack entries in LDS (AO rays start deep in the tree and are short: the walk rarely holds more; the rest spills)
-constexpr int kAoPoolFields = 11;   // o.xyz d.xyz inv.xyz entry slot
-constexpr uint32_t kAoPoolTake = 8; // idle lanes at which the wave turns to the pool (ArtTuning.trace_refill overrides)
-template <bool ALPHA = false>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_trace_ao(TraceArgs a) {
-    __shared__ int stack[kAoLds * kTraceBlock];
-    __shared__ float pool[kAoPoolFields][kTraceBlock];
-    int ovf[kOvfStack4 + (kLdsStack - kAoLds)];
-    const uint32_t leaf_batch = a.leaf_batch;
-    int *lds = &stack[threadIdx.x];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;
-    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u; // HW_REG_XCC_ID: speed only
-    uint32_t shards_left = 8;
-    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
-    uint32_t pool_n = 0;         // wave-uniform: rays in the pool
-    bool exhausted = false, active = false;
-    Trav4<true, kAoLds, ALPHA> tr;
-    tr.r.tmin = a.ao_radius * 0.01f; tr.r.tmax = a.ao_radius;
-    uint32_t slot = 0;
-    for (;;) {
-        const uint64_t idle = ballot64(!active);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (n_idle >= a.refill) {
-            if (pool_n == 0 && !exhausted) {      // the pool is empty: the WHOLE wave makes the next (up to) 64 rays of its chunk
-                if (cur == end) {
-                    uint32_t got = 0xFFFFFFFFu;
-                    if (lane == 0) {
-                        while (shards_left) {
-                            uint32_t lo = (n_chunks * shard) >> 3, hi = (n_chunks * (shard + 1u)) >> 3;
-                            uint32_t c = hi > lo ? atomicAdd(&a.cursors[shard * kCursorStride], 1u) : 0u;
-                            if (hi > lo && c < hi - lo) { got = lo + c; break; }
-                            shard = (shard + 1u) & 7u; shards_left--;
-                        }
-                    }
-                    got = __builtin_amdgcn_readfirstlane(got);
-                    shard = __builtin_amdgcn_readfirstlane(shard);
-                    shards_left = __builtin_amdgcn_readfirstlane(shards_left);
-                    if (got >= n_chunks) exhausted = true;
-                    else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
-                }
-                if (!exhausted) {
-                    const uint32_t take = min(64u, end - cur), sidx = cur + lane;
-                    bool has = false;
-                    V3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 1.f); int entry = kAoNothingNear;
-                    if (lane < take) {
-                        uint32_t p, smp;
-                        const bool real = ao_slot_decode(sidx, a.spp, p, smp);
-                        float4 po = real ? a.ao_pix[2 * (size_t)p] : make_float4(0.f, 0.f, 0.f, __int_as_float(kAoNothingNear));
-                        float4 pn = real ? a.ao_pix[2 * (size_t)p + 1] : make_float4(0.f, 0.f, 1.f, 0.f);
-                        asm volatile("" : "+v"(pn.x), "+v"(pn.y), "+v"(pn.z), "+v"(pn.w));
-                        entry = __float_as_int(po.w);
-                        if (entry != kAoNothingNear) {
-                            float4 t = a.ao_tab[smp * kAoNoiseTile + __float_as_uint(pn.w)];
-                            o = mk(po.x, po.y, po.z); d = ao_dir(mk(pn.x, pn.y, pn.z), t.x, t.y, t.z);
-                            has = ray_finite(o, d);   // (a non-finite ray accepts nothing: unoccluded, like tr.start's dead ray)
-                        }
-                        if (!has) a.occl[sidx] = 0;    // a padding slot, a miss pixel, no box within the AO radius, a dead ray: nothing to trace
-                    }
-                    const uint64_t hm = ballot64(has);
-                    if (has) {
-                        const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-                        const V3 inv = mk(1.0f / safe_dir(d.x), 1.0f / safe_dir(d.y), 1.0f / safe_dir(d.z));   // ray_init's operations
-                        pool[0][at] = o.x; pool[1][at] = o.y; pool[2][at] = o.z; pool[3][at] = d.x; pool[4][at] = d.y; pool[5][at] = d.z;
-                        pool[6][at] = inv.x; pool[7][at] = inv.y; pool[8][at] = inv.z; pool[9][at] = __int_as_float(entry); pool[10][at] = __uint_as_float(sidx);
-                    }
-                    pool_n = (uint32_t)__popcll(hm);
-                    cur += take;
-                }
-            }
-            if (pool_n) {                             // idle lanes take rays from the top of the pool
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (!active && rank < pool_n) {
-                    const uint32_t at = pool_n - 1u - rank;
-                    tr.r.o = mk(pool[0][at], pool[1][at], pool[2][at]); tr.r.d = mk(pool[3][at], pool[4][at], pool[5][at]); tr.r.inv = mk(pool[6][at], pool[7][at], pool[8][at]);
-                    tr.r.ood = mk(tr.r.o.x * tr.r.inv.x, tr.r.o.y * tr.r.inv.y, tr.r.o.z * tr.r.inv.z);
-                    tr.tbest = tr.r.tmax; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.sp = 0;
-                    tr.cur = __float_as_int(pool[9][at]); slot = __float_as_uint(pool[10][at]);
-                    active = true;
-                }
-                pool_n -= min(n_idle, pool_n);
-            } else if (exhausted) { if (n_idle == 64u) break; }
-            if (ballot64(active) == 0ull) continue;   // nothing to trace yet (a chunk of padding / misses): make more
-        }
-        bool done = false;
-#pragma unroll
-        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
-            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
-        const bool on_leaf = active && !done && tr.cur < 0;
-        const uint64_t lm = ballot64(on_leaf);
-        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf, a.alpha); }
-        if (done) { active = false; a.occl[slot] = tr.bpos != kNoHit ? 1 : 0; }
-    }
-}
-
-// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT): k_trace_ao's shape with the rays read instead of made.  The whole
-// wave reads the next (up to) 64 rays of its chunk -- two 16-byte loads a lane, 2 KB a wave in one piece -- and writes the live ones into the pool with everything ray_init makes
-// of them; a dead ray (non-finite origin or direction, NaN tmax: TravBase::start's rule) gets its miss record there and then and never enters the pool.  A lane that finishes
-// takes its next ray from the pool at once.  One walk for every context, whatever ArtTuning says: Trav4 over the quantised 4-wide nodes (hits are structure-independent,
-// DESIGN.md 1.1).  Closest hits leave as t,u,v,0 and (primitive, triangle in the primitive): the walk carries the best candidate's gid, tri_prim names its primitive and
-// first_tri that primitive's first gid -- no triangle record, no host.  Any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's record depends on
-// the ray alone.
-struct CastK {
-    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
-    const float4 *rays; float4 *tuv; int2 *ids; uint8_t *hit;
-    uint32_t total, chunk, refill, leaf_batch;
-    uint32_t *cursors;        // 8 per-XCD chunk cursors, kCursorStride words apart (zeroed in front of the launch)
-    AlphaView alpha;          // the instances with the mask / alpha test only
-};
-static_assert(kCastCursorWords == 8u * kCursorStride, "a cast's cursor block");
-constexpr int kCastLds = 8;           // per-lane stack entries in LDS: 2 KB + the pool's 3 KB a wave = 32 waves in a CU's 160 KB
-constexpr int kCastPoolFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
-constexpr uint32_t kCastPoolTake = 8; // idle lanes at which the wave turns to the pool (ArtTuning.trace_refill overrides)
-template <bool ANY, bool ALPHA>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) {
-    __shared__ int stack[kCastLds * kTraceBlock];
-    __shared__ float pool[kCastPoolFields][kTraceBlock];
-    int ovf[kOvfStack4 + (kLdsStack - kCastLds)];
+// The pooled per-ray tracer (round 4, first for the AO launch): rays enter the wave sixty-four at a time -- the WHOLE wave makes or reads the next (up to) 64 slots of its chunk
+// and writes the live ones into a pool in LDS with everything ray_init makes of them -- and a lane that finishes TAKES its next ray from the top of the pool at once (a dozen
+// LDS reads).  In k_trace a finished lane waits until two dozen lanes are idle, because a refill there is ~80 instructions whoever runs it: 48 of 64 lanes held a ray
+// (profiles/README.md round 3).  LDS a wave: LDSN = 8 stack entries a lane, 2 KB, + the pool's 3 KB = 32 waves in a CU's 160 KB.  One walk, Trav4 over the quantised 4-wide
+// nodes (hits are structure-independent).  What differs between the two launches that run this loop is their Source:
+//   kFields                      pool fields a ray: o.xyz d.xyz inv.xyz, one or two of the source's own (e0, e1), slot
+//   init(tr)                     once per lane, before the loop
+//   fetch(sidx, o, d, e0, e1)    slot sidx's ray; returns whether there is one to walk, and has written the slot's record itself where there is none
+//   begin(tr, e0, e1)            a lane takes a ray: what the source's own fields set
+//   finish(tr, slot)             the finished ray's record
+constexpr uint32_t kPoolTake = 8;   // idle lanes at which the wave turns to the pool (ArtTuning.trace_refill overrides)
+template <int LDSN, bool ANY, bool ALPHA, class ARGS, class SOURCE>
+__device__ __forceinline__ void pooled_trace(const ARGS &a, const SOURCE &src) {
+    constexpr int kSlotField = SOURCE::kFields - 1;
+    static_assert(kSlotField == 10 || kSlotField == 11, "nine fields of the ray, one or two of the source, the slot");
+    __shared__ int stack[LDSN * kTraceBlock];
+    __shared__ float pool[SOURCE::kFields][kTraceBlock];
+    int ovf[kOvfStack4 + (kLdsStack - LDSN)];
     const uint32_t leaf_batch = a.leaf_batch;
     int *lds = &stack[threadIdx.x];
     const uint32_t lane = threadIdx.x & 63u;
@@ -1107,47 +998,31 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
     uint32_t pool_n = 0;         // wave-uniform: rays in the pool
     bool exhausted = false, active = false;
-    Trav4<ANY, kCastLds, ALPHA> tr;
+    Trav4<ANY, LDSN, ALPHA> tr;
+    src.init(tr);
     uint32_t slot = 0;
     for (;;) {
         const uint64_t idle = ballot64(!active);
         const uint32_t n_idle = (uint32_t)__popcll(idle);
         if (n_idle >= a.refill) {
-            if (pool_n == 0 && !exhausted) {      // the pool is empty: the WHOLE wave reads the next (up to) 64 rays of its chunk
+            if (pool_n == 0 && !exhausted) {      // the pool is empty: the WHOLE wave fetches the next (up to) 64 slots of its chunk
                 if (cur == end) {
-                    uint32_t got = 0xFFFFFFFFu;
-                    if (lane == 0) {
-                        while (shards_left) {
-                            uint32_t lo = (n_chunks * shard) >> 3, hi = (n_chunks * (shard + 1u)) >> 3;
-                            uint32_t c = hi > lo ? atomicAdd(&a.cursors[shard * kCursorStride], 1u) : 0u;
-                            if (hi > lo && c < hi - lo) { got = lo + c; break; }
-                            shard = (shard + 1u) & 7u; shards_left--;
-                        }
-                    }
-                    got = __builtin_amdgcn_readfirstlane(got);
-                    shard = __builtin_amdgcn_readfirstlane(shard);
-                    shards_left = __builtin_amdgcn_readfirstlane(shards_left);
+                    const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
                     if (got >= n_chunks) exhausted = true;   // (also the never-expected out-of-range pop: no record beyond total is touched)
                     else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
                 }
                 if (!exhausted) {
                     const uint32_t take = min(64u, end - cur), sidx = cur + lane;
                     bool has = false;
-                    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, 0.f);
-                    if (lane < take) {
-                        r0 = a.rays[2 * (size_t)sidx]; r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
-                        has = ray_finite(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z)) && r1.w == r1.w;
-                        if (!has) {                // a dead ray accepts nothing: its miss record, without a walk
-                            if (ANY) a.hit[sidx] = 0;
-                            else { a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1); }
-                        }
-                    }
+                    V3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 1.f); float e0 = 0.f, e1 = 0.f;
+                    if (lane < take) has = src.fetch(sidx, o, d, e0, e1);
                     const uint64_t hm = ballot64(has);
                     if (has) {
                         const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-                        const V3 inv = mk(1.0f / safe_dir(r1.x), 1.0f / safe_dir(r1.y), 1.0f / safe_dir(r1.z));   // ray_init's operations
-                        pool[0][at] = r0.x; pool[1][at] = r0.y; pool[2][at] = r0.z; pool[3][at] = r1.x; pool[4][at] = r1.y; pool[5][at] = r1.z;
-                        pool[6][at] = inv.x; pool[7][at] = inv.y; pool[8][at] = inv.z; pool[9][at] = r0.w; pool[10][at] = r1.w; pool[11][at] = __uint_as_float(sidx);
+                        const V3 inv = mk(1.0f / safe_dir(d.x), 1.0f / safe_dir(d.y), 1.0f / safe_dir(d.z));   // ray_init's operations
+                        pool[0][at] = o.x; pool[1][at] = o.y; pool[2][at] = o.z; pool[3][at] = d.x; pool[4][at] = d.y; pool[5][at] = d.z;
+                        pool[6][at] = inv.x; pool[7][at] = inv.y; pool[8][at] = inv.z; pool[9][at] = e0; if (kSlotField == 11) pool[10][at] = e1;
+                        pool[kSlotField][at] = __uint_as_float(sidx);
                     }
                     pool_n = (uint32_t)__popcll(hm);
                     cur += take;
@@ -1159,33 +1034,95 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                     const uint32_t at = pool_n - 1u - rank;
                     tr.r.o = mk(pool[0][at], pool[1][at], pool[2][at]); tr.r.d = mk(pool[3][at], pool[4][at], pool[5][at]); tr.r.inv = mk(pool[6][at], pool[7][at], pool[8][at]);
                     tr.r.ood = mk(tr.r.o.x * tr.r.inv.x, tr.r.o.y * tr.r.inv.y, tr.r.o.z * tr.r.inv.z);
-                    tr.r.tmin = pool[9][at]; tr.r.tmax = pool[10][at];
-                    tr.tbest = tr.r.tmax; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.sp = 0; tr.cur = 0;
-                    slot = __float_as_uint(pool[11][at]);
+                    src.begin(tr, pool[9][at], kSlotField == 11 ? pool[10][at] : 0.f);
+                    tr.tbest = tr.r.tmax; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.sp = 0;
+                    slot = __float_as_uint(pool[kSlotField][at]);
                     active = true;
                 }
                 pool_n -= min(n_idle, pool_n);
             } else if (exhausted) { if (n_idle == 64u) break; }
-            if (ballot64(active) == 0ull) continue;   // nothing to trace yet (64 dead rays): read more
+            if (ballot64(active) == 0ull) continue;   // nothing to trace yet (a chunk of padding / misses, 64 dead rays): fetch more
         }
-        bool done = false;
+        bool done = false;   // k_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
 #pragma unroll
         for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
             if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
         const bool on_leaf = active && !done && tr.cur < 0;
         const uint64_t lm = ballot64(on_leaf);
         if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a.tris, lds, ovf, a.alpha); }
-        if (done) {
-            active = false;
-            if (ANY) a.hit[slot] = tr.bpos != kNoHit ? 1 : 0;
-            else if (tr.bgid != kNoHit) {             // the ids, on the device: gid -> primitive (k_soup's table) -> triangle in the primitive
-                const uint32_t prim = a.tri_prim[tr.bgid];
-                a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
-                a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
-            } else { a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1); }
-        }
+        if (done) { active = false; src.finish(tr, slot); }
     }
 }
+
+// The AO launch's rays are MADE: the pixel's point, entry node and normal (k_ao_pixels), the sample's tangent-frame direction (k_ao_table) and a frame from the normal.
+// Same slots, same rays, same walks as k_trace<MODE_AO, 4> (Trav4, any hit): the occlusion bytes cannot differ.
+constexpr int kAoLds = 8;           // per-lane stack entries in LDS (AO rays start deep in the tree and are short: the walk rarely holds more; the rest spills)
+struct AoSource {
+    static constexpr int kFields = 11;   // o.xyz d.xyz inv.xyz entry slot
+    const TraceArgs &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.r.tmin = a.ao_radius * 0.01f; tr.r.tmax = a.ao_radius; }   // the same for every ray
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &) const {
+        uint32_t p, smp;
+        const bool real = ao_slot_decode(sidx, a.spp, p, smp);
+        float4 po = real ? a.ao_pix[2 * (size_t)p] : make_float4(0.f, 0.f, 0.f, __int_as_float(kAoNothingNear));
+        float4 pn = real ? a.ao_pix[2 * (size_t)p + 1] : make_float4(0.f, 0.f, 1.f, 0.f);
+        asm volatile("" : "+v"(pn.x), "+v"(pn.y), "+v"(pn.z), "+v"(pn.w));
+        bool has = false;
+        e0 = po.w;   // the entry node
+        if (__float_as_int(po.w) != kAoNothingNear) {
+            float4 t = a.ao_tab[smp * kAoNoiseTile + __float_as_uint(pn.w)];
+            o = mk(po.x, po.y, po.z); d = ao_dir(mk(pn.x, pn.y, pn.z), t.x, t.y, t.z);
+            has = ray_finite(o, d);   // (a non-finite ray accepts nothing: unoccluded, like tr.start's dead ray)
+        }
+        if (!has) a.occl[sidx] = 0;    // a padding slot, a miss pixel, no box within the AO radius, a dead ray: nothing to trace
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float) const { tr.cur = __float_as_int(e0); }   // the walk starts below the part of the tree that every ray of this pixel would cross alike
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const { a.occl[slot] = tr.bpos != kNoHit ? 1 : 0; }
+};
+template <bool ALPHA = false>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_trace_ao(TraceArgs a) { pooled_trace<kAoLds, true, ALPHA>(a, AoSource{a}); }
+
+// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT), are READ -- two 16-byte loads a lane, 2 KB a wave in one
+// piece.  A dead ray (non-finite origin or direction, NaN tmax: TravBase::start's rule) gets its miss record there and then and never enters the pool.  One walk for every
+// context, whatever ArtTuning says.  Closest hits leave as t,u,v,0 and (primitive, triangle in the primitive): the walk carries the best candidate's gid, tri_prim names its
+// primitive and first_tri that primitive's first gid -- no triangle record, no host.  Any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's
+// record depends on the ray alone.
+struct CastK {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *rays; float4 *tuv; int2 *ids; uint8_t *hit;
+    uint32_t total, chunk, refill, leaf_batch;
+    uint32_t *cursors;        // 8 per-XCD chunk cursors, kCursorStride words apart (zeroed in front of the launch)
+    AlphaView alpha;          // the instances with the mask / alpha test only
+};
+static_assert(kCastCursorWords == 8u * kCursorStride, "a cast's cursor block");
+constexpr int kCastLds = 8;           // per-lane stack entries in LDS
+template <bool ANY> struct CastSource {
+    static constexpr int kFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
+    const CastK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &) const {}
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
+        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+        const bool has = ray_finite(o, d) && r1.w == r1.w;
+        if (!has) {                // a dead ray accepts nothing: its miss record, without a walk
+            if (ANY) a.hit[sidx] = 0;
+            else { a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1); }
+        }
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
+        if (ANY) a.hit[slot] = tr.bpos != kNoHit ? 1 : 0;
+        else if (tr.bgid != kNoHit) {             // the ids, on the device: gid -> primitive (k_soup's table) -> triangle in the primitive
+            const uint32_t prim = a.tri_prim[tr.bgid];
+            a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
+            a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+        } else { a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1); }
+    }
+};
+template <bool ANY, bool ALPHA>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) { pooled_trace<kCastLds, ANY, ALPHA>(a, CastSource<ANY>{a}); }
 
 // ------------------------------------------------------------------------------------------------ lights (light.glsl)
 __device__ V3 compute_barycentric(V3 a, V3 b, V3 c, V3 p) { // light.glsl:50-68
@@ -1846,7 +1783,7 @@ void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint
 void math_sweep_guard(float guard[2]) { guard[0] = kExactLo; guard[1] = kExactHi; }
 // rays in device buffers (art_cast_rays and, through it, the queries): {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernel has -- a cast is
 // throughput-bound like it -- with the context's ArtTuning overrides
-static const Tune kCastPreset = {256, kCastPoolTake, 2048, 8};
+static const Tune kCastPreset = {256, kPoolTake, 2048, 8};
 void launch_cast(const CastArgs &c, hipStream_t s) {
     if (!c.n) return;
     const Tune t = tune_over(kCastPreset, c.tune);
@@ -1901,12 +1838,11 @@ void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, fl
     k_ao_pixels<<<blocks_for(f.n_local), kBlock, 0, s>>>(f, ((f.trace_kind[2] == 4 || f.trace_kind[2] == 6) && entry_search) ? f.wide : nullptr, radius, pix); // one point, normal and entry node per pixel for its spp rays
     const uint32_t n_slots = (f.n_local / 16u) * (((spp + 3u) >> 2) * 64u); // ao_slot_decode
     TraceArgs a{};
-    a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = n_slots; a.cursors = f.counters + 64 + 16 * kCursorStride; a.cam = f.cam; a.W = f.W; a.H = f.H;
-    a.tile_list = f.tile_list; a.tiles_x = f.tiles_x; a.depth = f.depth; a.normal = f.normal; a.spp = spp; a.ao_radius = radius; a.occl = occl;
+    a.nodes = f.nodes; a.wide = f.wide; a.tris = f.tris; a.total = n_slots; a.cursors = f.counters + 64 + 16 * kCursorStride; a.spp = spp; a.ao_radius = radius; a.occl = occl;
     a.ao_pix = pix; a.ao_tab = tab; a.alpha = alpha_view(f, 2);
     if (f.trace_kind[2] == 4) {   // the default: the AO launch's own tracer (rays made by the whole wave into a pool); 6 = the same walk through the generic tracer (round 3's form), 2 = binary nodes
         Tune t = tune(f.pipelined, true, f.tune);
-        if (!(f.tune.refill >= 1 && f.tune.refill <= 64)) t.refill = kAoPoolTake;
+        if (!(f.tune.refill >= 1 && f.tune.refill <= 64)) t.refill = kPoolTake;
         a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch;
         if (f.alpha) k_trace_ao<true><<<persistent_blocks(a.total, t), kTraceBlock, 0, s>>>(a);
         else k_trace_ao<<<persistent_blocks(a.total, t), kTraceBlock, 0, s>>>(a);

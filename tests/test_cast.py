@@ -139,6 +139,61 @@ def test_sizes_at_which_the_kernel_can_go_wrong(R, torch, orc, get_scene):
     r.close()
 
 
+_PARTLY_DEAD = {}
+
+
+def _partly_dead(ref, n=193):
+    """n of the reference's rays -- by the oracle's records one that hits, one that hits, one that misses, and so on -- with every third one, the first of each three, dead
+    by _dead_rays' three rules in rotation, and the oracle's records for them: computed once, never written"""
+    if not _PARTLY_DEAD:
+        hits, misses = np.flatnonzero(ref["ids"][:, 0] >= 0), np.flatnonzero(ref["ids"][:, 0] < 0)
+        pick = np.empty(n, np.int64)
+        pick[0::3], pick[1::3], pick[2::3] = hits[:len(pick[0::3])], hits[n:n + len(pick[1::3])], misses[:len(pick[2::3])]
+        out = {}
+        for key in ("rays", "short"):
+            rays = ref[key][pick]
+            rays[0::3] = _dead_rays(rays[0::3])
+            out[key] = rays
+        out["tuv"], out["ids"] = ref["S"].trace_closest(out["rays"])[:2]
+        out["hit"] = ref["S"].trace_any(out["short"])[0]
+        for a in out.values():
+            a.setflags(write=False)
+        _PARTLY_DEAD.update(out)
+    return _PARTLY_DEAD
+
+
+def test_the_partly_dead_rays_are_a_mixed_lot(orc, get_scene):
+    """without a GPU: of the 193 rays of the test below every third is dead -- a miss in the oracle's records -- and the live ones hold at least 50 hits and 50 misses"""
+    pd = _partly_dead(_ref(orc, get_scene, "sponza_like", 0.12, 20000))
+    dead = np.arange(193) % 3 == 0
+    assert not np.isfinite(pd["rays"][dead]).all(axis=1).any() and np.isfinite(pd["rays"][~dead]).all()
+    assert (pd["ids"][dead] == -1).all() and not pd["hit"][dead].any()
+    hits = int((pd["ids"][~dead, 0] >= 0).sum())
+    assert hits >= 50 and int((~dead).sum()) - hits >= 50 and 0 < int(pd["hit"][~dead].sum()) < int((~dead).sum())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("refill", [1, 64])
+def test_a_partly_dead_pool_filling_is_compacted(R, torch, orc, get_scene, refill):
+    """193 rays, every third dead, ArtTuning.trace_chunk = 64: each pool filling holds 21 or 22 dead slots between live ones, so the live rays are compacted around records
+    written at once; idle lanes take from the pool one at a time (trace_refill = 1) or only once the whole wave is idle (64).  Closest records and any-hit bytes are the
+    oracle's, and the records behind the n-th keep what they held"""
+    pd = _partly_dead(_ref(orc, get_scene, "sponza_like", 0.12, 20000))
+    n, pad = pd["rays"].shape[0], 5
+    r = R.renderer_for_scene(_ref(orc, get_scene, "sponza_like", 0.12, 20000)["scene"], (64, 64), tuning={"trace_chunk": 64, "trace_refill": refill})
+    d_rays, d_short = _up(torch, pd["rays"]), _up(torch, pd["short"])
+    o_tuv = torch.full((n + pad, 4), PATTERN, dtype=torch.int32, device="cuda").view(torch.float32)
+    o_ids = torch.full((n + pad, 2), PATTERN, dtype=torch.int32, device="cuda")
+    o_hit = torch.full((n + pad,), 0xA5, dtype=torch.uint8, device="cuda")
+    r.cast_rays(d_rays, out=(o_tuv, o_ids))
+    r.cast_rays(d_short, kind="any", out=o_hit)
+    torch.cuda.synchronize()
+    _same_closest((o_tuv[:n], o_ids[:n]), (pd["tuv"], pd["ids"]), f"refill {refill}")
+    _same_any(o_hit[:n], pd["hit"], f"refill {refill}")
+    assert (o_tuv[n:].view(torch.int32) == PATTERN).all() and (o_ids[n:] == PATTERN).all() and (o_hit[n:] == 0xA5).all(), "records behind the n-th were written"
+    r.close()
+
+
 # ---- the alpha card of tests/test_alpha.py (its construction, restated) ---------------------------------------------------------------------------------
 def _tex(alpha, rgb=(180, 150, 120)):
     th, tw = alpha.shape

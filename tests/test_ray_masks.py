@@ -615,10 +615,13 @@ _FILTERED = {(1, 1, 1, 1): (62, 0), (1, 1, 1, 0): (61, 0), (1, 1, 0, 1): (62, 0)
 # k_trace<MODE, WIDTH, true>: (VGPRs, scratch bytes -- the per-lane stacks' overflow area).  MODE 0, the primary tracer, is launched at 4 to 8 waves a SIMD
 # (amdgpu_waves_per_eu(4, 8)) and has been above 64 registers since before any filter, with and without it: 68 / 77 unfiltered, 71 / 77 with the alpha rule; the
 # visibility rule added nothing to either, which is what is pinned here.  Every other filtered instance stays within 64.
-_TRACE = {(0, 2): (71, 336), (0, 4): (77, 1168), (1, 2): (58, 336), (1, 4): (61, 1168), (2, 2): (63, 336), (2, 4): (63, 1168),
-          (3, 2): (57, 336), (3, 4): (60, 1168), (4, 2): (57, 336), (4, 4): (63, 1168)}
+_TRACE = {(0, 2): (71, 336), (0, 4): (77, 1168), (1, 2): (58, 336), (1, 4): (61, 1168), (4, 2): (57, 336), (4, 4): (63, 1168)}
 _TRACE_OVER_64 = {(0, 2), (0, 4)}
 _AO = (61, 1200)
+# the pooled tracer's instances (one loop, two sources): mangled name -> (VGPRs, scratch bytes, LDS bytes a workgroup: 2 KB of stacks + 11 or 12 pool fields x 256 bytes)
+_POOLED = {"_ZN3art10k_trace_aoILb0EEEvNS_9TraceArgsE": (60, 1200, 4864), "_ZN3art10k_trace_aoILb1EEEvNS_9TraceArgsE": (61, 1200, 4864),
+           "_ZN3art6k_castILb0ELb0EEEvNS_5CastKE": (58, 1200, 5120), "_ZN3art6k_castILb0ELb1EEEvNS_5CastKE": (59, 1200, 5120),
+           "_ZN3art6k_castILb1ELb0EEEvNS_5CastKE": (60, 1200, 5120), "_ZN3art6k_castILb1ELb1EEEvNS_5CastKE": (61, 1200, 5120)}
 
 
 def test_the_filtered_instances_in_the_code_object():
@@ -634,7 +637,7 @@ def test_the_filtered_instances_in_the_code_object():
     for key, (vgpr, scratch) in _FILTERED.items():
         d = k[_FRAME.format(*key, 1)]
         assert d["vgpr"] + d["agpr"] <= 64 and (d["vgpr"], d["scratch"]) == (vgpr, scratch), (key, d)
-    assert len(_FILTERED) == 16 and len(_TRACE) == 10
+    assert len(_FILTERED) == 16 and len(_TRACE) == 6
     for (mode, width), (vgpr, scratch) in _TRACE.items():
         d = k[f"_ZN3art7k_traceILi{mode}ELi{width}ELb1EEEvNS_9TraceArgsE"]
         plain = k[f"_ZN3art7k_traceILi{mode}ELi{width}ELb0EEEvNS_9TraceArgsE"]
@@ -642,3 +645,6 @@ def test_the_filtered_instances_in_the_code_object():
         assert (d["vgpr"] <= 64) == ((mode, width) not in _TRACE_OVER_64), (mode, width, d)
     d = k["_ZN3art10k_trace_aoILb1EEEvNS_9TraceArgsE"]
     assert d["vgpr"] + d["agpr"] <= 64 and (d["vgpr"], d["scratch"]) == _AO, d
+    for name, figures in _POOLED.items():
+        d = k[name]
+        assert d["vgpr"] + d["agpr"] <= 64 and (d["vgpr"], d["scratch"], d["lds"]) == figures, (name, d)

@@ -4,7 +4,7 @@
   --mode cast    per ordering and kind (closest, any): device time per cast from events on the cast's stream around --casts casts after --warmup of them; Mray/s
   --mode query   the same rays through art_query_closest / art_query_any (host buffers): runs on a build without art_cast_rays too (ART_LIB_PATH, or a checkout of an
                  earlier commit) -- the kernel's time then comes from `rocprofv3 --kernel-trace --stats -- python tools/cast_probe.py --mode query` (k_trace<2, ..> there,
-                 k_cast<..> here), in a run of its own; --repeats queries per ordering
+                 k_cast<..> here: this build has no k_trace<2, ..> instance any more), in a run of its own; --repeats queries per ordering
   --mode frames  what a 1920 x 1080 frame costs (8 ring slots, --steps frames, fenced at both ends) alone and with casts of the shuffled rays kept in flight beside it
 One JSON line.
     python tools/cast_probe.py --mode cast [--casts 20] [--warmup 5] [--leaf-batch N] [--refill N] [--chunk N]"""

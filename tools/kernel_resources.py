@@ -83,5 +83,5 @@ if __name__ == "__main__":
     pats = sys.argv[1:]   # (mangled: k_frame<true, ...> is "k_frameILb1...")
     for name, k in sorted(kernel_resources().items()):
         if all(p in name for p in pats):
-            print(f"{k['vgpr']:4d} vgpr {k['agpr']:3d} agpr {k['sgpr']:3d} sgpr {k['scratch']:6d} B scratch  spills v{k['spill_v']} s{k['spill_s']}  "
+            print(f"{k['vgpr']:4d} vgpr {k['agpr']:3d} agpr {k['sgpr']:3d} sgpr {k['scratch']:6d} B scratch {k['lds']:6d} B lds  spills v{k['spill_v']} s{k['spill_s']}  "
                   f"{k['waves_per_simd']} waves/SIMD  {name}")
