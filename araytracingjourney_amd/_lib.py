@@ -69,12 +69,19 @@ class ArtTuning(C.Structure):
 ART_CAST_CLOSEST, ART_CAST_ANY = 0, 1
 ART_CAST_MAX_RAYS = 2147418112   # 2^31 - 65536 (include/art.h)
 ART_CAST_POOL = 32               # casts in flight before art_cast_rays waits for the oldest
+ART_CAST_MAX_HITS = 8            # art_cast_rays_multi: the most records a ray
 
 
 class ArtRayCast(C.Structure):
     """one art_cast_rays: device pointers, the stream, and what to trace"""
     _fields_ = [("rays_dev", C.c_void_p), ("tuv_dev", C.c_void_p), ("ids_dev", C.c_void_p), ("hit_dev", C.c_void_p), ("hip_stream", C.c_void_p),
                 ("n", C.c_uint32), ("kind", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ArtRayCastMulti(C.Structure):
+    """one art_cast_rays_multi: the first max_hits hits of each ray, in order"""
+    _fields_ = [("rays_dev", C.c_void_p), ("tuv_dev", C.c_void_p), ("ids_dev", C.c_void_p), ("count_dev", C.c_void_p), ("hip_stream", C.c_void_p),
+                ("n", C.c_uint32), ("max_hits", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class ArtLayout(C.Structure):
@@ -126,6 +133,7 @@ SYMBOLS = {
     "art_trace": (_I32, [_P]),
     "art_sync": (_I32, [_P]),
     "art_cast_rays": (_I32, [_P, _P]),
+    "art_cast_rays_multi": (_I32, [_P, _P]),
     "art_cast_sync": (_I32, [_P]),
     "art_cast_counts": (_I32, [_P, _P, _P, _P]),
     "art_present": (_I32, [_P]),

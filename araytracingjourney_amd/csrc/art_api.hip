@@ -1979,7 +1979,8 @@ static int32_t cast_setup(ArtContext *c) {
     return ART_OK;
 }
 // Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
-static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block) {
+// max_hits > 0: art_cast_rays_multi's cast (any false; hit = its count bytes, or null) -- the same blocks, version hold, events and refit, another kernel.
+static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0) {
     int32_t r = use_device(c); if (r) return r;
     r = cast_setup(c); if (r) return r;
     CastState &K = c->cast;
@@ -2005,7 +2006,8 @@ static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool an
     const AsPtrs as = as_ptrs(c, ver);
     CastArgs a{};
     a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
-    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = (uint8_t *)hit; a.cursors = cursors;
+    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = max_hits ? nullptr : (uint8_t *)hit; a.cursors = cursors;
+    a.max_hits = max_hits; a.count = max_hits ? (uint8_t *)hit : nullptr;
     a.tune = TraceTune{c->tuning.trace_chunk, c->tuning.trace_refill, c->tuning.trace_blocks, c->tuning.trace_leaf_batch};
     a.alpha = c->alpha_live || cull == 0u;   // the filtered instances run while the scene needs them or the mask is 0 (such rays see nothing, and no leaf bit says so)
     a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p; a.cull = cull;
@@ -2037,6 +2039,21 @@ int32_t art_cast_rays(ArtContext *c, const ArtRayCast *d) {
     if (!c->built) return fail(ART_E_STATE, "art_cast_rays: scene not built (art_scene_build)");
     if (d->n == 0u) return ART_OK;
     return cast_enqueue(c, d->rays_dev, d->n, any, d->cull_mask, d->tuv_dev, d->ids_dev, d->hit_dev, (hipStream_t)d->hip_stream, nullptr);
+}
+
+int32_t art_cast_rays_multi(ArtContext *c, const ArtRayCastMulti *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_cast_rays_multi: null argument");
+    if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return fail(ART_E_INVALID, "art_cast_rays_multi: max_hits: 1 .. ART_CAST_MAX_HITS");
+    if (d->flags != 0u) return fail(ART_E_INVALID, "art_cast_rays_multi: flags: must be 0");
+    if (d->cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_cast_rays_multi: cull_mask: above 0xFF");
+    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_cast_rays_multi: n: above ART_CAST_MAX_RAYS");
+    auto bad = [&](const void *p, size_t align) { return (p == nullptr && d->n != 0u) || ((uintptr_t)p & (align - 1)) != 0; };   // (n = 0 touches nothing, as in art_cast_rays)
+    if (bad(d->rays_dev, 16)) return fail(ART_E_INVALID, "art_cast_rays_multi: rays_dev: null or not 16-byte aligned");
+    if (bad(d->tuv_dev, 16)) return fail(ART_E_INVALID, "art_cast_rays_multi: tuv_dev: null or not 16-byte aligned");
+    if (bad(d->ids_dev, 8)) return fail(ART_E_INVALID, "art_cast_rays_multi: ids_dev: null or not 8-byte aligned");
+    if (!c->built) return fail(ART_E_STATE, "art_cast_rays_multi: scene not built (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    return cast_enqueue(c, d->rays_dev, d->n, false, d->cull_mask, d->tuv_dev, d->ids_dev, d->count_dev, (hipStream_t)d->hip_stream, nullptr, d->max_hits);
 }
 
 int32_t art_cast_sync(ArtContext *c) {

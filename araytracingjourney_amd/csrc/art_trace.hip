@@ -982,7 +982,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MOD
 //   begin(tr, e0, e1)            a lane takes a ray: what the source's own fields set
 //   finish(tr, slot)             the finished ray's record
 constexpr uint32_t kPoolTake = 8;   // idle lanes at which the wave turns to the pool (ArtTuning.trace_refill overrides)
-template <int LDSN, bool ANY, bool ALPHA, class ARGS, class SOURCE>
+template <int LDSN, bool ANY, bool ALPHA, class ARGS, class SOURCE, class TRAV = Trav4<ANY, LDSN, ALPHA>>   // TRAV: the candidate policy (any | closest; TravMulti: the first K)
 __device__ __forceinline__ void pooled_trace(const ARGS &a, const SOURCE &src) {
     constexpr int kSlotField = SOURCE::kFields - 1;
     static_assert(kSlotField == 10 || kSlotField == 11, "nine fields of the ray, one or two of the source, the slot");
@@ -998,7 +998,7 @@ __device__ __forceinline__ void pooled_trace(const ARGS &a, const SOURCE &src) {
     uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
     uint32_t pool_n = 0;         // wave-uniform: rays in the pool
     bool exhausted = false, active = false;
-    Trav4<ANY, LDSN, ALPHA> tr;
+    TRAV tr;
     src.init(tr);
     uint32_t slot = 0;
     for (;;) {
@@ -1123,6 +1123,85 @@ template <bool ANY> struct CastSource {
 };
 template <bool ANY, bool ALPHA>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) { pooled_trace<kCastLds, ANY, ALPHA>(a, CastSource<ANY>{a}); }
+
+// The first K hits of each ray, in order (art_cast_rays_multi): the third candidate policy.  The closest walk keeps ONE best candidate; this one keeps a list
+// of up to K entries (t_eff, u, v, gid) a lane in ascending (t_eff, gid) -- in LDS, [entry][lane] like the walk stack, 16 bytes an entry, so the insertion runs on ds_read /
+// ds_write_b128 with the entry index in a register and nothing goes to scratch.  tbest / bgid are the walk's LIMIT: (tmax, none) until the list is full, the K-th entry's pair
+// from then on -- every box test of Trav4 and the leaf's exact slab cull against it as they cull against the best candidate in the closest walk, and a candidate enters iff it
+// is below the limit in the total order, which is the closest walk's comparison, word for word (K = 1 IS the closest walk).  Every triangle sits in one leaf and a walk visits a
+// leaf at most once: no entry can arrive twice, nothing is checked.  Only a candidate that would enter is put to the mask / alpha test.  (step_leaf is TravBase's text up to
+// the candidate's fate: a hook inside TravBase for it would be a change to the code of k_cast and k_trace_ao, whose registers are pinned.)
+template <int KMAX, int LDSN, bool ALPHA> struct TravMulti : Trav4<false, LDSN, ALPHA> {
+    uint32_t K, cnt;   // K: 1..KMAX, wave-uniform; cnt: entries held, 0..K
+    uint4 *list;       // this lane's entry 0; entry j at list[j * kTraceBlock]
+    __device__ __forceinline__ void bind(uint32_t k) {
+        __shared__ uint4 hits[KMAX * kTraceBlock];
+        K = min(max(k, 1u), (uint32_t)KMAX); cnt = 0u; list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+    }
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+        uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // an absent child (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
+        float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];
+        asm volatile("" : "+v"(td.x), "+v"(td.y), "+v"(td.z), "+v"(td.w), "+v"(tc.y), "+v"(tc.z), "+v"(tc.w));
+        float te, t, u, v;
+        if (moller_trumbore(this->r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v)) {
+            if (slab(this->r, tc.y, tc.z, tc.w, td.x, td.y, td.z, this->tbest, te)) {
+                const float teff = fmaxf(t, te);
+                const uint32_t gid = __float_as_uint(td.w);
+                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && (!ALPHA || !alpha_cut(av, pos, u, v))) {
+                    uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
+                    while (j > 0u) {                 // entries above the candidate move up one
+                        const uint4 p = list[(j - 1u) * kTraceBlock];
+                        const float pt = __uint_as_float(p.x);
+                        if (pt < teff || (pt == teff && p.w < gid)) break;
+                        list[j * kTraceBlock] = p; j--;
+                    }
+                    list[j * kTraceBlock] = make_uint4(__float_as_uint(teff), __float_as_uint(u), __float_as_uint(v), gid);
+                    cnt = min(cnt + 1u, K);
+                    if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; this->tbest = __uint_as_float(e.x); this->bgid = e.w; }   // full: the K-th entry is the limit
+                }
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+};
+struct CastMultiK : CastK { uint8_t *count; uint32_t max_hits; };   // tuv / ids: max_hits records a ray, ray-major; count: a byte a ray, or null
+template <int KMAX> struct CastMultiSource {
+    static constexpr int kFields = 12;   // CastSource's
+    const CastMultiK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.bind(a.max_hits); }
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];
+        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+        const bool has = ray_finite(o, d) && r1.w == r1.w;
+        if (!has) {                // a dead ray: K miss records with tmax as given, no walk
+            const size_t base = (size_t)sidx * a.max_hits;
+            for (uint32_t j = 0; j < a.max_hits; j++) { a.tuv[base + j] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[base + j] = make_int2(-1, -1); }
+            if (a.count) a.count[sidx] = 0;
+        }
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; tr.cnt = 0u; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
+        const size_t base = (size_t)slot * tr.K;
+        for (uint32_t j = 0; j < tr.K; j++) {
+            if (j < tr.cnt) {      // the ids as CastSource makes them
+                const uint4 e = tr.list[j * kTraceBlock];
+                const uint32_t prim = a.tri_prim[e.w];
+                a.tuv[base + j] = make_float4(__uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z), 0.f);
+                a.ids[base + j] = make_int2((int)prim, (int)(e.w - a.first_tri[prim]));
+            } else { a.tuv[base + j] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[base + j] = make_int2(-1, -1); }
+        }
+        if (a.count) a.count[slot] = (uint8_t)tr.cnt;
+    }
+};
+// KMAX 4 | 8: the list is KMAX KB of LDS a wave on top of the 5 KB of stack and pool, and LDS is what bounds the waves a CU holds -- small K keeps more resident.
+// (waves_per_eu: LDS allows four waves a SIMD with KMAX 4 and three with KMAX 8, so the registers of that many are the kernel's to use)
+template <int KMAX, bool ALPHA>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 4, 4))) void k_cast_multi(CastMultiK a) {
+    pooled_trace<kCastLds, false, ALPHA, CastMultiK, CastMultiSource<KMAX>, TravMulti<KMAX, kCastLds, ALPHA>>(a, CastMultiSource<KMAX>{a});
+}
 
 // ------------------------------------------------------------------------------------------------ lights (light.glsl)
 __device__ V3 compute_barycentric(V3 a, V3 b, V3 c, V3 p) { // light.glsl:50-68
@@ -1792,6 +1871,13 @@ void launch_cast(const CastArgs &c, hipStream_t s) {
     a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
     a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
     const uint32_t nb = persistent_blocks(c.n, t);
+    if (c.max_hits) {   // the first K hits: the instance with the smallest list that holds K
+        CastMultiK m{}; static_cast<CastK &>(m) = a; m.count = c.count; m.max_hits = c.max_hits;
+        if (c.max_hits <= 4u) { if (c.alpha) k_cast_multi<4, true><<<nb, kTraceBlock, 0, s>>>(m); else k_cast_multi<4, false><<<nb, kTraceBlock, 0, s>>>(m); }
+        else if (c.alpha) k_cast_multi<8, true><<<nb, kTraceBlock, 0, s>>>(m);
+        else k_cast_multi<8, false><<<nb, kTraceBlock, 0, s>>>(m);
+        return;
+    }
     if (c.any) { if (c.alpha) k_cast<true, true><<<nb, kTraceBlock, 0, s>>>(a); else k_cast<true, false><<<nb, kTraceBlock, 0, s>>>(a); }
     else if (c.alpha) k_cast<false, true><<<nb, kTraceBlock, 0, s>>>(a);
     else k_cast<false, false><<<nb, kTraceBlock, 0, s>>>(a);

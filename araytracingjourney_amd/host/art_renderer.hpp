@@ -270,6 +270,14 @@ public:
         ArtRayCast d{}; d.rays_dev = rays_dev; d.hit_dev = hit_dev; d.hip_stream = hip_stream; d.n = n; d.kind = ART_CAST_ANY; d.cull_mask = cull_mask;
         return d;
     }
+    // the first max_hits hits of each ray in ascending (t, global triangle id): n x max_hits records, ray-major, and (optionally) a count byte a ray (art_cast_rays_multi)
+    static ArtRayCastMulti multi_cast(const void *rays_dev, uint32_t n, uint32_t max_hits, void *tuv_dev, void *ids_dev, void *count_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtRayCastMulti d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.count_dev = count_dev; d.hip_stream = hip_stream; d.n = n; d.max_hits = max_hits; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtRayCastMulti) == 56, "ArtRayCastMulti is part of the ABI");
+    static void cast_rays_multi(ArtContext *ctx, const ArtRayCastMulti &d) { check(art_cast_rays_multi(ctx, &d)); }
+    void cast_rays_multi(const ArtRayCastMulti &d) { cast_rays_multi(ctx_, d); }
     static void cast_rays(ArtContext *ctx, const ArtRayCast &d) { check(art_cast_rays(ctx, &d)); }   // panics like every other call of the mirror
     void cast_rays(const ArtRayCast &d) { cast_rays(ctx_, d); }
     void cast_sync() { check(art_cast_sync(ctx_)); }

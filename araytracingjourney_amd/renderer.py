@@ -711,6 +711,40 @@ class Renderer:
         check(self._L.art_cast_rays(self._ctx, C.byref(d)))
         return res
 
+    def cast_rays_multi(self, rays, max_hits, cull_mask=0xFF, out=None, stream=None):
+        """The first max_hits hits along each ray, in order (art_cast_rays_multi).  rays: as cast_rays.  Returns (tuv, ids, count): (n, K, 4) float32 t,u,v,0, (n, K, 2) int32
+        (primitive, triangle in the primitive) and (n,) uint8 -- record j of ray i is its j-th hit in ascending (t, global triangle id) while j < count[i], and the miss
+        record (tmax, 0, 0, 0), (-1, -1) from there on.  out: (tuv, ids, count) to write instead of new ones, of at least n rays and exactly K records a ray, not overlapping
+        the rays or each other.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        import torch
+        m = _mask_value("cull_mask", cull_mask)
+        k = int(max_hits)
+        if k != max_hits or not 1 <= k <= _lib.ART_CAST_MAX_HITS:
+            raise ValueError(f"max_hits must be an integer in 1..{_lib.ART_CAST_MAX_HITS}")
+        if self._device < 0:
+            self._device = torch.cuda.current_device()
+        dev = self._device
+        if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device.index != dev:
+            raise ValueError(f"rays must be a torch tensor on cuda:{dev}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.data_ptr() % 16:
+            raise ValueError("rays must be float32 of shape (n, 8), contiguous and 16-byte aligned")
+        n = rays.shape[0]
+        if out is None:
+            out = (torch.empty((n, k, 4), dtype=torch.float32, device=rays.device), torch.empty((n, k, 2), dtype=torch.int32, device=rays.device),
+                   torch.empty((n,), dtype=torch.uint8, device=rays.device))
+        tuv, ids, count = out
+        for t, name, dtype, width, align in ((tuv, "tuv", torch.float32, (k, 4), 16), (ids, "ids", torch.int32, (k, 2), 8), (count, "count", torch.uint8, (), 1)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and
+                    t.shape[0] >= n and tuple(t.shape[1:]) == width):
+                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n,{''.join(' ' + str(w) + ',' for w in width)}), {align}-byte aligned")
+        d = _lib.ArtRayCastMulti(rays_dev=rays.data_ptr() or None, tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, count_dev=count.data_ptr() or None,
+                                 n=n, max_hits=k, cull_mask=m, flags=0)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+        check(self._L.art_cast_rays_multi(self._ctx, C.byref(d)))
+        return tuv, ids, count
+
     def cast_sync(self):
         """every cast enqueued so far has finished, on whichever stream (art_cast_sync)"""
         check(self._L.art_cast_sync(self._ctx))

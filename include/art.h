@@ -295,6 +295,32 @@ typedef struct ArtRayCast {
     uint32_t flags;        /* must be 0 */
 } ArtRayCast;
 int32_t art_cast_rays(ArtContext *ctx, const ArtRayCast *cast);
+/* The first K hits along each ray, in order: what the ray goes through -- multi-return lidar, thickness and penetration, transparency the caller composites
+ * itself.  In Vulkan terms an any-hit shader that records the intersection and calls ignoreIntersectionEXT, in one pass: no peeling, and hits that tie on t are all there.
+ *  - Results: for a ray let A be the triangles accept() takes that the visibility masks do not discard (primitive's mask & cull_mask != 0; tested first) and
+ *    the alpha cutoff does not cut.  Records 0 .. c-1 of the ray, c = min(|A|, max_hits), are the first c elements of A in ascending (t_eff, global triangle id), each the
+ *    closest cast's record: (t_eff, u, v, 0) and (primitive id, triangle in the primitive).  Records c .. max_hits-1 are the miss record (tmax, 0, 0, 0), (-1, -1), and
+ *    count_dev[i] = c.  A ray with a non-finite origin or direction or a NaN tmax has c = 0 and max_hits miss records that carry tmax as given.  With max_hits = 1 the
+ *    records are those of ART_CAST_CLOSEST, bit for bit.  A ray's records depend on that ray alone.
+ *  - Everything else is art_cast_rays's: asynchronous on hip_stream (NULL: the context's cast stream), the scene as of the call with the refit in front of the cast and the
+ *    version held until the cast finishes, the same ring of ART_CAST_POOL cursor blocks and the same host waits; art_cast_counts counts it, art_cast_sync, art_sync,
+ *    art_scene_build and the others wait for it.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null or misaligned rays_dev / tuv_dev / ids_dev (with n = 0 a null buffer is
+ *    one of no rays); max_hits 0 or above ART_CAST_MAX_HITS; cull_mask above 0xFF; flags other than 0; n above ART_CAST_MAX_RAYS.  ART_E_STATE: the scene is not built, or
+ *    art_scene_needs_build.  The output buffers must not overlap the rays or each other: the caller's contract, not checked. */
+#define ART_CAST_MAX_HITS 8u
+typedef struct ArtRayCastMulti {
+    const void *rays_dev;  /* n x 8 floats, as ArtRayCast; 16-byte aligned */
+    void *tuv_dev;         /* n x max_hits x 4 floats, ray-major: ray i's record j at (i*max_hits + j); 16-byte aligned */
+    void *ids_dev;         /* n x max_hits x 2 int32, same order; 8-byte aligned */
+    void *count_dev;       /* n x uint8: records that are hits, 0..max_hits; may be NULL */
+    void *hip_stream;      /* as ArtRayCast */
+    uint32_t n;            /* 0 is legal: nothing is enqueued */
+    uint32_t max_hits;     /* K: 1..ART_CAST_MAX_HITS */
+    uint32_t cull_mask;    /* 0..0xFF */
+    uint32_t flags;        /* must be 0 */
+} ArtRayCastMulti;        /* 56 bytes */
+int32_t art_cast_rays_multi(ArtContext *ctx, const ArtRayCastMulti *cast);
 /* every cast enqueued so far has finished (those on callers' streams included) */
 int32_t art_cast_sync(ArtContext *ctx);
 /* since art_create: casts enqueued (n > 0), their rays, and the times art_cast_rays (or a refit in front of a frame) waited on the host for a cast.  Any pointer may be NULL. */

@@ -1,0 +1,483 @@
+"""art_cast_rays_multi (include/art.h): the first K hits along each ray, in ascending (t_eff, global triangle id).
+
+The reference is the CPU oracle, one triangle at a time: an orc.Scene that holds a single triangle says, per ray, whether that triangle accepts the ray, with the bits of
+its t_eff, u, v -- accept() and t_eff are structure-independent.  The table of all those answers (sparse: hits only), sorted by (t_eff, gid) within a ray
+and cut at K, is what the device must write, ids and bits.  The CPU tests below first check that table against the oracle's own whole-scene walks."""
+import ctypes as C
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+from helpers import random_rays
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PATTERN = -0x5A5A5A5B   # tests/test_cast.py's: what oversized output buffers are filled with
+N = 4096
+
+
+@pytest.fixture(scope="module")
+def R():
+    from araytracingjourney_amd import renderer
+    return renderer
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    return t
+
+
+# ---- the reference ------------------------------------------------------------------------------------------------------------------------------------------
+def hit_table(orc, primitives, rays):
+    """every (ray, triangle) pair the oracle accepts, triangle by triangle in gid order (the running index over the primitives in add order): ray, gid, primitive,
+    triangle in the primitive, and t_eff, u, v as the single-triangle scene's closest record has them"""
+    ray, gid, prim, tri, tuv = [], [], [], [], []
+    g = 0
+    for p, P in enumerate(primitives):
+        idx = np.ascontiguousarray(P.indices).reshape(-1, 3)
+        for k in range(idx.shape[0]):
+            S = orc.Scene()
+            S.add_primitive(P.verts, np.ascontiguousarray(idx[k]), P.tex, P.model)
+            S.build(30)
+            t, ids = S.trace_closest(rays)[:2]
+            at = np.flatnonzero(ids[:, 0] >= 0)
+            if at.size:
+                ray.append(at); gid.append(np.full(at.size, g, np.int64)); prim.append(np.full(at.size, p, np.int32)); tri.append(np.full(at.size, k, np.int32))
+                tuv.append(t[at, :3].astype(np.float32))
+            g += 1
+    cat = lambda xs, dt, shape: np.concatenate(xs) if xs else np.zeros(shape, dt)   # noqa: E731
+    tab = dict(ray=cat(ray, np.int64, 0), gid=cat(gid, np.int64, 0), prim=cat(prim, np.int32, 0), tri=cat(tri, np.int32, 0), tuv=cat(tuv, np.float32, (0, 3)), n_tris=g)
+    for a in tab.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return tab
+
+
+def expected(tab, rays, K, keep=None):
+    """(tuv[n, K, 4], ids[n, K, 2], count[n]): the table's rows (those of `keep`) in ascending (t_eff, gid) within each ray, cut at K; the rest miss records with the
+    ray's tmax as given"""
+    n = rays.shape[0]
+    rows = np.arange(tab["ray"].size) if keep is None else np.flatnonzero(keep)
+    ray, gid, t = tab["ray"][rows], tab["gid"][rows], tab["tuv"][rows, 0]
+    order = np.lexsort((gid, t, ray))   # by ray, then t_eff, then gid
+    rows, ray = rows[order], ray[order]
+    first = np.searchsorted(ray, np.arange(n))          # where each ray's rows start
+    rank = np.arange(ray.size) - first[ray]
+    total = np.bincount(ray, minlength=n)
+    tuv = np.zeros((n, K, 4), np.float32)
+    tuv[:, :, 0] = rays[:, 7:8]
+    ids = np.full((n, K, 2), -1, np.int32)
+    take = rank < K
+    tuv[ray[take], rank[take], :3] = tab["tuv"][rows[take]]
+    ids[ray[take], rank[take], 0] = tab["prim"][rows[take]]
+    ids[ray[take], rank[take], 1] = tab["tri"][rows[take]]
+    return tuv, ids, np.minimum(total, K).astype(np.uint8)
+
+
+def hits_per_ray(tab, n):
+    return np.bincount(tab["ray"], minlength=n)
+
+
+def tied_rays(tab, n, K):
+    """rays with two records of equal t_eff among their first K"""
+    tuv, _, count = expected(tab, np.zeros((n, 8), np.float32), K)
+    t = tuv[:, :, 0]
+    both = np.arange(1, K)[None, :] < count[:, None]
+    return int(((t[:, 1:] == t[:, :-1]) & both).any(axis=1).sum())
+
+
+_REF = {}
+
+
+def _ref(orc, get_scene, name, detail):
+    """scene, random_rays(4097, 7) (ray k does not depend on how many there are: the first 4096 are random_rays(4096, 7)) and their table: computed once, shared, never
+    written"""
+    key = (name, detail)
+    if key not in _REF:
+        sc = get_scene(name, detail)
+        rays = random_rays(N + 1, 7)
+        rays.setflags(write=False)
+        _REF[key] = dict(scene=sc, rays=rays, tab=hit_table(orc, sc.primitives, rays))
+    return _REF[key]
+
+
+def _same(got, want, what=""):
+    (tuv, ids, count), (rtuv, rids, rcount) = got, want
+    tuv, ids = np.ascontiguousarray(tuv.cpu().numpy()), ids.cpu().numpy()
+    assert tuv.shape == rtuv.shape and ids.shape == rids.shape, what
+    assert np.array_equal(ids, rids), f"{what}: the ids of {int((ids != rids).any(axis=(1, 2)).sum())} rays differ"
+    assert np.array_equal(tuv.view(np.uint32)[..., :3], np.ascontiguousarray(rtuv).view(np.uint32)[..., :3]), f"{what}: t, u, v differ"
+    assert not tuv.view(np.uint32)[..., 3].any(), f"{what}: the fourth word is not 0"
+    if count is not None:
+        assert np.array_equal(count.cpu().numpy(), rcount), f"{what}: counts differ"
+
+
+def _up(torch, a):
+    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared references are read-only)
+
+
+# ---- without a GPU ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,detail", [("cornell", 1.0), ("sponza_like", 0.05)])
+def test_the_table_reproduces_the_whole_scene_walks(orc, get_scene, name, detail):
+    """the reference of the GPU tests, checked before they use it: the table's first record per ray is the oracle's whole-scene closest hit -- ids and the bits of t, u, v
+    -- and a ray has a row iff the whole-scene any-hit walk says so.  The figures the GPU tests lean on (ties, overflow) are asserted here as well"""
+    ref = _ref(orc, get_scene, name, detail)
+    rays, tab = ref["rays"][:N], ref["tab"]
+    assert tab["n_tris"] == sum(np.asarray(p.indices).size // 3 for p in ref["scene"].primitives)
+    S = orc.Scene(ref["scene"].primitives, morton_bits=30)
+    keep = tab["ray"] < N
+    tuv, ids, count = expected(tab, rays, 1, keep)
+    rtuv, rids = S.trace_closest(rays)[:2]
+    assert np.array_equal(ids[:, 0], rids)
+    assert np.array_equal(tuv[:, 0, :3].view(np.uint32), np.ascontiguousarray(rtuv[:, :3], np.float32).view(np.uint32))
+    assert np.array_equal(count, S.trace_any(rays)[0])
+    per_ray = hits_per_ray(tab, N + 1)[:N]
+    if name == "cornell":
+        assert tied_rays(tab, N + 1, 8) >= 50 and int((per_ray > 3).sum()) >= 300
+    else:
+        assert int((per_ray > 8).sum()) >= 50
+
+
+def _gcc_layout(name):
+    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "tools", "gen_rust_bindings.py"))
+    g = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(g)
+    structs = [s for s in g.parse(open(g.HDR).read())[2] if s[0] == name]
+    assert len(structs) == 1
+    return g.c_layout(structs), [f for f, _ in structs[0][2]]
+
+
+def test_the_ctypes_descriptor_is_the_headers():
+    """ArtRayCastMulti as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 56 bytes"""
+    from araytracingjourney_amd import _lib
+    lay, fields = _gcc_layout("ArtRayCastMulti")
+    assert fields == [n for n, _ in _lib.ArtRayCastMulti._fields_] == ["rays_dev", "tuv_dev", "ids_dev", "count_dev", "hip_stream", "n", "max_hits", "cull_mask", "flags"]
+    assert C.sizeof(_lib.ArtRayCastMulti) == lay["ArtRayCastMulti"] == 56
+    for f in fields:
+        assert getattr(_lib.ArtRayCastMulti, f).offset == lay["ArtRayCastMulti." + f], f
+    assert f"#define ART_CAST_MAX_HITS {_lib.ART_CAST_MAX_HITS}u" in open(os.path.join(ROOT, "include", "art.h")).read() and _lib.ART_CAST_MAX_HITS == 8
+
+
+def test_a_multi_cast_without_a_context_is_invalid_on_any_machine():
+    """art_cast_rays_multi(NULL, NULL) needs no device to say ART_E_INVALID"""
+    from araytracingjourney_amd import _lib
+    L = _lib.load()
+    assert L.art_cast_rays_multi(None, None) == _lib.ART_E_INVALID and L.art_last_error().startswith(b"art_cast_rays_multi: ")
+    d = _lib.ArtRayCastMulti(n=0, max_hits=1)
+    assert L.art_cast_rays_multi(None, C.byref(d)) == _lib.ART_E_INVALID
+
+
+# ---- on the device ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_cornell_first_k_hits_are_the_tables(R, torch, orc, get_scene):
+    """K = 1, 2, 3, 8 on Cornell: ids, counts and the bits of t, u, v are the table's, the fourth word is 0; K = 1 is the closest cast and the whole-scene oracle; a
+    permutation of the rays gives the permuted records.  At least 50 rays hold a tie on t_eff among their first records (order by gid) and at least 300 have more than
+    three hits (the list overflows at K = 3) -- counted in the table, not in the output"""
+    ref = _ref(orc, get_scene, "cornell", 1.0)
+    rays, tab = ref["rays"][:N], ref["tab"]
+    keep = tab["ray"] < N
+    assert tied_rays(tab, N + 1, 8) >= 50 and tied_rays(tab, N + 1, 3) >= 50 and int((hits_per_ray(tab, N + 1)[:N] > 3).sum()) >= 300
+    r = R.renderer_for_scene(ref["scene"], (64, 64))
+    perm = np.random.default_rng(3).permutation(N)
+    d_rays, d_perm = _up(torch, rays), _up(torch, rays[perm])
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        got = {K: r.cast_rays_multi(d_rays, K) for K in (1, 2, 3, 8)}
+        got_p = {K: r.cast_rays_multi(d_perm, K) for K in (3, 8)}
+        closest = r.cast_rays(d_rays)
+    s.synchronize()
+    for K, g in got.items():
+        assert g[0].shape == (N, K, 4) and g[1].shape == (N, K, 2) and g[2].shape == (N,) and g[2].dtype == torch.uint8
+        _same(g, expected(tab, rays, K, keep), f"K = {K}")
+    for K, g in got_p.items():
+        want = expected(tab, rays, K, keep)
+        _same(g, tuple(w[perm] for w in want), f"K = {K}, permuted")
+    one = got[1]
+    assert np.array_equal(one[0].cpu().numpy().view(np.uint32)[:, 0], closest[0].cpu().numpy().view(np.uint32)) and np.array_equal(one[1].cpu().numpy()[:, 0], closest[1].cpu().numpy())
+    S = orc.Scene(ref["scene"].primitives, morton_bits=30)
+    rtuv, rids = S.trace_closest(rays)[:2]
+    assert np.array_equal(one[1].cpu().numpy()[:, 0], rids) and np.array_equal(one[0].cpu().numpy()[:, 0, :3].view(np.uint32), np.ascontiguousarray(rtuv[:, :3], np.float32).view(np.uint32))
+    assert r.cast_counts() == dict(casts=7, rays=7 * N, host_waits=0)
+    r.close()
+
+
+@pytest.mark.gpu
+def test_sponza_full_lists_move_the_bound(R, torch, orc, get_scene):
+    """sponza_like at detail 0.05, K = 4 and 8: at least 50 rays have more than 8 hits, so the walk's limit moves on a full list"""
+    ref = _ref(orc, get_scene, "sponza_like", 0.05)
+    rays, tab = ref["rays"][:N], ref["tab"]
+    keep = tab["ray"] < N
+    assert int((hits_per_ray(tab, N + 1)[:N] > 8).sum()) >= 50
+    r = R.renderer_for_scene(ref["scene"], (64, 64))
+    d_rays = _up(torch, rays)
+    got = {K: r.cast_rays_multi(d_rays, K) for K in (4, 8)}
+    torch.cuda.synchronize()
+    for K, g in got.items():
+        _same(g, expected(tab, rays, K, keep), f"K = {K}")
+    r.close()
+
+
+def _dead_rays(base):
+    """tests/test_cast.py's: NaN direction, infinite origin, NaN tmax in turn"""
+    d = base.copy()
+    d[0::3, 4] = np.nan
+    d[1::3, 0] = np.inf
+    d[2::3, 7] = np.nan
+    return d
+
+
+def _outward_rays(base):
+    """tests/test_cast.py's: from the sphere around the scene, away from it"""
+    out = base[(np.arange(base.shape[0]) % 3) != 0].copy()
+    out[:, 4:7] = out[:, 0:3] / np.linalg.norm(out[:, 0:3], axis=1, keepdims=True)
+    return out
+
+
+@pytest.mark.gpu
+def test_sizes_and_records(R, torch, orc, get_scene):
+    """ArtTuning.trace_chunk = 64: no rays, one, a wave less one, a wave, a wave and one, chunks and a ray more or less, several workgroups, at K = 3 (the KMAX 4 instance,
+    not full) and K = 8; nothing behind n * K records or n counts is written; dead rays have no hits and K miss records with tmax as given (a NaN's bits included);
+    outward rays miss; one cast has no count buffer"""
+    ref = _ref(orc, get_scene, "cornell", 1.0)
+    tab = ref["tab"]
+    r = R.renderer_for_scene(ref["scene"], (64, 64), tuning={"trace_chunk": 64})
+    s = torch.cuda.Stream()
+    batches = []
+    for n in (0, 1, 63, 64, 65, 127, 511, 513, 4097):
+        batches.append((ref["rays"][:n], tab, tab["ray"] < n, f"n = {n}"))
+    dead, outward = _dead_rays(ref["rays"][:130]), _outward_rays(ref["rays"][:195])
+    for rays, what in ((dead, "all dead"), (outward, "all miss")):
+        t = hit_table(orc, ref["scene"].primitives, rays)
+        assert t["ray"].size == 0, what
+        batches.append((rays, t, None, what))
+    pad, casts = 5, 0
+    for K in (3, 8):
+        for rays, t, keep, what in batches:
+            n = rays.shape[0]
+            d_rays = _up(torch, rays.reshape(n, 8))
+            o_tuv = torch.full((n + pad, K, 4), PATTERN, dtype=torch.int32, device="cuda").view(torch.float32)
+            o_ids = torch.full((n + pad, K, 2), PATTERN, dtype=torch.int32, device="cuda")
+            o_cnt = torch.full((n + pad,), 0xA5, dtype=torch.uint8, device="cuda")
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                got = r.cast_rays_multi(d_rays, K, out=(o_tuv, o_ids, o_cnt))
+            s.synchronize()
+            casts += n > 0
+            assert got[0] is o_tuv and got[1] is o_ids and got[2] is o_cnt
+            want = expected(t, rays.reshape(n, 8), K, keep)
+            _same((o_tuv[:n], o_ids[:n], o_cnt[:n]), want, f"K = {K}, {what}")
+            assert (o_tuv[n:].view(torch.int32) == PATTERN).all() and (o_ids[n:] == PATTERN).all() and (o_cnt[n:] == 0xA5).all(), f"K = {K}, {what}: written behind the n-th ray"
+            if what in ("all dead", "all miss"):
+                assert not want[2].any() and (want[1] == -1).all()
+                assert np.array_equal(o_tuv[:n, :, 0].cpu().numpy().view(np.uint32), np.repeat(rays[:, 7:8], K, axis=1).view(np.uint32)), f"{what}: tmax as given"
+    assert r.cast_counts()["casts"] == casts
+    # no count buffer: the descriptor by hand
+    from araytracingjourney_amd import _lib
+    n, K = 513, 5
+    rays = ref["rays"][:n]
+    d_rays = _up(torch, rays)
+    tuv = torch.empty((n, K, 4), dtype=torch.float32, device="cuda")
+    ids = torch.empty((n, K, 2), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    d = _lib.ArtRayCastMulti(rays_dev=d_rays.data_ptr(), tuv_dev=tuv.data_ptr(), ids_dev=ids.data_ptr(), count_dev=None, hip_stream=None, n=n, max_hits=K, cull_mask=0xFF, flags=0)
+    assert r._L.art_cast_rays_multi(r._ctx, C.byref(d)) == 0
+    r.cast_sync()   # hip_stream NULL: the context's cast stream, fenced by art_cast_sync
+    _same((tuv, ids, None), expected(tab, rays, K, tab["ray"] < n), "count_dev NULL")
+    r.close()
+
+
+@pytest.mark.gpu
+def test_ranges(R, torch, orc, get_scene):
+    """the same rays with tmax = 1.5, and with tmin raised to the first hit's t_eff: the table traced with those ranges is the reference"""
+    ref = _ref(orc, get_scene, "cornell", 1.0)
+    base, tab = ref["rays"][:N], ref["tab"]
+    first = expected(tab, base, 1, tab["ray"] < N)
+    short = base.copy()
+    short[:, 7] = 1.5
+    late = base.copy()
+    hit = first[2] > 0
+    late[hit, 3] = first[0][hit, 0, 0]
+    r = R.renderer_for_scene(ref["scene"], (64, 64))
+    for rays, what in ((short, "tmax 1.5"), (late, "tmin at the first hit")):
+        t = hit_table(orc, ref["scene"].primitives, rays)
+        full = hits_per_ray(tab, N + 1)[:N]
+        assert int((hits_per_ray(t, N) < full).sum()) >= 1000, f"{what}: the range cuts hits of many rays"   # from the tables
+        d_rays = _up(torch, rays)
+        got = {K: r.cast_rays_multi(d_rays, K) for K in (2, 6)}
+        torch.cuda.synchronize()
+        for K, g in got.items():
+            _same(g, expected(t, rays, K), f"{what}, K = {K}")
+    r.close()
+
+
+def _tex(alpha_value, tw=8, th=8):
+    """tests/test_alpha.py's three layers, alpha the same in every texel: no sampler is needed to know the alpha anywhere"""
+    t = np.zeros((3, th, tw, 4), np.uint8)
+    t[0, ..., 0], t[0, ..., 1], t[0, ..., 2], t[0, ..., 3] = 180, 150, 120, alpha_value
+    t[1, ..., 0], t[1, ..., 1], t[1, ..., 2], t[1, ..., 3] = 255, 160, 0, 255
+    t[2, ..., 0], t[2, ..., 1], t[2, ..., 2], t[2, ..., 3] = 128, 128, 255, 255
+    return t
+
+
+@pytest.mark.gpu
+def test_masks_and_alpha(R, torch, orc, get_scene, scenes):
+    """Cornell and two horizontal cards, one with alpha 0 in every texel and one with alpha 255: with a cutoff of 0.5 on both the first vanishes and the second stays.
+    Primitive masks and cull masks filter the table by primitive; cull_mask = 0 sees nothing"""
+    base = get_scene("cornell")
+    prims = list(base.primitives)
+    for y, a in ((0.3, 0), (-0.2, 255)):
+        mb = scenes.MeshBuilder()
+        scenes.quad(mb, (-0.35, y, -0.35), (0.7, 0.0, 0.0), (0.0, 0.0, 0.7), 2, 2, (1.0, 1.0))
+        prims.append(mb.finish(_tex(a)))
+    sc = scenes.Scene(base.name + "+cards", prims, base.camera, base.lights)
+    clear, solid = len(prims) - 2, len(prims) - 1
+    rays = random_rays(2048, 5, radius=0.9)
+    tab = hit_table(orc, sc.primitives, rays)
+    assert int((tab["prim"] == clear).sum()) > 50 and int((tab["prim"] == solid).sum()) > 50
+    masks = {0: 0x01, 1: 0x02, solid: 0x03}
+    r = R.renderer_for_scene(sc, (64, 64))
+    m = r.models_mut()[0]
+    d_rays = _up(torch, rays)
+    # the opaque, unmasked scene first (the plain instances), then cutoffs and masks set after the build (the cast takes them up)
+    got = r.cast_rays_multi(d_rays, 8)
+    torch.cuda.synchronize()
+    _same(got, expected(tab, rays, 8), "opaque")
+    m.set_alpha_cutoff(clear, 0.5); m.set_alpha_cutoff(solid, 0.5)
+    for i, v in masks.items():
+        m.set_mask(i, v)
+    vis = np.array([masks.get(p, 0xFF) for p in range(len(prims))])
+    for cull in (0xFF, 0x01, 0x02, 0):
+        keep = ((vis[tab["prim"]] & cull) != 0) & (tab["prim"] != clear)
+        got = {K: r.cast_rays_multi(d_rays, K, cull_mask=cull) for K in (2, 8)}
+        torch.cuda.synchronize()
+        for K, g in got.items():
+            _same(g, expected(tab, rays, K, keep), f"cull {cull:#x}, K = {K}")
+        if cull == 0:
+            assert not got[8][2].any() and (got[8][1] == -1).all()
+    r.close()
+
+
+@pytest.mark.gpu
+def test_a_moved_model(R, torch, orc, get_scene):
+    """Cornell's last primitive moved with art_scene_set_model_matrix and no build in between: the table built with the new matrix"""
+    sc = get_scene("cornell")
+    rays = _ref(orc, get_scene, "cornell", 1.0)["rays"][:N]
+    r = R.Renderer((64, 64), tuning={"refit_rebuild_ratio": -1.0})
+    r.add_model(list(sc.primitives[:-1]))
+    r.add_model([sc.primitives[-1]])
+    r.prepare_first_frame()
+    moving = sc.primitives[-1]
+    m = np.ascontiguousarray(np.asarray(moving.model, np.float32).reshape(3, 4).copy())
+    m[:, 3] += np.array([0.06, 0.03, -0.06], np.float32)
+    d_rays = _up(torch, rays)
+    before = r.cast_rays_multi(d_rays, 4)
+    r.models_mut()[1].set_model_matrix(m)
+    after = r.cast_rays_multi(d_rays, 4)
+    torch.cuda.synchronize()
+    _same(before, expected(_ref(orc, get_scene, "cornell", 1.0)["tab"], rays, 4, _ref(orc, get_scene, "cornell", 1.0)["tab"]["ray"] < N), "before the move")
+    tab = hit_table(orc, list(sc.primitives[:-1]) + [type(moving)(moving.verts, moving.indices, moving.tex, m)], rays)
+    _same(after, expected(tab, rays, 4), "after the move")
+    assert not np.array_equal(before[0].cpu().numpy().view(np.uint32), after[0].cpu().numpy().view(np.uint32))
+    st = r.stats()
+    assert st["refits"] == 1 and st["rebuilds"] == 0
+    r.close()
+
+
+@pytest.mark.gpu
+def test_errors_change_nothing_and_enqueue_nothing(R, torch, get_scene):
+    """every ART_E_INVALID case of include/art.h and ART_E_STATE before the build and while the scene needs one: the counts stay what they were and every message names
+    art_cast_rays_multi"""
+    from araytracingjourney_amd import _lib
+    sc = get_scene("cornell")
+    r = R.Renderer((64, 64))
+    r.add_model(sc.primitives)
+    L, ctx = r._L, r._ctx
+    n, K = 64, 4
+    rays = _up(torch, random_rays(n + 1, 7))
+    tuv = torch.zeros((n + 1, K, 4), dtype=torch.float32, device="cuda")
+    ids = torch.zeros((n + 1, K, 2), dtype=torch.int32, device="cuda")
+    cnt = torch.zeros((n + 1,), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def desc(**kw):
+        d = dict(rays_dev=rays.data_ptr(), tuv_dev=tuv.data_ptr(), ids_dev=ids.data_ptr(), count_dev=cnt.data_ptr(), hip_stream=None, n=n, max_hits=K, cull_mask=0xFF, flags=0)
+        d.update(kw)
+        return _lib.ArtRayCastMulti(**d)
+
+    def code(d):
+        return L.art_cast_rays_multi(ctx, C.byref(d) if d is not None else None)
+
+    assert code(desc()) == _lib.ART_E_STATE and L.art_last_error().startswith(b"art_cast_rays_multi: ") and b"not built" in L.art_last_error()
+    r.prepare_first_frame()
+    zero = dict(casts=0, rays=0, host_waits=0)
+    assert r.cast_counts() == zero
+    assert L.art_cast_rays_multi(None, C.byref(desc())) == _lib.ART_E_INVALID and L.art_last_error().startswith(b"art_cast_rays_multi: ")
+    assert code(None) == _lib.ART_E_INVALID and L.art_last_error().startswith(b"art_cast_rays_multi: ")
+    bad = [desc(rays_dev=None), desc(tuv_dev=None), desc(ids_dev=None), desc(rays_dev=rays.data_ptr() + 4), desc(rays_dev=rays.data_ptr() + 8), desc(tuv_dev=tuv.data_ptr() + 8),
+           desc(ids_dev=ids.data_ptr() + 4), desc(max_hits=0), desc(max_hits=_lib.ART_CAST_MAX_HITS + 1), desc(max_hits=0xFFFFFFFF), desc(cull_mask=0x100),
+           desc(cull_mask=0xFFFFFFFF), desc(flags=1), desc(flags=0x80000000), desc(n=_lib.ART_CAST_MAX_RAYS + 1), desc(n=0xFFFFFFFF)]
+    for d in bad:
+        assert code(d) == _lib.ART_E_INVALID and L.art_last_error().startswith(b"art_cast_rays_multi: "), (d.n, d.max_hits, d.cull_mask, d.flags)
+    assert r.cast_counts() == zero
+    r.cast_sync()
+    assert not tuv.any() and not ids.any() and not cnt.any()
+    assert code(desc(n=0)) == 0 and code(desc(n=0, rays_dev=None, tuv_dev=None, ids_dev=None, count_dev=None)) == 0 and r.cast_counts() == zero   # n = 0 is legal and enqueues nothing
+    assert code(desc()) == 0
+    r.cast_sync()
+    assert r.cast_counts() == dict(casts=1, rays=n, host_waits=0) and cnt[:n].any() and not cnt[n:].any() and not ids[n:].any()
+    r.add_model([sc.primitives[0]])   # a primitive added since the build: art_scene_needs_build
+    assert r.needs_build() and code(desc()) == _lib.ART_E_STATE and L.art_last_error().startswith(b"art_cast_rays_multi: ") and r.cast_counts()["casts"] == 1
+    # the wrapper's own checks
+    for args, kw in (((rays.cpu(), 4), {}), ((rays.double(), 4), {}), ((rays[:, :7], 4), {}), ((rays, 0), {}), ((rays, 9), {}), ((rays, 2.5), {}), ((rays, 4), dict(cull_mask=0x100)),
+                     ((rays, 4), dict(out=(tuv[:8], ids, cnt))), ((rays, 3), dict(out=(tuv, ids, cnt))), ((rays, 4), dict(out=(tuv, ids, cnt.to(torch.int32))))):
+        with pytest.raises(ValueError):
+            r.cast_rays_multi(*args, **kw)
+    with pytest.raises(ValueError):
+        r.cast_rays(rays, kind="nearest")
+    assert r.cast_counts()["casts"] == 1
+    r.close()
+
+
+@pytest.mark.gpu
+def test_traffic(R, torch, orc, get_scene):
+    """40 casts -- multi, closest and any in turn -- on two torch streams with frames traced in between and no synchronisation until all are enqueued: more than the
+    pool of cursor blocks holds.  Every record is right and the counts add up"""
+    from araytracingjourney_amd import _lib
+    ref = _ref(orc, get_scene, "cornell", 1.0)
+    rays, tab = ref["rays"][:N], ref["tab"]
+    keep = tab["ray"] < N
+    assert 40 > _lib.ART_CAST_POOL
+    want = {K: expected(tab, rays, K, keep) for K in (1, 3, 5, 8)}
+    r = R.renderer_for_scene(ref["scene"], (96, 96), frames_in_flight=2)
+    d_rays = _up(torch, rays)
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    for s in streams:
+        s.wait_stream(torch.cuda.current_stream())
+    outs = []
+    for i in range(40):
+        with torch.cuda.stream(streams[(i // 3) % 2]):
+            if i % 3 == 0:
+                K = (1, 3, 5, 8)[(i // 3) % 4]
+                outs.append((K, r.cast_rays_multi(d_rays, K)))
+            elif i % 3 == 1:
+                outs.append(("closest", r.cast_rays(d_rays)))
+            else:
+                outs.append(("any", r.cast_rays(d_rays, kind="any")))
+        if i % 4 == 3:
+            r.upload_state(); r.trace()
+    counts = r.cast_counts()
+    r.sync()
+    for s in streams:
+        s.synchronize()
+    for i, (kind, got) in enumerate(outs):
+        if kind == "closest":
+            assert np.array_equal(got[1].cpu().numpy(), want[1][1][:, 0]) and np.array_equal(got[0].cpu().numpy().view(np.uint32)[:, :3], want[1][0][:, 0, :3].view(np.uint32)), f"cast {i}"
+        elif kind == "any":
+            assert np.array_equal(got.cpu().numpy(), want[1][2]), f"cast {i}"
+        else:
+            _same(got, want[kind], f"cast {i}, K = {kind}")
+    assert counts["casts"] == 40 and counts["rays"] == 40 * N
+    r.close()
