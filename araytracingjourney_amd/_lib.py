@@ -84,6 +84,12 @@ class ArtRayCastMulti(C.Structure):
                 ("n", C.c_uint32), ("max_hits", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class ArtHitResolve(C.Structure):
+    """one art_resolve_hits: the hit records of a cast in, the surface attributes wanted out (a null output is not written)"""
+    _fields_ = [("tuv_dev", C.c_void_p), ("ids_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("ng_dev", C.c_void_p), ("ns_dev", C.c_void_p), ("uv_dev", C.c_void_p),
+                ("albedo_dev", C.c_void_p), ("orm_dev", C.c_void_p), ("hip_stream", C.c_void_p), ("n", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class ArtLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "frames_in_flight", "frames_per_launch", "shard_rank", "shard_count", "tiles_owned", "tiles_padded",
                                           "tile_bytes", "reserved")]
@@ -134,6 +140,7 @@ SYMBOLS = {
     "art_sync": (_I32, [_P]),
     "art_cast_rays": (_I32, [_P, _P]),
     "art_cast_rays_multi": (_I32, [_P, _P]),
+    "art_resolve_hits": (_I32, [_P, _P]),
     "art_cast_sync": (_I32, [_P]),
     "art_cast_counts": (_I32, [_P, _P, _P, _P]),
     "art_present": (_I32, [_P]),

@@ -1978,9 +1978,10 @@ static int32_t cast_setup(ArtContext *c) {
     K.cursors = cur; K.stream = s;
     return ART_OK;
 }
-// Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
-// max_hits > 0: art_cast_rays_multi's cast (any false; hit = its count bytes, or null) -- the same blocks, version hold, events and refit, another kernel.
-static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0) {
+// The host side every enqueue on the ring shares -- a cast's and a resolve's (art_resolve_hits traces nothing, but it reads a version of the scene and has to be waited
+// for like a cast).  cast_claim: the scene as of the call, the stream, the version to read (an event wait on that stream while its refit may still run) and the next ring
+// block, free.  cast_commit: the block's event behind what the caller launched, and the version it holds.
+static int32_t cast_claim(ArtContext *c, hipStream_t user, hipStream_t *stream, uint32_t *version, uint32_t *block) {
     int32_t r = use_device(c); if (r) return r;
     r = cast_setup(c); if (r) return r;
     CastState &K = c->cast;
@@ -2001,6 +2002,23 @@ static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool an
         if (hipEventQuery(B.ev) != hipSuccess) { (void)hipGetLastError(); HIPC(hipEventSynchronize(B.ev)); K.host_waits++; }
         B.set = false;
     }
+    *stream = s; *version = ver; *block = bi;
+    return ART_OK;
+}
+static int32_t cast_commit(ArtContext *c, uint32_t bi, uint32_t ver, hipStream_t s) {
+    CastState &K = c->cast;
+    CastBlock &B = K.block[bi];
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(B.ev, s));
+    B.set = true; B.version = ver; K.next++;
+    return ART_OK;
+}
+// Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
+// max_hits > 0: art_cast_rays_multi's cast (any false; hit = its count bytes, or null) -- the same blocks, version hold, events and refit, another kernel.
+static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0) {
+    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
+    int32_t r = cast_claim(c, user, &s, &ver, &bi); if (r) return r;
+    CastState &K = c->cast;
     uint32_t *cursors = K.cursors + (size_t)bi * kCastCursorWords;
     HIPC(hipMemsetAsync(cursors, 0, kCastCursorWords * 4, s));
     const AsPtrs as = as_ptrs(c, ver);
@@ -2012,9 +2030,8 @@ static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool an
     a.alpha = c->alpha_live || cull == 0u;   // the filtered instances run while the scene needs them or the mask is 0 (such rays see nothing, and no leaf bit says so)
     a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p; a.cull = cull;
     launch_cast(a, s);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(B.ev, s));
-    B.set = true; B.version = ver; K.next++; K.casts++; K.rays += n;
+    r = cast_commit(c, bi, ver, s); if (r) return r;
+    K.casts++; K.rays += n;
     if (block) *block = bi;
     return ART_OK;
 }
@@ -2054,6 +2071,35 @@ int32_t art_cast_rays_multi(ArtContext *c, const ArtRayCastMulti *d) {
     if (!c->built) return fail(ART_E_STATE, "art_cast_rays_multi: scene not built (art_scene_build)");
     if (d->n == 0u) return ART_OK;
     return cast_enqueue(c, d->rays_dev, d->n, false, d->cull_mask, d->tuv_dev, d->ids_dev, d->count_dev, (hipStream_t)d->hip_stream, nullptr, d->max_hits);
+}
+
+// ---- the surface behind hit records (include/art.h: art_resolve_hits) ---------------------------------------------------------------------------
+// A resolve goes through the casts' ring: it claims a block (whose cursors it has no use for), holds the version it reads and leaves the block's event behind its
+// launch, so art_cast_sync, sync_all and scene_refresh wait for it where they wait for casts.  It is not counted as a cast: it traces nothing.
+int32_t art_resolve_hits(ArtContext *c, const ArtHitResolve *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_resolve_hits: null argument");
+    if (d->flags != 0u) return fail(ART_E_INVALID, "art_resolve_hits: flags: must be 0");
+    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_resolve_hits: n: above ART_CAST_MAX_RAYS");
+    auto bad = [&](const void *p, size_t align) { return (p == nullptr && d->n != 0u) || ((uintptr_t)p & (align - 1)) != 0; };   // (n = 0 touches nothing, as in art_cast_rays)
+    auto misaligned = [](const void *p, size_t align) { return ((uintptr_t)p & (align - 1)) != 0; };                              // (an output may be null: not wanted)
+    if (bad(d->tuv_dev, 16)) return fail(ART_E_INVALID, "art_resolve_hits: tuv_dev: null or not 16-byte aligned");
+    if (bad(d->ids_dev, 8)) return fail(ART_E_INVALID, "art_resolve_hits: ids_dev: null or not 8-byte aligned");
+    if (misaligned(d->pos_dev, 16) || misaligned(d->ng_dev, 16) || misaligned(d->ns_dev, 16) || misaligned(d->albedo_dev, 16) || misaligned(d->orm_dev, 16))
+        return fail(ART_E_INVALID, "art_resolve_hits: pos_dev / ng_dev / ns_dev / albedo_dev / orm_dev: not 16-byte aligned");
+    if (misaligned(d->uv_dev, 8)) return fail(ART_E_INVALID, "art_resolve_hits: uv_dev: not 8-byte aligned");
+    if (d->n != 0u && !d->pos_dev && !d->ng_dev && !d->ns_dev && !d->uv_dev && !d->albedo_dev && !d->orm_dev) return fail(ART_E_INVALID, "art_resolve_hits: no output buffer given");
+    if (!c->built) return fail(ART_E_STATE, "art_resolve_hits: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
+    int32_t r = cast_claim(c, (hipStream_t)d->hip_stream, &s, &ver, &bi); if (r) return r;
+    const AsPtrs as = as_ptrs(c, ver);
+    ResolveArgs a{};
+    a.tuv = (const float4 *)d->tuv_dev; a.ids = (const int2 *)d->ids_dev; a.n = d->n;
+    a.n_prims = (uint32_t)c->h_dev_prims.size(); a.T = c->T;   // (after cast_claim: a rebuild the cost rule started made them anew, with the table)
+    a.prims = as.prims; a.shade = as.shade; a.gid_leaf = c->bvh.gid_leaf; a.tex_pool = c->d_tex.p;
+    a.pos = (float4 *)d->pos_dev; a.ng = (float4 *)d->ng_dev; a.ns = (float4 *)d->ns_dev; a.uv = (float2 *)d->uv_dev; a.albedo = (float4 *)d->albedo_dev; a.orm = (float4 *)d->orm_dev;
+    launch_resolve(a, s);
+    return cast_commit(c, bi, ver, s);
 }
 
 int32_t art_cast_sync(ArtContext *c) {

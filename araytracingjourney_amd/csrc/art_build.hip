@@ -173,6 +173,14 @@ __global__ __launch_bounds__(256) void k_leaves(uint32_t T, const uint32_t *__re
     shade_tris[p] = st;
 }
 
+// gid -> leaf position: the inverse of the sort's permutation (Lbvh::gid_leaf).  A refit never moves a leaf, so the table lives as long as the tree
+__global__ __launch_bounds__(256) void k_gid_leaf(uint32_t T, const uint32_t *__restrict__ leaf_gid, uint32_t *__restrict__ gid_leaf) {
+    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= T) return;
+    uint32_t g = leaf_gid[p];
+    if (g < T) gid_leaf[g] = p;
+}
+
 // bottom-up refit: the second thread to arrive at a node owns it (its sibling's box is complete and visible)
 __global__ __launch_bounds__(256) void k_refit(uint32_t T, const int32_t *__restrict__ child, const int32_t *__restrict__ parent_int,
                                                const int32_t *__restrict__ parent_leaf, const float *__restrict__ leaf_lo, const float *__restrict__ leaf_hi,
@@ -882,7 +890,7 @@ void lbvh_free(Lbvh &l) {
     hipFree(l.wide); hipFree(l.widef); hipFree(l.leaf_parent); hipFree(l.node_parent);
     hipFree(l.sub_nodes); hipFree(l.sub_leaves); hipFree(l.sub_off);
     if (l.trav_child != l.res_trav_child) { hipFree(l.trav_child); hipFree(l.trav_lo); hipFree(l.trav_hi); }   // (allocations of their own: no room was reserved)
-    hipFree(l.block);   // leaf_gid .. shade_tris, cbounds, res_trav_*
+    hipFree(l.block);   // leaf_gid .. shade_tris, cbounds, res_trav_*, gid_leaf
     l = Lbvh{};
 }
 hipError_t lbvh_claim_trav(Lbvh &l, uint32_t NI) {
@@ -917,8 +925,8 @@ hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node
         arrive = A.take<uint32_t>(NI); parent_int = A.take<int32_t>(NI); parent_leaf = A.take<int32_t>(T);
         tmp = A.take<char>(tmp_bytes ? tmp_bytes : 16);
         {   // everything that outlives the build: one allocation (and room for the traversal tree some builder will make over these leaves)
-            const size_t sizes[15] = {(size_t)T * 4, (size_t)T * 8, (size_t)NI * 8, (size_t)NI * 12, (size_t)NI * 12, (size_t)T * 12, (size_t)T * 12, (size_t)T * sizeof(DevTri), (size_t)NI * sizeof(DevNode),
-                                      (size_t)T * 4, (size_t)T * sizeof(DevShadeTri), 32, (size_t)NI * 8, (size_t)NI * 12, (size_t)NI * 12};
+            const size_t sizes[16] = {(size_t)T * 4, (size_t)T * 8, (size_t)NI * 8, (size_t)NI * 12, (size_t)NI * 12, (size_t)T * 12, (size_t)T * 12, (size_t)T * sizeof(DevTri), (size_t)NI * sizeof(DevNode),
+                                      (size_t)T * 4, (size_t)T * sizeof(DevShadeTri), 32, (size_t)NI * 8, (size_t)NI * 12, (size_t)NI * 12, (size_t)T * 4};
             size_t total = 0; for (size_t b : sizes) total += Arena::pad(b);
             HIPQ(hipMalloc(&out.block, total));
             char *p = out.block; auto cut = [&](size_t bytes) { char *q = p; p += Arena::pad(bytes); return q; };
@@ -926,6 +934,7 @@ hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node
             out.leaf_lo = (float *)cut(sizes[5]); out.leaf_hi = (float *)cut(sizes[6]); out.tris = (DevTri *)cut(sizes[7]); out.nodes = (DevNode *)cut(sizes[8]); out.tri_prim = (uint32_t *)cut(sizes[9]);
             out.shade_tris = (DevShadeTri *)cut(sizes[10]); out.cbounds = (uint32_t *)cut(sizes[11]);
             out.res_trav_child = (int32_t *)cut(sizes[12]); out.res_trav_lo = (float *)cut(sizes[13]); out.res_trav_hi = (float *)cut(sizes[14]);
+            out.gid_leaf = (uint32_t *)cut(sizes[15]);
         }
         k_cb_init<<<1, kCbSlots, 0, s>>>(cslots);
         HIPQ(hipMemsetAsync(arrive, 0, (size_t)NI * 4, s));
@@ -935,6 +944,7 @@ hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node
         k_morton<<<GT, B, 0, s>>>(T, in.morton_bits, tlo, thi, out.cbounds, keys_in, gid_in);
         HIPQ(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, out.keys, gid_in, out.leaf_gid, T, 0, 64, s));
         k_leaves<<<GT, B, 0, s>>>(T, out.leaf_gid, triw, tlo, thi, out.tri_prim, in.prim_first_tri, out.leaf_lo, out.leaf_hi, out.tris, in.prims, out.shade_tris);
+        k_gid_leaf<<<GT, B, 0, s>>>(T, out.leaf_gid, out.gid_leaf);
         if (T > 1) {
             k_karras<<<(T - 1 + B - 1) / B, B, 0, s>>>((int)T, out.keys, out.leaf_gid, out.child, parent_int, parent_leaf);
             if (node_boxes) k_refit<<<GT, B, 0, s>>>(T, out.child, parent_int, parent_leaf, out.leaf_lo, out.leaf_hi, out.node_lo, out.node_hi, arrive); // (1.8 ms of arrival-counter waits on config 2: skipped when nothing will read the boxes)

@@ -114,6 +114,7 @@ struct Lbvh {               // canonical binary LBVH, device arrays
     DevTri *tris;           // [T] leaf order
     DevNode *nodes;         // [max(T-1,1)]
     uint32_t *tri_prim;     // [T] gid -> primitive
+    uint32_t *gid_leaf;     // [T] gid -> position in leaf order, the inverse of leaf_gid (art_resolve_hits: a hit record names its triangle by gid; the shading records are in leaf order)
     DevNode4 *wide;         // [n_wide] collapsed + quantised traversal structure
     DevNodeW *widef;        // [n_wide] the same topology with float boxes (packet walk)
     uint32_t n_wide;
@@ -304,6 +305,15 @@ struct CastArgs {
 };
 constexpr uint32_t kCastCursorWords = 8 * 32;           // eight per-XCD cursors, a 128-byte line each
 void launch_cast(const CastArgs &c, hipStream_t s);
+// One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
+// table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
+struct ResolveArgs {
+    const float4 *tuv; const int2 *ids; uint32_t n;
+    uint32_t n_prims, T;                                // the bounds a record's ids are checked against
+    const DevPrim *prims; const DevShadeTri *shade; const uint32_t *gid_leaf; const uint32_t *tex_pool;
+    float4 *pos, *ng, *ns; float2 *uv; float4 *albedo, *orm;
+};
+void launch_resolve(const ResolveArgs &r, hipStream_t s);
 // the bits of FrameArgs::alpha_bits: bit p of word p / 32 |= (prims[primitive of leaf p] has a cutoff > 0 or a visibility mask other than 0xFF); never cleared between builds (art_build.hip)
 void launch_alpha_bits(uint32_t T, const uint32_t *leaf_gid, const uint32_t *tri_prim, const DevPrim *prims, uint32_t *bits, hipStream_t s);
 // per-frame counter block (zeroed every frame): [64..] primary cursors, [64+256..] shadow cursors, [64+512..] AO cursors,

@@ -745,6 +745,60 @@ class Renderer:
         check(self._L.art_cast_rays_multi(self._ctx, C.byref(d)))
         return tuv, ids, count
 
+    _RESOLVE_OUTPUTS = dict(pos=4, ng=4, ns=4, uv=2, albedo=4, orm=4)   # name -> floats a record (the order of ArtHitResolve's fields)
+
+    def resolve_hits(self, tuv, ids, want=("pos", "ng", "ns", "uv", "albedo", "orm"), out=None, stream=None):
+        """What the rays hit (art_resolve_hits): the surface attributes behind hit records.  tuv, ids: the tensors cast_rays (kind "closest") or cast_rays_multi returned --
+        (n, 4) float32 / (n, 2) int32, or (n, K, 4) / (n, K, 2) -- or records of the caller's own making in that layout.  Returns a dict with one float32 tensor per name in
+        `want`, shaped like the records ((n, w) or (n, K, w)): pos (w 4: world position, w = 1 resolved / 0 miss), ng (4: geometric normal by winding, w 0), ns (4: the
+        frame's shading normal, w 0), uv (2), albedo (4: texture layer 0, r g b a in [0, 1], no gamma; a is what the alpha cutoff tests), orm (4: layer 1; y roughness,
+        z metallic).  A miss record (-1, -1) -- and any record that names nothing in the built structure, or holds a non-finite u or v -- gives zeros everywhere.  out: a
+        dict name -> tensor to write instead of new ones (exactly the record shape).  Enqueued on `stream` (default: torch's current stream) without host
+        synchronisation, behind the cast that wrote the records when that ran on the same stream.
+
+        Transparency the caller composites itself, without a host copy of any scene data:
+            tuv, ids, count = r.cast_rays_multi(rays, 4)
+            a = r.resolve_hits(tuv, ids, want=("albedo",))["albedo"][..., 3]          # (n, 4): alpha of every surface crossed, 0 in the tail records
+            through = torch.cumprod(1 - a, dim=1)[:, -1]                               # what is left of the ray behind its first four surfaces"""
+        import torch
+        if self._device < 0:
+            self._device = torch.cuda.current_device()
+        dev = self._device
+        want = tuple(want)
+        if not want or len(set(want)) != len(want) or any(w not in self._RESOLVE_OUTPUTS for w in want):
+            raise ValueError(f"want must name one or more of {tuple(self._RESOLVE_OUTPUTS)}, each once")
+        for t, name, dtype, width, align in ((tuv, "tuv", torch.float32, 4, 16), (ids, "ids", torch.int32, 2, 8)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.dim() in (2, 3) and t.shape[-1] == width and
+                    t.is_contiguous() and t.data_ptr() % align == 0):
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (n, {width}) or (n, K, {width}), {align}-byte aligned")
+        lead = tuple(tuv.shape[:-1])
+        if tuple(ids.shape[:-1]) != lead:
+            raise ValueError("tuv and ids must hold the same records")
+        n = 1
+        for k in lead:
+            n *= k
+        res = {}
+        for name in want:
+            width = self._RESOLVE_OUTPUTS[name]
+            t = out[name] if out is not None and name in out else torch.empty(lead + (width,), dtype=torch.float32, device=tuv.device)
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == torch.float32 and t.is_contiguous() and
+                    tuple(t.shape) == lead + (width,) and t.data_ptr() % (4 * width) == 0):
+                raise ValueError(f"out: {name} must be a contiguous float32 tensor on cuda:{dev} of shape {lead + (width,)}, {4 * width}-byte aligned")
+            res[name] = t
+        d = _lib.ArtHitResolve(tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, n=n, flags=0)
+        for name, t in res.items():
+            setattr(d, name + "_dev", t.data_ptr() or None)
+        if stream is None:
+            stream = torch.cuda.current_stream(tuv.device)
+        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+        check(self._L.art_resolve_hits(self._ctx, C.byref(d)))
+        return res
+
+    def cast_surface(self, rays, cull_mask=0xFF, want=("pos", "ng", "ns", "uv", "albedo", "orm"), stream=None):
+        """One closest cast and one resolve of its records on the same stream: ((tuv, ids), surface dict) -- cast_rays and resolve_hits, nothing in between."""
+        tuv, ids = self.cast_rays(rays, "closest", cull_mask, stream=stream)
+        return (tuv, ids), self.resolve_hits(tuv, ids, want, stream=stream)
+
     def cast_sync(self):
         """every cast enqueued so far has finished, on whichever stream (art_cast_sync)"""
         check(self._L.art_cast_sync(self._ctx))

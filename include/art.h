@@ -325,6 +325,41 @@ int32_t art_cast_rays_multi(ArtContext *ctx, const ArtRayCastMulti *cast);
 int32_t art_cast_sync(ArtContext *ctx);
 /* since art_create: casts enqueued (n > 0), their rays, and the times art_cast_rays (or a refit in front of a frame) waited on the host for a cast.  Any pointer may be NULL. */
 int32_t art_cast_counts(ArtContext *ctx, uint64_t *casts, uint64_t *rays, uint64_t *host_waits);
+/* The surface behind hit records: what the ray hit.  Takes the (t,u,v) and (primitive, triangle) records art_cast_rays / art_cast_rays_multi write and
+ * leaves, per record, the attributes the frame's own shading interpolates -- a G-buffer for the caller's rays: lidar intensity from the normal, compositing from alpha and
+ * colour, picking and collision from the position.  No light, no shadow ray, no BRDF, no camera: a gather and an interpolation.
+ *  - Values: those of the frame's surface block in its plain form (shade_surface_body<false>: no guarded fast path), same operations, same order.  Barycentrics (1-u-v, u, v)
+ *    over the triangle's shading record; pos = object-to-world of the interpolated position; uv the interpolated texture coordinate (not wrapped); ns the frame's N
+ *    (interpolated normal through world-to-object, tangent by Gram-Schmidt, binormal with vertex 0's handedness, texture layer 2, normalised); albedo and orm texture layers
+ *    0 and 1 at uv through the frame's sampler (bilinear, REPEAT, LOD 0), raw: r,g,b,a in [0,1], no gamma -- albedo.a is the value the alpha cutoff tests.  ng =
+ *    normalize(cross(w1 - w0, w2 - w0)) over the world-space vertices: orientation by winding, not flipped towards any ray; (0,0,0) where the cross product is zero.
+ *  - The miss record is all zeros in every buffer given (pos.w = 0; a resolved record has pos.w = 1).  It is written for ids (-1,-1) and for every record that cannot be
+ *    resolved safely: a primitive id outside [0, num_primitives), a triangle outside the primitive's, a primitive the built structure does not hold (added since the
+ *    build, disabled at the build), a non-finite u or v.  The records are the caller's: all of it is checked before an address is formed -- a property of the kernel, not an
+ *    error.  Finite u, v outside the triangle extrapolate.  A primitive that left the structure by residency (art_scene_set_primitive_enabled(.., 0) on a built one)
+ *    still resolves: its shading records stay.  t is not read, and no rays are needed.  A record depends on its input record alone.  A NULL buffer is not written.
+ *  - Scene and asynchrony: art_cast_rays's.  The scene as of the call (a pending move, deformation, residency switch or cutoff is taken up first, the refit on the context's
+ *    streams in front of the resolve), the version current at the call held until the resolve finishes; enqueued on hip_stream (NULL: the context's cast stream) behind
+ *    earlier work there -- a cast followed by a resolve of its buffers on one stream needs nothing in between -- without hipMalloc, hipFree or synchronisation on the steady
+ *    path.  It takes a block of the casts' ring (ART_CAST_POOL): art_cast_sync, art_sync, art_scene_build and the others wait for it as for a cast, a refit that would
+ *    rewrite the version it reads waits for it, and art_cast_counts' host_waits counts a wait it caused; casts and rays do not count it (it traces nothing).
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null or misaligned tuv_dev / ids_dev (with n = 0 null is fine); a misaligned
+ *    output; all six outputs NULL with n > 0; flags other than 0; n above ART_CAST_MAX_RAYS.  ART_E_STATE: the scene is not built, or art_scene_needs_build.  Overlap
+ *    between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtHitResolve {
+    const void *tuv_dev;   /* n x 4 floats t,u,v,- : records as art_cast_rays / art_cast_rays_multi write them (for multi: n = rays x max_hits); 16-byte aligned */
+    const void *ids_dev;   /* n x 2 int32 (primitive id, triangle in the primitive), -1,-1 = miss; 8-byte aligned */
+    void *pos_dev;         /* n x float4: world position xyz; w = 1 for a resolved record, 0 for a miss record.  16-byte aligned.  May be NULL */
+    void *ng_dev;          /* n x float4: geometric normal (unit, world space, orientation by winding: NOT flipped towards any ray), w = 0.  May be NULL */
+    void *ns_dev;          /* n x float4: shading normal N (interpolated, TBN, normal map: the frame's N), w = 0.  May be NULL */
+    void *uv_dev;          /* n x float2: interpolated texture coordinate (the frame's tu, tv; not wrapped); 8-byte aligned.  May be NULL */
+    void *albedo_dev;      /* n x float4: texture layer 0 at uv as sample_tex returns it: r,g,b,a in [0,1], NO gamma (a is what the alpha cutoff tests).  May be NULL */
+    void *orm_dev;         /* n x float4: texture layer 1 at uv, same sampler (y roughness, z metallic).  May be NULL */
+    void *hip_stream;      /* as ArtRayCast: NULL = the context's cast stream */
+    uint32_t n;            /* 0 is legal: nothing is enqueued */
+    uint32_t flags;        /* must be 0 */
+} ArtHitResolve;           /* 80 bytes */
+int32_t art_resolve_hits(ArtContext *ctx, const ArtHitResolve *r);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,

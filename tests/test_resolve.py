@@ -1,0 +1,674 @@
+"""art_resolve_hits (include/art.h): the surface behind the hit records of a cast.
+
+The witness is tests/np_shading.py::shade_pixel's first half (raytrace.rgen.glsl:107-150 up to N, the texture coordinate, albedo before ** 2.2, orm) restated for many records
+at once, plus the geometric normal of the world triangle; a CPU test ties it to shade_pixel itself.  It runs in float64 (the reference) and in float32 (what float32 can
+do with the same expressions): the largest difference between the two on the records of a case, per output, is the MEASURED error of the number format, and four times it --
+the device contracts nothing but its dot and cross products are FMA chains in another order than numpy's -- is what a case allows.  Where the two happen to agree to
+better than half a unit in the last place of the output's magnitude (a constant texture, an axis-aligned normal) the floor 2^-24 x magnitude stands in for the
+measurement: float32 cannot promise more.  Both figures per case are committed in tests/golden/resolve_margins.json (python tests/test_resolve.py --write-margins makes the file);
+a CPU test measures again and compares.  The records the CPU measures on are the oracle's closest hits -- the casts' records bit for bit (tests/test_cast.py)."""
+import ctypes as C
+import importlib.util
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import random_rays, seam_scene
+import np_shading as nps
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MARGINS = os.path.join(ROOT, "tests", "golden", "resolve_margins.json")
+OUTPUTS = dict(pos=4, ng=4, ns=4, uv=2, albedo=4, orm=4)
+SHORT = 1e-3          # |interpolated normal|, |interpolated tangent| or |tangent after Gram-Schmidt| below this: the normalisation amplifies without bound, ns is not compared
+LEFT_OUT_CAP = 0.005  # at most this share of a case's hit records may be left out that way
+SENTINEL = -12345.5
+
+
+@pytest.fixture(scope="module")
+def R():
+    from araytracingjourney_amd import renderer
+    return renderer
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    return t
+
+
+# ---- the witness ------------------------------------------------------------------------------------------------------------------------------------------------
+def _nz(a):
+    return a / np.sqrt(np.sum(a * a, axis=1, keepdims=True))
+
+
+def _inv3x4(model):
+    """the inverse of a row-major 3x4 affine matrix by cofactors, float64 (no LAPACK: the same digits everywhere) -> (3x3 inverse of the linear part)"""
+    A = np.asarray(model, np.float64).reshape(3, 4)[:, :3]
+    c = np.array([np.cross(A[1], A[2]), np.cross(A[2], A[0]), np.cross(A[0], A[1])])   # rows: cofactors
+    return c.T / (A[0] @ c[0])
+
+
+def _texture(layer, uv, dt):
+    """np_shading.texture for many coordinates: linear, REPEAT, LOD 0"""
+    th, tw = layer.shape[:2]
+    x, y = uv[:, 0] * dt(tw) - dt(0.5), uv[:, 1] * dt(th) - dt(0.5)
+    x0, y0 = np.floor(x), np.floor(y)
+    fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+    xi, yi = x0.astype(np.int64), y0.astype(np.int64)
+    t = lambda xx, yy: layer[yy % th, xx % tw].astype(dt) / dt(255.0)   # noqa: E731
+    one = dt(1.0)
+    return (t(xi, yi) * (one - fx) + t(xi + 1, yi) * fx) * (one - fy) + (t(xi, yi + 1) * (one - fx) + t(xi + 1, yi + 1) * fx) * fy
+
+
+def witness(prims, tuv, ids, dt):
+    """the six outputs of the records (tuv[n, >= 3], ids[n, 2]) in dtype dt, zeros for ids (-1, -1); also `short`: records whose ns is not to be compared (SHORT)"""
+    n = ids.shape[0]
+    out = {k: np.zeros((n, w), dt) for k, w in OUTPUTS.items()}
+    short = np.zeros(n, bool)
+    for p, P in enumerate(prims):
+        sel = np.flatnonzero(ids[:, 0] == p)
+        if not sel.size:
+            continue
+        idx = np.asarray(P.indices).reshape(-1, 3)[ids[sel, 1]].astype(np.int64)
+        V = np.asarray(P.verts).astype(dt)
+        v0, v1, v2 = V[idx[:, 0]], V[idx[:, 1]], V[idx[:, 2]]
+        u, v = tuv[sel, 1].astype(dt)[:, None], tuv[sel, 2].astype(dt)[:, None]
+        b0 = dt(1.0) - u - v
+        interp = lambda a, b: (v0[:, a:b] * b0 + v1[:, a:b] * u) + v2[:, a:b] * v   # noqa: E731
+        M = np.asarray(P.model, np.float64).reshape(3, 4).astype(dt)
+        A, t = M[:, :3], M[:, 3]
+        Ainv = _inv3x4(P.model).astype(dt)
+        rows = lambda q, m: (q[:, 0:1] * m[0] + q[:, 1:2] * m[1]) + q[:, 2:3] * m[2]   # noqa: E731  (q @ m, element by element: no BLAS, the same sums everywhere)
+        to_world = lambda q: rows(q, A.T) + t   # noqa: E731
+        out["pos"][sel, :3] = to_world(interp(0, 3)); out["pos"][sel, 3] = 1
+        uv = interp(3, 5)
+        out["uv"][sel] = uv
+        ni, ti = interp(5, 8), interp(8, 11)
+        wn = _nz(rows(_nz(ni), Ainv))                                   # normal * world_to_object
+        wt = _nz(rows(_nz(ti), A.T))
+        gs = wt - np.sum(wt * wn, axis=1, keepdims=True) * wn
+        wt = _nz(gs)
+        wb = np.cross(wn, wt) * v0[:, 11:12]
+        nt = _nz(_texture(P.tex[2], uv, dt)[:, :3] * dt(2.0) - dt(1.0))
+        out["ns"][sel, :3] = _nz(wt * nt[:, 0:1] + wb * nt[:, 1:2] + wn * nt[:, 2:3])
+        short[sel] = (np.linalg.norm(ni, axis=1) < SHORT) | (np.linalg.norm(ti, axis=1) < SHORT) | (np.linalg.norm(gs, axis=1) < SHORT)
+        out["albedo"][sel] = _texture(P.tex[0], uv, dt)
+        out["orm"][sel] = _texture(P.tex[1], uv, dt)
+        w0, w1, w2 = to_world(v0[:, :3]), to_world(v1[:, :3]), to_world(v2[:, :3])
+        c = np.cross(w1 - w0, w2 - w0)
+        ln = np.sqrt(np.sum(c * c, axis=1, keepdims=True))
+        out["ng"][sel, :3] = np.where(ln > 0, c / np.where(ln > 0, ln, 1), 0)
+    return out, short
+
+
+def extent_of(prims):
+    tris = nps.world_triangles(prims)[0].reshape(-1, 3)
+    return float(np.linalg.norm(tris.max(0) - tris.min(0)))
+
+
+def magnitudes(w64, extent):
+    """what half a unit in the last place is relative to, per output: the scene's extent for positions, the largest coordinate for uv, 1 for unit vectors and colours"""
+    return dict(pos=extent, ng=1.0, ns=1.0, uv=max(1.0, float(np.abs(w64["uv"]).max())), albedo=1.0, orm=1.0)
+
+
+def measure(prims, tuv, ids):
+    """-> (w64, short, figures): figures = per output the largest |float32 witness - float64 witness| (positions: relative to the extent), the allowance 4 x max(that, 2^-24 x
+    magnitude) in the output's own units, and the share of hit records left out of the ns comparison"""
+    w64, short = witness(prims, tuv, ids, np.float64)
+    w32, _ = witness(prims, tuv, ids, np.float32)
+    ext = extent_of(prims)
+    mag = magnitudes(w64, ext)
+    hit = ids[:, 0] >= 0
+    keep = {k: (hit & ~short) if k == "ns" else hit for k in OUTPUTS}
+    measured = {k: float(np.abs(w32[k][keep[k]].astype(np.float64) - w64[k][keep[k]]).max(initial=0.0)) for k in OUTPUTS}
+    allowed = {k: 4.0 * max(measured[k], 2.0 ** -24 * mag[k]) for k in OUTPUTS}
+    measured["pos"] /= ext
+    return w64, short, dict(extent=ext, records=int(ids.shape[0]), hits=int(hit.sum()), left_out=float(short[hit].mean()) if hit.any() else 0.0, measured=measured, allowed=allowed)
+
+
+# ---- the cases: scene, rays, the oracle's records, the witness -- made once, shared, never written --------------------------------------------------------------------
+def _warp(i, extra=np.eye(4)):
+    """test_gpu_parity's warped pose: rotated, carried along, mirrored, scaled differently along each axis and sheared (a negative determinant: normals go by the inverse
+    transpose, the binormal by v0's handedness)"""
+    import math
+    a, b = 0.21 * i, 0.13 * i
+    ry = np.array([[math.cos(a), 0, math.sin(a), 0], [0, 1, 0, 0], [-math.sin(a), 0, math.cos(a), 0], [0, 0, 0, 1]])
+    rz = np.array([[math.cos(b), -math.sin(b), 0, 0], [math.sin(b), math.cos(b), 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
+    t = np.eye(4); t[:3, 3] = (0.25 * math.sin(0.4 * i), 0.05 * i - 0.3, 0.2 * math.cos(0.3 * i) - 0.2)
+    w = np.array([[-0.8, 0.15, 0, 0], [0, 1.3, 0, 0], [0.1, 0, 0.6, 0], [0, 0, 0, 1]])
+    return np.ascontiguousarray((t @ ry @ rz @ w @ extra)[:3], np.float32).reshape(-1)
+
+
+def warped_scene(scenes, poses=(9, 4)):
+    """two textured primitives -- a displaced sphere with left-handed tangents, a tilted 3 x 3 patch whose uv leave [0, 1] -- under mirrored and sheared model matrices"""
+    import math
+    a, b = scenes.MeshBuilder(), scenes.MeshBuilder()
+    scenes.displaced_sphere(a, (0.0, 0.0, 0.0), 0.55, 2, 3, 0.3, handed=-1.0)
+    scenes.quad(b, (-0.9, -0.7, 0.5), (1.8, 0.0, 0.2), (0.0, 1.4, 0.3), nu=3, nv=3, uv_scale=(2.5, 1.5))
+    prims = [a.finish(scenes.make_texture(5, 16, (0.8, 0.5, 0.3), False), model=_warp(poses[0])),
+             b.finish(scenes.make_texture(11, 8, (0.3, 0.6, 0.8), True), model=_warp(poses[1]))]
+    return scenes.Scene("warped", prims, dict(pos=(0.0, 0.0, -2.2), dir=(0.0, 0.0, 1.0), fovy=math.pi / 3, znear=0.1, zfar=1000.0),
+                        [dict(kind="point", pos=(0.0, 0.5, -1.0), color=(6.0, 6.0, 6.0), falloff=6.0, casts_shadows=False)])
+
+
+def _with_models(scenes, sc, models):
+    P = type(sc.primitives[0])
+    return scenes.Scene(sc.name, [P(p.verts, p.indices, p.tex, np.asarray(m, np.float32).reshape(-1)) for p, m in zip(sc.primitives, models)], sc.camera, sc.lights)
+
+
+def deformed_vertices(verts):
+    """new positions, normals, tangents and uvs for a primitive: bulged and twisted about y (normals and tangents turned with it), uv shifted and stretched"""
+    v = np.array(verts, np.float64)
+    ang = 0.6 * v[:, 1]
+    c, s = np.cos(ang), np.sin(ang)
+    rot = lambda q: np.stack([c * q[:, 0] + s * q[:, 2], q[:, 1], -s * q[:, 0] + c * q[:, 2]], 1)   # noqa: E731
+    v[:, 0:3] = rot(v[:, 0:3]) * (1.0 + 0.2 * np.sin(5.0 * v[:, 1:2]))
+    v[:, 5:8] = rot(v[:, 5:8]); v[:, 8:11] = rot(v[:, 8:11])
+    v[:, 3:5] = v[:, 3:5] * (1.3, 0.7) + (0.37, -0.21)
+    return np.ascontiguousarray(v, np.float32)
+
+
+CORNELL_MOVE = np.array([1, 0, 0, 0.4, 0, 1, 0, 0.9, 0, 0, 1, -0.5], np.float32)   # where test 8 puts Cornell's first primitive before the rebuild
+ORACLE_SHIFT = 0.95   # Cornell moved along +z by its camera's distance: the eye of test 2 sits at the origin
+
+
+def scene_of(name, scenes, get_scene):
+    if name == "cornell":
+        return get_scene("cornell", 1.0)
+    if name == "seams":
+        return seam_scene(scenes)
+    if name == "warped":
+        return warped_scene(scenes)
+    if name == "warped-moved":      # test 6: primitive 1 at another warped pose
+        sc = warped_scene(scenes)
+        return _with_models(scenes, sc, [sc.primitives[0].model, _warp(6)])
+    if name == "warped-deformed":   # test 6: then primitive 0 with new vertices
+        sc = scene_of("warped-moved", scenes, get_scene)
+        P = type(sc.primitives[0])
+        p = sc.primitives[0]
+        return scenes.Scene(sc.name, [P(deformed_vertices(p.verts), p.indices, p.tex, p.model), sc.primitives[1]], sc.camera, sc.lights)
+    if name == "cornell-moved":     # test 8
+        sc = get_scene("cornell", 1.0)
+        return _with_models(scenes, sc, [CORNELL_MOVE] + [p.model for p in sc.primitives[1:]])
+    if name == "cornell-shifted":   # test 2
+        sc = get_scene("cornell", 1.0)
+        cam = dict(sc.camera, pos=(0.0, 0.0, 0.0))
+        sh = _with_models(scenes, sc, [np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, ORACLE_SHIFT], np.float32)] * len(sc.primitives))
+        return scenes.Scene("cornell-shifted", sh.primitives, cam, sc.lights)
+    raise KeyError(name)
+
+
+def camera_rays(orc, sc, w=64, h=64):
+    c = sc.camera
+    return np.ascontiguousarray(orc.gen_primary(orc.camera_from_params(c["pos"], c["dir"], w / h, c["fovy"], c["znear"], c["zfar"]), w, h), np.float32)
+
+
+CASES = ["cornell/camera", "cornell/random", "seams/camera", "seams/random", "warped/camera", "warped/random", "warped-moved/random", "warped-deformed/random",
+         "cornell-moved/random", "cornell-shifted/camera", "cornell/multi4"]
+_CASE = {}
+
+
+def case(key, orc, scenes, get_scene):
+    if key not in _CASE:
+        name, kind = key.split("/")
+        sc = scene_of(name, scenes, get_scene)
+        if kind == "multi4":
+            from test_cast_multi import expected, hit_table
+            rays = random_rays(1024, 7)
+            tuv, ids, count = expected(hit_table(orc, sc.primitives, rays), rays, 4)
+            tuv, ids = tuv.reshape(-1, 4), ids.reshape(-1, 2)
+        else:
+            rays = camera_rays(orc, sc) if kind == "camera" else random_rays(4096, 7)
+            S = orc.Scene(sc.primitives, morton_bits=30)
+            tuv, ids = S.trace_closest(rays)[:2]
+            tuv, ids, count = np.ascontiguousarray(tuv, np.float32), np.ascontiguousarray(ids, np.int32), None
+        w64, short, fig = measure(sc.primitives, tuv, ids)
+        d = dict(scene=sc, rays=rays, tuv=tuv, ids=ids, count=count, w64=w64, short=short, figures=fig)
+        for a in [rays, tuv, ids, short] + list(w64.values()):
+            a.setflags(write=False)
+        _CASE[key] = d
+    return _CASE[key]
+
+
+def oracle_normal(view_inv, ns, dt):
+    """the frame's normal output from N: normalize(flip(mat3(transpose(view_inv)) * N)) * 0.5 + 0.5 (raytrace.rgen.glsl:192-196)"""
+    on = ns[:, :3].astype(dt) @ view_inv[:3, :3].astype(dt)
+    on[:, 1:] = -on[:, 1:]
+    with np.errstate(invalid="ignore"):   # (a miss record's N is zero: its row is not looked at)
+        return _nz(on) * dt(0.5) + dt(0.5)
+
+
+def all_figures(orc, scenes, get_scene):
+    fig = {k: case(k, orc, scenes, get_scene)["figures"] for k in CASES}
+    # test 2's normal image: the same N through the view's rotation, in both precisions
+    c = case("cornell-shifted/camera", orc, scenes, get_scene)
+    sc = c["scene"]
+    view_inv = nps.camera_matrices(sc.camera["pos"], sc.camera["dir"], 1.0, sc.camera["fovy"], sc.camera["znear"], sc.camera["zfar"])[1]
+    w32 = witness(sc.primitives, c["tuv"], c["ids"], np.float32)[0]
+    keep = (c["ids"][:, 0] >= 0) & ~c["short"]
+    m = float(np.abs(oracle_normal(view_inv, w32["ns"], np.float32).astype(np.float64) - oracle_normal(view_inv, c["w64"]["ns"], np.float64))[keep].max())
+    fig["oracle/normal"] = dict(measured=dict(normal=m), allowed=dict(normal=4.0 * max(m, 2.0 ** -24)))
+    return fig
+
+
+def margins():
+    return json.load(open(MARGINS))["cases"]
+
+
+def write_margins():
+    from araytracingjourney_amd import scenes
+    from oracle import orc
+    orc.build()
+    doc = dict(how="tests/test_resolve.py::measure -- per case and output: measured = max |float32 witness - float64 witness| over the case's hit records (pos: relative to "
+                   "the scene's extent); allowed = 4 x max(measured, 2^-24 x magnitude) in the output's units (magnitude: extent for pos, max |uv| for uv, 1 otherwise); "
+                   "left_out = share of hit records whose ns is not compared (a normal or tangent shorter than 1e-3 before a normalisation)",
+               cases=all_figures(orc, scenes, lambda n, d=1.0: scenes.get_scene(n, d)))
+    json.dump(doc, open(MARGINS, "w"), indent=1, sort_keys=True)
+    print(json.dumps(doc["cases"], indent=1, sort_keys=True))
+
+
+# ---- without a GPU ----------------------------------------------------------------------------------------------------------------------------------------------
+def _gcc_layout(name):
+    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "tools", "gen_rust_bindings.py"))
+    g = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(g)
+    structs = [s for s in g.parse(open(g.HDR).read())[2] if s[0] == name]
+    assert len(structs) == 1
+    return g.c_layout(structs), [f for f, _ in structs[0][2]]
+
+
+def test_the_ctypes_descriptor_is_the_headers():
+    """ArtHitResolve as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 80 bytes"""
+    from araytracingjourney_amd import _lib
+    lay, fields = _gcc_layout("ArtHitResolve")
+    assert fields == [n for n, _ in _lib.ArtHitResolve._fields_] == ["tuv_dev", "ids_dev", "pos_dev", "ng_dev", "ns_dev", "uv_dev", "albedo_dev", "orm_dev", "hip_stream", "n", "flags"]
+    assert C.sizeof(_lib.ArtHitResolve) == lay["ArtHitResolve"] == 80
+    for f in fields:
+        assert getattr(_lib.ArtHitResolve, f).offset == lay["ArtHitResolve." + f], f
+
+
+def test_the_entry_point_is_exported_bound_and_wrapped():
+    """libart.so exports art_resolve_hits, bindings/art_sys.rs declares it, and Renderer has resolve_hits and cast_surface"""
+    from araytracingjourney_amd import _lib, renderer
+    L = _lib.load()
+    assert hasattr(L, "art_resolve_hits") and "art_resolve_hits" in _lib.SYMBOLS
+    rs = open(os.path.join(ROOT, "bindings", "art_sys.rs")).read()
+    assert "pub fn art_resolve_hits(" in rs and "pub struct ArtHitResolve" in rs and "size_of::<ArtHitResolve>() == 80)" in rs
+    assert callable(renderer.Renderer.resolve_hits) and callable(renderer.Renderer.cast_surface)
+
+
+def test_a_resolve_without_a_context_is_invalid_on_any_machine():
+    """art_resolve_hits(NULL, ...) and a null descriptor need no device to say ART_E_INVALID"""
+    from araytracingjourney_amd import _lib
+    L = _lib.load()
+    assert L.art_resolve_hits(None, None) == _lib.ART_E_INVALID and L.art_last_error().startswith(b"art_resolve_hits: ")
+    d = _lib.ArtHitResolve(n=0)
+    assert L.art_resolve_hits(None, C.byref(d)) == _lib.ART_E_INVALID
+    assert L.art_resolve_hits(C.c_void_p(16), None) == _lib.ART_E_INVALID   # (a descriptor is looked at before the context is)
+
+
+def test_the_witness_is_shade_pixels_first_half(orc, scenes, get_scene):
+    """the vectorised float64 witness against np_shading.shade_pixel, record by record, on the warped scene (mirrored matrices, left-handed tangents, wrapped uv): the
+    normal image shade_pixel returns is oracle_normal of the witness's N, its depth the witness's position through the view matrix -- to 1e-12"""
+    c = case("warped/camera", orc, scenes, get_scene)
+    sc = c["scene"]
+    view, view_inv = nps.camera_matrices(sc.camera["pos"], sc.camera["dir"], 1.0, sc.camera["fovy"], sc.camera["znear"], sc.camera["zfar"])[:2]
+    hits = np.flatnonzero((c["ids"][:, 0] >= 0) & ~c["short"])[::23]
+    assert hits.size > 40 and set(c["ids"][hits, 0]) == {0, 1}
+    on = oracle_normal(view_inv, c["w64"]["ns"], np.float64)
+    for i in hits:
+        p, t = c["ids"][i]
+        _, depth, normal, _ = nps.shade_pixel(sc.primitives[p], int(t), float(c["tuv"][i, 1]), float(c["tuv"][i, 2]), view, view_inv, np.asarray(sc.camera["pos"], np.float64), [], 0)
+        assert abs(depth + (view @ np.append(c["w64"]["pos"][i, :3], 1.0))[2]) < 1e-12 and np.abs(normal - on[i]).max() < 1e-12
+    # and the texture restatement against np_shading.texture, wrap included
+    uv = np.array([[-1.3, 2.2], [0.01, 0.99], [5.5, -4.25], [0.5, 0.5]])
+    for layer in sc.primitives[1].tex:
+        got = _texture(layer, uv, np.float64)
+        assert all(np.abs(got[k] - nps.texture(layer, uv[k])).max() < 1e-15 for k in range(len(uv)))
+
+
+def test_the_committed_margins_are_what_the_witness_measures(orc, scenes, get_scene):
+    """tests/golden/resolve_margins.json holds, for every case the GPU tests run, what measure() finds here -- within 5 % (numpy's float32 loops may round a sum another
+    way on another CPU) -- and allowances that are four times the measurement or the format's floor; every case leaves at most 0.5 % of its hits out of the ns comparison
+    and hits something; the oracle's view matrix of test 2 has only 0 and +-1 in it"""
+    got, want = all_figures(orc, scenes, get_scene), margins()
+    assert set(got) == set(want)
+    for key, g in got.items():
+        w = want[key]
+        for k, m in g["measured"].items():
+            assert abs(m - w["measured"][k]) <= 0.05 * w["measured"][k] + 1e-12, (key, k, m, w["measured"][k])
+            assert abs(g["allowed"][k] - w["allowed"][k]) <= 0.05 * w["allowed"][k], (key, k)
+        if "left_out" in g:
+            assert g["left_out"] <= LEFT_OUT_CAP and g["hits"] >= g["records"] // 8 and w["records"] == g["records"] and w["hits"] == g["hits"], (key, g)
+    sc = case("cornell-shifted/camera", orc, scenes, get_scene)["scene"]
+    cam = orc.camera_from_params(sc.camera["pos"], sc.camera["dir"], 1.0, sc.camera["fovy"], sc.camera["znear"], sc.camera["zfar"])
+    assert set(np.array(list(cam.view), np.float64).tolist()) <= {0.0, 1.0, -1.0} and set(np.array(list(cam.view_inv), np.float64).tolist()) <= {0.0, 1.0, -1.0}
+
+
+# ---- on the device ----------------------------------------------------------------------------------------------------------------------------------------------
+def _up(torch, a):
+    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared references are read-only)
+
+
+def _host(surf):
+    return {k: v.cpu().numpy() for k, v in surf.items()}
+
+
+def _check(surf, c, allowed, what, rows=None):
+    """surf (numpy, name -> [n, w]) against the case's float64 witness on `rows` (default: all records): miss records all zero bits, pos.w the hit flag exactly, the w of the
+    normals 0, every output within its allowance; prints each figure first"""
+    rows = np.arange(c["ids"].shape[0]) if rows is None else rows
+    ids, short = c["ids"][rows], c["short"][rows]
+    hit = ids[:, 0] >= 0
+    assert hit.any() and float(short[hit].mean()) <= LEFT_OUT_CAP
+    for k, got in surf.items():
+        got = got.reshape(-1, OUTPUTS[k])
+        assert got.shape[0] == rows.size and got.dtype == np.float32, (what, k)
+        assert not np.ascontiguousarray(got[~hit]).view(np.uint32).any(), f"{what}: {k}: a miss record is not all zeros"
+        want = c["w64"][k][rows]
+        keep = hit & ~short if k == "ns" else hit
+        err = float(np.abs(got[keep].astype(np.float64) - want[keep]).max())
+        print(f"[resolve] {what}: {k}: worst |device - float64 witness| {err:.3e}, allowed {allowed[k]:.3e}")
+        assert np.isfinite(got[hit & ~short]).all(), f"{what}: {k}: non-finite values"
+        assert err <= allowed[k], f"{what}: {k}: off by {err:.3e}, allowed {allowed[k]:.3e}"
+        if k == "pos":
+            assert np.array_equal(got[:, 3], hit.astype(np.float32)), f"{what}: pos.w is not the hit flag"
+        if k in ("ng", "ns"):
+            assert not got[:, 3].any(), f"{what}: {k}.w is not 0"
+
+
+def _cast_and_check(R, torch, c, allowed, what, r=None, **kw):
+    r = r or R.renderer_for_scene(c["scene"], (64, 64), **kw)
+    (tuv, ids), surf = r.cast_surface(_up(torch, c["rays"]))
+    torch.cuda.synchronize()
+    assert np.array_equal(ids.cpu().numpy(), c["ids"]), f"{what}: the cast's ids are not the oracle's"
+    assert np.array_equal(tuv.cpu().numpy().view(np.uint32)[:, :3], c["tuv"].view(np.uint32)[:, :3]), f"{what}: the cast's t, u, v are not the oracle's"
+    assert set(surf) == set(OUTPUTS) and all(v.shape == (c["ids"].shape[0], OUTPUTS[k]) for k, v in surf.items())
+    _check(_host(surf), c, allowed, what)
+    return r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", ["cornell/camera", "cornell/random", "seams/camera", "seams/random", "warped/camera", "warped/random"])
+def test_against_the_fp64_witness(R, torch, orc, scenes, get_scene, key):
+    """1: a closest cast and a resolve of its records on one stream -- the 64 x 64 camera rays and random_rays(4096, 7) on Cornell, the seam quad (REPEAT wrap, uv outside
+    [0, 1]) and two textured primitives under mirrored, sheared matrices -- all six outputs against the float64 witness within the committed allowances; ids, the hit flag and
+    the miss zeros exact"""
+    _cast_and_check(R, torch, case(key, orc, scenes, get_scene), margins()[key]["allowed"], key).close()
+
+
+@pytest.mark.gpu
+def test_against_the_oracle_frame(R, torch, orc, scenes, get_scene):
+    """2: Cornell 64 x 64 seen from the origin along +z (the scene is moved instead of the eye: the oracle's view matrix holds only 0 and +-1): the oracle's depth of every
+    hit pixel IS the matching signed component of pos, bit for bit; pos.w == 0 exactly where the oracle's hit id is -1; the oracle's normal image is
+    normalize(flip(view_inv^T ns)) * 0.5 + 0.5 within the measured allowance"""
+    key = "cornell-shifted/camera"
+    c = case(key, orc, scenes, get_scene)
+    sc = c["scene"]
+    cam = orc.camera_from_params(sc.camera["pos"], sc.camera["dir"], 1.0, sc.camera["fovy"], sc.camera["znear"], sc.camera["zfar"])
+    view = np.array(list(cam.view), np.float64).reshape(4, 4).T         # (column-major in the block)
+    view_inv = np.array(list(cam.view_inv), np.float64).reshape(4, 4).T
+    assert set(view.reshape(-1).tolist()) <= {0.0, 1.0, -1.0} and not view[2, 3]
+    ref = orc.Scene(sc.primitives, morton_bits=30).render(cam, orc.make_lights(sc.lights), len(sc.lights), 64, 64, threads=2, debug=True)
+    r = _cast_and_check(R, torch, c, margins()[key]["allowed"], key)
+    surf = _host(r.cast_surface(_up(torch, c["rays"]), want=("pos", "ns"))[1])
+    r.close()
+    hit = ref["hit_id"].reshape(-1, 2)[:, 0] >= 0
+    assert np.array_equal(surf["pos"][:, 3] != 0, hit) and hit.sum() > 3000
+    axis = int(np.flatnonzero(view[2, :3])[0])
+    depth = (np.float32(-view[2, axis]) * surf["pos"][:, axis])[hit]       # -(view * pos).z with a row of 0 and +-1: no rounding anywhere
+    assert np.array_equal(depth.view(np.uint32), np.ascontiguousarray(ref["depth"].reshape(-1)[hit], np.float32).view(np.uint32)), "depth is not pos's component, bit for bit"
+    keep = hit & ~c["short"]
+    err = float(np.abs(oracle_normal(view_inv, surf["ns"], np.float64) - ref["normal"].reshape(-1, 4)[:, :3].astype(np.float64))[keep].max())
+    allowed = margins()["oracle/normal"]["allowed"]["normal"]
+    print(f"[resolve] oracle normal image: worst difference {err:.3e}, allowed {allowed:.3e}")
+    assert err <= allowed
+
+
+@pytest.mark.gpu
+def test_albedo_alpha_is_what_the_cutoff_tests(R, torch, get_scene):
+    """2 (alpha): on tests/test_alpha.py's banner scene, rays from the camera towards points on the banners: with the banners' cutoff at 0.5 a closest cast returns no banner
+    hit whose resolved albedo.a is below 0.5; the same cast with cutoff 0 returns some that are"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from alpha_probe import BANNERS, banner_scene
+    sc = banner_scene(get_scene("sponza_like", 1.0))
+    rng = np.random.default_rng(5)
+    targets = []
+    for i in BANNERS:
+        p = sc.primitives[i]
+        M = np.asarray(p.model, np.float64).reshape(3, 4)
+        tri = np.asarray(p.indices).reshape(-1, 3)[rng.integers(0, p.n_tris, 342)]
+        b = rng.dirichlet((1.0, 1.0, 1.0), 342)
+        q = np.einsum("ij,ijk->ik", b, np.asarray(p.verts, np.float64)[:, :3][tri])
+        targets.append(q @ M[:, :3].T + M[:, 3])
+    targets = np.concatenate(targets)
+    rays = np.zeros((targets.shape[0], 8), np.float32)
+    o = np.asarray(sc.camera["pos"], np.float64)
+    d = targets - o
+    rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, 0.001, d / np.linalg.norm(d, axis=1, keepdims=True), 1000.0
+    r = R.renderer_for_scene(sc, (64, 64))
+    d_rays = _up(torch, rays)
+
+    def banner_alpha():
+        (tuv, ids), surf = r.cast_surface(d_rays, want=("albedo",))
+        on = torch.isin(ids[:, 0], torch.tensor(BANNERS, dtype=torch.int32, device=ids.device))
+        return surf["albedo"][on, 3].cpu().numpy()
+    opaque = banner_alpha()
+    assert opaque.size > 1000 and (opaque < 0.5).sum() > 50 and (opaque >= 0.5).sum() > 50, "the rays do not straddle the banners' holes"
+    for i in BANNERS:
+        r.models_mut()[0].set_alpha_cutoff(i, 0.5)
+    cut = banner_alpha()
+    r.close()
+    assert cut.size > 50 and (cut >= 0.5).all(), f"{int((cut < 0.5).sum())} hits got past the cutoff with a resolved alpha below it"
+
+
+def _raw_resolve(r, torch, tuv, ids, n, bufs, flags=0, stream=0):
+    """art_resolve_hits through ctypes: bufs name -> tensor | raw address | None; returns the code"""
+    from araytracingjourney_amd import _lib
+    ptr = lambda t: None if t is None else (int(t) if not hasattr(t, "data_ptr") else t.data_ptr())   # noqa: E731
+    d = _lib.ArtHitResolve(tuv_dev=ptr(tuv), ids_dev=ptr(ids), n=n, flags=flags, hip_stream=stream or None)
+    for k, t in bufs.items():
+        setattr(d, k + "_dev", ptr(t))
+    return r._L.art_resolve_hits(r._ctx, C.byref(d))
+
+
+@pytest.mark.gpu
+def test_hand_made_records(R, torch, orc, scenes, get_scene):
+    """3: 67 records (the last wave partly full): hits of a real cast interleaved with (-1, -1), primitive = num_primitives, 2^31 - 1 and -7, triangle = n_tri and -1,
+    u = NaN and v = +inf -- every bad record gives the zero record, every valid one the witness's; then n = 1, and n = 0, which writes nothing and takes null inputs"""
+    from araytracingjourney_amd import _lib
+    key = "cornell/random"
+    c = case(key, orc, scenes, get_scene)
+    r = R.renderer_for_scene(c["scene"], (64, 64))
+    n_prims, n_tri = r.stats()["num_primitives"], [p.n_tris for p in c["scene"].primitives]
+    rows = np.flatnonzero(c["ids"][:, 0] >= 0)[:67]
+    tuv, ids = c["tuv"][rows].copy(), c["ids"][rows].copy()
+    bad = {}
+    for j, (at, what) in enumerate(zip(range(1, 67, 8), ["miss", "prim=n", "prim=max", "prim=-7", "tri=n_tri", "tri=-1", "u=nan", "v=inf"])):
+        bad[at] = what
+        if what == "miss": ids[at] = (-1, -1)
+        elif what == "prim=n": ids[at, 0] = n_prims
+        elif what == "prim=max": ids[at, 0] = 2 ** 31 - 1
+        elif what == "prim=-7": ids[at, 0] = -7
+        elif what == "tri=n_tri": ids[at, 1] = n_tri[ids[at, 0]]
+        elif what == "tri=-1": ids[at, 1] = -1
+        elif what == "u=nan": tuv[at, 1] = np.nan
+        elif what == "v=inf": tuv[at, 2] = np.inf
+    assert len(bad) == 8
+    surf = _host(r.resolve_hits(_up(torch, tuv), _up(torch, ids)))
+    torch.cuda.synchronize()
+    good = np.array([k not in bad for k in range(67)])
+    for k, a in surf.items():
+        assert not np.ascontiguousarray(a[~good]).view(np.uint32).any(), f"{k}: a bad record is not the zero record: {[bad[i] for i in np.flatnonzero(~good) if a[i].any()]}"
+    sub = dict(c, ids=c["ids"][rows][good], short=c["short"][rows][good], w64={k: v[rows][good] for k, v in c["w64"].items()})
+    _check({k: a[good] for k, a in surf.items()}, sub, margins()[key]["allowed"], "67 hand-made records")
+    one = _host(r.resolve_hits(_up(torch, tuv[:1]), _up(torch, ids[:1])))
+    torch.cuda.synchronize()
+    assert all(np.array_equal(one[k].view(np.uint32), surf[k][:1].view(np.uint32)) for k in OUTPUTS), "n = 1 differs from record 0 of n = 67"
+    keep = torch.full((4, 4), SENTINEL, dtype=torch.float32, device="cuda")
+    assert _raw_resolve(r, torch, None, None, 0, dict(pos=keep)) == _lib.ART_OK
+    empty = r.resolve_hits(torch.empty((0, 4), dtype=torch.float32, device="cuda"), torch.empty((0, 2), dtype=torch.int32, device="cuda"))
+    r.cast_sync(); torch.cuda.synchronize()
+    assert (keep == SENTINEL).all() and all(v.shape == (0, OUTPUTS[k]) for k, v in empty.items())
+    r.close()
+
+
+@pytest.mark.gpu
+def test_multi_hit_records(R, torch, orc, scenes, get_scene):
+    """4: cast_rays_multi(K = 4) on Cornell with random_rays(1024, 7), the (n, 4) records resolved in one call: every record j < count is the witness's, every tail record is
+    zero; alpha summed front to back in torch with no scene data on the host (the docstring's example)"""
+    key = "cornell/multi4"
+    c = case(key, orc, scenes, get_scene)
+    r = R.renderer_for_scene(c["scene"], (64, 64))
+    tuv, ids, count = r.cast_rays_multi(_up(torch, c["rays"]), 4)
+    surf = r.resolve_hits(tuv, ids)
+    a = surf["albedo"][..., 3]
+    through = torch.cumprod(1 - a, dim=1)[:, -1]
+    total = a.sum(dim=1)
+    torch.cuda.synchronize()
+    assert np.array_equal(ids.cpu().numpy().reshape(-1, 2), c["ids"]) and np.array_equal(count.cpu().numpy(), c["count"])
+    assert all(v.shape == (1024, 4, OUTPUTS[k]) for k, v in surf.items())
+    _check(_host(surf), c, margins()[key]["allowed"], key)
+    tail = np.arange(4)[None, :] >= c["count"][:, None]
+    assert tail.any() and (~tail).any()
+    for k, v in _host(surf).items():
+        assert not np.ascontiguousarray(v[tail]).view(np.uint32).any(), f"{k}: a tail record is not zero"
+    # Cornell is opaque: every hit record has alpha 1, so the sum counts them and nothing gets through a ray that hit
+    assert np.allclose(total.cpu().numpy(), c["count"], atol=1e-5) and np.array_equal(through.cpu().numpy() < 0.5, c["count"] > 0)
+    r.close()
+
+
+@pytest.mark.gpu
+def test_output_selection_and_errors(R, torch, orc, scenes, get_scene):
+    """5: six buffers full of a sentinel, three of them not given: the three given are written, the others keep the sentinel; all six NULL, pos_dev at base + 4, flags = 1 are
+    ART_E_INVALID and write nothing; before art_scene_build the call is ART_E_STATE"""
+    from araytracingjourney_amd import _lib
+    key = "cornell/random"
+    c = case(key, orc, scenes, get_scene)
+    r = R.renderer_for_scene(c["scene"], (64, 64))
+    n = c["ids"].shape[0]
+    tuv, ids = _up(torch, c["tuv"]), _up(torch, c["ids"])
+    bufs = {k: torch.full((n + 1, w), SENTINEL, dtype=torch.float32, device="cuda") for k, w in OUTPUTS.items()}
+    given = ("ng", "uv", "orm")
+    assert _raw_resolve(r, torch, tuv, ids, n, {k: bufs[k] for k in given}) == _lib.ART_OK
+    r.cast_sync()
+    got = {k: v.cpu().numpy() for k, v in bufs.items()}
+    for k in OUTPUTS:
+        assert (got[k][n] == SENTINEL).all(), f"{k}: written past n records"
+        if k not in given:
+            assert (got[k] == SENTINEL).all(), f"{k} was not given and was written"
+    _check({k: got[k][:n] for k in given}, c, margins()[key]["allowed"], "three of six outputs")
+    fresh = {k: torch.full((n + 1, w), SENTINEL, dtype=torch.float32, device="cuda") for k, w in OUTPUTS.items()}
+    assert _raw_resolve(r, torch, tuv, ids, n, {}) == _lib.ART_E_INVALID
+    assert _raw_resolve(r, torch, tuv, ids, n, dict(pos=fresh["pos"].data_ptr() + 4)) == _lib.ART_E_INVALID
+    assert _raw_resolve(r, torch, tuv, ids, n, dict(pos=fresh["pos"], uv=fresh["uv"].data_ptr() + 4)) == _lib.ART_E_INVALID
+    assert _raw_resolve(r, torch, tuv, ids, n, dict(pos=fresh["pos"]), flags=1) == _lib.ART_E_INVALID
+    assert _raw_resolve(r, torch, tuv.data_ptr() + 8, ids, n, dict(pos=fresh["pos"])) == _lib.ART_E_INVALID
+    assert _raw_resolve(r, torch, tuv, None, n, dict(pos=fresh["pos"])) == _lib.ART_E_INVALID
+    r.cast_sync(); torch.cuda.synchronize()
+    assert all((v == SENTINEL).all() for v in fresh.values()), "a refused call wrote something"
+    r.close()
+    r2 = R.Renderer((64, 64))
+    r2.add_model(c["scene"].primitives)
+    assert _raw_resolve(r2, torch, tuv, ids, n, dict(pos=fresh["pos"])) == _lib.ART_E_STATE
+    with pytest.raises(_lib.ArtError):
+        r2.resolve_hits(tuv, ids)
+    with pytest.raises(ValueError):
+        r2.resolve_hits(tuv, ids, want=("pos", "colour"))
+    r2.close()
+
+
+@pytest.mark.gpu
+def test_the_scene_as_of_the_call(R, torch, orc, scenes, get_scene):
+    """6: a scene built with ART_FLAG_DYNAMIC_SCENE.  art_scene_set_model_matrix, then cast + resolve with no art_trace in between: the witness at the new pose;
+    art_scene_set_vertices with new positions, normals and uvs, cast + resolve: the witness with the new vertices; after art_scene_set_primitive_enabled(p, 0) records that name
+    p, taken before, still resolve; after a primitive is added without a build the call is ART_E_STATE; ArtStats.rebuilds stays 0"""
+    from araytracingjourney_amd import _lib
+    base = warped_scene(scenes)
+    r = R.Renderer((64, 64), dynamic_scene=True, tuning=dict(refit_rebuild_ratio=-1.0))
+    models = [r.add_model([p]) and r.models_mut()[-1] for p in base.primitives]
+    r.prepare_first_frame()
+    moved = case("warped-moved/random", orc, scenes, get_scene)
+    models[1].set_model_matrix(moved["scene"].primitives[1].model)
+    _cast_and_check(R, torch, moved, margins()["warped-moved/random"]["allowed"], "after a move", r=r)
+    deformed = case("warped-deformed/random", orc, scenes, get_scene)
+    models[0].set_vertices(0, deformed["scene"].primitives[0].verts)
+    _cast_and_check(R, torch, deformed, margins()["warped-deformed/random"]["allowed"], "after a deformation", r=r)
+    tuv, ids = _up(torch, deformed["tuv"]), _up(torch, deformed["ids"])
+    assert (deformed["ids"][:, 0] == 1).sum() > 100
+    check = lambda what: _check(_host(r.resolve_hits(tuv, ids)), deformed, margins()["warped-deformed/random"]["allowed"], what)   # noqa: E731
+    assert r._L.art_scene_set_primitive_enabled(r._ctx, 1, 0) == _lib.ART_OK and not r.needs_build()
+    check("records of a primitive that left by residency")
+    assert (r.cast_rays(_up(torch, deformed["rays"]))[1][:, 0] != 1).all(), "the disabled primitive is still hit"
+    st = r.stats()
+    assert st["rebuilds"] == 0 and st["refits"] >= 2
+    r.add_model([base.primitives[0]])
+    assert r.needs_build() and _raw_resolve(r, torch, tuv, ids, ids.shape[0], dict(pos=torch.empty((ids.shape[0], 4), device="cuda"))) == _lib.ART_E_STATE
+    assert r.stats()["rebuilds"] == 0
+    r.close()
+
+
+@pytest.mark.gpu
+def test_streams_counts_and_the_pool(R, torch, orc, scenes, get_scene):
+    """7: cast -> resolve -> a torch reduction on a non-default stream with nothing in between, right after one stream.synchronize(); with hip_stream NULL art_cast_sync is
+    the fence; art_cast_counts' casts and rays do not count resolves; 40 resolves back to back (more than ART_CAST_POOL in flight) all complete"""
+    from araytracingjourney_amd import _lib
+    key = "cornell/random"
+    c = case(key, orc, scenes, get_scene)
+    r = R.renderer_for_scene(c["scene"], (64, 64))
+    d_rays = _up(torch, c["rays"])
+    hit = c["ids"][:, 0] >= 0
+    want_sum = c["w64"]["pos"][:, :3].sum(0)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        (tuv, ids), surf = r.cast_surface(d_rays, want=("pos",))
+        total = surf["pos"].double().sum(0)
+    s.synchronize()
+    total = total.cpu().numpy()
+    assert total[3] == hit.sum() and np.abs(total[:3] - want_sum).max() <= hit.sum() * margins()[key]["allowed"]["pos"]
+    before = r.cast_counts()
+    pos = torch.full((c["ids"].shape[0], 4), SENTINEL, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    assert _raw_resolve(r, torch, tuv, ids, c["ids"].shape[0], dict(pos=pos), stream=0) == _lib.ART_OK    # the context's cast stream
+    r.cast_sync()
+    assert np.array_equal(pos.cpu().numpy().view(np.uint32), surf["pos"].cpu().numpy().view(np.uint32))
+    outs = [r.resolve_hits(tuv, ids, want=("pos", "uv")) for _ in range(40)]
+    assert _lib.ART_CAST_POOL < 40
+    r.cast_sync()
+    after = r.cast_counts()
+    assert (after["casts"], after["rays"]) == (before["casts"], before["rays"]) and after["host_waits"] >= before["host_waits"]
+    ref = surf["pos"].cpu().numpy().view(np.uint32)
+    assert all(np.array_equal(o["pos"].cpu().numpy().view(np.uint32), ref) for o in outs)
+    r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["fast_build", "rebuilt"])
+def test_both_builders(R, torch, orc, scenes, get_scene, how):
+    """8: test 1's Cornell case on an ART_FLAG_FAST_BUILD tree (the LBVH alone), and after a rebuild the cost rule starts by itself (refit_rebuild_ratio so low that the first
+    move rebuilds): the gid -> leaf table is the new tree's, and the records resolve to the witness where the primitive is now"""
+    if how == "fast_build":
+        key = "cornell/random"
+        _cast_and_check(R, torch, case(key, orc, scenes, get_scene), margins()[key]["allowed"], how, fast_build=True).close()
+        return
+    c0, c1 = case("cornell/random", orc, scenes, get_scene), case("cornell-moved/random", orc, scenes, get_scene)
+    r = R.Renderer((64, 64), tuning=dict(refit_rebuild_ratio=1e-6))
+    models = [r.add_model([p]) and r.models_mut()[-1] for p in c0["scene"].primitives]
+    r.prepare_first_frame()
+    _cast_and_check(R, torch, c0, margins()["cornell/random"]["allowed"], "before the move", r=r)
+    lb0 = r.get_lbvh()["leaf_gid"].copy()
+    models[0].set_model_matrix(CORNELL_MOVE)
+    _cast_and_check(R, torch, c1, margins()["cornell-moved/random"]["allowed"], "after the rebuild", r=r)
+    assert r.stats()["rebuilds"] == 1
+    assert not np.array_equal(r.get_lbvh()["leaf_gid"], lb0), "the move did not change the leaf order: the test shows nothing about the table"
+    r.close()
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["--write-margins"]:
+        sys.path.insert(0, ROOT)
+        write_margins()
