@@ -1,0 +1,224 @@
+// art_cast.hip -- rays in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits) and the queries of include/art_parity.h
+// over them: the host side of the ring of cast blocks (CastState, art_context.h).  Every use of a CastState / CastBlock field is in this file; the kernels are
+// art_trace.hip's and art_resolve.hip's.
+#include "art_context.h"
+
+// the first cast of a context: its stream (counted against the budget beside kMaxFrameSlots), the cursor blocks and their events
+static int32_t cast_setup(ArtContext *c) {
+    CastState &K = c->cast;
+    if (K.stream) return ART_OK;
+    uint32_t *cur = nullptr;
+    HIPC(hipMalloc(&cur, (size_t)ART_CAST_POOL * kCastCursorWords * 4));
+    hipError_t e = hipSuccess;
+    for (CastBlock &b : K.block) if (e == hipSuccess && !b.ev) e = hipEventCreateWithFlags(&b.ev, hipEventDisableTiming);
+    hipStream_t s = nullptr;
+    if (e == hipSuccess) e = acquire_stream(c->device, &s);
+    if (e != hipSuccess) { (void)hipFree(cur); return hipfail(e, "art_cast_rays: the cast stream, cursor blocks and events"); }   // (events made so far stay: art_destroy)
+    K.cursors = cur; K.stream = s;
+    return ART_OK;
+}
+// every cast enqueued so far has finished, on whichever stream it runs
+static int32_t cast_wait_all(ArtContext *c) {
+    for (CastBlock &b : c->cast.block) if (b.set) { HIPC(hipEventSynchronize(b.ev)); b.set = false; }
+    return ART_OK;
+}
+int32_t art::cast_sync(ArtContext *c) {
+    int32_t r = cast_wait_all(c); if (r) return r;
+    if (c->cast.stream) HIPC(hipStreamSynchronize(c->cast.stream));   // (a refit a cast put there, the zeroing of a block)
+    return ART_OK;
+}
+int32_t art::cast_drain(ArtContext *c) {
+    if (!c->cast.stream) return ART_OK;   // nothing was ever cast
+    int32_t r = use_device(c); if (r) return r;
+    return cast_wait_all(c);
+}
+// the casts that hold `version` (scene_refresh is about to rewrite it): the host waits for those still running -- one CastState::host_waits per call that waited
+int32_t art::cast_wait_version(ArtContext *c, uint32_t version) {
+    bool waited = false;
+    for (CastBlock &b : c->cast.block) if (b.set && b.version == version) {
+        if (hipEventQuery(b.ev) != hipSuccess) { (void)hipGetLastError(); HIPC(hipEventSynchronize(b.ev)); waited = true; }
+        b.set = false;
+    }
+    if (waited) c->cast.host_waits++;
+    return ART_OK;
+}
+void art::cast_release(ArtContext *c) {
+    CastState &K = c->cast;
+    (void)cast_wait_all(c);   // casts on callers' streams too
+    for (CastBlock &b : K.block) if (b.ev) (void)hipEventDestroy(b.ev);
+    if (K.cursors) (void)hipFree(K.cursors);
+    K.q_rays.release(); K.q_out.release();
+    if (K.stream) release_stream(c->device, K.stream);
+}
+// The host side every enqueue on the ring shares -- a cast's and a resolve's (art_resolve_hits traces nothing, but it reads a version of the scene and has to be waited
+// for like a cast).  cast_claim: the scene as of the call, the stream, the version to read (an event wait on that stream while its refit may still run) and the next ring
+// block, free.  cast_commit: the block's event behind what the caller launched, and the version it holds.
+static int32_t cast_claim(ArtContext *c, hipStream_t user, hipStream_t *stream, uint32_t *version, uint32_t *block) {
+    int32_t r = use_device(c); if (r) return r;
+    r = cast_setup(c); if (r) return r;
+    CastState &K = c->cast;
+    if (c->xform_dirty) { r = scene_refresh(c, ~0u, K.stream); if (r) return r; }   // the scene as of the call: the refit in front of the cast (past the cost threshold: a rebuild)
+    r = ensure_wide(c, true); if (r) return r;
+    hipStream_t s = user ? user : K.stream;
+    const uint32_t ver = c->as_cur;
+    r = as_wait_ready(c, ver, s, ~0u); if (r) return r;   // the refit that wrote this version may still run: an event wait on the cast's stream, nothing on the host
+    const uint32_t bi = K.next % ART_CAST_POOL;
+    CastBlock &B = K.block[bi];
+    if (B.set) {   // the ring of cursor blocks is lapped: its oldest cast has to be over
+        if (hipEventQuery(B.ev) != hipSuccess) { (void)hipGetLastError(); HIPC(hipEventSynchronize(B.ev)); K.host_waits++; }
+        B.set = false;
+    }
+    *stream = s; *version = ver; *block = bi;
+    return ART_OK;
+}
+static int32_t cast_commit(ArtContext *c, uint32_t bi, uint32_t ver, hipStream_t s) {
+    CastState &K = c->cast;
+    CastBlock &B = K.block[bi];
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(B.ev, s));
+    B.set = true; B.version = ver; K.next++;
+    return ART_OK;
+}
+// Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
+// max_hits > 0: art_cast_rays_multi's cast (any false; hit = its count bytes, or null) -- the same blocks, version hold, events and refit, another kernel.
+static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0) {
+    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
+    int32_t r = cast_claim(c, user, &s, &ver, &bi); if (r) return r;
+    CastState &K = c->cast;
+    uint32_t *cursors = K.cursors + (size_t)bi * kCastCursorWords;
+    HIPC(hipMemsetAsync(cursors, 0, kCastCursorWords * 4, s));
+    const AsPtrs as = as_ptrs(c, ver);
+    CastArgs a{};
+    a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
+    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = max_hits ? nullptr : (uint8_t *)hit; a.cursors = cursors;
+    a.max_hits = max_hits; a.count = max_hits ? (uint8_t *)hit : nullptr;
+    a.tune = c->trace_tune();
+    a.alpha = c->alpha_live || cull == 0u;   // the filtered instances run while the scene needs them or the mask is 0 (such rays see nothing, and no leaf bit says so)
+    a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p; a.cull = cull;
+    launch_cast(a, s);
+    r = cast_commit(c, bi, ver, s); if (r) return r;
+    K.casts++; K.rays += n;
+    if (block) *block = bi;
+    return ART_OK;
+}
+
+// a buffer of n records: null only when there are none (n = 0 touches nothing: a null buffer is one of no rays), and aligned; an output that may be null (not wanted): aligned
+static bool misaligned(const void *p, size_t align) { return ((uintptr_t)p & (align - 1)) != 0; }
+static bool bad(const void *p, size_t align, uint32_t n) { return (p == nullptr && n != 0u) || misaligned(p, align); }
+// what art_cast_rays and art_cast_rays_multi ask of the fields their descriptors share
+static int32_t cast_check(const char *who, uint32_t flags, uint32_t cull_mask, uint32_t n, const void *rays_dev) {
+    if (flags != 0u) return fail(ART_E_INVALID, std::string(who) + ": flags: must be 0");
+    if (cull_mask > 0xFFu) return fail(ART_E_INVALID, std::string(who) + ": cull_mask: above 0xFF");
+    if (n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, std::string(who) + ": n: above ART_CAST_MAX_RAYS");
+    if (bad(rays_dev, 16, n)) return fail(ART_E_INVALID, std::string(who) + ": rays_dev: null or not 16-byte aligned");
+    return ART_OK;
+}
+
+extern "C" {
+
+int32_t art_cast_rays(ArtContext *c, const ArtRayCast *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_cast_rays: null argument");
+    if (d->kind != ART_CAST_CLOSEST && d->kind != ART_CAST_ANY) return fail(ART_E_INVALID, "art_cast_rays: kind: ART_CAST_CLOSEST or ART_CAST_ANY");
+    int32_t r = cast_check("art_cast_rays", d->flags, d->cull_mask, d->n, d->rays_dev); if (r) return r;
+    const bool any = d->kind == ART_CAST_ANY;
+    if (any) {
+        if (d->tuv_dev || d->ids_dev) return fail(ART_E_INVALID, "art_cast_rays: tuv_dev / ids_dev: must be NULL for ART_CAST_ANY");
+        if (bad(d->hit_dev, 1, d->n)) return fail(ART_E_INVALID, "art_cast_rays: hit_dev: null");
+    } else {
+        if (d->hit_dev) return fail(ART_E_INVALID, "art_cast_rays: hit_dev: must be NULL for ART_CAST_CLOSEST");
+        if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_cast_rays: tuv_dev: null or not 16-byte aligned");
+        if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_cast_rays: ids_dev: null or not 8-byte aligned");
+    }
+    if (!c->built) return fail(ART_E_STATE, "art_cast_rays: scene not built (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    return cast_enqueue(c, d->rays_dev, d->n, any, d->cull_mask, d->tuv_dev, d->ids_dev, d->hit_dev, (hipStream_t)d->hip_stream, nullptr);
+}
+
+int32_t art_cast_rays_multi(ArtContext *c, const ArtRayCastMulti *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_cast_rays_multi: null argument");
+    if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return fail(ART_E_INVALID, "art_cast_rays_multi: max_hits: 1 .. ART_CAST_MAX_HITS");
+    int32_t r = cast_check("art_cast_rays_multi", d->flags, d->cull_mask, d->n, d->rays_dev); if (r) return r;
+    if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_cast_rays_multi: tuv_dev: null or not 16-byte aligned");
+    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_cast_rays_multi: ids_dev: null or not 8-byte aligned");
+    if (!c->built) return fail(ART_E_STATE, "art_cast_rays_multi: scene not built (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    return cast_enqueue(c, d->rays_dev, d->n, false, d->cull_mask, d->tuv_dev, d->ids_dev, d->count_dev, (hipStream_t)d->hip_stream, nullptr, d->max_hits);
+}
+
+// ---- the surface behind hit records (include/art.h: art_resolve_hits) ---------------------------------------------------------------------------
+// A resolve goes through the casts' ring: it claims a block (whose cursors it has no use for), holds the version it reads and leaves the block's event behind its
+// launch, so art_cast_sync, sync_all and scene_refresh wait for it where they wait for casts.  It is not counted as a cast: it traces nothing.
+int32_t art_resolve_hits(ArtContext *c, const ArtHitResolve *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_resolve_hits: null argument");
+    if (d->flags != 0u) return fail(ART_E_INVALID, "art_resolve_hits: flags: must be 0");
+    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_resolve_hits: n: above ART_CAST_MAX_RAYS");
+    if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_resolve_hits: tuv_dev: null or not 16-byte aligned");
+    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_resolve_hits: ids_dev: null or not 8-byte aligned");
+    if (misaligned(d->pos_dev, 16) || misaligned(d->ng_dev, 16) || misaligned(d->ns_dev, 16) || misaligned(d->albedo_dev, 16) || misaligned(d->orm_dev, 16))
+        return fail(ART_E_INVALID, "art_resolve_hits: pos_dev / ng_dev / ns_dev / albedo_dev / orm_dev: not 16-byte aligned");
+    if (misaligned(d->uv_dev, 8)) return fail(ART_E_INVALID, "art_resolve_hits: uv_dev: not 8-byte aligned");
+    if (d->n != 0u && !d->pos_dev && !d->ng_dev && !d->ns_dev && !d->uv_dev && !d->albedo_dev && !d->orm_dev) return fail(ART_E_INVALID, "art_resolve_hits: no output buffer given");
+    if (!c->built) return fail(ART_E_STATE, "art_resolve_hits: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
+    int32_t r = cast_claim(c, (hipStream_t)d->hip_stream, &s, &ver, &bi); if (r) return r;
+    const AsPtrs as = as_ptrs(c, ver);
+    ResolveArgs a{};
+    a.tuv = (const float4 *)d->tuv_dev; a.ids = (const int2 *)d->ids_dev; a.n = d->n;
+    a.n_prims = (uint32_t)c->h_dev_prims.size(); a.T = c->T;   // (after cast_claim: a rebuild the cost rule started made them anew, with the table)
+    a.prims = as.prims; a.shade = as.shade; a.gid_leaf = c->bvh.gid_leaf; a.tex_pool = c->d_tex.p;
+    a.pos = (float4 *)d->pos_dev; a.ng = (float4 *)d->ng_dev; a.ns = (float4 *)d->ns_dev; a.uv = (float2 *)d->uv_dev; a.albedo = (float4 *)d->albedo_dev; a.orm = (float4 *)d->orm_dev;
+    launch_resolve(a, s);
+    return cast_commit(c, bi, ver, s);
+}
+
+int32_t art_cast_sync(ArtContext *c) {
+    if (!c) return fail(ART_E_INVALID, "art_cast_sync: null context");
+    return cast_drain(c);
+}
+
+int32_t art_cast_counts(ArtContext *c, uint64_t *casts, uint64_t *rays, uint64_t *host_waits) {
+    if (!c) return fail(ART_E_INVALID, "art_cast_counts: null context");
+    if (casts) *casts = c->cast.casts;
+    if (rays) *rays = c->cast.rays;
+    if (host_waits) *host_waits = c->cast.host_waits;
+    return ART_OK;
+}
+
+// The queries of include/art_parity.h: host wrappers over the cast -- the rays into a device buffer the context keeps (it only grows), one cast on the context's cast stream,
+// that cast's event as the fence, the records back.  Frames in flight are not waited for.
+static int32_t query_by_cast(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, bool any, float *tuv, int32_t *ids, uint8_t *hit, const char *who) {
+    if (n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, std::string(who) + ": more than ART_CAST_MAX_RAYS rays");
+    int32_t r = use_device(c); if (r) return r;
+    CastState &K = c->cast;
+    const size_t out_bytes = any ? (size_t)n : (size_t)n * 24;   // t,u,v,0 of every ray, then the id pairs
+    HIPC(K.q_rays.ensure((size_t)n * 2)); HIPC(K.q_out.ensure(out_bytes));   // (the cast that read them last was fenced by its query)
+    HIPC(hipMemcpy(K.q_rays.p, rays, (size_t)n * 32, hipMemcpyHostToDevice));
+    uint32_t bi = 0;
+    r = cast_enqueue(c, K.q_rays.p, n, any, cull_mask, any ? nullptr : K.q_out.p, any ? nullptr : K.q_out.p + (size_t)n * 16, any ? K.q_out.p : nullptr, nullptr, &bi);
+    if (r) return r;
+    HIPC(hipEventSynchronize(K.block[bi].ev)); K.block[bi].set = false;
+    if (any) HIPC(hipMemcpy(hit, K.q_out.p, n, hipMemcpyDeviceToHost));
+    else { HIPC(hipMemcpy(tuv, K.q_out.p, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(ids, K.q_out.p + (size_t)n * 16, (size_t)n * 8, hipMemcpyDeviceToHost)); }
+    return ART_OK;
+}
+int32_t art_query_closest(ArtContext *c, const float *rays, uint32_t n, float *tuv, int32_t *ids) { return art_query_closest_masked(c, rays, n, 0xFFu, tuv, ids); }
+// (the rays' cull mask, DESIGN.md 3.4: 0xFF is art_query_closest; the filtered tracer instances run while the scene needs them or the mask is 0)
+int32_t art_query_closest_masked(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, float *tuv, int32_t *ids) {
+    if (!c || (n && (!rays || !tuv || !ids))) return fail(ART_E_INVALID, "art_query_closest: null argument");
+    if (cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_query_closest_masked: cull_mask: above 0xFF");
+    if (!c->built) return fail(ART_E_STATE, "art_query_closest: scene not built");
+    if (n == 0) return ART_OK;
+    return query_by_cast(c, rays, n, cull_mask, false, tuv, ids, nullptr, "art_query_closest");
+}
+
+int32_t art_query_any(ArtContext *c, const float *rays, uint32_t n, uint8_t *hit) { return art_query_any_masked(c, rays, n, 0xFFu, hit); }
+int32_t art_query_any_masked(ArtContext *c, const float *rays, uint32_t n, uint32_t cull_mask, uint8_t *hit) {
+    if (!c || (n && (!rays || !hit))) return fail(ART_E_INVALID, "art_query_any: null argument");
+    if (cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_query_any_masked: cull_mask: above 0xFF");
+    if (!c->built) return fail(ART_E_STATE, "art_query_any: scene not built");
+    if (n == 0) return ART_OK;
+    return query_by_cast(c, rays, n, cull_mask, true, nullptr, nullptr, hit, "art_query_any");
+}
+
+} // extern "C"
