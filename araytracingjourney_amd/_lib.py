@@ -90,6 +90,12 @@ class ArtHitResolve(C.Structure):
                 ("albedo_dev", C.c_void_p), ("orm_dev", C.c_void_p), ("hip_stream", C.c_void_p), ("n", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class ArtPointQuery(C.Structure):
+    """one art_closest_points: points and radii in, distance / barycentrics, ids and (optionally) the nearest points out"""
+    _fields_ = [("points_dev", C.c_void_p), ("duv_dev", C.c_void_p), ("ids_dev", C.c_void_p), ("point_dev", C.c_void_p), ("hip_stream", C.c_void_p),
+                ("n", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ArtLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "frames_in_flight", "frames_per_launch", "shard_rank", "shard_count", "tiles_owned", "tiles_padded",
                                           "tile_bytes", "reserved")]
@@ -141,6 +147,7 @@ SYMBOLS = {
     "art_cast_rays": (_I32, [_P, _P]),
     "art_cast_rays_multi": (_I32, [_P, _P]),
     "art_resolve_hits": (_I32, [_P, _P]),
+    "art_closest_points": (_I32, [_P, _P]),
     "art_cast_sync": (_I32, [_P]),
     "art_cast_counts": (_I32, [_P, _P, _P, _P]),
     "art_present": (_I32, [_P]),

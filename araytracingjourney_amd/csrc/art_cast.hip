@@ -1,4 +1,4 @@
-// art_cast.hip -- rays in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points; DESIGN.md 3.5 .. 3.8) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h).  Every use of a CastState / CastBlock field is in this file; the kernels are
 // art_trace.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -169,6 +169,36 @@ int32_t art_resolve_hits(ArtContext *c, const ArtHitResolve *d) {
     a.prims = as.prims; a.shade = as.shade; a.gid_leaf = c->bvh.gid_leaf; a.tex_pool = c->d_tex.p;
     a.pos = (float4 *)d->pos_dev; a.ng = (float4 *)d->ng_dev; a.ns = (float4 *)d->ns_dev; a.uv = (float2 *)d->uv_dev; a.albedo = (float4 *)d->albedo_dev; a.orm = (float4 *)d->orm_dev;
     launch_resolve(a, s);
+    return cast_commit(c, bi, ver, s);
+}
+
+// ---- nearest surface points (include/art.h: art_closest_points) ---------------------------------------------------------------------------------
+// A batch of queries goes through the casts' ring like a cast -- claim, the block's cursors zeroed on its stream, the launch, commit -- and like a resolve it is not
+// counted as a cast: it traces no ray.
+int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_closest_points: null argument");
+    if (d->flags != 0u) return fail(ART_E_INVALID, "art_closest_points: flags: must be 0");
+    if (d->reserved != 0u) return fail(ART_E_INVALID, "art_closest_points: reserved: must be 0");
+    if (d->cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_closest_points: cull_mask: above 0xFF");
+    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_closest_points: n: above ART_CAST_MAX_RAYS");
+    if (bad(d->points_dev, 16, d->n)) return fail(ART_E_INVALID, "art_closest_points: points_dev: null or not 16-byte aligned");
+    if (bad(d->duv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_closest_points: duv_dev: null or not 16-byte aligned");
+    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_closest_points: ids_dev: null or not 8-byte aligned");
+    if (misaligned(d->point_dev, 16)) return fail(ART_E_INVALID, "art_closest_points: point_dev: not 16-byte aligned");
+    if (!c->built) return fail(ART_E_STATE, "art_closest_points: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
+    int32_t r = cast_claim(c, (hipStream_t)d->hip_stream, &s, &ver, &bi); if (r) return r;
+    uint32_t *cursors = c->cast.cursors + (size_t)bi * kCastCursorWords;
+    HIPC(hipMemsetAsync(cursors, 0, kCastCursorWords * 4, s));
+    const AsPtrs as = as_ptrs(c, ver);
+    ClosestArgs a{};
+    a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
+    a.points = (const float4 *)d->points_dev; a.n = d->n; a.duv = (float4 *)d->duv_dev; a.ids = (int2 *)d->ids_dev; a.point = (float4 *)d->point_dev; a.cursors = cursors;
+    a.tune = c->trace_tune();
+    a.filter = c->alpha_live || d->cull_mask == 0u;   // the casts' condition: while the scene has a mask or a cutoff (the leaf bits mark both), or the queries see nothing
+    a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.cull = d->cull_mask;
+    launch_closest(a, s);
     return cast_commit(c, bi, ver, s);
 }
 

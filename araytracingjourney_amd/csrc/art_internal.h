@@ -305,6 +305,17 @@ struct CastArgs {
 };
 constexpr uint32_t kCastCursorWords = 8 * 32;           // eight per-XCD cursors, a 128-byte line each
 void launch_cast(const CastArgs &c, hipStream_t s);
+// One batch of nearest-point queries (art_closest_points): points[i] = p.xyz, r; duv[i] = d,u,v,0 and ids[i] as a closest cast's -- a miss is r,0,0,0 and
+// -1,-1; point (optional) = the surface point, w = 1 (a miss: zeros).  filter: the instance with the visibility masks (CastArgs::alpha's condition).
+struct ClosestArgs {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *points; uint32_t n;
+    float4 *duv; int2 *ids; float4 *point;
+    uint32_t *cursors;                                  // a cast's cursor block, zeroed in front of the launch
+    TraceTune tune;
+    bool filter; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;
+};
+void launch_closest(const ClosestArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
 struct ResolveArgs {

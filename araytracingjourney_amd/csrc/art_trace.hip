@@ -1203,6 +1203,205 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMA
     pooled_trace<kCastLds, false, ALPHA, CastMultiK, CastMultiSource<KMAX>, TravMulti<KMAX, kCastLds, ALPHA>>(a, CastMultiSource<KMAX>{a});
 }
 
+// ---- nearest surface points (art_closest_points) ------------------------------------------------------------------------------------------------
+// A query is a point and a radius, not a ray: the pooled loop's ray fields (inv, ood, tmin / tmax, the slab of every policy) have no meaning for it, and a query is ONE
+// 16-byte load -- nothing a pool would save.  So the walk has a loop of its own: the idle lanes of a wave read the next queries of its chunk directly (pop_chunk and the
+// cursor block are the casts').  Stack entries are pairs (reference, the child's box_d2): `limit` only ever falls, and an entry whose box has fallen behind it by the time
+// it is popped is dropped without a fetch.  Eight pairs a lane in LDS (4 KB a wave: 40 waves fit a CU's 160 KB, more than its 32 slots); deeper entries spill to scratch
+// as references alone.
+// No fmaf in anything that decides a record: d2_tri, box_d2 of a triangle and the point are restated by numpy float32 bit for bit (tests/np_closest.py).
+__device__ __forceinline__ float dotp(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 crossp(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+// |w - (u e1 + v e2)|^2: the one distance every feature is measured by, and the point art_closest_points reports
+__device__ __forceinline__ float tri_uv_d2(V3 w, V3 e1, V3 e2, float u, float v) {
+    const float dx = w.x - (u * e1.x + v * e2.x), dy = w.y - (u * e1.y + v * e2.y), dz = w.z - (u * e1.z + v * e2.z);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// the parameter of the point of segment {s e, 0 <= s <= 1} nearest to w; a segment of no length is its first end point
+__device__ __forceinline__ float seg_param(V3 w, V3 e) {
+    const float den = dotp(e, e);
+    float s = dotp(w, e) / (den > 0.0f ? den : 1.0f);
+    s = den > 0.0f ? s : 0.0f;
+    s = s > 0.0f ? s : 0.0f;   // (selects, not fmaxf / fminf: a NaN becomes 0 here and in numpy.where alike)
+    return s < 1.0f ? s : 1.0f;
+}
+// d2_tri of DESIGN.md 3.8: the face where the projection falls inside it, then the edges v0v1, v0v2, v1v2 clamped; the first of the smallest wins.  +inf: no feature gave
+// a number (a triangle nowhere, a non-finite one).  u, v: barycentrics of vertices 1 and 2 of the winning point.
+__device__ __forceinline__ float tri_closest(V3 w, V3 e1, V3 e2, float &u, float &v) {
+    float best = INFINITY; u = 0.0f; v = 0.0f;
+    const V3 n = crossp(e1, e2);
+    const float nn = dotp(n, n), den = nn > 0.0f ? nn : 1.0f;
+    const float fu = dotp(crossp(w, e2), n) / den, fv = dotp(crossp(e1, w), n) / den;
+    if ((nn > 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f)) {
+        const float d = tri_uv_d2(w, e1, e2, fu, fv);
+        if (d < best) { best = d; u = fu; v = fv; }
+    }
+    const float sa = seg_param(w, e1), da = tri_uv_d2(w, e1, e2, sa, 0.0f);
+    if (da < best) { best = da; u = sa; v = 0.0f; }
+    const float sb = seg_param(w, e2), db = tri_uv_d2(w, e1, e2, 0.0f, sb);
+    if (db < best) { best = db; u = 0.0f; v = sb; }
+    const float sc = seg_param(w - e1, e2 - e1), uc = 1.0f - sc, dc = tri_uv_d2(w, e1, e2, uc, sc);
+    if (dc < best) { best = dc; u = uc; v = sc; }
+    return best;
+}
+__device__ __forceinline__ float box_d2(V3 p, float lx, float ly, float lz, float hx, float hy, float hz) {
+    const float ex = fmaxf(fmaxf(lx - p.x, p.x - hx), 0.0f), ey = fmaxf(fmaxf(ly - p.y, p.y - hy), 0.0f), ez = fmaxf(fmaxf(lz - p.z, p.z - hz), 0.0f);
+    return (ex * ex + ey * ey) + ez * ez;
+}
+struct ClosestK {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *points; float4 *duv; int2 *ids; float4 *point;   // point: may be null
+    uint32_t total, chunk, refill, leaf_batch;
+    uint32_t *cursors;        // a cast's cursor block
+    const uint32_t *bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;   // FILTER instance only: AlphaView's leaf bits, records and table; the queries' cull mask
+};
+constexpr int kClosestLds = 8;                                     // stack pairs a lane in LDS
+constexpr int kClosestOvf = kOvfStack4 + (kLdsStack - kClosestLds);   // Trav4's bound on pending siblings holds for any walk of the tree
+template <bool FILTER> struct TravPoint {
+    V3 p;
+    float limit, bu, bv;     // limit: r*r, then the best candidate's d2_eff
+    uint32_t bpos, bgid;
+    int cur, sp;
+    // (a spilled entry is the reference alone, TravBase's: pairs there would double the scratch every wave slot of the device reserves; it is visited unasked)
+    __device__ __forceinline__ void push(int ref, float d2, int2 *lds, int *ovf) {
+        if (sp < kClosestLds) lds[sp * kTraceBlock] = make_int2(ref, __float_as_int(d2)); else if (sp < kClosestLds + kClosestOvf) *(volatile int *)&ovf[sp - kClosestLds] = ref;   // (volatile: TravBase::push)
+        sp = min(sp + 1, kClosestLds + kClosestOvf);
+    }
+    // the next entry whose box is still within the limit; true: none left, the query is finished
+    __device__ __forceinline__ bool pop(int2 *lds, int *ovf) {
+        while (sp > 0) {
+            sp--;
+            if (sp >= kClosestLds) { cur = *(volatile int *)&ovf[sp - kClosestLds]; return false; }
+            const int2 e = lds[sp * kTraceBlock];
+            if (!(__int_as_float(e.y) > limit)) { cur = e.x; return false; }
+        }
+        return true;
+    }
+    __device__ __forceinline__ bool visible(const ClosestK &a, uint32_t pos) const {
+        if (!FILTER) return true;
+        if (a.cull == 0u) return false;
+        if (!((a.bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
+        const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(a.shade + pos)[8].z);
+        return (prim_vis(a.prims[prim].masked) & a.cull) != 0u;
+    }
+    __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~cur;
+        if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const float bd = box_d2(p, tc.y, tc.z, tc.w, td.x, td.y, td.z);
+        float u, v;
+        const float dt = tri_closest(p - mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), u, v);
+        if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum: fmaxf would drop a NaN
+            const float de = fmaxf(dt, bd);
+            const uint32_t gid = __float_as_uint(td.w);
+            if ((de < limit || (de == limit && gid < bgid)) && visible(a, pos)) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; }
+        }
+        return pop(lds, ovf);
+    }
+    __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
+        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
+        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
+        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
+        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
+        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
+        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        float d2[4]; bool h[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t lxq = (b.x >> (8 * i)) & 255u, hxq = (b.w >> (8 * i)) & 255u;
+            const float lx = fmaf((float)lxq, sx, ox), hx = fmaf((float)hxq, sx, ox);
+            const float ly = fmaf((float)((b.y >> (8 * i)) & 255u), sy, oy), hy = fmaf((float)((c.x >> (8 * i)) & 255u), sy, oy);
+            const float lz = fmaf((float)((b.z >> (8 * i)) & 255u), sz, oz), hz = fmaf((float)((c.y >> (8 * i)) & 255u), sz, oz);
+            d2[i] = box_d2(p, lx, ly, lz, hx, hy, hz);
+            h[i] = (lxq <= hxq) & !(d2[i] > limit);   // an inverted box (255 / 0): an absent child or a masked subtree -- a distance to it means nothing, so it is asked
+        }
+        // on with the nearest child within the limit; the others wait with their distances, the farthest at the bottom: what is popped next is the nearest of them, and
+        // the limit has fallen the most by the time the far ones come up.  (A five-comparator network over (box_d2, reference); a child that is out sorts as +inf with
+        // the absent reference, which is pushed nowhere and, should it come first, is a leaf that is nothing.  The order is speed only: the answer does not depend on it.)
+        float k[4]; int rf[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { k[i] = h[i] ? d2[i] : INFINITY; rf[i] = h[i] ? refs[i] : kAbsentChild; }
+#define ART_CSWAP(x, y) { const bool sw = k[y] < k[x]; const float tk = sw ? k[x] : k[y]; k[x] = sw ? k[y] : k[x]; k[y] = tk; const int tr_ = sw ? rf[x] : rf[y]; rf[x] = sw ? rf[y] : rf[x]; rf[y] = tr_; }
+        ART_CSWAP(0, 1) ART_CSWAP(2, 3) ART_CSWAP(0, 2) ART_CSWAP(1, 3) ART_CSWAP(1, 2)
+#undef ART_CSWAP
+#pragma unroll
+        for (int i = 3; i >= 1; i--) if (rf[i] != kAbsentChild) push(rf[i], k[i], lds, ovf);
+        if (rf[0] == kAbsentChild) return pop(lds, ovf);
+        cur = rf[0];
+        return false;
+    }
+};
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_closest(ClosestK a) {
+    __shared__ int2 stack[kClosestLds * kTraceBlock];
+    int ovf[kClosestOvf];
+    int2 *lds = &stack[threadIdx.x];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t leaf_batch = a.leaf_batch;
+    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
+    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // HW_REG_XCC_ID: speed only
+    uint32_t shards_left = 8;
+    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
+    bool exhausted = false, active = false;
+    TravPoint<FILTER> tr;
+    tr.sp = 0; tr.cur = 0;
+    float radius = 0.0f;
+    uint32_t slot = 0;
+    for (;;) {
+        const uint64_t idle = ballot64(!active);
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        if (n_idle >= a.refill) {
+            if (!exhausted && cur == end) {
+                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
+                if (got >= n_chunks) exhausted = true;
+                else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
+            }
+            if (!exhausted) {   // the idle lanes read the next queries of the chunk, one each
+                const uint32_t take = min(n_idle, end - cur);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (!active && rank < take) {
+                    const uint32_t sidx = cur + rank;
+                    const float4 q = a.points[sidx];
+                    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
+                    if (z == 0.0f && q.w == q.w && !(q.w < 0.0f)) {
+                        tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
+                        radius = q.w; slot = sidx; active = true;
+                    } else {   // a non-finite point, a NaN or negative radius: the miss record, without a walk
+                        a.duv[sidx] = make_float4(q.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1);
+                        if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                }
+                cur += take;
+            } else if (n_idle == 64u) break;
+            if (ballot64(active) == 0ull) continue;
+        }
+        bool done = false;   // pooled_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
+#pragma unroll
+        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
+            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
+        const bool on_leaf = active && !done && tr.cur < 0;
+        const uint64_t lm = ballot64(on_leaf);
+        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
+        if (done) {
+            active = false;
+            if (tr.bgid != kNoHit) {   // the ids as CastSource::finish makes them; the point from the winning triangle's record
+                const uint32_t prim = a.tri_prim[tr.bgid];
+                a.duv[slot] = make_float4(sqrtf(tr.limit), tr.bu, tr.bv, 0.f);
+                a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+                if (a.point) {
+                    const float4 *tq = reinterpret_cast<const float4 *>(a.tris + tr.bpos);
+                    const float4 ta = tq[0], tb = tq[1], tc = tq[2];
+                    a.point[slot] = make_float4(ta.x + (tr.bu * ta.w + tr.bv * tb.z), ta.y + (tr.bu * tb.x + tr.bv * tb.w), ta.z + (tr.bu * tb.y + tr.bv * tc.x), 1.0f);
+                }
+            } else {
+                a.duv[slot] = make_float4(radius, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1);
+                if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ lights (light.glsl)
 __device__ V3 compute_barycentric(V3 a, V3 b, V3 c, V3 p) { // light.glsl:50-68
     V3 v0 = b - a, v1 = c - a, v2 = p - a;
@@ -1881,6 +2080,17 @@ void launch_cast(const CastArgs &c, hipStream_t s) {
     if (c.any) { if (c.alpha) k_cast<true, true><<<nb, kTraceBlock, 0, s>>>(a); else k_cast<true, false><<<nb, kTraceBlock, 0, s>>>(a); }
     else if (c.alpha) k_cast<false, true><<<nb, kTraceBlock, 0, s>>>(a);
     else k_cast<false, false><<<nb, kTraceBlock, 0, s>>>(a);
+}
+// nearest surface points (art_closest_points): the casts' launch shape -- as throughput-bound as they are -- with the context's ArtTuning overrides
+void launch_closest(const ClosestArgs &c, hipStream_t s) {
+    if (!c.n) return;
+    const Tune t = tune_over(kCastPreset, c.tune);
+    ClosestK a{};
+    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.points = c.points; a.duv = c.duv; a.ids = c.ids; a.point = c.point;
+    a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
+    a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    const uint32_t nb = persistent_blocks(c.n, t);
+    if (c.filter) k_closest<true><<<nb, kTraceBlock, 0, s>>>(a); else k_closest<false><<<nb, kTraceBlock, 0, s>>>(a);
 }
 // AO resolve: occluded count -> uint(pow(visibility, 2.2) * 255 + 0.5) through a host-built table; 255 where nothing was hit
 #ifdef ART_PACKET_PROF

@@ -280,6 +280,14 @@ public:
     void cast_rays_multi(const ArtRayCastMulti &d) { cast_rays_multi(ctx_, d); }
     static void cast_rays(ArtContext *ctx, const ArtRayCast &d) { check(art_cast_rays(ctx, &d)); }   // panics like every other call of the mirror
     void cast_rays(const ArtRayCast &d) { cast_rays(ctx_, d); }
+    // the nearest surface point to each of n points (p.xyz, r) in device memory: n x 4 floats d,u,v,0, n x 2 int32 and (optionally) n x float4 points (art_closest_points)
+    static ArtPointQuery point_query(const void *points_dev, uint32_t n, void *duv_dev, void *ids_dev, void *point_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtPointQuery d{}; d.points_dev = points_dev; d.duv_dev = duv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtPointQuery) == 56, "ArtPointQuery is part of the ABI");
+    static void closest_points(ArtContext *ctx, const ArtPointQuery &d) { check(art_closest_points(ctx, &d)); }
+    void closest_points(const ArtPointQuery &d) { closest_points(ctx_, d); }
     void cast_sync() { check(art_cast_sync(ctx_)); }
     struct CastCounts { uint64_t casts, rays, host_waits; };
     CastCounts cast_counts() { CastCounts c{}; check(art_cast_counts(ctx_, &c.casts, &c.rays, &c.host_waits)); return c; }

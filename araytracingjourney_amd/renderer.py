@@ -799,6 +799,45 @@ class Renderer:
         tuv, ids = self.cast_rays(rays, "closest", cull_mask, stream=stream)
         return (tuv, ids), self.resolve_hits(tuv, ids, want, stream=stream)
 
+    def closest_points(self, points, cull_mask=0xFF, out=None, stream=None):
+        """The nearest surface point to each point (art_closest_points).  points: a torch tensor on this context's device, float32, shape (n, 4) -- p.xyz and the search
+        radius r (inf: unbounded) -- contiguous and 16-byte aligned.  Returns (duv, ids, point): (n, 4) float32 d,u,v,0 -- the distance and the barycentrics of vertices 1
+        and 2 of the nearest point -- (n, 2) int32 (primitive, triangle in the primitive) and (n, 4) float32 the point itself, w = 1.  Nothing within r (or a non-finite
+        point, a NaN or negative r) is the miss record: (r, 0, 0, 0), (-1, -1) and a point of zeros.  Alpha cutoffs are not tested; primitive masks are, against cull_mask.
+        out: (duv, ids, point) to write instead of new ones, of at least n records, not overlapping the points or each other.  Enqueued on `stream` (default: torch's
+        current stream) without host synchronisation, like cast_rays."""
+        import torch
+        m = _mask_value("cull_mask", cull_mask)
+        if self._device < 0:
+            self._device = torch.cuda.current_device()
+        dev = self._device
+        if not isinstance(points, torch.Tensor) or not points.is_cuda or points.device.index != dev:
+            raise ValueError(f"points must be a torch tensor on cuda:{dev}")
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.data_ptr() % 16:
+            raise ValueError("points must be float32 of shape (n, 4), contiguous and 16-byte aligned")
+        n = points.shape[0]
+        if out is None:
+            out = (torch.empty((n, 4), dtype=torch.float32, device=points.device), torch.empty((n, 2), dtype=torch.int32, device=points.device),
+                   torch.empty((n, 4), dtype=torch.float32, device=points.device))
+        duv, ids, point = out
+        for t, name, dtype, width, align in ((duv, "duv", torch.float32, (4,), 16), (ids, "ids", torch.int32, (2,), 8), (point, "point", torch.float32, (4,), 16)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and
+                    t.shape[0] >= n and tuple(t.shape[1:]) == width):
+                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n, {width[0]}), {align}-byte aligned")
+        d = _lib.ArtPointQuery(points_dev=points.data_ptr() or None, duv_dev=duv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
+                               n=n, cull_mask=m, flags=0, reserved=0)
+        if stream is None:
+            stream = torch.cuda.current_stream(points.device)
+        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+        check(self._L.art_closest_points(self._ctx, C.byref(d)))
+        return duv, ids, point
+
+    def closest_surface(self, points, cull_mask=0xFF, want=("pos", "ng", "ns", "uv", "albedo", "orm"), stream=None):
+        """closest_points and one resolve of its records on the same stream: ((duv, ids, point), surface dict) -- the normal for a signed distance or a contact, the
+        material under the nearest point.  Miss records resolve to zeros."""
+        duv, ids, point = self.closest_points(points, cull_mask, stream=stream)
+        return (duv, ids, point), self.resolve_hits(duv, ids, want, stream=stream)
+
     def cast_sync(self):
         """every cast enqueued so far has finished, on whichever stream (art_cast_sync)"""
         check(self._L.art_cast_sync(self._ctx))

@@ -360,6 +360,38 @@ typedef struct ArtHitResolve {
     uint32_t flags;        /* must be 0 */
 } ArtHitResolve;           /* 80 bytes */
 int32_t art_resolve_hits(ArtContext *ctx, const ArtHitResolve *r);
+/* The nearest surface point to a point (new functionality: Embree's rtcPointQuery -- the reference has no call for it, and no bundle of rays finds a
+ * nearest point): collision and penetration depth, snapping, proximity and clearance, distance-field sampling, contact generation.  A query is (p.xyz, r): the nearest
+ * point of the scene's triangles within distance r of p.
+ *  - Results: defined exactly, like the casts', and independent of the structure.  For a triangle with global id g let d2_tri be the squared distance from p to it
+ *    (DESIGN.md 3.8's formula: the face, then the three clamped edges, in fp32 without fused operations; a zero-area triangle is its segment or point), box_d2 the
+ *    squared distance from p to the triangle's own box, d2_eff = max(d2_tri, box_d2).  The candidates are the triangles whose primitive's mask & cull_mask != 0 (tested
+ *    first), with d2_tri and box_d2 finite and d2_eff <= r*r; the answer is the argmin over all of them of (d2_eff, g).  duv_dev[i] = (sqrtf(d2_eff), u, v, 0), u, v the
+ *    barycentrics of vertices 1 and 2 of the nearest point (u, v >= 0, u + v <= 1 up to one rounding: a record art_resolve_hits takes); ids_dev[i] = (primitive id,
+ *    triangle in the primitive) as a closest cast's; point_dev[i] (optional) = (v0 + (u*e1 + v*e2), 1).  A miss -- nothing within r -- is (r as given, 0, 0, 0), (-1, -1)
+ *    and a point of zeros.  A query with a non-finite p, a NaN r or r < 0 is a miss; r = +inf is legal (a primitive that left the structure by residency is nowhere and
+ *    is never returned), and so is -0.0.  A record depends on its query alone.
+ *  - Alpha cutoffs are NOT tested: there is no ray to let through, and a triangle whose nearest point is cut would not have its nearest uncut point found.  Visibility
+ *    masks apply as for casts: cull_mask 0 sees nothing.
+ *  - Asynchrony and scene: art_cast_rays's.  The call enqueues on hip_stream (NULL: the context's cast stream) and returns: no hipMalloc / hipFree and no synchronisation
+ *    on the steady path.  The scene as of the call -- a pending move, deformation, residency switch or primitive mask is taken up first, the refit in front of the
+ *    queries -- and the version held until they finish.  It takes a block of the casts' ring (ART_CAST_POOL): art_cast_sync, art_sync, art_scene_build and the others
+ *    wait for it as for a cast, and art_cast_counts' host_waits counts a wait it caused; casts and rays do not count it (it traces no ray).
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null or misaligned points_dev / duv_dev (16 bytes) / ids_dev (8 bytes) --
+ *    with n = 0 null is fine; a misaligned point_dev; cull_mask above 0xFF; flags or reserved other than 0; n above ART_CAST_MAX_RAYS.  ART_E_STATE: the scene is not
+ *    built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtPointQuery {
+    const void *points_dev; /* n x 4 floats p.xyz, r; 16-byte aligned */
+    void *duv_dev;          /* n x 4 floats d,u,v,0 -- a miss is (r,0,0,0); 16-byte aligned */
+    void *ids_dev;          /* n x 2 int32 (primitive id, triangle in the primitive), -1,-1 for a miss; 8-byte aligned */
+    void *point_dev;        /* n x float4: the nearest point xyz, w = 1; a miss is all zeros.  16-byte aligned.  May be NULL */
+    void *hip_stream;       /* as ArtRayCast: NULL = the context's cast stream */
+    uint32_t n;             /* 0 is legal: nothing is enqueued */
+    uint32_t cull_mask;     /* 0..0xFF; 0 sees nothing */
+    uint32_t flags;         /* must be 0 */
+    uint32_t reserved;      /* must be 0 */
+} ArtPointQuery;            /* 56 bytes */
+int32_t art_closest_points(ArtContext *ctx, const ArtPointQuery *q);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
