@@ -96,6 +96,12 @@ class ArtPointQuery(C.Structure):
                 ("n", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ArtSphereCast(C.Structure):
+    """one art_cast_spheres: rays and one radius in, t / barycentrics, ids and (optionally) the contact points out"""
+    _fields_ = [("rays_dev", C.c_void_p), ("tuv_dev", C.c_void_p), ("ids_dev", C.c_void_p), ("point_dev", C.c_void_p), ("hip_stream", C.c_void_p),
+                ("n", C.c_uint32), ("cull_mask", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_float)]
+
+
 class ArtLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "frames_in_flight", "frames_per_launch", "shard_rank", "shard_count", "tiles_owned", "tiles_padded",
                                           "tile_bytes", "reserved")]
@@ -148,6 +154,7 @@ SYMBOLS = {
     "art_cast_rays_multi": (_I32, [_P, _P]),
     "art_resolve_hits": (_I32, [_P, _P]),
     "art_closest_points": (_I32, [_P, _P]),
+    "art_cast_spheres": (_I32, [_P, _P]),
     "art_cast_sync": (_I32, [_P]),
     "art_cast_counts": (_I32, [_P, _P, _P, _P]),
     "art_present": (_I32, [_P]),

@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points; DESIGN.md 3.5 .. 3.8) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres; DESIGN.md 3.5 .. 3.9) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h).  Every use of a CastState / CastBlock field is in this file; the kernels are
 // art_trace.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -81,7 +81,8 @@ static int32_t cast_commit(ArtContext *c, uint32_t bi, uint32_t ver, hipStream_t
 }
 // Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
 // max_hits > 0: art_cast_rays_multi's cast (any false; hit = its count bytes, or null) -- the same blocks, version hold, events and refit, another kernel.
-static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0) {
+// radius >= 0: art_cast_spheres' cast (any false, max_hits 0; hit = its contact points, or null) -- likewise.
+static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0, float radius = -1.0f) {
     hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
     int32_t r = cast_claim(c, user, &s, &ver, &bi); if (r) return r;
     CastState &K = c->cast;
@@ -90,8 +91,10 @@ static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool an
     const AsPtrs as = as_ptrs(c, ver);
     CastArgs a{};
     a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
-    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = max_hits ? nullptr : (uint8_t *)hit; a.cursors = cursors;
+    const bool sweep = radius >= 0.0f;
+    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = max_hits || sweep ? nullptr : (uint8_t *)hit; a.cursors = cursors;
     a.max_hits = max_hits; a.count = max_hits ? (uint8_t *)hit : nullptr;
+    a.sweep = sweep; a.radius = sweep ? radius : 0.0f; a.point = sweep ? (float4 *)hit : nullptr;
     a.tune = c->trace_tune();
     a.alpha = c->alpha_live || cull == 0u;   // the filtered instances run while the scene needs them or the mask is 0 (such rays see nothing, and no leaf bit says so)
     a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p; a.cull = cull;
@@ -200,6 +203,20 @@ int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
     a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.cull = d->cull_mask;
     launch_closest(a, s);
     return cast_commit(c, bi, ver, s);
+}
+
+// ---- a ball along each ray (include/art.h: art_cast_spheres) -----------------------------------------------------------------------------------------
+// A cast like the others -- cast_enqueue: claim, cursors, launch, commit, counted in casts and rays -- with another kernel behind launch_cast.
+int32_t art_cast_spheres(ArtContext *c, const ArtSphereCast *d) {
+    if (!c || !d) return fail(ART_E_INVALID, "art_cast_spheres: null argument");
+    int32_t r = cast_check("art_cast_spheres", d->flags, d->cull_mask, d->n, d->rays_dev); if (r) return r;
+    if (!(d->radius >= 0.0f) || d->radius == INFINITY) return fail(ART_E_INVALID, "art_cast_spheres: radius: NaN, negative or infinite");
+    if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_cast_spheres: tuv_dev: null or not 16-byte aligned");
+    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_cast_spheres: ids_dev: null or not 8-byte aligned");
+    if (misaligned(d->point_dev, 16)) return fail(ART_E_INVALID, "art_cast_spheres: point_dev: not 16-byte aligned");
+    if (!c->built) return fail(ART_E_STATE, "art_cast_spheres: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    return cast_enqueue(c, d->rays_dev, d->n, false, d->cull_mask, d->tuv_dev, d->ids_dev, d->point_dev, (hipStream_t)d->hip_stream, nullptr, 0, d->radius + 0.0f);   // (-0.0 + 0.0 is +0.0)
 }
 
 int32_t art_cast_sync(ArtContext *c) {

@@ -302,6 +302,7 @@ struct CastArgs {
     bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool;   // alpha: FrameArgs' (the mask / alpha test)
     uint32_t cull;                                      // the rays' cull mask
     uint32_t max_hits; uint8_t *count;                  // art_cast_rays_multi: K > 0 -- tuv / ids hold K records a ray, ray-major; count (optional) a byte a ray.  0: the casts above
+    bool sweep; float radius; float4 *point;            // art_cast_spheres: a ball of this radius along each ray (any false, max_hits 0); tuv / ids as a closest cast's, point (optional) the contact point, w = 1 (a miss: zeros)
 };
 constexpr uint32_t kCastCursorWords = 8 * 32;           // eight per-XCD cursors, a 128-byte line each
 void launch_cast(const CastArgs &c, hipStream_t s);

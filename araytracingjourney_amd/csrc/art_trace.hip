@@ -1402,6 +1402,161 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     }
 }
 
+// ---- a ball along a ray (art_cast_spheres) --------------------------------------------------------------------------------------------------------
+// The rays are the casts' -- 32 bytes a ray, everything ray_init makes of them -- so the loop is pooled_trace with a fourth candidate policy.  The ball's radius is the
+// same for every ray of a launch: boxes grow by it (one subtraction / addition a plane, before the slab), and a triangle answers with the first time the ball's centre is
+// within it of the triangle: at tmin already (S), or where it enters the slab round the face, a cylinder round an edge or a sphere round a vertex.
+// No fmaf in anything that decides a record but the slab's: tests/np_sweep.py restates every operation in numpy float32.
+struct SweepK : CastK { float4 *point; float radius; };   // point: may be null
+// the ENTRY root of A t^2 + 2 B t + Cq = 0
+__device__ __forceinline__ bool sweep_root(float A, float B, float Cq, float &t) {
+    const float disc = B * B - A * Cq;
+    t = (-B - sqrtf(disc >= 0.0f ? disc : 0.0f)) / (A > 0.0f ? A : 1.0f);
+    return (A > 0.0f) & (disc >= 0.0f);
+}
+// the cylinder of radius sqrt(rr) round the line {m + s e}: the direction of the edge is projected out of m and d before the quadratic (second order in lengths)
+__device__ __forceinline__ bool sweep_edge(V3 m, V3 e, V3 d, float rr, float &t, float &s) {
+    const float ee = dotp(e, e), q = ee > 0.0f ? ee : 1.0f, qm = dotp(m, e) / q, qd = dotp(d, e) / q;
+    const V3 mp = mk(m.x - qm * e.x, m.y - qm * e.y, m.z - qm * e.z), dp = mk(d.x - qd * e.x, d.y - qd * e.y, d.z - qd * e.z);
+    const bool ok = sweep_root(dotp(dp, dp), dotp(mp, dp), dotp(mp, mp) - rr, t);
+    s = qm + t * qd;
+    return (ee > 0.0f) & ok & (s >= 0.0f) & (s <= 1.0f);
+}
+__device__ __forceinline__ void sweep_take(bool ok, float t, float u, float v, float tmin, float tmax, float &bt, float &bu, float &bv) {
+    if (ok & (t >= tmin) & (t < tmax) & (t < bt)) { bt = t; bu = u; bv = v; }   // (a NaN never wins)
+}
+// t_tri of DESIGN.md 3.9 for w0 = o - v0: the smallest t in [tmin, tmax) among S, F, E01, E02, E12, V0, V1, V2, the first of equals; +inf: none.  u, v: its barycentrics
+__device__ __forceinline__ float tri_sweep(V3 w0, V3 d, V3 e1, V3 e2, float rho, float tmin, float tmax, float &u, float &v) {
+    float bt = INFINITY, t, s; u = 0.0f; v = 0.0f;
+    const float rr = rho * rho, dd = dotp(d, d);
+    {   // S: the ball touches the triangle where it starts
+        float su, sv;
+        const float d2 = tri_closest(mk(w0.x + tmin * d.x, w0.y + tmin * d.y, w0.z + tmin * d.z), e1, e2, su, sv);
+        sweep_take(d2 <= rr, tmin, su, sv, tmin, tmax, bt, u, v);
+    }
+    {   // F: the centre reaches the plane at distance rho on its own side, above the face
+        const V3 n = crossp(e1, e2);
+        const float nn = dotp(n, n), h = dotp(n, w0), nd = dotp(n, d);
+        float off = rho * sqrtf(nn); off = h >= 0.0f ? off : -off;
+        t = (off - h) / (nd != 0.0f ? nd : 1.0f);
+        const V3 w = mk(w0.x + t * d.x, w0.y + t * d.y, w0.z + t * d.z);
+        const float den = nn > 0.0f ? nn : 1.0f, fu = dotp(crossp(w, e2), n) / den, fv = dotp(crossp(e1, w), n) / den;
+        sweep_take((nn > 0.0f) & (nd != 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f), t, fu, fv, tmin, tmax, bt, u, v);
+    }
+    const V3 w1 = w0 - e1, w2 = w0 - e2;
+    bool ok = sweep_edge(w0, e1, d, rr, t, s); sweep_take(ok, t, s, 0.0f, tmin, tmax, bt, u, v);
+    ok = sweep_edge(w0, e2, d, rr, t, s); sweep_take(ok, t, 0.0f, s, tmin, tmax, bt, u, v);
+    ok = sweep_edge(w1, e2 - e1, d, rr, t, s); sweep_take(ok, t, 1.0f - s, s, tmin, tmax, bt, u, v);
+    ok = sweep_root(dd, dotp(w0, d), dotp(w0, w0) - rr, t); sweep_take(ok, t, 0.0f, 0.0f, tmin, tmax, bt, u, v);
+    ok = sweep_root(dd, dotp(w1, d), dotp(w1, w1) - rr, t); sweep_take(ok, t, 1.0f, 0.0f, tmin, tmax, bt, u, v);
+    ok = sweep_root(dd, dotp(w2, d), dotp(w2, w2) - rr, t); sweep_take(ok, t, 0.0f, 1.0f, tmin, tmax, bt, u, v);
+    return bt;
+}
+// The candidate policy: TravBase's state, stack and tie rule; boxes inflated by rho.  FILTER: the visibility masks (k_closest's visible(); alpha cutoffs are not tested)
+template <int LDSN, bool FILTER> struct TravSweep : TravBase<false, kOvfStack4 + (kLdsStack - LDSN), LDSN, false> {
+    using Nodes = const DevNode4 *;
+    float rho;
+    __device__ __forceinline__ bool visible(const AlphaView &av, uint32_t pos) const {
+        if (!FILTER) return true;
+        if (av.cull == 0u) return false;
+        if (!((av.bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
+        const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(av.shade + pos)[8].z);
+        return (prim_vis(av.prims[prim].masked) & av.cull) != 0u;
+    }
+    // the triangle's own box, inflated, against tbest first -- an exact cull: a candidate's t_eff is at least its box's entry and at least tmin -- then the eight features
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const Ray &r = this->r;
+        float te;
+        if (slab(r, tc.y - rho, tc.z - rho, tc.w - rho, td.x + rho, td.y + rho, td.z + rho, this->tbest, te)) {
+            float u, v;
+            const float tt = tri_sweep(r.o - mk(ta.x, ta.y, ta.z), r.d, mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), rho, r.tmin, r.tmax, u, v);
+            if (tt < INFINITY) {
+                const float teff = fmaxf(tt, te);
+                const uint32_t gid = __float_as_uint(td.w);
+                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && visible(av, pos)) { this->tbest = teff; this->bu = u; this->bv = v; this->bpos = pos; this->bgid = gid; }
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+    // Trav4's sign-selected slab with each child's near plane moved out and its far plane moved out by rho.  An absent child or a masked subtree carries an inverted byte box
+    // (255 / 0): "left before it is entered" no longer holds once the planes have moved, so it is skipped by TravPoint's explicit test
+    __device__ __forceinline__ bool step_internal(Nodes wide, int *lds, int *ovf) {
+        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + this->cur);
+        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
+        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
+        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
+        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
+        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        float te[4]; bool h[4];
+        const Ray &r = this->r;
+        const bool ngx = r.inv.x < 0.0f, ngy = r.inv.y < 0.0f, ngz = r.inv.z < 0.0f;
+        const uint32_t nxw = ngx ? b.w : b.x, fxw = ngx ? b.x : b.w, nyw = ngy ? c.x : b.y, fyw = ngy ? b.y : c.x, nzw = ngz ? c.y : b.z, fzw = ngz ? b.z : c.y;
+        const float px = ngx ? rho : -rho, py = ngy ? rho : -rho, pz = ngz ? rho : -rho;   // what the near plane moves by (lo - rho is lo + (-rho), bit for bit); the far plane by the opposite
+        const float lim = this->tbest;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float tnx = fmaf(fmaf((float)((nxw >> (8 * i)) & 255u), sx, ox) + px, r.inv.x, -r.ood.x), tfx = fmaf(fmaf((float)((fxw >> (8 * i)) & 255u), sx, ox) - px, r.inv.x, -r.ood.x);
+            const float tny = fmaf(fmaf((float)((nyw >> (8 * i)) & 255u), sy, oy) + py, r.inv.y, -r.ood.y), tfy = fmaf(fmaf((float)((fyw >> (8 * i)) & 255u), sy, oy) - py, r.inv.y, -r.ood.y);
+            const float tnz = fmaf(fmaf((float)((nzw >> (8 * i)) & 255u), sz, oz) + pz, r.inv.z, -r.ood.z), tfz = fmaf(fmaf((float)((fzw >> (8 * i)) & 255u), sz, oz) - pz, r.inv.z, -r.ood.z);
+            const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
+            te[i] = tn;
+            h[i] = (((b.x >> (8 * i)) & 255u) <= ((b.w >> (8 * i)) & 255u)) & (fmaxf(tn, r.tmin) <= fminf(tf, lim));
+        }
+        float tn = 3.0e38f; int ni = -1;   // on with the nearest child, the others wait: the order is speed only
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (h[i] && te[i] < tn) { tn = te[i]; ni = i; }
+        if (ni < 0) {   // (a child entered at 3e38 or beyond -- a structure nowhere -- is still a child: the first of them)
+#pragma unroll
+            for (int i = 3; i >= 0; i--) if (h[i]) ni = i;
+            if (ni < 0) return this->pop(lds, ovf);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (h[i] && i != ni) this->push(refs[i], lds, ovf);
+        this->cur = ni == 0 ? refs[0] : (ni == 1 ? refs[1] : (ni == 2 ? refs[2] : refs[3]));
+        return false;
+    }
+};
+struct SweepSource {
+    static constexpr int kFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
+    const SweepK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.rho = a.radius; }   // the same for every ray
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
+        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+        const bool has = ray_finite(o, d) && r1.w == r1.w;
+        if (!has) {                // a dead ray (CastSource's rule): its miss record, without a walk
+            a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1);
+            if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
+        if (tr.bgid != kNoHit) {   // the ids as CastSource::finish makes them; the contact point from the winning triangle's record
+            const uint32_t prim = a.tri_prim[tr.bgid];
+            a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
+            a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+            if (a.point) {
+                const float4 *tq = reinterpret_cast<const float4 *>(a.tris + tr.bpos);
+                const float4 ta = tq[0], tb = tq[1], tc = tq[2];
+                a.point[slot] = make_float4(ta.x + (tr.bu * ta.w + tr.bv * tb.z), ta.y + (tr.bu * tb.x + tr.bv * tb.w), ta.z + (tr.bu * tb.y + tr.bv * tc.x), 1.0f);
+            }
+        } else {
+            a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1);
+            if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+};
+// 6 waves a SIMD: the eight-feature test holds 79 VGPRs without a spill; at 8 waves (64) the compiler spills two dozen of them to scratch, at 4 it uses no more than at 6
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_sweep(SweepK a) {
+    pooled_trace<kCastLds, false, FILTER, SweepK, SweepSource, TravSweep<kCastLds, FILTER>>(a, SweepSource{a});
+}
+
 // ------------------------------------------------------------------------------------------------ lights (light.glsl)
 __device__ V3 compute_barycentric(V3 a, V3 b, V3 c, V3 p) { // light.glsl:50-68
     V3 v0 = b - a, v1 = c - a, v2 = p - a;
@@ -2070,6 +2225,11 @@ void launch_cast(const CastArgs &c, hipStream_t s) {
     a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
     a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
     const uint32_t nb = persistent_blocks(c.n, t);
+    if (c.sweep) {      // a ball along each ray (art_cast_spheres): the filtered instance under the casts' condition -- it tests masks, never a cutoff
+        SweepK w{}; static_cast<CastK &>(w) = a; w.point = c.point; w.radius = c.radius;
+        if (c.alpha) k_sweep<true><<<nb, kTraceBlock, 0, s>>>(w); else k_sweep<false><<<nb, kTraceBlock, 0, s>>>(w);
+        return;
+    }
     if (c.max_hits) {   // the first K hits: the instance with the smallest list that holds K
         CastMultiK m{}; static_cast<CastK &>(m) = a; m.count = c.count; m.max_hits = c.max_hits;
         if (c.max_hits <= 4u) { if (c.alpha) k_cast_multi<4, true><<<nb, kTraceBlock, 0, s>>>(m); else k_cast_multi<4, false><<<nb, kTraceBlock, 0, s>>>(m); }

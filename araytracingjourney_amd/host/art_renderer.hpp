@@ -288,6 +288,14 @@ public:
     static_assert(sizeof(ArtPointQuery) == 56, "ArtPointQuery is part of the ABI");
     static void closest_points(ArtContext *ctx, const ArtPointQuery &d) { check(art_closest_points(ctx, &d)); }
     void closest_points(const ArtPointQuery &d) { closest_points(ctx_, d); }
+    // where a ball of `radius` along each of n rays in device memory first touches the scene: records as a closest cast's and (optionally) n x float4 contact points (art_cast_spheres)
+    static ArtSphereCast sphere_cast(const void *rays_dev, uint32_t n, float radius, void *tuv_dev, void *ids_dev, void *point_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtSphereCast d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask; d.radius = radius;
+        return d;
+    }
+    static_assert(sizeof(ArtSphereCast) == 56, "ArtSphereCast is part of the ABI");
+    static void cast_spheres(ArtContext *ctx, const ArtSphereCast &d) { check(art_cast_spheres(ctx, &d)); }
+    void cast_spheres(const ArtSphereCast &d) { cast_spheres(ctx_, d); }
     void cast_sync() { check(art_cast_sync(ctx_)); }
     struct CastCounts { uint64_t casts, rays, host_waits; };
     CastCounts cast_counts() { CastCounts c{}; check(art_cast_counts(ctx_, &c.casts, &c.rays, &c.host_waits)); return c; }

@@ -838,6 +838,49 @@ class Renderer:
         duv, ids, point = self.closest_points(points, cull_mask, stream=stream)
         return (duv, ids, point), self.resolve_hits(duv, ids, want, stream=stream)
 
+    def cast_spheres(self, rays, radius, cull_mask=0xFF, out=None, stream=None):
+        """Where a ball of `radius` moving along each ray first touches the scene (art_cast_spheres).  rays: cast_rays' tensor, float32 of shape (n, 8) -- o.xyz, tmin,
+        d.xyz, tmax; the ball's centre is o + t*d -- contiguous and 16-byte aligned; radius: one finite float >= 0 for the whole call.  Returns (tuv, ids, point): (n, 4)
+        float32 t,u,v,0 -- the centre's t at first contact and the barycentrics of vertices 1 and 2 of the contact point -- (n, 2) int32 (primitive, triangle in the
+        primitive) and (n, 4) float32 the contact point, w = 1; the contact normal is normalize(o + t*d - point).  A miss (or a dead ray) is (tmax, 0, 0, 0), (-1, -1) and a
+        point of zeros.  Alpha cutoffs are not tested; primitive masks are, against cull_mask.  out: (tuv, ids, point) to write instead of new ones, of at least n records,
+        not overlapping the rays or each other.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        import math
+        import torch
+        m = _mask_value("cull_mask", cull_mask)
+        radius = float(radius)
+        if not (radius >= 0.0 and math.isfinite(radius)):
+            raise ValueError("radius must be a finite number >= 0")
+        if self._device < 0:
+            self._device = torch.cuda.current_device()
+        dev = self._device
+        if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device.index != dev:
+            raise ValueError(f"rays must be a torch tensor on cuda:{dev}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.data_ptr() % 16:
+            raise ValueError("rays must be float32 of shape (n, 8), contiguous and 16-byte aligned")
+        n = rays.shape[0]
+        if out is None:
+            out = (torch.empty((n, 4), dtype=torch.float32, device=rays.device), torch.empty((n, 2), dtype=torch.int32, device=rays.device),
+                   torch.empty((n, 4), dtype=torch.float32, device=rays.device))
+        tuv, ids, point = out
+        for t, name, dtype, width, align in ((tuv, "tuv", torch.float32, (4,), 16), (ids, "ids", torch.int32, (2,), 8), (point, "point", torch.float32, (4,), 16)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and
+                    t.shape[0] >= n and tuple(t.shape[1:]) == width):
+                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n, {width[0]}), {align}-byte aligned")
+        d = _lib.ArtSphereCast(rays_dev=rays.data_ptr() or None, tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
+                               n=n, cull_mask=m, flags=0, radius=radius)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+        check(self._L.art_cast_spheres(self._ctx, C.byref(d)))
+        return tuv, ids, point
+
+    def cast_spheres_surface(self, rays, radius, cull_mask=0xFF, want=("pos", "ng", "ns", "uv", "albedo", "orm"), stream=None):
+        """cast_spheres and one resolve of its records on the same stream: ((tuv, ids, point), surface dict) -- the surface under the contact point.  Miss records
+        resolve to zeros."""
+        tuv, ids, point = self.cast_spheres(rays, radius, cull_mask, stream=stream)
+        return (tuv, ids, point), self.resolve_hits(tuv, ids, want, stream=stream)
+
     def cast_sync(self):
         """every cast enqueued so far has finished, on whichever stream (art_cast_sync)"""
         check(self._L.art_cast_sync(self._ctx))

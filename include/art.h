@@ -392,6 +392,38 @@ typedef struct ArtPointQuery {
     uint32_t reserved;      /* must be 0 */
 } ArtPointQuery;            /* 56 bytes */
 int32_t art_closest_points(ArtContext *ctx, const ArtPointQuery *q);
+/* A ball along a ray (new functionality: PhysX's sweep, Unity's SphereCast -- the reference has no call for it, a ray misses what the ball clips with
+ * its side, and art_closest_points answers only where the ball stands): character and robot-link motion, drone and probe clearance along a path, continuous collision
+ * of a thrown object, a lidar beam of finite width as a conservative tube.  A query is a ray of the casts' layout (o.xyz, tmin, d.xyz, tmax) and ONE radius for the
+ * whole call: the ball's centre is c(t) = o + t*d (d need not be unit), and the answer is where the ball first touches the scene's triangles with tmin <= t < tmax.
+ *  - Results: defined exactly, like the casts', and independent of the structure.  For a triangle with global id g, t_tri is the smallest t among the taken features --
+ *    the ball overlaps the triangle at tmin already (S), its centre reaches the plane at distance radius above the face (F), the cylinder round an edge (E01, E02, E12:
+ *    the entry root, the edge's direction projected out first) or the sphere round a vertex (V0, V1, V2), DESIGN.md 3.9's formulas in that order, fp32 without fused
+ *    operations, the first of equals; tn the entry of section 1.1's slab into the triangle's own box inflated by the radius; t_eff = max(t_tri, tn).  The candidates
+ *    are the triangles whose primitive's mask & cull_mask != 0 (tested first), with some feature taken and the slab passed; the answer is the argmin over all of
+ *    them of (t_eff, g).  tuv_dev[i] = (t_eff, u, v, 0), u, v the barycentrics of vertices 1 and 2 of the contact point (a record art_resolve_hits takes); ids_dev[i]
+ *    as a closest cast's; point_dev[i] (optional) = (v0 + (u*e1 + v*e2), 1): the contact normal is normalize(c(t) - point).  A miss is (tmax as given, 0, 0, 0),
+ *    (-1, -1) and a point of zeros.  A ray with a non-finite o or d or a NaN tmax is a miss.  d = 0 is legal: a ball that does not move, only S answers.  radius = 0
+ *    is legal: a thin ray BY THIS FORMULA, not bit-equal to ART_CAST_CLOSEST (no fattened edges, other operations).  A record depends on its ray and the radius alone.
+ *  - Alpha cutoffs are NOT tested, for art_closest_points' reason.  Visibility masks apply as for casts: cull_mask 0 sees nothing.  A primitive that left the
+ *    structure by residency is nowhere and is never returned.
+ *  - Asynchrony and scene: art_cast_rays's, with no path of its own -- stream, no allocation or synchronisation on the steady path, the scene as of the call, the
+ *    version held, a block of the casts' ring (ART_CAST_POOL), the same fences.  It traces rays: art_cast_counts counts it in casts and rays.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null or misaligned rays_dev / tuv_dev (16 bytes) / ids_dev (8 bytes) --
+ *    with n = 0 null is fine; a misaligned point_dev; a radius that is NaN, negative (-0.0 is 0) or infinite; cull_mask above 0xFF; flags other than 0; n above
+ *    ART_CAST_MAX_RAYS.  ART_E_STATE: the scene is not built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtSphereCast {
+    const void *rays_dev;   /* n x 8 floats o.xyz,tmin,d.xyz,tmax; 16-byte aligned */
+    void *tuv_dev;          /* n x 4 floats t,u,v,0 -- a miss is (tmax,0,0,0); 16-byte aligned */
+    void *ids_dev;          /* n x 2 int32 (primitive id, triangle in the primitive), -1,-1 for a miss; 8-byte aligned */
+    void *point_dev;        /* n x float4: the contact point xyz, w = 1; a miss is all zeros.  16-byte aligned.  May be NULL */
+    void *hip_stream;       /* as ArtRayCast: NULL = the context's cast stream */
+    uint32_t n;             /* 0 is legal: nothing is enqueued */
+    uint32_t cull_mask;     /* 0..0xFF; 0 sees nothing */
+    uint32_t flags;         /* must be 0 */
+    float radius;           /* of the ball, for every ray of the call: finite, >= 0 */
+} ArtSphereCast;            /* 56 bytes */
+int32_t art_cast_spheres(ArtContext *ctx, const ArtSphereCast *s);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
