@@ -277,6 +277,28 @@ def pending_on_first_descent_wide(floats, ray):
     return pending
 
 
+def pending_on_first_descent_point(lo, hi, valid, child, point):
+    """the same for a nearest-point walk of the quantised 4-wide nodes (lo, hi, valid of dequantise(); child: words 12..15 of the records as int32) with r = inf: on
+    with the nearest valid child by the distance to its box, every other valid child pushed -- nothing is beyond an infinite limit.  Equal distances (a point inside
+    several boxes: 0) are ordered as the walk's five-comparator network orders them, which is not by index"""
+    p = np.asarray(point[0:3], np.float32)
+    cur, pending = 0, 0
+    while cur >= 0:
+        with np.errstate(all="ignore"):
+            e = np.fmax(np.fmax(lo[cur] - p, p - hi[cur]), np.float32(0))
+            d2 = ((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]).astype(np.float32)
+        k = [d2[i] if valid[cur, i] else np.float32(np.inf) for i in range(4)]
+        rf = [int(child[cur, i]) if valid[cur, i] else None for i in range(4)]
+        for x, y in ((0, 1), (2, 3), (0, 2), (1, 3), (1, 2)):
+            if k[y] < k[x]:
+                k[x], k[y], rf[x], rf[y] = k[y], k[x], rf[y], rf[x]
+        if rf[0] is None:
+            return pending
+        pending += sum(r is not None for r in rf[1:])
+        cur = rf[0]
+    return pending
+
+
 def dequantise(quantised):
     """the child boxes of the (n, 16) uint32 quantised records as the per-ray walks evaluate them: float32(q * 2^(e - 127) + origin), one rounding (q * scale is exact,
     and the float64 sum rounds to float32 like the exact one: q * scale has 8 bits) -> lo, hi [n, 4, 3] float32 and the valid mask [n, 4]"""
