@@ -228,6 +228,7 @@ PARITY_SYMBOLS = {
     "art_get_traversal_tree": (_I32, [_P, _P, _P, _P]),
     "art_get_wide_nodes": (_I32, [_P, _P, _P, _SZ, _P]),
     "art_parity_math_sweep": (_I32, [_P, _U32, _U32, C.c_uint64, _U32, _P, _P, _P, _P]),
+    "art_parity_radiance_sweep": (_I32, [_P, _U32, _U32, C.c_uint64, _U32, C.c_float, _P, _P, _P, _P]),
     "art_mgpu_pending": (_I32, [_P, _P, _P]),
 }
 

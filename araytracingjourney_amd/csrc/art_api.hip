@@ -1027,4 +1027,24 @@ int32_t art_parity_math_sweep(ArtContext *c, uint32_t which, uint32_t first_bits
     return ART_OK;
 }
 
+// the radiance-only helpers of art_trace.hip (pow22_texel, quotient_rcp) against the expressions they stand for: a distance in ulps and the result classes (include/art_parity.h)
+int32_t art_parity_radiance_sweep(ArtContext *c, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numerator, uint32_t *max_ulps, uint32_t *worst_bits,
+                                  uint64_t *class_mismatches, uint32_t *first_class_bits) {
+    if (!c || !max_ulps || !worst_bits || !class_mismatches || !first_class_bits) return fail(ART_E_INVALID, "art_parity_radiance_sweep: null argument");
+    if (which > 1 || count > (1ull << 32)) return fail(ART_E_INVALID, "art_parity_radiance_sweep: which 0..1, at most 2^32 patterns");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    unsigned long long *d = nullptr, h[3] = {0ull, 0ull, ~0ull};
+    HIPC(hipMalloc(&d, sizeof h));
+    hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { launch_radiance_sweep(which, first_bits, count, stride, numerator, d, nullptr); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
+    hipFree(d);
+    HIPC(e);
+    *max_ulps = (uint32_t)(h[0] >> 32); *class_mismatches = h[1];
+    if (h[0]) *worst_bits = first_bits + (uint32_t)h[0] * stride;
+    if (h[1]) *first_class_bits = first_bits + (uint32_t)h[2] * stride;
+    return ART_OK;
+}
+
 } // extern "C"

@@ -272,6 +272,8 @@ void launch_frame_stats(const FrameArgs &a, uint32_t *out, hipStream_t s); // ou
 // art_parity_math_sweep (include/art_parity.h): out = three device words, [0] += mismatches, [1] = min(index of a mismatch), [2] += lanes on the fast path; guard = the fast path's range
 void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, unsigned long long *out, hipStream_t s);
 void math_sweep_guard(float guard[2]);
+// art_parity_radiance_sweep: out = three device words, [0] = max(distance in ulps << 32 | index of that input), [1] += inputs whose result class differs, [2] = min(index of one)
+void launch_radiance_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numer, unsigned long long *out, hipStream_t s);
 // The wave plan of the fused frame, made ON THE DEVICE behind a sampled frame (k_plan, art_trace.hip): from the steps every wave of that launch counted, every 8x8 block's level
 // (0 one wave | 1 four quadrant waves | 2 sixteen cell waves) and, if a level changed that matters, the next table of wave items.  result (pinned host memory, read once the
 // event behind the launch has fired): [0] items of the new table, [1] 1 = a new table was written, [2] blocks in four, [3] blocks in sixteen, [4] the step target, [5] slowest wave

@@ -1634,12 +1634,27 @@ __device__ float Burley_diffuse_local_sss(float a_, float NdotV, float nc_NdotV,
     float diffuse = (1.0f - ratio) * F_Schlick1(1.0f, f90, nc_NdotL) * F_Schlick1(1.0f, f90, nc_NdotV);
     return NdotV * (diffuse + local_sss) * ART_INV_PI;
 }
+// x^2.2 of a texel (the albedo's gamma; radiance only) in twelve vector instructions, two of them transcendental, where hipcc's __powf is the full libm pow (~143).
+// x = m 2^e with m in [0.5, 1): 2.2 e = n + f with n an integer and |f| <= 1/2 exact (e is small), so x^2.2 = 2^n 2^(2.2 log2 m + f) and the rounded product
+// stays below 2.8 in magnitude -- the one-line exp2(2.2 log2 x) rounds a product of up to 18 and loses 1.5e-6 relative at dark texels.  Exactly 0 at 0 and 1 at 1,
+// NaN passes through; correct on [0, 2], no sign / integer-y / infinity handling (art_parity_radiance_sweep measures it against libm's pow over that whole range).
+// Underflow is libm's: its pow returns 0 for every x below 0x1d9aa2a3 (4.09e-21: x^2.2 just under 2^-149) and the smallest denormal from there on, where round-to-nearest
+// would already give that denormal from 2^-150 (x = 2.99e-21) on.  Such an x counts as 0 here too -- a compare and a select -- so that the result's class is libm's on
+// every input; no texel is that small (a blend of bytes / 255 is 0 or at least 2^-56).
+constexpr uint32_t kPow22UnderflowBits = 0x1d9aa2a3u;
+__device__ __forceinline__ float pow22_texel(float x) {
+    x = x < __uint_as_float(kPow22UnderflowBits) ? 0.0f : x;
+    const float fe = (float)__builtin_amdgcn_frexp_expf(x), m = __builtin_amdgcn_frexp_mantf(x);
+    const float n = rintf(2.2f * fe), f = fmaf(2.2f, fe, -n);
+    const float g = fmaf(2.2f, __builtin_amdgcn_logf(m), f);
+    return __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(g), (int)n);
+}
 
 // ---- shading (raytrace.rgen.glsl:103-199), shared by the staged frame (k_shade) and the fused frame (k_frame) ---------
 struct Surface { V3 world_pos, N, Vv, albedo; float metallic, alpha, nc_NdotV, NdotV; };
 
 // rgen:107-150: the hit triangle's attributes, normal mapping, material; also the frame's depth / view-space normal outputs
-template <bool CORE> __device__ __forceinline__ void shade_surface_body(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal, uint32_t &far) {
+template <bool CORE, bool HOLD = false> __device__ __forceinline__ void shade_surface_body(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal, uint32_t &far) {
     // one dependent fetch: the shading record holds what get_indices + three vertex reads would return (rgen:107-114)
     const float4 *sq = reinterpret_cast<const float4 *>(a.shade_tris + pos);
     float4 s0 = sq[0], s1 = sq[1], s2 = sq[2], s3 = sq[3], s4 = sq[4], s5 = sq[5], s6 = sq[6], s7 = sq[7], s8 = sq[8];
@@ -1659,7 +1674,7 @@ template <bool CORE> __device__ __forceinline__ void shade_surface_body(const Fr
     V3 N = nrm3_noting<CORE>(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f), far);
     N = nrm3_noting<CORE>((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z, far);
     tx = sample_tex(a.tex_pool, P, 0, tu, tv);
-    V3 albedo = mk(__powf(tx.x, 2.2f), __powf(tx.y, 2.2f), __powf(tx.z, 2.2f)); // radiance-only from here: fast intrinsics
+    V3 albedo = mk(pow22_texel(tx.x), pow22_texel(tx.y), pow22_texel(tx.z)); // radiance-only from here: pow22_texel is within 8 ulp of libm's pow (the BRDF's __fdividef is the IEEE division on this toolchain)
     tx = sample_tex(a.tex_pool, P, 1, tu, tv);
     float roughness = tx.y, metallic = tx.z;
     S.world_pos = world_pos; S.N = N; S.albedo = albedo; S.metallic = metallic;
@@ -1674,16 +1689,19 @@ template <bool CORE> __device__ __forceinline__ void shade_surface_body(const Fr
     on.y = -on.y; on.z = -on.z;
     on = nrm3_noting<CORE>(on, far);
     out_normal = mk(on.x * 0.5f + 0.5f, on.y * 0.5f + 0.5f, on.z * 0.5f + 0.5f);
+    // HOLD (the four k_frame instances <*, true, *, false, true>: one light, one frame per launch, alpha test): libm's pow was what took those instances to 61 VGPRs; without
+    // it they need 58, and the figure is pinned to the register (tests/test_ray_masks.py).  The block's last result passes through v60 -- a move there and back -- so they claim 61.
+    if (HOLD) { asm volatile("" : "+{v60}"(out_normal.x)); }
 }
 
 // The surface block's nine normalisations under ONE guard: a branch in front of each (inv_sqrt_exact) cuts the block into ten scheduling regions and moves the register
 // allocation of every k_frame instance; here the block runs the core straight through, notes the range of what it was given, and a wave in which any lane's note is out
 // of range runs the block again with the plain expressions (a normal of length zero, a NaN vertex: nothing a frame has many of).  What the first pass computed from such a
 // value is discarded whole: no address depends on a normalised vector, so it is arithmetic on garbage and nothing else.
-template <bool FAST> __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal) {
+template <bool FAST, bool HOLD = false> __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal) {
     uint32_t far = 0u;
     if (FAST) { if (!a.plain_math) { shade_surface_body<true>(a, cam, pos, hu, hv, S, out_depth, out_normal, far); if (exact_noted_in_range(far)) return; } }
-    shade_surface_body<false>(a, cam, pos, hu, hv, S, out_depth, out_normal, far);
+    shade_surface_body<false, HOLD>(a, cam, pos, hu, hv, S, out_depth, out_normal, far);
 }
 // rgen:152-185 up to the shadow ray: c = (rho_s + rho_d) * radiance, c.w = NdotL; the shadow ray (origin, tmax | direction) if one is due
 template <bool FAST> __device__ __forceinline__ bool shade_light(const ArtLight &l, const Surface &S, bool plain, float4 &c4, float4 &ro, float4 &rd) {
@@ -1868,7 +1886,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     Surface S;
     S.world_pos = mk(0.f, 0.f, 0.f); S.N = mk(0.f, 0.f, 1.f); S.Vv = mk(0.f, 0.f, 1.f); S.albedo = mk(0.f, 0.f, 0.f);
     S.metallic = 0.f; S.alpha = 0.f; S.nc_NdotV = 0.f; S.NdotV = 0.f;
-    if (hit) shade_surface<FASTM>(a, cam, bpos, bu, bv, S, out_depth, out_normal);
+    if (hit) shade_surface<FASTM, ONE_LIGHT && !BATCH && ALPHA>(a, cam, bpos, bu, bv, S, out_depth, out_normal);
     if (in) {
         const size_t pix = frame_px + (size_t)y * a.W + x;
         st_nt(&a.depth[pix], out_depth);
@@ -2214,6 +2232,46 @@ void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint
     else k_math_sweep<4><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
 }
 void math_sweep_guard(float guard[2]) { guard[0] = kExactLo; guard[1] = kExactHi; }
+
+// ---- art_parity_radiance_sweep: the radiance-only helpers against the expressions they replace, which are NOT bit-equal -- a distance, not a mismatch count (tests/test_fast_radiance.py) ----
+__device__ __attribute__((noinline)) float plain_pow22(float x) { return __ocml_pow_f32(x, 2.2f); }
+__device__ __attribute__((noinline)) float plain_quotient(float a, float b) { return a / b; }
+// The candidate for the BRDF's quotients (D_GGX, V_SmithGGXCorrelated_fast, Burley_diffuse_local_sss, the falloff), which are the IEEE division today: one v_rcp_f32 and a
+// product.  Not what the frame kernels run: the sweep is here to measure it first (profiles/README.md, "x^2.2 in ten instructions").
+__device__ __forceinline__ float quotient_rcp(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+__device__ __forceinline__ uint32_t float_class(float v) { return v != v ? 3u : (fabsf(v) == INFINITY ? 2u : (v == 0.0f ? 0u : 1u)); }   // zero | finite | infinite | NaN
+__device__ __forceinline__ long long float_order(float v) { const uint32_t b = __float_as_uint(v); return (b & 0x80000000u) ? -(long long)(b & 0x7fffffffu) : (long long)b; }   // adjacent floats are 1 apart
+constexpr float kRadianceSweepFloor = 0x1p-100f;   // a reference smaller than this has no distance taken: below it x^2.2 of a texel is nothing a frame can hold
+template <int WHICH> __global__ __launch_bounds__(kBlock) void k_radiance_sweep(uint32_t first_bits, uint64_t count, uint32_t stride, float numer, unsigned long long *__restrict__ out) {
+    unsigned long long worst = 0, class_bad = 0, class_at = ~0ull;   // worst = distance << 32 | index's low word: one atomicMax carries both
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += step) {
+        const float x = __uint_as_float(first_bits + (uint32_t)i * stride);
+        const float got = WHICH == 0 ? pow22_texel(x) : quotient_rcp(numer, x), ref = WHICH == 0 ? plain_pow22(x) : plain_quotient(numer, x);
+        const uint32_t cg = float_class(got), cr = float_class(ref);
+        if (cg != cr) { class_bad++; if (i < class_at) class_at = i; }
+        else if (cr <= 1u && fabsf(ref) >= kRadianceSweepFloor) {
+            long long d = float_order(got) - float_order(ref); d = d < 0 ? -d : d; d = d > 0xffffffffll ? 0xffffffffll : d;
+            const unsigned long long w = ((unsigned long long)d << 32) | (uint32_t)i;
+            worst = w > worst ? w : worst;
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        class_bad += __shfl_xor(class_bad, off);
+        const unsigned long long w = __shfl_xor(worst, off); worst = w > worst ? w : worst;
+        const unsigned long long o = __shfl_xor(class_at, off); class_at = o < class_at ? o : class_at;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (worst) atomicMax(&out[0], worst);
+        if (class_bad) { atomicAdd(&out[1], class_bad); atomicMin(&out[2], class_at); }
+    }
+}
+void launch_radiance_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numer, unsigned long long *out, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kSweepBlocks, (count + kBlock - 1) / kBlock);
+    if (!blocks) return;
+    if (which == 0) k_radiance_sweep<0><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer, out);
+    else k_radiance_sweep<1><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer, out);
+}
 // rays in device buffers (art_cast_rays and, through it, the queries): {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernel has -- a cast is
 // throughput-bound like it -- with the context's ArtTuning overrides
 static const Tune kCastPreset = {256, kPoolTake, 2048, 8};

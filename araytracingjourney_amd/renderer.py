@@ -663,6 +663,13 @@ class Renderer:
         check(self._L.art_parity_math_sweep(self._ctx, which, first_bits, count, stride, C.byref(bad), C.byref(first), C.byref(fast), guard))
         return dict(mismatches=bad.value, first_bad_bits=first.value if bad.value else None, fast_lanes=fast.value, guard=(guard[0], guard[1]))
 
+    def radiance_sweep(self, which, first_bits=0, count=1 << 32, stride=1, numerator=1.0):
+        """art_parity_radiance_sweep: the albedo's x^2.2 helper against libm's powf (which 0) or numerator * rcp(x) against numerator / x (1) on the bit patterns
+        first_bits + i * stride, i < count -> dict(max_ulps, worst_bits (None at distance 0), class_mismatches, first_class_bits (None without one))"""
+        ulps, worst, bad, first = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        check(self._L.art_parity_radiance_sweep(self._ctx, which, first_bits, count, stride, numerator, C.byref(ulps), C.byref(worst), C.byref(bad), C.byref(first)))
+        return dict(max_ulps=ulps.value, worst_bits=worst.value if ulps.value else None, class_mismatches=bad.value, first_class_bits=first.value if bad.value else None)
+
     def set_ray_masks(self, primary=0xFF, shadow=0xFF, ao=0xFF):
         """the cull masks of the rays trace() (primary, shadow) and trace_ao() (ao) cast (Vulkan: traceRayEXT's cullMask; the reference hard-codes 0xFF,
         raytrace.rgen.glsl:92,169): a ray sees a primitive iff its mask (Model.set_mask) shares a bit with the ray's.  Per-launch state like the camera: a

@@ -87,6 +87,15 @@ int32_t art_get_wide_nodes(ArtContext *ctx, void *quantised, void *floats, size_
  * which = 4: v_rsq_f32 alone under that guard -- a 1-ulp approximation, the sweep's own control: it must report mismatches.  Synchronises. */
 int32_t art_parity_math_sweep(ArtContext *ctx, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint64_t *mismatches, uint32_t *first_bad_bits,
                               uint64_t *fast_lanes, float guard[2]);
+/* how far the radiance-only helpers of the shading kernels are from the expressions they stand for (they are NOT bit-equal: DESIGN.md 1 keeps radiance to 1e-4 relative).
+ * which = 0: the albedo's x^2.2 (pow22_texel: frexp, one hardware log2, one exp2, ldexp) against libm's powf(x, 2.2f), the frame kernels' form; which = 1: numerator * rcp(x),
+ * the candidate for the BRDF's quotients, against the IEEE numerator / x (the kernels still run the division).  x = the bit patterns first_bits + i * stride (mod 2^32),
+ * i < count <= 2^32; the reference is a non-inlined copy in the same translation unit.  *max_ulps = the largest distance in units of the reference's last place over the inputs
+ * whose two results are both zero-or-finite and whose reference is at least 2^-100 in magnitude, *worst_bits = an input where it occurs (untouched when the distance is 0),
+ * *class_mismatches = inputs whose two results are not of the same class (zero | finite | infinite | NaN), *first_class_bits = the lowest such i's pattern (untouched when there
+ * is none).  Synchronises. */
+int32_t art_parity_radiance_sweep(ArtContext *ctx, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numerator, uint32_t *max_ulps, uint32_t *worst_bits,
+                                  uint64_t *class_mismatches, uint32_t *first_class_bits);
 
 
 /* ---- building blocks of art_mgpu_* (rehearsals of other exchange loops) ---- */

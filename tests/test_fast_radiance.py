@@ -1,0 +1,171 @@
+"""The albedo's x^2.2 in twelve vector instructions (art_trace.hip: pow22_texel) where hipcc's __powf is the whole libm pow.  It feeds radiance only, so it need not
+return libm's bits (1e-4 relative) -- but it has to stay far inside that tolerance, be the same in every instance of the frame (the forms of a frame are
+compared bit for bit), and be exact at the two ends of a texel's range.  art_parity_radiance_sweep measures it against libm's pow on every input a texel can be.
+
+The bound of 8 ulp is derived, not measured: 8 ulp is under 1e-6 relative, which leaves the pinned margin rule of tests/test_gpu_parity.py (worst_rel_err <= 2 x
+committed + 1e-7: 5.6e-6 allowed on config 2 against 2.7e-6 committed) more than half its slack; a float32 model of the helper with the hardware's log2 and exp2
+each a unit in the last place off predicts about 4."""
+import math
+import struct
+
+import numpy as np
+import pytest
+
+from conftest import assert_radiance_close
+from helpers import oracle_camera, oracle_for
+
+
+def _bits(x):
+    return struct.unpack("<I", struct.pack("<f", x))[0]
+
+
+def _float(b):
+    return struct.unpack("<f", struct.pack("<I", b))[0]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from araytracingjourney_amd import renderer
+    r = renderer.Renderer((64, 64))
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def R():
+    from araytracingjourney_amd import renderer
+    return renderer
+
+
+@pytest.mark.gpu
+def test_pow22_on_every_texel_value(ctx):
+    """every bit pattern from 0 to 2.0f (2^30 + 1 inputs): where libm's result is at least 2^-100 the helper is within 8 ulp of it, and the result's class is libm's
+    everywhere -- also where x^2.2 underflows: libm's pow returns 0 below x = 0x1d9aa2a3 (4.09e-21) and the smallest denormal from there on, and the helper takes such an x
+    for 0 (without that, round-to-nearest gives the denormal from 2.99e-21 on: 3 732 124 inputs of another class)"""
+    got = ctx.radiance_sweep(0, 0, _bits(2.0) + 1, 1)
+    worst = None if got["worst_bits"] is None else _float(got["worst_bits"])
+    print(f"\npow22_texel against powf(x, 2.2f) on [0, 2]: {got}, worst input {worst!r}")
+    assert got["max_ulps"] <= 8
+    assert got["class_mismatches"] == 0, f"{got['class_mismatches']} inputs whose result class differs, the first {got['first_class_bits']:#010x}"
+
+
+@pytest.mark.gpu
+def test_pow22_class_on_what_a_texel_can_hold(ctx):
+    """a texel channel is a bilinear blend of bytes / 255: zero, or at least 2^-8 times a product of two float32 weights, each zero or at least 2^-24 -- nothing between 0 and
+    2^-56.  From 2^-64 (x^2.2 = 2^-140.8: a denormal on both sides) to 2.0f, and at 0, the class is libm's and the distance at most 8 ulp"""
+    lo = _bits(2.0 ** -64)
+    got = ctx.radiance_sweep(0, lo, _bits(2.0) - lo + 1, 1)
+    print(f"\npow22_texel against powf(x, 2.2f) on [2^-64, 2]: {got}")
+    assert got["class_mismatches"] == 0 and got["max_ulps"] <= 8
+    assert ctx.radiance_sweep(0, 0, 1, 1)["class_mismatches"] == 0
+
+
+@pytest.mark.gpu
+def test_pow22_is_exact_at_zero_and_one_and_passes_nan(ctx):
+    """0 -> 0 and 1 -> 1 exactly (libm's pow gives both, so a distance of 0 is equality; 0 is below the distance's floor, so its class -- zero -- is what is checked),
+    NaN -> NaN; a count that is no multiple of the wave; which above 1 is refused"""
+    from araytracingjourney_amd._lib import ArtError
+    one = ctx.radiance_sweep(0, _bits(1.0), 1, 1)
+    assert one == dict(max_ulps=0, worst_bits=None, class_mismatches=0, first_class_bits=None)
+    assert ctx.radiance_sweep(0, 0, 1, 1)["class_mismatches"] == 0            # both zero
+    assert ctx.radiance_sweep(0, 0x7FC00000, 1, 1)["class_mismatches"] == 0   # both NaN
+    part = ctx.radiance_sweep(0, _bits(0.25), 1000, 1)
+    assert part["class_mismatches"] == 0 and part["max_ulps"] <= 8
+    with pytest.raises(ArtError):
+        ctx.radiance_sweep(2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("numerator", [0.5, 1.0, 0.36])
+def test_quotient_candidate_where_nothing_is_denormal(ctx, numerator):
+    """numerator * rcp(b), the candidate for the BRDF's quotients (the kernels still divide: profiles/README.md): for b in [2^-120, 2^120] neither b, 1 / b nor the
+    quotient is denormal, v_rcp_f32 is within 1 ulp and the product rounds once -- at most 2 ulp, the class equal; and the class is the IEEE quotient's at +-0, +-inf and NaN"""
+    lo, hi = _bits(2.0 ** -120), _bits(2.0 ** 120)
+    got = ctx.radiance_sweep(1, lo, (hi - lo) // 7 + 1, 7, numerator)
+    print(f"\n{numerator} * rcp(b) against {numerator} / b, b in [2^-120, 2^120]: {got}")
+    assert got["class_mismatches"] == 0 and got["max_ulps"] <= 2
+    for special in (0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000):
+        assert ctx.radiance_sweep(1, special, 1, 1, numerator)["class_mismatches"] == 0, hex(special)
+
+
+def _frame(r):
+    return {"color": r.read_color().copy(), "depth": r.read_depth().copy(), "normal": r.read_normal().copy(), "shadow_bits": r.read_shadow_bits().copy()}
+
+
+def _traced(R, sc, extent, **kw):
+    r = R.renderer_for_scene(sc, extent, keep_debug=True, **kw)
+    r.upload_state(); r.trace(); r.sync()
+    return r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_lights", [1, 4])
+def test_every_instance_of_the_frame_has_the_same_albedo(R, orc, scenes, get_scene, n_lights):
+    """sponza_like at detail 0.05, 128x72, every primitive textured: the default form, the binary-node packets, the staged frame (k_shade), two frames per launch, a
+    filtered context (a visibility mask, cutoff 0: the instances with the alpha test) and plain_math = 1 give the same colour bit for bit -- no instance kept libm's pow --
+    and the frame is the oracle's: hits, depth, normal and shadow bits to the bit, colour within the radiance tolerance"""
+    sc = get_scene("sponza_like", 0.05)
+    sc = scenes.Scene(sc.name, sc.primitives, sc.camera, scenes.sponza_lights(n_lights))
+    w, h = 128, 72
+    r = _traced(R, sc, (w, h))
+    base, (tuv, ids) = _frame(r), r.read_hits()
+    r.close()
+    frames = {}
+    for name, tuning in (("binary", {"packet_wide": 2}), ("staged", {"frame_form": 2}), ("plain_math", {"plain_math": 1})):
+        r = _traced(R, sc, (w, h), tuning=tuning)
+        frames[name] = _frame(r)
+        r.close()
+    r = R.renderer_for_scene(sc, (w, h), keep_debug=True, frames_in_flight=2)
+    r.set_frames_per_launch(2)
+    r.upload_state()
+    r.set_camera_batch([r.camera_mut(), r.camera_mut()])
+    r.trace(); r.sync()
+    for b in (0, 1):
+        r.set_read_frame(b)
+        frames[f"two_per_launch[{b}]"] = {"color": r.read_color().copy(), "depth": r.read_depth().copy(), "normal": r.read_normal().copy()}
+    r.close()
+    r = R.renderer_for_scene(sc, (w, h), keep_debug=True)
+    r.models_mut()[0].set_mask(0, 0x7F)   # still seen by every ray (the cull masks are 0xFF), but the context now runs the filtered instances
+    r.upload_state(); r.trace(); r.sync()
+    frames["filtered"] = _frame(r)
+    r.close()
+    for name, f in frames.items():
+        for k, v in f.items():
+            assert np.array_equal(v.view(np.uint32), base[k].view(np.uint32)), f"{name}: {k} differs in {int((v.view(np.uint32) != base[k].view(np.uint32)).sum())} words"
+    S, L, nl = oracle_for(orc, sc)
+    ref = S.render(oracle_camera(orc, sc, w, h), L, nl, w, h, threads=8, debug=True)
+    assert np.array_equal(ids, ref["hit_id"]) and (ids[..., 0] >= 0).sum() > w * h // 2
+    assert np.array_equal(tuv.view(np.uint32)[..., :3], ref["hit_tuv"].view(np.uint32)[..., :3])
+    assert np.array_equal(base["shadow_bits"], ref["shadow_bits"])
+    for k in ("depth", "normal"):
+        want = np.asarray(ref[k], dtype=np.float32)
+        assert np.array_equal(base[k].view(np.uint32), want.view(np.uint32)), f"{k}: {int((base[k].view(np.uint32) != want.view(np.uint32)).sum())} words differ from the oracle"
+    assert_radiance_close(base["color"], ref["color"])
+
+
+def _black_and_white_quad(scenes):
+    """one quad under a 2 x 2 albedo texture of black and white texels: bilinear blends run from exactly 0 to exactly 1"""
+    tex = np.zeros((3, 2, 2, 4), np.uint8)
+    tex[0, 0, 0] = tex[0, 1, 1] = (255, 255, 255, 255)
+    tex[0, 0, 1] = tex[0, 1, 0] = (0, 0, 0, 255)
+    tex[1, ..., 0] = 255; tex[1, ..., 1] = 128
+    tex[2, ..., :] = (128, 128, 255, 255)
+    mb = scenes.MeshBuilder()
+    mb.add([(-0.8, -0.6, 0.5), (0.8, -0.6, 0.5), (0.8, 0.6, 0.7), (-0.8, 0.6, 0.7)], [(0, 0), (1, 0), (1, 1), (0, 1)], [(0, 0, -1)] * 4, [(1, 0, 0, 1)] * 4, [0, 1, 2, 0, 2, 3])
+    return scenes.Scene("black_and_white", [mb.finish(tex)], dict(pos=(0.0, 0.0, -0.6), dir=(0.0, 0.0, 1.0), fovy=math.pi / 2, znear=0.1, zfar=1000.0),
+                        [dict(kind="point", pos=(0.3, -0.2, -0.3), color=(6.0, 5.0, 4.0), falloff=4.0, casts_shadows=False)])
+
+
+@pytest.mark.gpu
+def test_black_and_white_texels_shade_finite(R, orc, scenes):
+    """a black and a white texel in view (x = 0: log2 is -inf inside the helper; x = 1): colour is finite everywhere and the oracle's (the quad fills the view and shows the whole texture)"""
+    sc = _black_and_white_quad(scenes)
+    w, h = 64, 64
+    r = _traced(R, sc, (w, h))
+    color, (_, ids) = r.read_color().copy(), r.read_hits()
+    r.close()
+    assert (ids[..., 0] >= 0).sum() > w * h // 4
+    assert np.isfinite(color).all()
+    S, L, nl = oracle_for(orc, sc)
+    ref = S.render(oracle_camera(orc, sc, w, h), L, nl, w, h, threads=2, debug=True)
+    assert_radiance_close(color, ref["color"])
