@@ -230,6 +230,21 @@ __device__ __forceinline__ bool moller_trumbore_flat(const Ray &r, V3 v0, V3 e1,
     return (det != 0.0f) & (u >= -ART_BARY_EPS) & (u <= 1.0f + ART_BARY_EPS) & (v >= -ART_BARY_EPS) & (u + v <= 1.0f + ART_BARY_EPS) & (t > r.tmin) & (t < r.tmax);
 }
 
+// the same test for a packet: the lanes that pass, as a mask (each compare's ballot lands in a scalar register pair, the conjunction is scalar work)
+__device__ __forceinline__ uint64_t moller_trumbore_mask(const Ray &r, V3 v0, V3 e1, V3 e2, float &t, float &u, float &v) {
+    V3 p = cross3(r.d, e2);
+    float det = dot3(e1, p);
+    float inv = 1.0f / det;
+    V3 tv = r.o - v0;
+    u = dot3(tv, p) * inv;
+    V3 q = cross3(tv, e1);
+    v = dot3(r.d, q) * inv;
+    t = dot3(e2, q) * inv;
+    return __builtin_amdgcn_ballot_w64(det != 0.0f) & __builtin_amdgcn_ballot_w64(u >= -ART_BARY_EPS) & __builtin_amdgcn_ballot_w64(u <= 1.0f + ART_BARY_EPS) &
+           __builtin_amdgcn_ballot_w64(v >= -ART_BARY_EPS) & __builtin_amdgcn_ballot_w64(u + v <= 1.0f + ART_BARY_EPS) & __builtin_amdgcn_ballot_w64(t > r.tmin) &
+           __builtin_amdgcn_ballot_w64(t < r.tmax);
+}
+
 constexpr int kLdsStack = 16;   // per-lane short stack in LDS ([entry][lane], conflict-free); deeper entries spill to scratch
 constexpr int kOvfStack = 80;   // 16 + 80 >= the deepest possible radix tree (63 key bits + 32 index bits)
 constexpr int kBlock = 256;
@@ -407,8 +422,19 @@ __device__ __forceinline__ V3 ao_dir(V3 N, float tx, float ty, float tz);
 
 __device__ __forceinline__ void ao_ray(const CameraArg &cam, uint32_t W, uint32_t H, uint32_t x, uint32_t y, float depth, float4 nm, uint32_t smp, V3 &o, V3 &d);
 
+// the same value, but the compiler cannot know it: what is computed from it is computed again instead of being kept in registers.
+// (A "memory" clobber would do that too, and would turn every wave-uniform node fetch after it from a scalar into a vector load.)
+__device__ __forceinline__ uint32_t launder(uint32_t v) { asm volatile("" : "+s"(v)); return v; }   // wave-uniform values
+__device__ __forceinline__ uint32_t launder_v(uint32_t v) { asm volatile("" : "+v"(v)); return v; } // per-lane values
 // v_cmp straight into an SGPR pair (HIP's __ballot(int) goes through v_cndmask + v_cmp_ne)
 __device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// Only of a bare compare, though: the ballot of any other predicate -- a conjunction, a value that met another at the end of a branch -- is re-made on the vector unit
+// (v_cndmask 0, 1 and v_cmp_ne).  The packet walks therefore keep what they know about lanes as MASKS -- one ballot per compare, combined on the scalar unit -- and change
+// the per-lane ray state with selects that take a mask and write the register they read: x = lane in m ? y : x.  (Written as C++ selects, the closest-hit state had two
+// definitions per loop trip and five register copies behind every triangle step.)  m is always the result of a scalar operation, never a v_cmp's own destination.
+__device__ __forceinline__ void sel(float &x, float y, uint64_t m) { asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(x) : "v"(y), "s"(m)); }
+__device__ __forceinline__ void sel(uint32_t &x, uint32_t y, uint64_t m) { asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(x) : "v"(y), "s"(m)); }
+__device__ __forceinline__ void sel_off(float &x, uint64_t m) { asm("v_cndmask_b32_e64 %0, %0, -1.0, %1" : "+v"(x) : "s"(m)); }   // x = lane in m ? -1 : x
 
 // streaming records (hits, shadow rays, contributions, frame outputs) are written once and read once: non-temporal accesses keep
 // them from pushing the BVH out of the 4 MB L2s that the walks of all the frames in flight live in
@@ -478,8 +504,16 @@ __device__ __forceinline__ PacketHints hints_seed(int *stk, uint32_t w0, uint32_
     if (w0 < n_leaves) { if (lane0) stk[h.sp] = h.cur; h.sp++; h.cur = (int)~w0; }
     return h;
 }
-template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false, bool HINTS = false>   // HINTS: an any-hit walk that takes and leaves hints
-__device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
+// ON: what the walk knows its live lanes by -- uint64_t, their mask (the form described at sel()), or bool, a predicate per lane and C++ selects: the form every instance had
+// before, kept for the instances whose register allocation the mask form moves (kFrameMoves).  The same compares on the same values either way: no bit differs.
+// What a triangle step of the mask form changes in the ray state: who (m) and to what.  The predicate form has no such state (NoUpdate), and the variable lives at the
+// walk's scope, not the loop's: a local of the loop's scope, even an empty one, gives the loop's exits a block of their own, and the alpha-test instances' any-hit walks
+// then compile to more instructions than the parent commit's (7 224 -> 7 278 in k_frame<true, true, true, true, true>).
+struct StepUpdate { uint64_t m = 0ull; float t, u, v; uint32_t pos, gid; };
+struct NoUpdate {};
+template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false, bool HINTS = false, class ON>   // HINTS: an any-hit walk that takes and leaves hints
+__device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, ON &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
+    constexpr bool MASKS = std::is_same<ON, uint64_t>::value;
     int cur = HINTS ? h.cur : 0, sp = HINTS ? h.sp : 0; // wave-uniform
     constexpr int kPop = kAbsentChild;
     // ray visibility masks: the cull mask of this walk's rays, a kernel argument; rays with a cull mask of 0 see nothing
@@ -492,10 +526,12 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
 #ifdef ART_PACKET_PROF
     if (HINTS) hints_left_ = sp;   // (every seeded hint put one reference on the stack)
 #endif
+    typename std::conditional<MASKS, StepUpdate, NoUpdate>::type up;   // a step's changes to the ray state (set by a triangle step, read only where up.m says so)
     for (;;) {
 #ifdef ART_PACKET_PROF
         const unsigned long long tk0_ = __builtin_amdgcn_s_memtime(); const bool was_node_ = cur >= 0;
 #endif
+        if constexpr (MASKS) up.m = 0ull;
         if (COUNT) steps++; // wave-uniform: nodes + triangles the packet visited (the fused frame's wave plan feeds on it; one s_add here costs 3.5 %, so only sampled frames count)
         if (cur >= 0 && WIDE) {
             // 4-wide node, float boxes (128 B, two scalar loads).  Its children were sorted at build time along the axis `ax` their centroids spread
@@ -522,7 +558,9 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
 #endif
             const uint32_t ax = __float_as_uint(w7.y);                   // 0..2 (wave-uniform)
             // mixed packets (OCT 8) go by the majority sign on that axis
-            const bool rev = OCT < 8 ? ((OCT >> ax) & 1) != 0 : 2 * (int)__popcll(ballot64(on && (ax == 0 ? r.inv.x : (ax == 1 ? r.inv.y : r.inv.z)) < 0.0f)) > (int)__popcll(ballot64(on));
+            bool rev = ((OCT >> ax) & 1) != 0;
+            if constexpr (OCT >= 8 && MASKS) rev = 2 * (int)__popcll(on & ballot64((ax == 0 ? r.inv.x : (ax == 1 ? r.inv.y : r.inv.z)) < 0.0f)) > (int)__popcll(on);
+            else if constexpr (OCT >= 8) rev = 2 * (int)__popcll(ballot64(on && (ax == 0 ? r.inv.x : (ax == 1 ? r.inv.y : r.inv.z)) < 0.0f)) > (int)__popcll(ballot64(on));
             const bool lane0 = (threadIdx.x & 63u) == 0;
             int next = kPop;
             if (!rev) { // near -> far = 0,1,2,3: stack the far ones first
@@ -574,43 +612,86 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
                 float te = 0.f, t = 0.f, u = 0.f, v = 0.f;
                 // accept() = slab(AABB(tri)) AND Moeller-Trumbore: the conjunction is evaluated triangle test first -- the parent already
                 // tested this very box for the packet, so nearly every wave would pay for the slab, while few lanes survive the triangle test
-                bool acc = moller_trumbore_flat(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v) && on;
-                if (acc) acc = slab_oct<OCT>(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te);
-                // the alpha test: the triangle is wave-uniform, so its leaf bit, its shading record's uv and primitive id and that primitive's cutoff
-                // are scalar loads, made only when the bit is set and some lane took the candidate; then the lanes that did fetch their four texels
-                const auto alpha_keep = [&](bool cand) -> bool {
-                    if (!ALPHA || ballot64(cand) == 0ull || !flagged()) return cand;
-                    ConstQuads sq = const_quads(a.shade_tris + pos);
-                    const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
-                    const Words P = (Words)(uintptr_t)(a.prims + __float_as_uint(s8.z));
-                    const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
-                    if (!(c > 0.0f)) return cand;
-                    const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
-                    if (cand) cand = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
-                    return cand;
-                };
-                // the ray state changes through selects, outside the divergent branches (no register copies around them)
-                if (ANY) { // first accepted triangle: this lane is done
-                    if (ALPHA) acc = alpha_keep(acc);
-                    bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest;
-                    // a triangle that occluded some ray is next frame's hint (only accepting triangles are kept, so a hint that accepted nothing is forgotten after one frame)
-                    if (HINTS && ballot64(acc) != 0ull) { if ((threadIdx.x & 63u) == 0) stk[kPacketStack + (h.n & 3u)] = (int)pos; h.n++; }
-                }
-                else {
-                    float teff;   // = fmaxf(t, te): one v_max_f32 (fmaxf first quiets both operands, which are the results of arithmetic here: two more instructions a step)
-                    asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
-                    uint32_t gid = __float_as_uint(td.w);
-                    bool better = acc & ((teff < tbest) | ((teff == tbest) & (gid < bgid))); // (bitwise: three compares and three mask operations, no nested exec regions)
-                    if (ALPHA) better = alpha_keep(better);   // (only a candidate that would win is tested: a cut one that would lose changes nothing)
-                    tbest = better ? teff : tbest; bu = better ? u : bu; bv = better ? v : bv; bpos = better ? pos : bpos; bgid = better ? gid : bgid;
-                }
+                if constexpr (MASKS) {
+                    uint64_t acc = moller_trumbore_mask(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v) & on;
+                    if (acc != 0ull) acc &= ballot64(slab_oct<OCT>(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te));   // (a wave-uniform branch: te is only read where acc is set)
+                    // the alpha test: the triangle is wave-uniform, so its leaf bit, its shading record's uv and primitive id and that primitive's cutoff
+                    // are scalar loads, made only when the bit is set and some lane took the candidate; then the lanes that did fetch their four texels
+                    const auto alpha_keep = [&](uint64_t cand) -> uint64_t {
+                        if (!ALPHA || cand == 0ull || !flagged()) return cand;
+                        ConstQuads sq = const_quads(a.shade_tris + pos);
+                        const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+                        const Words P = (Words)(uintptr_t)(a.prims + __float_as_uint(s8.z));
+                        const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
+                        if (!(c > 0.0f)) return cand;
+                        const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
+                        bool keep = __builtin_amdgcn_inverse_ballot_w64(cand);
+                        if (keep) keep = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
+                        return cand & ballot64(keep);
+                    };
+                    // the ray state itself changes behind the step (below): here only who changes, and to what
+                    if (ANY) { // first accepted triangle: this lane is done
+                        if (ALPHA) acc = alpha_keep(acc);
+                        up.m = acc; up.pos = pos; on &= ~acc;
+                        // a triangle that occluded some ray is next frame's hint (only accepting triangles are kept, so a hint that accepted nothing is forgotten after one frame)
+                        // (the count is wave-uniform and stays in a scalar register: the ring index is scalar arithmetic)
+                        if (HINTS && acc != 0ull) { const uint32_t n = launder(h.n); if ((threadIdx.x & 63u) == 0) stk[kPacketStack + (n & 3u)] = (int)pos; h.n = n + 1u; }
+                    }
+                    else {
+                        float teff;   // = fmaxf(t, te): one v_max_f32 (fmaxf first quiets both operands, which are the results of arithmetic here: two more instructions a step)
+                        asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
+                        uint32_t gid = __float_as_uint(td.w);
+                        uint64_t better = acc & (ballot64(teff < tbest) | (ballot64(teff == tbest) & ballot64(gid < bgid))); // three compares and three mask operations
+                        if (ALPHA) better = alpha_keep(better);   // (only a candidate that would win is tested: a cut one that would lose changes nothing)
+                        up.m = better; up.t = teff; up.u = u; up.v = v; up.pos = pos; up.gid = gid;
+                    }
 #ifdef ART_PACKET_PROF
-                { uint64_t am_ = ballot64(acc); pp_[2]++; pp_[3] += from_stack_; pp_[4] += am_ != 0ull; pp_[5] += __popcll(am_); }
-                if (ANY && hints_left_ > 0) { pp_[10]++; pp_[11] += ballot64(on) == 0ull; hints_left_--; }
+                    { uint64_t am_ = acc; pp_[2]++; pp_[3] += from_stack_; pp_[4] += am_ != 0ull; pp_[5] += __popcll(am_); }
+                    if (ANY && hints_left_ > 0) { pp_[10]++; pp_[11] += on == 0ull; hints_left_--; }
 #endif
-                if (ANY && ballot64(on) == 0ull) break; // every ray of the packet is occluded
+                } else {   // the same step on per-lane predicates
+                    bool acc = moller_trumbore_flat(r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v) && on;
+                    if (acc) acc = slab_oct<OCT>(r, tc.y, tc.z, tc.w, td.x, td.y, td.z, tbest, te);
+                    const auto alpha_keep = [&](bool cand) -> bool {
+                        if (!ALPHA || ballot64(cand) == 0ull || !flagged()) return cand;
+                        ConstQuads sq = const_quads(a.shade_tris + pos);
+                        const float4 s2 = sq[2], s3 = sq[3], s8 = sq[8];
+                        const Words P = (Words)(uintptr_t)(a.prims + __float_as_uint(s8.z));
+                        const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
+                        if (!(c > 0.0f)) return cand;
+                        const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
+                        if (cand) cand = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
+                        return cand;
+                    };
+                    // the ray state changes through selects, outside the divergent branches (no register copies around them)
+                    if (ANY) { // first accepted triangle: this lane is done
+                        if (ALPHA) acc = alpha_keep(acc);
+                        bpos = acc ? pos : bpos; on = on && !acc; tbest = acc ? -1.0f : tbest;
+                        if (HINTS && ballot64(acc) != 0ull) { if ((threadIdx.x & 63u) == 0) stk[kPacketStack + (h.n & 3u)] = (int)pos; h.n++; }
+                    }
+                    else {
+                        float teff;
+                        asm("v_max_f32 %0, %1, %2" : "=v"(teff) : "v"(t), "v"(te));
+                        uint32_t gid = __float_as_uint(td.w);
+                        bool better = acc & ((teff < tbest) | ((teff == tbest) & (gid < bgid))); // (bitwise: three compares and three mask operations, no nested exec regions)
+                        if (ALPHA) better = alpha_keep(better);
+                        tbest = better ? teff : tbest; bu = better ? u : bu; bv = better ? v : bv; bpos = better ? pos : bpos; bgid = better ? gid : bgid;
+                    }
+#ifdef ART_PACKET_PROF
+                    { uint64_t am_ = ballot64(acc); pp_[2]++; pp_[3] += from_stack_; pp_[4] += am_ != 0ull; pp_[5] += __popcll(am_); }
+                    if (ANY && hints_left_ > 0) { pp_[10]++; pp_[11] += ballot64(on) == 0ull; hints_left_--; }
+#endif
+                }
+                if constexpr (!MASKS) { if (ANY && ballot64(on) == 0ull) break; } // every ray of the packet is occluded (the mask form: below, behind the change to the ray state)
             }
             cur = kPop;
+        }
+        // The ray state changes here, in one place on the way to the next step, through in-place selects under the step's mask: the loop-carried registers have this one
+        // definition, and a step that changed no ray (a node step, most triangle steps) passes it by on a scalar branch.  (Inside the triangle step the new values met the
+        // node step's unchanged ones at the end of the branch in registers of their own, and five copies brought them home.)
+        if constexpr (MASKS) if (up.m != 0ull) {
+            if (ANY) { sel(bpos, up.pos, up.m); sel_off(tbest, up.m); if (on == 0ull) break; }   // (every ray of the packet is occluded: the walk ends)
+            else { sel(tbest, up.t, up.m); sel(bu, up.u, up.m); sel(bv, up.v, up.m); sel(bpos, up.pos, up.m); sel(bgid, up.gid, up.m); }
         }
         if (cur == kPop) {
             if (sp == 0) break;
@@ -630,14 +711,26 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, bo
 }
 
 // one packet through the walk that fits its rays' direction signs
-template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false, bool HINTS = false>
-__device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, bool &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
-    uint64_t act = ballot64(on);
-    if (act == 0ull) return;
-    // direction signs per axis: all set, none set, or mixed over the packet's rays
-    uint64_t nx = ballot64(on && r.inv.x < 0.0f), ny = ballot64(on && r.inv.y < 0.0f), nz = ballot64(on && r.inv.z < 0.0f);
-    bool uniform = (nx == 0ull || nx == act) && (ny == 0ull || ny == act) && (nz == 0ull || nz == act);
-    int oct = !uniform ? 8 : (nx ? 1 : 0) | (ny ? 2 : 0) | (nz ? 4 : 0);
+template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false, bool HINTS = false, bool MASKS = true>   // MASKS: the walk in its mask form (packet_walk's ON)
+__device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, bool alive, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
+    typename std::conditional<MASKS, uint64_t, bool>::type on;
+    int oct;
+    if constexpr (MASKS) {
+        on = ballot64(alive);   // the packet's live lanes: a mask from here on (an any-hit walk takes lanes out of it)
+        const uint64_t act = on;
+        if (act == 0ull) return;
+        // direction signs per axis: all set, none set, or mixed over the packet's rays -- three compares, the rest is scalar work
+        uint64_t nx = act & ballot64(r.inv.x < 0.0f), ny = act & ballot64(r.inv.y < 0.0f), nz = act & ballot64(r.inv.z < 0.0f);
+        bool uniform = (nx == 0ull || nx == act) && (ny == 0ull || ny == act) && (nz == 0ull || nz == act);
+        oct = !uniform ? 8 : (int)(launder(nx ? 2u : 0u) >> 1) | (ny ? 2 : 0) | (nz ? 4 : 0);   // ("nx ? 1 : 0" widens a predicate, which is done on the vector unit)
+    } else {
+        on = alive;
+        uint64_t act = ballot64(on);
+        if (act == 0ull) return;
+        uint64_t nx = ballot64(on && r.inv.x < 0.0f), ny = ballot64(on && r.inv.y < 0.0f), nz = ballot64(on && r.inv.z < 0.0f);
+        bool uniform = (nx == 0ull || nx == act) && (ny == 0ull || ny == act) && (nz == 0ull || nz == act);
+        oct = !uniform ? 8 : (nx ? 1 : 0) | (ny ? 2 : 0) | (nz ? 4 : 0);
+    }
     switch (oct) {
     case 0: packet_walk<ANY, WIDE, 0, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
     case 1: packet_walk<ANY, WIDE, 1, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
@@ -1800,10 +1893,6 @@ __global__ __launch_bounds__(kBlock) void k_shade(FrameArgs a) {
 // latency and ALU of the shading), which is what the staged frame needed a dozen frames in flight for.  The arithmetic and its
 // order are the staged kernels': the frames are bit-identical.  pix_bits[p]: bit i = light i shadowed, bit 16+i = shadow ray
 // traced (art_get_stats counts rays from it on demand; art_read_shadow_bits).
-// the same value, but the compiler cannot know it: what is computed from it is computed again instead of being kept in registers.
-// (A "memory" clobber would do that too, and would turn every wave-uniform node fetch after it from a scalar into a vector load.)
-__device__ __forceinline__ uint32_t launder(uint32_t v) { asm volatile("" : "+s"(v)); return v; }   // wave-uniform values
-__device__ __forceinline__ uint32_t launder_v(uint32_t v) { asm volatile("" : "+v"(v)); return v; } // per-lane values
 // what lane `__lane_id()` of wave item `wid` traces: local pixel id, frame coordinates, whether the item's cell mask covers it; returns "traces a ray"
 __device__ __forceinline__ bool frame_pixel(const FrameArgs &a, uint32_t wid, uint32_t &p, uint32_t &x, uint32_t &y, bool &mine) {
     // wave-uniform, read-only tables: constant address space, so these stay scalar loads behind the frame's stores too (no divisions either)
@@ -1840,20 +1929,50 @@ template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constex
 // profiles/exact_math_kres_{parent,new}.txt, profiles/README.md "exact 1/sqrt").  Those compile the plain expressions, as before.  Any subset is the same frame: the fast
 // paths change no bit.
 template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr bool kFrameFastMath = ONE_LIGHT && !BATCH && !ALPHA;
+// Which of the instruction-saving forms an instance of k_frame takes.  Bit 0: the packet walks in their mask form (sel(), packet_walk's ON).  Bits 1-5: the phases that read
+// their kernel arguments again (frame_args_again) -- 1 the hit record and the depth / normal outputs, 2 the surface (with 1), 3 each light and its hints, 4 the hint entry
+// behind a shadow walk, 5 the colour outputs.  Every form computes the same bits, so any subset is the same frame; an instance takes the largest subset that leaves its
+// register allocation (VGPRs, scratch, spills, occupancy; no more SGPRs) exactly where it was, and none (0: the parent commit's code, instruction for instruction) where
+// that subset left it with more v_readlane / v_writelane or more vector instructions than it had: eight instances with several frames per launch.  How the table was made:
+// all 64 subsets compiled for all 32 instances with -DART_MOVES_FORCE=n, the largest subset whose resource line is the parent's taken, the mask form first; then every
+// instance counted against the parent (profiles/moves_static_all.txt) and the eight set to 0 by hand.  tools/moves_sweep.py does the compiling and the counting and applies
+// all of these conditions at once, but prefers the FEWEST vector instructions, so it may print another table that is as valid; this one is the one that was measured
+// (profiles/README.md "moves").  23 of the 32 take the mask form, 15 everything; the default instance and its step-counting sibling take the mask form and phases 1 and 4 --
+// with the surface or the light read again they spill seven vector registers.  Indexed by WIDE << 4 | ONE_LIGHT << 3 | COUNT << 2 | BATCH << 1 | ALPHA.
+constexpr uint8_t kFrameMovesTable[32] = {55, 63, 63, 63, 55, 63, 0, 0, 49, 55, 63, 0, 49, 63, 63, 56, 31, 63, 63, 0, 63, 63, 63, 63, 19, 63, 0, 0, 19, 63, 0, 0};
+#ifdef ART_MOVES_FORCE
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr uint32_t kFrameMoves = ART_MOVES_FORCE;   // (the sweep that made the table)
+#else
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr uint32_t kFrameMoves = kFrameMovesTable[WIDE << 4 | ONE_LIGHT << 3 | COUNT << 2 | BATCH << 1 | ALPHA];
+#endif
+// The kernel's arguments, looked at again: k_frame's phases -- the camera ray, the surface, every light, the outputs -- each read what they need of FrameArgs from the
+// kernel-argument segment where they need it, through the constant address space (scalar loads that hit the scalar cache and stay scalar behind the frame's stores, like
+// ConstQuads), instead of through `a`, whose fields the compiler loads once at the top and then parks across the walks in the lanes of a vector register (v_writelane /
+// v_readlane, up to 86 of them in an instance).  The laundered pointer is what keeps a phase's loads from being merged with an earlier phase's.
+__device__ __forceinline__ const FrameArgs &frame_args_again(const FrameArgs &a) {
+#ifdef __HIP_DEVICE_COMPILE__
+    __attribute__((address_space(4))) const char *p = (__attribute__((address_space(4))) const char *)__builtin_amdgcn_kernarg_segment_ptr();   // FrameArgs is k_frame's first argument
+    asm volatile("" : "+s"(p));
+    return *(const FrameArgs *)p;
+#else
+    return a;   // (host pass of the compiler only)
+#endif
+}
 template <bool WIDE, bool ONE_LIGHT, bool COUNT = false, bool BATCH = false, bool ALPHA = false>   // WIDE: the 128-byte 4-wide nodes (the default) | the 64-byte binary nodes; ALPHA: the alpha test
-__global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_frame(FrameArgs a) {
+__global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_frame(FrameArgs a_) {
     // One wave per workgroup: the waves of a frame are independent (nothing is shared, no barrier), and a workgroup of four held its LDS and its place
     // in the dispatcher's books until its slowest wave was done -- packets differ 25x in steps.  Single-wave groups: +2.5 % rays/s (profiles/README.md r2).
     __shared__ int wstack[kPacketStack + 4];   // + the ring of a shadow walk's accepting leaf positions (PacketHints)
     constexpr bool HINTS = kFrameHints<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     constexpr bool FASTM = kFrameFastMath<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
+    constexpr uint32_t MV = kFrameMoves<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     int *stk = wstack;
     const uint32_t wid = blockIdx.x;
-    if (wid >= a.n_wave_items) return;
+    if (wid >= a_.n_wave_items) return;
     uint32_t steps = 0; // packet steps of this wave, all walks
     const uint32_t fb = BATCH ? blockIdx.y : 0u;   // which frame of the launch (wave-uniform)
-    const CameraArg &cam = (BATCH && fb) ? a.cam_more[fb - 1] : a.cam;
-    const size_t frame_px = (size_t)fb * a.W * a.H, frame_local = (size_t)fb * a.n_local;
+    const CameraArg &cam0 = (BATCH && fb) ? a_.cam_more[fb - 1] : a_.cam;
+    const size_t frame_px = (size_t)fb * a_.W * a_.H, frame_local = (size_t)fb * a_.n_local;
     // The pixel a lane works on is looked up again wherever it is needed (here, at the depth/normal stores, at the end) instead of being
     // carried through the walks: the walks run at the 64-register edge.
     bool in;
@@ -1863,20 +1982,23 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
 #endif
     {
         uint32_t p, x, y; bool mine;
-        in = frame_pixel(a, wid, p, x, y, mine);
+        in = frame_pixel(a_, wid, p, x, y, mine);
         float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
-        float dx = (fx / (float)a.W) * 2.0f - 1.0f, dy = (fy / (float)a.H) * 2.0f - 1.0f;
-        V3 org = mat4_mul(cam.view_inv, 0.f, 0.f, 0.f, 1.f);
-        V3 tgt = nrm3<FASTM>(mat4_mul(cam.proj_inv, dx, dy, 1.f, 1.f), a.plain_math);
-        V3 dir = mat4_mul(cam.view_inv, tgt.x, tgt.y, tgt.z, 0.f);
+        float dx = (fx / (float)a_.W) * 2.0f - 1.0f, dy = (fy / (float)a_.H) * 2.0f - 1.0f;
+        V3 org = mat4_mul(cam0.view_inv, 0.f, 0.f, 0.f, 1.f);
+        V3 tgt = nrm3<FASTM>(mat4_mul(cam0.proj_inv, dx, dy, 1.f, 1.f), a_.plain_math);
+        V3 dir = mat4_mul(cam0.view_inv, tgt.x, tgt.y, tgt.z, 0.f);
         ray_init(r, org, dir, 0.001f, 10000.0f);
     }
     bool on = in && ray_finite(r.o, r.d);
     PHASE(0, r.inv.x)
     float tbest = on ? r.tmax : -1.0f, bu = 0.f, bv = 0.f;
     uint32_t bpos = kNoHit, bgid = kNoHit;
-    { PacketHints none{0, 0, 0u}; walk_dispatch<false, WIDE, COUNT, ALPHA>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, none); }   // (closest-hit walks take no hints)
+    { PacketHints none{0, 0, 0u}; walk_dispatch<false, WIDE, COUNT, ALPHA, false, (MV & 1u) != 0u>(a_, r, on, stk, tbest, bu, bv, bpos, bgid, steps, none); }   // (closest-hit walks take no hints)
     PHASE(1, tbest)
+    const FrameArgs &a = (MV & 2u) ? frame_args_again(a_) : a_;   // the hit record, the depth and normal outputs
+    const FrameArgs &as = (MV & 4u) ? a : a_;                      // the surface
+    const CameraArg &cam = (BATCH && fb) ? as.cam_more[fb - 1] : as.cam;
     uint32_t p, x, y; bool mine;
     frame_pixel(a, wid, p, x, y, mine);
     if (a.keep_hits && mine) a.hits[frame_local + p] = bpos != kNoHit ? make_float4(tbest, bu, bv, __uint_as_float(bpos)) : make_float4(10000.0f, 0.f, 0.f, __uint_as_float(kNoHit));
@@ -1886,7 +2008,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     Surface S;
     S.world_pos = mk(0.f, 0.f, 0.f); S.N = mk(0.f, 0.f, 1.f); S.Vv = mk(0.f, 0.f, 1.f); S.albedo = mk(0.f, 0.f, 0.f);
     S.metallic = 0.f; S.alpha = 0.f; S.nc_NdotV = 0.f; S.NdotV = 0.f;
-    if (hit) shade_surface<FASTM, ONE_LIGHT && !BATCH && ALPHA>(a, cam, bpos, bu, bv, S, out_depth, out_normal);
+    if (hit) shade_surface<FASTM, ONE_LIGHT && !BATCH && ALPHA>(as, cam, bpos, bu, bv, S, out_depth, out_normal);
     if (in) {
         const size_t pix = frame_px + (size_t)y * a.W + x;
         st_nt(&a.depth[pix], out_depth);
@@ -1896,20 +2018,21 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     float rx = 0.f, ry = 0.f, rz = 0.f;
     uint32_t sbits = 0, more = 0;
     // (until the walks fetched their nodes into SGPRs the multi-light instance parked the surface record in LDS across each shadow walk; it fits now)
-    for (uint32_t i = 0; i < (ONE_LIGHT ? 1u : a.n_lights); i++) { // uniform loop: the shadow packet needs the whole wave
+    for (uint32_t i = 0; i < (ONE_LIGHT ? 1u : a_.n_lights); i++) { // uniform loop: the shadow packet needs the whole wave
+        const FrameArgs &b = (MV & 8u) ? frame_args_again(a_) : a_;   // this light, its hints
         // the block's shadow-occluder hints for this light slot (FrameArgs::hints): one wave-uniform 16-byte load through the constant address space; the parts of a split
         // block share their block's entry.  Hints off (null table): the walk starts at the root with nothing in front of it, and nothing is stored.
         PacketHints hn{0, 0, 0u};
         typedef uint32_t U4 __attribute__((ext_vector_type(4)));
-        if (HINTS && a.hints) {
-            const uint32_t blk = ((__attribute__((address_space(4))) const uint32_t *)(uintptr_t)a.wave_items)[2u * wid];
-            const U4 e = ((__attribute__((address_space(4))) const U4 *)(uintptr_t)a.hints)[blk * kHintLights + (i & (kHintLights - 1u))];
-            hn = hints_seed(stk, e.x, e.y, e.z, e.w, a.hint_leaves);
+        if (HINTS && b.hints) {
+            const uint32_t blk = ((__attribute__((address_space(4))) const uint32_t *)(uintptr_t)b.wave_items)[2u * wid];
+            const U4 e = ((__attribute__((address_space(4))) const U4 *)(uintptr_t)b.hints)[blk * kHintLights + (i & (kHintLights - 1u))];
+            hn = hints_seed(stk, e.x, e.y, e.z, e.w, b.hint_leaves);
         }
         float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f), ro = make_float4(0.f, 0.f, 0.f, 1.0f), rd = make_float4(0.f, 0.f, 1.f, 0.f);
         bool want = false;
-        const ArtLight L = ONE_LIGHT ? a.lights[0] : frame_light(a, i);
-        if (hit) want = shade_light<FASTM>(L, S, a.plain_math, c4, ro, rd);
+        const ArtLight L = ONE_LIGHT ? b.lights[0] : frame_light(b, i);
+        if (hit) want = shade_light<FASTM>(L, S, b.plain_math, c4, ro, rd);
         if (want) { if (i < 16u) sbits |= 1u << (16u + i); else more++; }   // (lights 16.. have no bits of their own: their shadow rays are counted)
         Ray sr;
         if (L.type == 2u) ray_init_inv(sr, mk(ro.x, ro.y, ro.z), ld3(L.area_pos2), ld3(L.area_pos3), 0.01f, L.penumbra_angle); // (wave-uniform branch)
@@ -1919,17 +2042,18 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         float st = son ? sr.tmax : -1.0f, su = 0.f, sv = 0.f;
         uint32_t spos = kNoHit, sgid = kNoHit;
         const uint64_t traced = HINTS ? ballot64(son) : 0ull;
-        walk_dispatch<true, WIDE, COUNT, ALPHA, HINTS>(a, sr, son, stk, st, su, sv, spos, sgid, steps, hn);
-        if (HINTS && a.hints && traced != 0ull) { // (no shadow ray: the entry is left alone -- the idle wave of a split block shares the entry of the block's working parts)
+        walk_dispatch<true, WIDE, COUNT, ALPHA, HINTS, (MV & 1u) != 0u>(b, sr, son, stk, st, su, sv, spos, sgid, steps, hn);
+        const FrameArgs &c = (MV & 16u) ? frame_args_again(a_) : a_;   // where the walk's hints go
+        if (HINTS && c.hints && traced != 0ull) { // (no shadow ray: the entry is left alone -- the idle wave of a split block shares the entry of the block's working parts)
             // the walk's occluders, the most recent first; the entry's address and what it holds now are looked up again (launder: like the pixel, nothing of this is carried
             // through the walk in registers); lane 0 writes them with one plain vector store unless the entry already says so
             uint32_t o[4];
 #pragma unroll
             for (uint32_t k = 0; k < 4u; k++) o[k] = k < hn.n ? (uint32_t)stk[kPacketStack + ((hn.n - 1u - k) & 3u)] : kHintEmpty;
-            const uint32_t blk = ((__attribute__((address_space(4))) const uint32_t *)(uintptr_t)a.wave_items)[2u * launder(wid)];
+            const uint32_t blk = ((__attribute__((address_space(4))) const uint32_t *)(uintptr_t)c.wave_items)[2u * launder(wid)];
             const size_t at = blk * kHintLights + (i & (kHintLights - 1u));
-            const U4 e = ((__attribute__((address_space(4))) const U4 *)(uintptr_t)a.hints)[at];
-            if (((e.x ^ o[0]) | (e.y ^ o[1]) | (e.z ^ o[2]) | (e.w ^ o[3])) != 0u && __lane_id() == 0) reinterpret_cast<uint4 *>(a.hints)[at] = make_uint4(o[0], o[1], o[2], o[3]);
+            const U4 e = ((__attribute__((address_space(4))) const U4 *)(uintptr_t)c.hints)[at];
+            if (((e.x ^ o[0]) | (e.y ^ o[1]) | (e.z ^ o[2]) | (e.w ^ o[3])) != 0u && __lane_id() == 0) reinterpret_cast<uint4 *>(c.hints)[at] = make_uint4(o[0], o[1], o[2], o[3]);
         }
         PHASE(4, st)
         if (want && spos != kNoHit) { // shadowed: the light keeps 0.05 of its contribution (raytrace.rgen.glsl:179-181)
@@ -1940,22 +2064,23 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     }
     if (!in) { rx = 0.f; ry = 0.f; rz = 0.f; }
     float4 o = make_float4(rx, ry, rz, 1.0f);
-    frame_pixel(a, wid, p, x, y, mine);
-    if (in) st_nt(&a.color[frame_px + (size_t)y * a.W + x], o);
-    if (a.color_tiles && mine) { // compact tile buffer for the gather: row-major inside each 32x32 tile
+    const FrameArgs &e = (MV & 32u) ? frame_args_again(a_) : a_;   // the outputs
+    frame_pixel(e, wid, p, x, y, mine);
+    if (in) st_nt(&e.color[frame_px + (size_t)y * e.W + x], o);
+    if (e.color_tiles && mine) { // compact tile buffer for the gather: row-major inside each 32x32 tile
         uint32_t q = p & 1023u, sub = q >> 6, l = q & 63u;
         uint32_t lx = (sub & 3u) * 8u + (l & 7u), ly = (sub >> 2) * 8u + (l >> 3);
-        size_t ti = (size_t)fb * a.tiles_stride + (size_t)(p >> 10) * kTilePixels + ly * kTile + lx;
-        if (a.tiles_packed) __builtin_nontemporal_store(pack_b10g11r11(o.x, o.y, o.z), reinterpret_cast<uint32_t *>(a.color_tiles) + ti);
-        else st_nt_rgb(a.color_tiles, ti, o);
+        size_t ti = (size_t)fb * e.tiles_stride + (size_t)(p >> 10) * kTilePixels + ly * kTile + lx;
+        if (e.tiles_packed) __builtin_nontemporal_store(pack_b10g11r11(o.x, o.y, o.z), reinterpret_cast<uint32_t *>(e.color_tiles) + ti);
+        else st_nt_rgb(e.color_tiles, ti, o);
     }
-    if (mine) a.pix_bits[frame_local + p] = sbits;
-    if (!ONE_LIGHT && a.pix_more && mine) a.pix_more[frame_local + p] = more;   // more than 16 lights: shadow rays of lights 16.. (art_get_stats)
+    if (mine) e.pix_bits[frame_local + p] = sbits;
+    if (!ONE_LIGHT && e.pix_more && mine) e.pix_more[frame_local + p] = more;   // more than 16 lights: shadow rays of lights 16.. (art_get_stats)
     PHASE(5, rx)
 #ifdef ART_PHASE_PROF
     if (__lane_id() == 0 && blockIdx.x < kPhaseWaves) { g_phase[6][blockIdx.x] = 1u; g_phase[7][blockIdx.x] = steps; }
 #endif
-    if (COUNT && __lane_id() == 0) a.wave_cost[wid] = steps; // feedback for the next plan (art_api.hip plan_poll)
+    if (COUNT && __lane_id() == 0) e.wave_cost[wid] = steps; // feedback for the next plan (art_api.hip plan_poll)
 }
 
 // ---- the wave plan, on the device ---------------------------------------------------------------------------------------------------------------------------------
