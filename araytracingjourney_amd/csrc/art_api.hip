@@ -938,7 +938,7 @@ int32_t art_get_stats(ArtContext *c, ArtStats *out) {
 }
 
 // ---- parity / debug surface ------------------------------------------------------------------------------------
-// local pixel p (tile, 8x8 block, lane) -> the frame's (x, y), as the kernels' local_to_xy (art_trace.hip); false: outside the frame (an edge tile)
+// local pixel p (tile, 8x8 block, lane) -> the frame's (x, y), as the kernels' local_to_xy (art_device.h); false: outside the frame (an edge tile)
 static bool local_to_xy(const ArtContext *c, uint32_t p, uint32_t &x, uint32_t &y) {
     const uint32_t tile = c->tile_list[p >> 10], q = p & 1023u, sub = q >> 6, l = q & 63u;
     x = (tile % c->tiles_x) * kTile + (sub & 3u) * 8u + (l & 7u); y = (tile / c->tiles_x) * kTile + (sub >> 2) * 8u + (l >> 3);
@@ -1007,7 +1007,7 @@ int32_t art_write_shadow_hints(ArtContext *c, const uint32_t *words, size_t n_wo
     return ART_OK;
 }
 
-// the guarded fast paths of art_trace.hip (inv_sqrt_exact / sqrt_exact) against the plain expressions over a set of bit patterns (include/art_parity.h)
+// the guarded fast paths of art_device.h (inv_sqrt_exact / sqrt_exact), swept by art_sweeps.hip against the plain expressions over a set of bit patterns (include/art_parity.h)
 int32_t art_parity_math_sweep(ArtContext *c, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint64_t *mismatches, uint32_t *first_bad_bits,
                               uint64_t *fast_lanes, float guard[2]) {
     if (!c || !mismatches || !first_bad_bits || !fast_lanes || !guard) return fail(ART_E_INVALID, "art_parity_math_sweep: null argument");
@@ -1027,7 +1027,7 @@ int32_t art_parity_math_sweep(ArtContext *c, uint32_t which, uint32_t first_bits
     return ART_OK;
 }
 
-// the radiance-only helpers of art_trace.hip (pow22_texel, quotient_rcp) against the expressions they stand for: a distance in ulps and the result classes (include/art_parity.h)
+// the radiance-only helpers (pow22_texel, art_shade.h; quotient_rcp, art_sweeps.hip) against the expressions they stand for: a distance in ulps and the result classes (include/art_parity.h)
 int32_t art_parity_radiance_sweep(ArtContext *c, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numerator, uint32_t *max_ulps, uint32_t *worst_bits,
                                   uint64_t *class_mismatches, uint32_t *first_class_bits) {
     if (!c || !max_ulps || !worst_bits || !class_mismatches || !first_class_bits) return fail(ART_E_INVALID, "art_parity_radiance_sweep: null argument");

@@ -1,6 +1,6 @@
 // art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres; DESIGN.md 3.5 .. 3.9) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h).  Every use of a CastState / CastBlock field is in this file; the kernels are
-// art_trace.hip's and art_resolve.hip's.
+// art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
 
 // the first cast of a context: its stream (counted against the budget beside kMaxFrameSlots), the cursor blocks and their events

@@ -91,7 +91,7 @@ struct WavePlan {
     uint32_t fixed_steps = 0;          // ArtTuning.split_fixed_steps: a fixed target instead (tests, experiments)
     uint32_t in_flight = 1;            // min(frames in flight, hardware queues)
     std::vector<uint32_t> order;       // launch order of the 256-pixel blocks (setup_frame)
-    // The plan is made ON THE DEVICE (k_plan, art_trace.hip) behind a sampled frame, on that frame's stream: every block's level lives there, the two tables alternate so that
+    // The plan is made ON THE DEVICE (k_plan, art_frame.hip) behind a sampled frame, on that frame's stream: every block's level lives there, the two tables alternate so that
     // frames in flight keep theirs, and the host learns "a new table of n items" from eight pinned words once the event behind the launch has fired.  (Rounds 1-3: counts up, one
     // host thread through 32 640 blocks, table down -- 0.3-0.9 ms inside an art_trace call now and then, ten frames' time; tools/camera_leg_probe.py, profiles/README.md round 4.)
     DevBuf<uint2> d_items[2]; uint32_t n_items[2] = {0, 0}; int cur = 0;

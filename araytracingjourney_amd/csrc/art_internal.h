@@ -80,7 +80,7 @@ constexpr uint32_t kTileRingMax = 8;    // caller-owned compact tile buffers per
 int32_t ring_rewind(ArtContext *ctx);   // art_api.hip: waits for every frame in flight, then the next art_trace is launch 0 again (ring slot 0, first tile buffer)
 void set_last_error(const char *msg);   // art_api.hip: the thread's art_last_error() string, for entry points that live in other files
 
-// ---- launch wrappers (art_build.hip / art_trace.hip) ---------------------------------------------------------
+// ---- launch wrappers (art_build.hip / art_trace.hip, art_frame.hip, art_query.hip, art_sweeps.hip, art_present.hip) ---------------------------------------------------------
 struct BuildInputs {
     const DevPrim *prims; uint32_t n_prims; const uint32_t *prim_first_tri; // device
     uint32_t T; uint32_t morton_bits;
@@ -257,7 +257,7 @@ struct FrameArgs {
     // Ray visibility masks: the cull masks of this launch's rays, primary | shadow << 8 | ao << 16.  Read by the instances with the alpha test only (`alpha` is
     // also set while a primitive has a visibility mask other than 0xFF or one of these is 0); alpha_bits marks the leaves of such primitives too.
     uint32_t ray_masks;
-    bool plain_math;           // ArtTuning.plain_math: the frame's square roots take the plain expressions (art_trace.hip inv_sqrt_exact / sqrt_exact: the fallback, in every wave)
+    bool plain_math;           // ArtTuning.plain_math: the frame's square roots take the plain expressions (art_device.h inv_sqrt_exact / sqrt_exact: the fallback, in every wave)
 };
 constexpr uint32_t kRayMasksAll = 0xFFFFFFu;
 constexpr uint32_t kHintLights = 4;
@@ -274,7 +274,7 @@ void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint
 void math_sweep_guard(float guard[2]);
 // art_parity_radiance_sweep: out = three device words, [0] = max(distance in ulps << 32 | index of that input), [1] += inputs whose result class differs, [2] = min(index of one)
 void launch_radiance_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numer, unsigned long long *out, hipStream_t s);
-// The wave plan of the fused frame, made ON THE DEVICE behind a sampled frame (k_plan, art_trace.hip): from the steps every wave of that launch counted, every 8x8 block's level
+// The wave plan of the fused frame, made ON THE DEVICE behind a sampled frame (k_plan, art_frame.hip): from the steps every wave of that launch counted, every 8x8 block's level
 // (0 one wave | 1 four quadrant waves | 2 sixteen cell waves) and, if a level changed that matters, the next table of wave items.  result (pinned host memory, read once the
 // event behind the launch has fired): [0] items of the new table, [1] 1 = a new table was written, [2] blocks in four, [3] blocks in sixteen, [4] the step target, [5] slowest wave
 struct PlanArgs {

@@ -1,4 +1,4 @@
-// art_plan.hip -- the host side of the fused frame's wave plan (WavePlan, art_context.h; k_plan, art_trace.hip): which wave of a launch traces what, when a frame is
+// art_plan.hip -- the host side of the fused frame's wave plan (WavePlan, art_context.h; k_plan, art_frame.hip): which wave of a launch traces what, when a frame is
 // sampled and when the table its plan wrote is adopted.  Every write of a WavePlan field is in this file.
 #include "art_context.h"
 #include <cstdio>

@@ -4,7 +4,8 @@
 //            colour (read back from the packed image) * ao/255 -> LpmFilter(LPM_CONFIG_709_709) -> pow(1/2.2) -> B8G8R8A8_UNORM
 // LpmSetup is the host-side port of vk_tonemap.rs:122-325 (itself a port of ffx_lpm.h's LpmSetup); LpmMap follows
 // ffx_lpm.h:727-832 with every path flag false (LPM_CONFIG_709_709, ffx_lpm.h:616).
-#include "art_internal.h"
+//   un-tile: gathered shard tiles -> frames (k_untile, k_untile_rgb), at the end.
+#include "art_device.h"
 #include <cmath>
 
 namespace art {
@@ -112,6 +113,60 @@ void launch_present(uint32_t n, const float4 *color, const float4 *normal, const
     for (int k = 0; k < 3; k++) { L.sat[k] = f[k]; L.lumaT[k] = f[6 + k]; L.crosstalk[k] = f[9 + k]; L.rcpLumaT[k] = f[12 + k]; }
     L.contrast = f[3]; L.tsb[0] = f[4]; L.tsb[1] = f[5];
     if (n) k_present<<<(n + 255) / 256, 256, 0, s>>>(n, color, normal, depth, ao, L, pcolor, pnormal, pdepth, bgra);
+}
+
+// ---- un-tile: the root of a sharded run turns the tiles it gathered back into frames (art_untile_gathered_frames, art_api.hip) ----
+// root side of the gather: shard s's j-th tile sits at gathered[(s*padded + j) * 1024]
+// n_frames frames per launch (grid.z): frame z reads its shards' tiles frame_stride tiles further on and writes the z-th output
+// frame.  A thread moves V consecutive pixels of one tile row (16 bytes when the width allows): no divisions, one table lookup.
+template <class T, int V> __global__ __launch_bounds__(kBlock) void k_untile(const T *__restrict__ gathered, const uint32_t *__restrict__ tile_slot, uint32_t shard_stride, uint32_t frame_stride,
+                                                                             uint32_t W, uint32_t H, T *__restrict__ frame) {
+    // A block moves a band of 32 x V pixels by 32 rows = one row of tiles: a thread takes V pixels of four rows of ONE tile (one table
+    // lookup, four independent loads, then four stores).  A quarter of the waves of a row per thread: on a root that keeps tracing,
+    // the un-tile of 20 frames was 162 000 one-kilobyte waves competing with the frames' 82 000 for slots.
+    const uint32_t tiles_x = (W + kTile - 1) / kTile;
+    const uint32_t x = (blockIdx.x * 32u + (threadIdx.x & 31u)) * V, y0 = blockIdx.y * kTile + (threadIdx.x >> 5);
+    if (x >= W || y0 >= H) return;
+    const uint32_t ts = tile_slot[blockIdx.y * tiles_x + x / kTile]; // owner << 24 | index among the owner's tiles (host table, setup_frame)
+    const size_t tile = (size_t)(ts >> 24) * shard_stride + (size_t)blockIdx.z * frame_stride + (ts & 0xFFFFFFu); // shard_stride: tiles between two shards' buffers
+    const T *src = gathered + tile * kTilePixels + (threadIdx.x >> 5) * kTile + (x % kTile);
+    T *dst = frame + (size_t)blockIdx.z * W * H + (size_t)y0 * W + x;
+    struct alignas(sizeof(T) * V) Pack { T v[V]; };
+    Pack p[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) p[i] = *reinterpret_cast<const Pack *>(src + (size_t)i * 8u * kTile); // rows y0, y0 + 8, + 16, + 24 of the tile (padding rows of a bottom tile are readable)
+#pragma unroll
+    for (int i = 0; i < 4; i++) if (y0 + 8u * i < H) *reinterpret_cast<Pack *>(dst + (size_t)i * 8u * W) = p[i];
+}
+
+// the same for RGB32F tiles (12 B per texel) into the RGBA32F frame: alpha = 1, the constant the colour output carries
+__global__ __launch_bounds__(kBlock) void k_untile_rgb(const float *__restrict__ gathered, const uint32_t *__restrict__ tile_slot, uint32_t shard_stride, uint32_t frame_stride,
+                                                       uint32_t W, uint32_t H, float4 *__restrict__ frame) {
+    const uint32_t tiles_x = (W + kTile - 1) / kTile;
+    const uint32_t x = blockIdx.x * 32u + (threadIdx.x & 31u), y0 = blockIdx.y * kTile + (threadIdx.x >> 5);
+    if (x >= W || y0 >= H) return;
+    const uint32_t ts = tile_slot[blockIdx.y * tiles_x + x / kTile];
+    const size_t tile = (size_t)(ts >> 24) * shard_stride + (size_t)blockIdx.z * frame_stride + (ts & 0xFFFFFFu);
+    const float *src = gathered + 3 * (tile * kTilePixels + (threadIdx.x >> 5) * kTile + (x % kTile));
+    float4 *dst = frame + (size_t)blockIdx.z * W * H + (size_t)y0 * W + x;
+    float4 p[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const float *q = src + (size_t)i * 8u * kTile * 3; p[i] = make_float4(q[0], q[1], q[2], 1.0f); }   // rows y0, y0 + 8, + 16, + 24 of the tile
+#pragma unroll
+    for (int i = 0; i < 4; i++) if (y0 + 8u * i < H) dst[(size_t)i * 8u * W] = p[i];
+}
+void launch_untile(const float4 *gathered, const uint32_t *tile_slot, uint32_t shard_stride, uint32_t n_frames, uint32_t frame_stride, uint32_t W, uint32_t H, float4 *frame, hipStream_t s) {
+    dim3 g((W + 31) / 32, (H + kTile - 1) / kTile, n_frames);
+    k_untile_rgb<<<g, kBlock, 0, s>>>(reinterpret_cast<const float *>(gathered), tile_slot, shard_stride, frame_stride, W, H, frame);
+}
+void launch_untile_packed(const uint32_t *gathered, const uint32_t *tile_slot, uint32_t shard_stride, uint32_t n_frames, uint32_t frame_stride, uint32_t W, uint32_t H, uint32_t *frame, hipStream_t s) {
+    if (W % 4 == 0 && ((uintptr_t)frame & 15u) == 0 && ((uintptr_t)gathered & 15u) == 0) { // four pixels (16 bytes) per thread
+        dim3 g((W / 4 + 31) / 32, (H + kTile - 1) / kTile, n_frames);
+        k_untile<uint32_t, 4><<<g, kBlock, 0, s>>>(gathered, tile_slot, shard_stride, frame_stride, W, H, frame);
+    } else {
+        dim3 g((W + 31) / 32, (H + kTile - 1) / kTile, n_frames);
+        k_untile<uint32_t, 1><<<g, kBlock, 0, s>>>(gathered, tile_slot, shard_stride, frame_stride, W, H, frame);
+    }
 }
 
 } // namespace art

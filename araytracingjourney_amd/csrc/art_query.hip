@@ -1,0 +1,520 @@
+// art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest) and
+// swept spheres (k_sweep), each a Source or a candidate policy of art_walk.h's pooled loop, and their launchers.  art_cast.hip is their host side.
+#include "art_walk.h"
+
+namespace art {
+
+// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT), are READ -- two 16-byte loads a lane, 2 KB a wave in one
+// piece.  A dead ray (non-finite origin or direction, NaN tmax: TravBase::start's rule) gets its miss record there and then and never enters the pool.  One walk for every
+// context, whatever ArtTuning says.  Closest hits leave as t,u,v,0 and (primitive, triangle in the primitive): the walk carries the best candidate's gid, tri_prim names its
+// primitive and first_tri that primitive's first gid -- no triangle record, no host.  Any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's
+// record depends on the ray alone.
+struct CastK {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *rays; float4 *tuv; int2 *ids; uint8_t *hit;
+    uint32_t total, chunk, refill, leaf_batch;
+    uint32_t *cursors;        // 8 per-XCD chunk cursors, kCursorStride words apart (zeroed in front of the launch)
+    AlphaView alpha;          // the instances with the mask / alpha test only
+};
+static_assert(kCastCursorWords == 8u * kCursorStride, "a cast's cursor block");
+constexpr int kCastLds = 8;           // per-lane stack entries in LDS
+template <bool ANY> struct CastSource {
+    static constexpr int kFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
+    const CastK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &) const {}
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
+        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+        const bool has = ray_finite(o, d) && r1.w == r1.w;
+        if (!has) {                // a dead ray accepts nothing: its miss record, without a walk
+            if (ANY) a.hit[sidx] = 0;
+            else { a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1); }
+        }
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
+        if (ANY) a.hit[slot] = tr.bpos != kNoHit ? 1 : 0;
+        else if (tr.bgid != kNoHit) {             // the ids, on the device: gid -> primitive (k_soup's table) -> triangle in the primitive
+            const uint32_t prim = a.tri_prim[tr.bgid];
+            a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
+            a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+        } else { a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1); }
+    }
+};
+template <bool ANY, bool ALPHA>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) { pooled_trace<kCastLds, ANY, ALPHA>(a, CastSource<ANY>{a}); }
+
+// The first K hits of each ray, in order (art_cast_rays_multi): the third candidate policy.  The closest walk keeps ONE best candidate; this one keeps a list
+// of up to K entries (t_eff, u, v, gid) a lane in ascending (t_eff, gid) -- in LDS, [entry][lane] like the walk stack, 16 bytes an entry, so the insertion runs on ds_read /
+// ds_write_b128 with the entry index in a register and nothing goes to scratch.  tbest / bgid are the walk's LIMIT: (tmax, none) until the list is full, the K-th entry's pair
+// from then on -- every box test of Trav4 and the leaf's exact slab cull against it as they cull against the best candidate in the closest walk, and a candidate enters iff it
+// is below the limit in the total order, which is the closest walk's comparison, word for word (K = 1 IS the closest walk).  Every triangle sits in one leaf and a walk visits a
+// leaf at most once: no entry can arrive twice, nothing is checked.  Only a candidate that would enter is put to the mask / alpha test.  (step_leaf is TravBase's text up to
+// the candidate's fate: a hook inside TravBase for it would be a change to the code of k_cast and k_trace_ao, whose registers are pinned.)
+template <int KMAX, int LDSN, bool ALPHA> struct TravMulti : Trav4<false, LDSN, ALPHA> {
+    uint32_t K, cnt;   // K: 1..KMAX, wave-uniform; cnt: entries held, 0..K
+    uint4 *list;       // this lane's entry 0; entry j at list[j * kTraceBlock]
+    __device__ __forceinline__ void bind(uint32_t k) {
+        __shared__ uint4 hits[KMAX * kTraceBlock];
+        K = min(max(k, 1u), (uint32_t)KMAX); cnt = 0u; list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+    }
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+        uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // an absent child (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
+        float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];
+        asm volatile("" : "+v"(td.x), "+v"(td.y), "+v"(td.z), "+v"(td.w), "+v"(tc.y), "+v"(tc.z), "+v"(tc.w));
+        float te, t, u, v;
+        if (moller_trumbore(this->r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v)) {
+            if (slab(this->r, tc.y, tc.z, tc.w, td.x, td.y, td.z, this->tbest, te)) {
+                const float teff = fmaxf(t, te);
+                const uint32_t gid = __float_as_uint(td.w);
+                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && (!ALPHA || !alpha_cut(av, pos, u, v))) {
+                    uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
+                    while (j > 0u) {                 // entries above the candidate move up one
+                        const uint4 p = list[(j - 1u) * kTraceBlock];
+                        const float pt = __uint_as_float(p.x);
+                        if (pt < teff || (pt == teff && p.w < gid)) break;
+                        list[j * kTraceBlock] = p; j--;
+                    }
+                    list[j * kTraceBlock] = make_uint4(__float_as_uint(teff), __float_as_uint(u), __float_as_uint(v), gid);
+                    cnt = min(cnt + 1u, K);
+                    if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; this->tbest = __uint_as_float(e.x); this->bgid = e.w; }   // full: the K-th entry is the limit
+                }
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+};
+struct CastMultiK : CastK { uint8_t *count; uint32_t max_hits; };   // tuv / ids: max_hits records a ray, ray-major; count: a byte a ray, or null
+template <int KMAX> struct CastMultiSource {
+    static constexpr int kFields = 12;   // CastSource's
+    const CastMultiK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.bind(a.max_hits); }
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];
+        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+        const bool has = ray_finite(o, d) && r1.w == r1.w;
+        if (!has) {                // a dead ray: K miss records with tmax as given, no walk
+            const size_t base = (size_t)sidx * a.max_hits;
+            for (uint32_t j = 0; j < a.max_hits; j++) { a.tuv[base + j] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[base + j] = make_int2(-1, -1); }
+            if (a.count) a.count[sidx] = 0;
+        }
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; tr.cnt = 0u; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
+        const size_t base = (size_t)slot * tr.K;
+        for (uint32_t j = 0; j < tr.K; j++) {
+            if (j < tr.cnt) {      // the ids as CastSource makes them
+                const uint4 e = tr.list[j * kTraceBlock];
+                const uint32_t prim = a.tri_prim[e.w];
+                a.tuv[base + j] = make_float4(__uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z), 0.f);
+                a.ids[base + j] = make_int2((int)prim, (int)(e.w - a.first_tri[prim]));
+            } else { a.tuv[base + j] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[base + j] = make_int2(-1, -1); }
+        }
+        if (a.count) a.count[slot] = (uint8_t)tr.cnt;
+    }
+};
+// KMAX 4 | 8: the list is KMAX KB of LDS a wave on top of the 5 KB of stack and pool, and LDS is what bounds the waves a CU holds -- small K keeps more resident.
+// (waves_per_eu: LDS allows four waves a SIMD with KMAX 4 and three with KMAX 8, so the registers of that many are the kernel's to use)
+template <int KMAX, bool ALPHA>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 4, 4))) void k_cast_multi(CastMultiK a) {
+    pooled_trace<kCastLds, false, ALPHA, CastMultiK, CastMultiSource<KMAX>, TravMulti<KMAX, kCastLds, ALPHA>>(a, CastMultiSource<KMAX>{a});
+}
+
+// ---- nearest surface points (art_closest_points) ------------------------------------------------------------------------------------------------
+// A query is a point and a radius, not a ray: the pooled loop's ray fields (inv, ood, tmin / tmax, the slab of every policy) have no meaning for it, and a query is ONE
+// 16-byte load -- nothing a pool would save.  So the walk has a loop of its own: the idle lanes of a wave read the next queries of its chunk directly (pop_chunk and the
+// cursor block are the casts').  Stack entries are pairs (reference, the child's box_d2): `limit` only ever falls, and an entry whose box has fallen behind it by the time
+// it is popped is dropped without a fetch.  Eight pairs a lane in LDS (4 KB a wave: 40 waves fit a CU's 160 KB, more than its 32 slots); deeper entries spill to scratch
+// as references alone.
+// No fmaf in anything that decides a record: d2_tri, box_d2 of a triangle and the point are restated by numpy float32 bit for bit (tests/np_closest.py).
+__device__ __forceinline__ float dotp(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 crossp(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+// |w - (u e1 + v e2)|^2: the one distance every feature is measured by, and the point art_closest_points reports
+__device__ __forceinline__ float tri_uv_d2(V3 w, V3 e1, V3 e2, float u, float v) {
+    const float dx = w.x - (u * e1.x + v * e2.x), dy = w.y - (u * e1.y + v * e2.y), dz = w.z - (u * e1.z + v * e2.z);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// the parameter of the point of segment {s e, 0 <= s <= 1} nearest to w; a segment of no length is its first end point
+__device__ __forceinline__ float seg_param(V3 w, V3 e) {
+    const float den = dotp(e, e);
+    float s = dotp(w, e) / (den > 0.0f ? den : 1.0f);
+    s = den > 0.0f ? s : 0.0f;
+    s = s > 0.0f ? s : 0.0f;   // (selects, not fmaxf / fminf: a NaN becomes 0 here and in numpy.where alike)
+    return s < 1.0f ? s : 1.0f;
+}
+// d2_tri of DESIGN.md 3.8: the face where the projection falls inside it, then the edges v0v1, v0v2, v1v2 clamped; the first of the smallest wins.  +inf: no feature gave
+// a number (a triangle nowhere, a non-finite one).  u, v: barycentrics of vertices 1 and 2 of the winning point.
+__device__ __forceinline__ float tri_closest(V3 w, V3 e1, V3 e2, float &u, float &v) {
+    float best = INFINITY; u = 0.0f; v = 0.0f;
+    const V3 n = crossp(e1, e2);
+    const float nn = dotp(n, n), den = nn > 0.0f ? nn : 1.0f;
+    const float fu = dotp(crossp(w, e2), n) / den, fv = dotp(crossp(e1, w), n) / den;
+    if ((nn > 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f)) {
+        const float d = tri_uv_d2(w, e1, e2, fu, fv);
+        if (d < best) { best = d; u = fu; v = fv; }
+    }
+    const float sa = seg_param(w, e1), da = tri_uv_d2(w, e1, e2, sa, 0.0f);
+    if (da < best) { best = da; u = sa; v = 0.0f; }
+    const float sb = seg_param(w, e2), db = tri_uv_d2(w, e1, e2, 0.0f, sb);
+    if (db < best) { best = db; u = 0.0f; v = sb; }
+    const float sc = seg_param(w - e1, e2 - e1), uc = 1.0f - sc, dc = tri_uv_d2(w, e1, e2, uc, sc);
+    if (dc < best) { best = dc; u = uc; v = sc; }
+    return best;
+}
+__device__ __forceinline__ float box_d2(V3 p, float lx, float ly, float lz, float hx, float hy, float hz) {
+    const float ex = fmaxf(fmaxf(lx - p.x, p.x - hx), 0.0f), ey = fmaxf(fmaxf(ly - p.y, p.y - hy), 0.0f), ez = fmaxf(fmaxf(lz - p.z, p.z - hz), 0.0f);
+    return (ex * ex + ey * ey) + ez * ez;
+}
+struct ClosestK {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *points; float4 *duv; int2 *ids; float4 *point;   // point: may be null
+    uint32_t total, chunk, refill, leaf_batch;
+    uint32_t *cursors;        // a cast's cursor block
+    const uint32_t *bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;   // FILTER instance only: AlphaView's leaf bits, records and table; the queries' cull mask
+};
+constexpr int kClosestLds = 8;                                     // stack pairs a lane in LDS
+constexpr int kClosestOvf = kOvfStack4 + (kLdsStack - kClosestLds);   // Trav4's bound on pending siblings holds for any walk of the tree
+template <bool FILTER> struct TravPoint {
+    V3 p;
+    float limit, bu, bv;     // limit: r*r, then the best candidate's d2_eff
+    uint32_t bpos, bgid;
+    int cur, sp;
+    // (a spilled entry is the reference alone, TravBase's: pairs there would double the scratch every wave slot of the device reserves; it is visited unasked)
+    __device__ __forceinline__ void push(int ref, float d2, int2 *lds, int *ovf) {
+        if (sp < kClosestLds) lds[sp * kTraceBlock] = make_int2(ref, __float_as_int(d2)); else if (sp < kClosestLds + kClosestOvf) *(volatile int *)&ovf[sp - kClosestLds] = ref;   // (volatile: TravBase::push)
+        sp = min(sp + 1, kClosestLds + kClosestOvf);
+    }
+    // the next entry whose box is still within the limit; true: none left, the query is finished
+    __device__ __forceinline__ bool pop(int2 *lds, int *ovf) {
+        while (sp > 0) {
+            sp--;
+            if (sp >= kClosestLds) { cur = *(volatile int *)&ovf[sp - kClosestLds]; return false; }
+            const int2 e = lds[sp * kTraceBlock];
+            if (!(__int_as_float(e.y) > limit)) { cur = e.x; return false; }
+        }
+        return true;
+    }
+    __device__ __forceinline__ bool visible(const ClosestK &a, uint32_t pos) const {
+        if (!FILTER) return true;
+        if (a.cull == 0u) return false;
+        if (!((a.bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
+        const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(a.shade + pos)[8].z);
+        return (prim_vis(a.prims[prim].masked) & a.cull) != 0u;
+    }
+    __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~cur;
+        if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const float bd = box_d2(p, tc.y, tc.z, tc.w, td.x, td.y, td.z);
+        float u, v;
+        const float dt = tri_closest(p - mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), u, v);
+        if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum: fmaxf would drop a NaN
+            const float de = fmaxf(dt, bd);
+            const uint32_t gid = __float_as_uint(td.w);
+            if ((de < limit || (de == limit && gid < bgid)) && visible(a, pos)) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; }
+        }
+        return pop(lds, ovf);
+    }
+    __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
+        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
+        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
+        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
+        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
+        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
+        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        float d2[4]; bool h[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t lxq = (b.x >> (8 * i)) & 255u, hxq = (b.w >> (8 * i)) & 255u;
+            const float lx = fmaf((float)lxq, sx, ox), hx = fmaf((float)hxq, sx, ox);
+            const float ly = fmaf((float)((b.y >> (8 * i)) & 255u), sy, oy), hy = fmaf((float)((c.x >> (8 * i)) & 255u), sy, oy);
+            const float lz = fmaf((float)((b.z >> (8 * i)) & 255u), sz, oz), hz = fmaf((float)((c.y >> (8 * i)) & 255u), sz, oz);
+            d2[i] = box_d2(p, lx, ly, lz, hx, hy, hz);
+            h[i] = (lxq <= hxq) & !(d2[i] > limit);   // an inverted box (255 / 0): an absent child or a masked subtree -- a distance to it means nothing, so it is asked
+        }
+        // on with the nearest child within the limit; the others wait with their distances, the farthest at the bottom: what is popped next is the nearest of them, and
+        // the limit has fallen the most by the time the far ones come up.  (A five-comparator network over (box_d2, reference); a child that is out sorts as +inf with
+        // the absent reference, which is pushed nowhere and, should it come first, is a leaf that is nothing.  The order is speed only: the answer does not depend on it.)
+        float k[4]; int rf[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { k[i] = h[i] ? d2[i] : INFINITY; rf[i] = h[i] ? refs[i] : kAbsentChild; }
+#define ART_CSWAP(x, y) { const bool sw = k[y] < k[x]; const float tk = sw ? k[x] : k[y]; k[x] = sw ? k[y] : k[x]; k[y] = tk; const int tr_ = sw ? rf[x] : rf[y]; rf[x] = sw ? rf[y] : rf[x]; rf[y] = tr_; }
+        ART_CSWAP(0, 1) ART_CSWAP(2, 3) ART_CSWAP(0, 2) ART_CSWAP(1, 3) ART_CSWAP(1, 2)
+#undef ART_CSWAP
+#pragma unroll
+        for (int i = 3; i >= 1; i--) if (rf[i] != kAbsentChild) push(rf[i], k[i], lds, ovf);
+        if (rf[0] == kAbsentChild) return pop(lds, ovf);
+        cur = rf[0];
+        return false;
+    }
+};
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_closest(ClosestK a) {
+    __shared__ int2 stack[kClosestLds * kTraceBlock];
+    int ovf[kClosestOvf];
+    int2 *lds = &stack[threadIdx.x];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t leaf_batch = a.leaf_batch;
+    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
+    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // HW_REG_XCC_ID: speed only
+    uint32_t shards_left = 8;
+    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
+    bool exhausted = false, active = false;
+    TravPoint<FILTER> tr;
+    tr.sp = 0; tr.cur = 0;
+    float radius = 0.0f;
+    uint32_t slot = 0;
+    for (;;) {
+        const uint64_t idle = ballot64(!active);
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        if (n_idle >= a.refill) {
+            if (!exhausted && cur == end) {
+                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
+                if (got >= n_chunks) exhausted = true;
+                else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
+            }
+            if (!exhausted) {   // the idle lanes read the next queries of the chunk, one each
+                const uint32_t take = min(n_idle, end - cur);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (!active && rank < take) {
+                    const uint32_t sidx = cur + rank;
+                    const float4 q = a.points[sidx];
+                    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
+                    if (z == 0.0f && q.w == q.w && !(q.w < 0.0f)) {
+                        tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
+                        radius = q.w; slot = sidx; active = true;
+                    } else {   // a non-finite point, a NaN or negative radius: the miss record, without a walk
+                        a.duv[sidx] = make_float4(q.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1);
+                        if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                }
+                cur += take;
+            } else if (n_idle == 64u) break;
+            if (ballot64(active) == 0ull) continue;
+        }
+        bool done = false;   // pooled_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
+#pragma unroll
+        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
+            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
+        const bool on_leaf = active && !done && tr.cur < 0;
+        const uint64_t lm = ballot64(on_leaf);
+        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
+        if (done) {
+            active = false;
+            if (tr.bgid != kNoHit) {   // the ids as CastSource::finish makes them; the point from the winning triangle's record
+                const uint32_t prim = a.tri_prim[tr.bgid];
+                a.duv[slot] = make_float4(sqrtf(tr.limit), tr.bu, tr.bv, 0.f);
+                a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+                if (a.point) {
+                    const float4 *tq = reinterpret_cast<const float4 *>(a.tris + tr.bpos);
+                    const float4 ta = tq[0], tb = tq[1], tc = tq[2];
+                    a.point[slot] = make_float4(ta.x + (tr.bu * ta.w + tr.bv * tb.z), ta.y + (tr.bu * tb.x + tr.bv * tb.w), ta.z + (tr.bu * tb.y + tr.bv * tc.x), 1.0f);
+                }
+            } else {
+                a.duv[slot] = make_float4(radius, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1);
+                if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+}
+
+// ---- a ball along a ray (art_cast_spheres) --------------------------------------------------------------------------------------------------------
+// The rays are the casts' -- 32 bytes a ray, everything ray_init makes of them -- so the loop is pooled_trace with a fourth candidate policy.  The ball's radius is the
+// same for every ray of a launch: boxes grow by it (one subtraction / addition a plane, before the slab), and a triangle answers with the first time the ball's centre is
+// within it of the triangle: at tmin already (S), or where it enters the slab round the face, a cylinder round an edge or a sphere round a vertex.
+// No fmaf in anything that decides a record but the slab's: tests/np_sweep.py restates every operation in numpy float32.
+struct SweepK : CastK { float4 *point; float radius; };   // point: may be null
+// the ENTRY root of A t^2 + 2 B t + Cq = 0
+__device__ __forceinline__ bool sweep_root(float A, float B, float Cq, float &t) {
+    const float disc = B * B - A * Cq;
+    t = (-B - sqrtf(disc >= 0.0f ? disc : 0.0f)) / (A > 0.0f ? A : 1.0f);
+    return (A > 0.0f) & (disc >= 0.0f);
+}
+// the cylinder of radius sqrt(rr) round the line {m + s e}: the direction of the edge is projected out of m and d before the quadratic (second order in lengths)
+__device__ __forceinline__ bool sweep_edge(V3 m, V3 e, V3 d, float rr, float &t, float &s) {
+    const float ee = dotp(e, e), q = ee > 0.0f ? ee : 1.0f, qm = dotp(m, e) / q, qd = dotp(d, e) / q;
+    const V3 mp = mk(m.x - qm * e.x, m.y - qm * e.y, m.z - qm * e.z), dp = mk(d.x - qd * e.x, d.y - qd * e.y, d.z - qd * e.z);
+    const bool ok = sweep_root(dotp(dp, dp), dotp(mp, dp), dotp(mp, mp) - rr, t);
+    s = qm + t * qd;
+    return (ee > 0.0f) & ok & (s >= 0.0f) & (s <= 1.0f);
+}
+__device__ __forceinline__ void sweep_take(bool ok, float t, float u, float v, float tmin, float tmax, float &bt, float &bu, float &bv) {
+    if (ok & (t >= tmin) & (t < tmax) & (t < bt)) { bt = t; bu = u; bv = v; }   // (a NaN never wins)
+}
+// t_tri of DESIGN.md 3.9 for w0 = o - v0: the smallest t in [tmin, tmax) among S, F, E01, E02, E12, V0, V1, V2, the first of equals; +inf: none.  u, v: its barycentrics
+__device__ __forceinline__ float tri_sweep(V3 w0, V3 d, V3 e1, V3 e2, float rho, float tmin, float tmax, float &u, float &v) {
+    float bt = INFINITY, t, s; u = 0.0f; v = 0.0f;
+    const float rr = rho * rho, dd = dotp(d, d);
+    {   // S: the ball touches the triangle where it starts
+        float su, sv;
+        const float d2 = tri_closest(mk(w0.x + tmin * d.x, w0.y + tmin * d.y, w0.z + tmin * d.z), e1, e2, su, sv);
+        sweep_take(d2 <= rr, tmin, su, sv, tmin, tmax, bt, u, v);
+    }
+    {   // F: the centre reaches the plane at distance rho on its own side, above the face
+        const V3 n = crossp(e1, e2);
+        const float nn = dotp(n, n), h = dotp(n, w0), nd = dotp(n, d);
+        float off = rho * sqrtf(nn); off = h >= 0.0f ? off : -off;
+        t = (off - h) / (nd != 0.0f ? nd : 1.0f);
+        const V3 w = mk(w0.x + t * d.x, w0.y + t * d.y, w0.z + t * d.z);
+        const float den = nn > 0.0f ? nn : 1.0f, fu = dotp(crossp(w, e2), n) / den, fv = dotp(crossp(e1, w), n) / den;
+        sweep_take((nn > 0.0f) & (nd != 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f), t, fu, fv, tmin, tmax, bt, u, v);
+    }
+    const V3 w1 = w0 - e1, w2 = w0 - e2;
+    bool ok = sweep_edge(w0, e1, d, rr, t, s); sweep_take(ok, t, s, 0.0f, tmin, tmax, bt, u, v);
+    ok = sweep_edge(w0, e2, d, rr, t, s); sweep_take(ok, t, 0.0f, s, tmin, tmax, bt, u, v);
+    ok = sweep_edge(w1, e2 - e1, d, rr, t, s); sweep_take(ok, t, 1.0f - s, s, tmin, tmax, bt, u, v);
+    ok = sweep_root(dd, dotp(w0, d), dotp(w0, w0) - rr, t); sweep_take(ok, t, 0.0f, 0.0f, tmin, tmax, bt, u, v);
+    ok = sweep_root(dd, dotp(w1, d), dotp(w1, w1) - rr, t); sweep_take(ok, t, 1.0f, 0.0f, tmin, tmax, bt, u, v);
+    ok = sweep_root(dd, dotp(w2, d), dotp(w2, w2) - rr, t); sweep_take(ok, t, 0.0f, 1.0f, tmin, tmax, bt, u, v);
+    return bt;
+}
+// The candidate policy: TravBase's state, stack and tie rule; boxes inflated by rho.  FILTER: the visibility masks (k_closest's visible(); alpha cutoffs are not tested)
+template <int LDSN, bool FILTER> struct TravSweep : TravBase<false, kOvfStack4 + (kLdsStack - LDSN), LDSN, false> {
+    using Nodes = const DevNode4 *;
+    float rho;
+    __device__ __forceinline__ bool visible(const AlphaView &av, uint32_t pos) const {
+        if (!FILTER) return true;
+        if (av.cull == 0u) return false;
+        if (!((av.bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
+        const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(av.shade + pos)[8].z);
+        return (prim_vis(av.prims[prim].masked) & av.cull) != 0u;
+    }
+    // the triangle's own box, inflated, against tbest first -- an exact cull: a candidate's t_eff is at least its box's entry and at least tmin -- then the eight features
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const Ray &r = this->r;
+        float te;
+        if (slab(r, tc.y - rho, tc.z - rho, tc.w - rho, td.x + rho, td.y + rho, td.z + rho, this->tbest, te)) {
+            float u, v;
+            const float tt = tri_sweep(r.o - mk(ta.x, ta.y, ta.z), r.d, mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), rho, r.tmin, r.tmax, u, v);
+            if (tt < INFINITY) {
+                const float teff = fmaxf(tt, te);
+                const uint32_t gid = __float_as_uint(td.w);
+                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && visible(av, pos)) { this->tbest = teff; this->bu = u; this->bv = v; this->bpos = pos; this->bgid = gid; }
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+    // Trav4's sign-selected slab with each child's near plane moved out and its far plane moved out by rho.  An absent child or a masked subtree carries an inverted byte box
+    // (255 / 0): "left before it is entered" no longer holds once the planes have moved, so it is skipped by TravPoint's explicit test
+    __device__ __forceinline__ bool step_internal(Nodes wide, int *lds, int *ovf) {
+        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + this->cur);
+        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
+        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
+        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
+        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
+        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        float te[4]; bool h[4];
+        const Ray &r = this->r;
+        const bool ngx = r.inv.x < 0.0f, ngy = r.inv.y < 0.0f, ngz = r.inv.z < 0.0f;
+        const uint32_t nxw = ngx ? b.w : b.x, fxw = ngx ? b.x : b.w, nyw = ngy ? c.x : b.y, fyw = ngy ? b.y : c.x, nzw = ngz ? c.y : b.z, fzw = ngz ? b.z : c.y;
+        const float px = ngx ? rho : -rho, py = ngy ? rho : -rho, pz = ngz ? rho : -rho;   // what the near plane moves by (lo - rho is lo + (-rho), bit for bit); the far plane by the opposite
+        const float lim = this->tbest;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float tnx = fmaf(fmaf((float)((nxw >> (8 * i)) & 255u), sx, ox) + px, r.inv.x, -r.ood.x), tfx = fmaf(fmaf((float)((fxw >> (8 * i)) & 255u), sx, ox) - px, r.inv.x, -r.ood.x);
+            const float tny = fmaf(fmaf((float)((nyw >> (8 * i)) & 255u), sy, oy) + py, r.inv.y, -r.ood.y), tfy = fmaf(fmaf((float)((fyw >> (8 * i)) & 255u), sy, oy) - py, r.inv.y, -r.ood.y);
+            const float tnz = fmaf(fmaf((float)((nzw >> (8 * i)) & 255u), sz, oz) + pz, r.inv.z, -r.ood.z), tfz = fmaf(fmaf((float)((fzw >> (8 * i)) & 255u), sz, oz) - pz, r.inv.z, -r.ood.z);
+            const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
+            te[i] = tn;
+            h[i] = (((b.x >> (8 * i)) & 255u) <= ((b.w >> (8 * i)) & 255u)) & (fmaxf(tn, r.tmin) <= fminf(tf, lim));
+        }
+        float tn = 3.0e38f; int ni = -1;   // on with the nearest child, the others wait: the order is speed only
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (h[i] && te[i] < tn) { tn = te[i]; ni = i; }
+        if (ni < 0) {   // (a child entered at 3e38 or beyond -- a structure nowhere -- is still a child: the first of them)
+#pragma unroll
+            for (int i = 3; i >= 0; i--) if (h[i]) ni = i;
+            if (ni < 0) return this->pop(lds, ovf);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (h[i] && i != ni) this->push(refs[i], lds, ovf);
+        this->cur = ni == 0 ? refs[0] : (ni == 1 ? refs[1] : (ni == 2 ? refs[2] : refs[3]));
+        return false;
+    }
+};
+struct SweepSource {
+    static constexpr int kFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
+    const SweepK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.rho = a.radius; }   // the same for every ray
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
+        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+        const bool has = ray_finite(o, d) && r1.w == r1.w;
+        if (!has) {                // a dead ray (CastSource's rule): its miss record, without a walk
+            a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1);
+            if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
+        if (tr.bgid != kNoHit) {   // the ids as CastSource::finish makes them; the contact point from the winning triangle's record
+            const uint32_t prim = a.tri_prim[tr.bgid];
+            a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
+            a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
+            if (a.point) {
+                const float4 *tq = reinterpret_cast<const float4 *>(a.tris + tr.bpos);
+                const float4 ta = tq[0], tb = tq[1], tc = tq[2];
+                a.point[slot] = make_float4(ta.x + (tr.bu * ta.w + tr.bv * tb.z), ta.y + (tr.bu * tb.x + tr.bv * tb.w), ta.z + (tr.bu * tb.y + tr.bv * tc.x), 1.0f);
+            }
+        } else {
+            a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1);
+            if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+};
+// 6 waves a SIMD: the eight-feature test holds 79 VGPRs without a spill; at 8 waves (64) the compiler spills two dozen of them to scratch, at 4 it uses no more than at 6
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_sweep(SweepK a) {
+    pooled_trace<kCastLds, false, FILTER, SweepK, SweepSource, TravSweep<kCastLds, FILTER>>(a, SweepSource{a});
+}
+
+// rays in device buffers (art_cast_rays and, through it, the queries): {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernel has -- a cast is
+// throughput-bound like it -- with the context's ArtTuning overrides
+static const Tune kCastPreset = {256, kPoolTake, 2048, 8};
+void launch_cast(const CastArgs &c, hipStream_t s) {
+    if (!c.n) return;
+    const Tune t = tune_over(kCastPreset, c.tune);
+    CastK a{};
+    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.rays = c.rays; a.tuv = c.tuv; a.ids = c.ids; a.hit = c.hit;
+    a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
+    a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
+    const uint32_t nb = persistent_blocks(c.n, t);
+    if (c.sweep) {      // a ball along each ray (art_cast_spheres): the filtered instance under the casts' condition -- it tests masks, never a cutoff
+        SweepK w{}; static_cast<CastK &>(w) = a; w.point = c.point; w.radius = c.radius;
+        if (c.alpha) k_sweep<true><<<nb, kTraceBlock, 0, s>>>(w); else k_sweep<false><<<nb, kTraceBlock, 0, s>>>(w);
+        return;
+    }
+    if (c.max_hits) {   // the first K hits: the instance with the smallest list that holds K
+        CastMultiK m{}; static_cast<CastK &>(m) = a; m.count = c.count; m.max_hits = c.max_hits;
+        if (c.max_hits <= 4u) { if (c.alpha) k_cast_multi<4, true><<<nb, kTraceBlock, 0, s>>>(m); else k_cast_multi<4, false><<<nb, kTraceBlock, 0, s>>>(m); }
+        else if (c.alpha) k_cast_multi<8, true><<<nb, kTraceBlock, 0, s>>>(m);
+        else k_cast_multi<8, false><<<nb, kTraceBlock, 0, s>>>(m);
+        return;
+    }
+    if (c.any) { if (c.alpha) k_cast<true, true><<<nb, kTraceBlock, 0, s>>>(a); else k_cast<true, false><<<nb, kTraceBlock, 0, s>>>(a); }
+    else if (c.alpha) k_cast<false, true><<<nb, kTraceBlock, 0, s>>>(a);
+    else k_cast<false, false><<<nb, kTraceBlock, 0, s>>>(a);
+}
+// nearest surface points (art_closest_points): the casts' launch shape -- as throughput-bound as they are -- with the context's ArtTuning overrides
+void launch_closest(const ClosestArgs &c, hipStream_t s) {
+    if (!c.n) return;
+    const Tune t = tune_over(kCastPreset, c.tune);
+    ClosestK a{};
+    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.points = c.points; a.duv = c.duv; a.ids = c.ids; a.point = c.point;
+    a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
+    a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    const uint32_t nb = persistent_blocks(c.n, t);
+    if (c.filter) k_closest<true><<<nb, kTraceBlock, 0, s>>>(a); else k_closest<false><<<nb, kTraceBlock, 0, s>>>(a);
+}
+
+} // namespace art

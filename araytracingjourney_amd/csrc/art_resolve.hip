@@ -1,43 +1,19 @@
 // art_resolve.hip -- art_resolve_hits (include/art.h): the surface behind the hit records a cast wrote.  A gather and an interpolation, one lane per
-// record: no rays, no tree, no lights.  The values are those of shade_surface_body<false> (art_trace.hip) up to N, the texture coordinate and the two material layers --
-// the plain expressions in the same order -- plus the geometric normal of the world triangle.  The sampler and the vector helpers it needs are RESTATED here on
-// purpose: sharing sample_tex by a call moved the default k_frame instances by a register, and tests pin those.
-#include "art_internal.h"
+// record: no rays, no tree, no lights.  The values are those of shade_surface_body<false> (art_shade.h) up to N, the texture coordinate and the two material layers --
+// the plain expressions in the same order -- plus the geometric normal of the world triangle.  The vector helpers and the sampler's pieces are art_device.h's own; only
+// the sampler's entry is restated (sample_layer: it clamps the texel coordinate of a caller's record, which sample_tex has no need to).
+#include "art_device.h"
 
 namespace art {
 
 namespace {
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 mk(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)); }
-__device__ __forceinline__ V3 cross3(V3 a, V3 b) {
-    return mk(fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)));
-}
-__device__ __forceinline__ V3 nrm3(V3 a) { return a * (1.0f / sqrtf(dot3(a, a))); }   // the plain expression: what nrm3_noting<false> computes
-__device__ __forceinline__ V3 xform_point(const float *m, V3 p) {
-    return mk(((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
-              ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]);
-}
-__device__ __forceinline__ V3 xform_vec(const float *m, V3 p) {
-    return mk((m[0] * p.x + m[1] * p.y) + m[2] * p.z, (m[4] * p.x + m[5] * p.y) + m[6] * p.z, (m[8] * p.x + m[9] * p.y) + m[10] * p.z);
-}
+__device__ __forceinline__ V3 nrm3_plain(V3 a) { return a * (1.0f / sqrtf(dot3(a, a))); }   // the plain expression: what nrm3_noting<false> computes
 __device__ __forceinline__ float4 f4(V3 a, float w) { return make_float4(a.x, a.y, a.z, w); }
 
-// sample_tex of art_trace.hip: sampler2DArray, linear / REPEAT, LOD 0.  One difference, for a caller's records: the texel coordinate is clamped to +-2^30 before it
+// sample_tex of art_device.h: sampler2DArray, linear / REPEAT, LOD 0.  One difference, for a caller's records: the texel coordinate is clamped to +-2^30 before it
 // becomes an integer (the frame's uv come from hits inside a triangle; a record may extrapolate to anything finite, and the product may overflow).  Inside that range --
 // every float with a fraction lies far inside it -- the operations and the bits are sample_tex's.
-__device__ __forceinline__ int wrapi(int i, int n) { int m = i % n; return m < 0 ? m + n : m; }
 __device__ __forceinline__ int texel_int(float f) { return (int)fminf(fmaxf(f, -1073741824.0f), 1073741824.0f); }   // (a NaN comes out as the bound: fmaxf returns the other operand)
-__device__ __forceinline__ float tex_channel(uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11, float fx, float fy, int c) {
-    const float k = 1.0f / 255.0f;
-    float A = (float)((t00 >> (8 * c)) & 255u) * k, B = (float)((t10 >> (8 * c)) & 255u) * k;
-    float Cc = (float)((t01 >> (8 * c)) & 255u) * k, D = (float)((t11 >> (8 * c)) & 255u) * k;
-    float top = A * (1.0f - fx) + B * fx, bot = Cc * (1.0f - fx) + D * fx;
-    return top * (1.0f - fy) + bot * fy;
-}
 __device__ __forceinline__ float4 sample_layer(const uint32_t *__restrict__ pool, uint32_t texture_offset, int tw, int th, int layer, float u, float v) {
     float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
     float x0f = floorf(x), y0f = floorf(y);
@@ -88,16 +64,16 @@ __global__ __launch_bounds__(256) void k_resolve(ResolveArgs a) {
         if (a.uv) o_uv = make_float2(tu, tv);
         const int tw = (int)P.tw, th = (int)P.th;
         if (a.ns) {
-            V3 nrm = nrm3((mk(s3.w, s4.x, s4.y) * bx + mk(s4.z, s4.w, s5.x) * by) + mk(s5.y, s5.z, s5.w) * bz);
+            V3 nrm = nrm3_plain((mk(s3.w, s4.x, s4.y) * bx + mk(s4.z, s4.w, s5.x) * by) + mk(s5.y, s5.z, s5.w) * bz);
             const float *Wm = P.w2o;
-            V3 world_normal = nrm3(mk(dot3(nrm, mk(Wm[0], Wm[4], Wm[8])), dot3(nrm, mk(Wm[1], Wm[5], Wm[9])), dot3(nrm, mk(Wm[2], Wm[6], Wm[10]))));
-            V3 tan = nrm3((mk(s6.x, s6.y, s6.z) * bx + mk(s6.w, s7.x, s7.y) * by) + mk(s7.z, s7.w, s8.x) * bz);
-            V3 world_tangent = nrm3(xform_vec(P.o2w, tan));
-            world_tangent = nrm3(world_tangent - world_normal * dot3(world_tangent, world_normal));
+            V3 world_normal = nrm3_plain(mk(dot3(nrm, mk(Wm[0], Wm[4], Wm[8])), dot3(nrm, mk(Wm[1], Wm[5], Wm[9])), dot3(nrm, mk(Wm[2], Wm[6], Wm[10]))));
+            V3 tan = nrm3_plain((mk(s6.x, s6.y, s6.z) * bx + mk(s6.w, s7.x, s7.y) * by) + mk(s7.z, s7.w, s8.x) * bz);
+            V3 world_tangent = nrm3_plain(xform_vec(P.o2w, tan));
+            world_tangent = nrm3_plain(world_tangent - world_normal * dot3(world_tangent, world_normal));
             V3 world_binormal = cross3(world_normal, world_tangent) * s8.y;
             float4 tx = sample_layer(a.tex_pool, P.texture_offset, tw, th, 2, tu, tv);
-            V3 N = nrm3(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f));
-            N = nrm3((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z);
+            V3 N = nrm3_plain(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f));
+            N = nrm3_plain((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z);
             o_ns = f4(N, 0.0f);
         }
         if (a.albedo) o_albedo = sample_layer(a.tex_pool, P.texture_offset, tw, th, 0, tu, tv);

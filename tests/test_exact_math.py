@@ -1,4 +1,4 @@
-"""The shading kernels' fast paths for sqrtf(x) and 1.0f / sqrtf(x) (art_trace.hip: inv_sqrt_exact / sqrt_exact and the surface block's guard): a wave
+"""The shading kernels' fast paths for sqrtf(x) and 1.0f / sqrtf(x) (art_device.h: inv_sqrt_exact / sqrt_exact; art_shade.h: the surface block's guard): a wave
 whose inputs all lie inside the guard's range runs the compiler's own core without the range handling around it, any other wave the plain expression.  Both functions are
 unary, so "the same bits" is proved, not sampled: art_parity_math_sweep runs all 2^32 inputs through the helper the frame kernels call and through a non-inlined copy of
 the plain expression and compares the results as integers."""

@@ -1,4 +1,4 @@
-"""The albedo's x^2.2 in twelve vector instructions (art_trace.hip: pow22_texel) where hipcc's __powf is the whole libm pow.  It feeds radiance only, so it need not
+"""The albedo's x^2.2 in twelve vector instructions (art_shade.h: pow22_texel) where hipcc's __powf is the whole libm pow.  It feeds radiance only, so it need not
 return libm's bits (1e-4 relative) -- but it has to stay far inside that tolerance, be the same in every instance of the frame (the forms of a frame are
 compared bit for bit), and be exact at the two ends of a texel's range.  art_parity_radiance_sweep measures it against libm's pow on every input a texel can be.
 

@@ -1,5 +1,5 @@
 """The fused frame's packet walks keep their lanes as masks and change the ray state with in-place selects; its phases read their kernel arguments again where they
-use them (art_trace.hip: sel(), packet_walk's ON, frame_args_again, kFrameMoves).  None of this may move a bit: every comparison here is np.array_equal on the bytes, and
+use them (art_frame.hip: sel(), packet_walk's ON, frame_args_again, kFrameMoves).  None of this may move a bit: every comparison here is np.array_equal on the bytes, and
 the reference is the staged per-ray form of the frame (frame_form=2), which shares none of that code.  Frames are 16x16 or 32x16: four to eight waves."""
 import math
 

@@ -97,7 +97,7 @@ def test_hints_on_cold_and_warm_equal_hints_off_and_the_oracles_bits(R, orc, sce
         on.trace()
     _assert_equal(_outputs(on), want, "warm")
     assert (off.read_shadow_hints() == EMPTY).all()   # off: the table is never written
-    if not (alpha and n_lights == 4):                 # (the plain multi-light instance with the alpha test is compiled without hints: kFrameHints, art_trace.hip)
+    if not (alpha and n_lights == 4):                 # (the plain multi-light instance with the alpha test is compiled without hints: kFrameHints, art_frame.hip)
         assert (on.read_shadow_hints() != EMPTY).any()
     if not alpha:
         S, L, nl = oracle_for(orc, sc)

@@ -1,19 +1,19 @@
 #!/usr/bin/env python3
-"""Checks and proposes kFrameMovesTable (araytracingjourney_amd/csrc/art_trace.hip): which of the instruction-saving forms each of the 32 k_frame instances takes.
+"""Checks and proposes kFrameMovesTable (araytracingjourney_amd/csrc/art_frame.hip): which of the instruction-saving forms each of the 32 k_frame instances takes.
 The committed table was not printed by this rule: it is the largest subset that keeps an instance's resource line (the mask form first), with the instances that then had
 more lane accesses or vector instructions than the parent set to 0 by hand (the comment at the table).  What this prints satisfies the same conditions and has the fewest
 vector instructions per instance; take it when the table has to be made again.
     python3 tools/moves_sweep.py [--jobs 8] [--work DIR] [--static-out profiles/moves_static_all.txt]
-Compiles art_trace.hip for the device 64 times with the Makefile's flags and -DART_MOVES_FORCE=n (every instance takes subset n; 0 is the code without any of the forms) and, with --base, once for the source to compare against,
+Compiles art_frame.hip for the device 64 times with the Makefile's flags and -DART_MOVES_FORCE=n (every instance takes subset n; 0 is the code without any of the forms) and, with --base, once for the source to compare against,
 each time twice: as the Makefile does (the assembly: vector instructions, lines beginning v_; v_readlane / v_writelane; the kernel info behind each kernel) and as
 tools/kres.sh does (the compiler's kernel-resource-usage remarks: asking for them moves the code of some instances a little, and both have to hold).  An instance may take subset n only if, against the baseline (--base, else subset 0), its VGPRs, scratch, spills, occupancy and LDS are equal in both compilations, it has no more
 SGPRs, no more lane accesses and no more vector instructions; of those it takes the one with the fewest vector instructions (then the fewest lane accesses, then the
-largest n).  Prints the table in the order art_trace.hip indexes it and, with --static-out, the per-instance counts of the baseline and of the chosen subset.
+largest n).  Prints the table in the order art_frame.hip indexes it and, with --static-out, the per-instance counts of the baseline and of the chosen subset.
 The table holds for one compiler and one source: run this again after touching k_frame, the packet walks or the toolchain; tools/kres.sh must then report subset 0's lines."""
 import argparse, concurrent.futures, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "araytracingjourney_amd", "csrc", "art_trace.hip")
+SRC = os.path.join(ROOT, "araytracingjourney_amd", "csrc", "art_frame.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-std=c++17"]
 
 
@@ -57,7 +57,7 @@ def main():
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--work", default=None)
     ap.add_argument("--static-out", default=None)
-    ap.add_argument("--base", default=None, help="the art_trace.hip to compare against, e.g. the parent commit's (git show <commit>:araytracingjourney_amd/csrc/art_trace.hip > file); default: subset 0 of this source")
+    ap.add_argument("--base", default=None, help="the unit with k_frame to compare against, e.g. the parent commit's (git show <commit>:araytracingjourney_amd/csrc/art_frame.hip > file; any path: art_trace.hip of a commit from before the split, which held k_frame then, does too); default: subset 0 of this source")
     a = ap.parse_args()
     work = a.work or tempfile.mkdtemp()
     os.makedirs(work, exist_ok=True)

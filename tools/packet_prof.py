@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the packet walks of the fused frame are made of (node steps, triangle steps, how many of them find a hit ...), per BASELINE config; needs a profiling build:
-    make -C araytracingjourney_amd/csrc art_trace.o EXTRA=-DART_PACKET_PROF -B && hipcc --offload-arch=gfx950 -shared -fPIC -o araytracingjourney_amd/libart_prof.so araytracingjourney_amd/csrc/*.o -lz -ldl
+    make -C araytracingjourney_amd/csrc art_frame.o EXTRA=-DART_PACKET_PROF -B && hipcc --offload-arch=gfx950 -shared -fPIC -o araytracingjourney_amd/libart_prof.so araytracingjourney_amd/csrc/*.o -lz -ldl
     ART_LIB_PATH=$PWD/araytracingjourney_amd/libart_prof.so python tools/packet_prof.py [--scene bistro] [--width W --height H --lights N] [--tuning k=v,...]"""
 import argparse, ctypes as C, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

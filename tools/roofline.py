@@ -37,9 +37,9 @@ HBM_PEAK = 8.0e12
 
 
 def kernel_source_hash():
-    """what the PMC counts belong to: the frame kernels' sources"""
+    """what the PMC counts belong to: the frame kernels' sources -- art_internal.h and, in this order, every file k_frame is compiled from"""
     h = hashlib.sha256()
-    for f in ("art_trace.hip", "art_internal.h"):
+    for f in ("art_internal.h", "art_device.h", "art_shade.h", "art_frame.hip"):
         h.update(open(os.path.join(ROOT, "araytracingjourney_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
 
