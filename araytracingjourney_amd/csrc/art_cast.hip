@@ -1,6 +1,6 @@
 // art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres; DESIGN.md 3.5 .. 3.9) and the queries of include/art_parity.h
-// over them: the host side of the ring of cast blocks (CastState, art_context.h).  Every use of a CastState / CastBlock field is in this file; the kernels are
-// art_query.hip's and art_resolve.hip's.
+// over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
+// entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
 
 // the first cast of a context: its stream (counted against the budget beside kMaxFrameSlots), the cursor blocks and their events
@@ -50,10 +50,11 @@ void art::cast_release(ArtContext *c) {
     K.q_rays.release(); K.q_out.release();
     if (K.stream) release_stream(c->device, K.stream);
 }
-// The host side every enqueue on the ring shares -- a cast's and a resolve's (art_resolve_hits traces nothing, but it reads a version of the scene and has to be waited
+// The host side every enqueue on the ring shares -- a query's and a resolve's (art_resolve_hits traces nothing, but it reads a version of the scene and has to be waited
 // for like a cast).  cast_claim: the scene as of the call, the stream, the version to read (an event wait on that stream while its refit may still run) and the next ring
-// block, free.  cast_commit: the block's event behind what the caller launched, and the version it holds.
-static int32_t cast_claim(ArtContext *c, hipStream_t user, hipStream_t *stream, uint32_t *version, uint32_t *block) {
+// block, free.  cast_commit: the block's event behind what the caller launched, the version it holds, and its rays in the counts of casts (0: it traces none).
+struct RingSlot { hipStream_t stream; uint32_t version, block; };
+static int32_t cast_claim(ArtContext *c, hipStream_t user, RingSlot *q) {
     int32_t r = use_device(c); if (r) return r;
     r = cast_setup(c); if (r) return r;
     CastState &K = c->cast;
@@ -68,69 +69,79 @@ static int32_t cast_claim(ArtContext *c, hipStream_t user, hipStream_t *stream, 
         if (hipEventQuery(B.ev) != hipSuccess) { (void)hipGetLastError(); HIPC(hipEventSynchronize(B.ev)); K.host_waits++; }
         B.set = false;
     }
-    *stream = s; *version = ver; *block = bi;
+    *q = RingSlot{s, ver, bi};
     return ART_OK;
 }
-static int32_t cast_commit(ArtContext *c, uint32_t bi, uint32_t ver, hipStream_t s) {
-    CastState &K = c->cast;
-    CastBlock &B = K.block[bi];
+static int32_t cast_commit(ArtContext *c, const RingSlot &q, uint32_t rays) {
+    CastState &K = c->cast; CastBlock &B = K.block[q.block]; hipStream_t s = q.stream;
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(B.ev, s));
-    B.set = true; B.version = ver; K.next++;
+    B.set = true; B.version = q.version; K.next++;
+    if (rays) { K.casts++; K.rays += rays; }
     return ART_OK;
 }
-// Enqueues one validated cast of n > 0 rays on `user` (NULL: the context's cast stream).  *block (optional) receives the ring block whose event stands behind it.
-// max_hits > 0: art_cast_rays_multi's cast (any false; hit = its count bytes, or null) -- the same blocks, version hold, events and refit, another kernel.
-// radius >= 0: art_cast_spheres' cast (any false, max_hits 0; hit = its contact points, or null) -- likewise.
-static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block, uint32_t max_hits = 0, float radius = -1.0f) {
-    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
-    int32_t r = cast_claim(c, user, &s, &ver, &bi); if (r) return r;
-    CastState &K = c->cast;
-    uint32_t *cursors = K.cursors + (size_t)bi * kCastCursorWords;
+// A query of n > 0 validated records on `user` (NULL: the context's cast stream): a block claimed, its cursors zeroed on the stream, and what every query reads of
+// the context and of the version it holds in `a`.  The caller adds the fields of its own, launches, and ends with cast_commit.
+static int32_t query_begin(ArtContext *c, hipStream_t user, uint32_t n, uint32_t cull, void *tuv, void *ids, QueryArgs &a, RingSlot *q) {
+    int32_t r = cast_claim(c, user, q); if (r) return r;
+    hipStream_t s = q->stream;
+    uint32_t *cursors = c->cast.cursors + (size_t)q->block * kCastCursorWords;
     HIPC(hipMemsetAsync(cursors, 0, kCastCursorWords * 4, s));
-    const AsPtrs as = as_ptrs(c, ver);
-    CastArgs a{};
+    const AsPtrs as = as_ptrs(c, q->version);
     a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
-    const bool sweep = radius >= 0.0f;
-    a.rays = (const float4 *)rays; a.n = n; a.any = any; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.hit = max_hits || sweep ? nullptr : (uint8_t *)hit; a.cursors = cursors;
-    a.max_hits = max_hits; a.count = max_hits ? (uint8_t *)hit : nullptr;
-    a.sweep = sweep; a.radius = sweep ? radius : 0.0f; a.point = sweep ? (float4 *)hit : nullptr;
+    a.n = n; a.tuv = (float4 *)tuv; a.ids = (int2 *)ids; a.cursors = cursors;
     a.tune = c->trace_tune();
-    a.alpha = c->alpha_live || cull == 0u;   // the filtered instances run while the scene needs them or the mask is 0 (such rays see nothing, and no leaf bit says so)
+    a.filter = c->alpha_live || cull == 0u;   // while the scene has a mask or a cutoff (the leaf bits mark both), or the query sees nothing
     a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.tex_pool = c->d_tex.p; a.cull = cull;
-    launch_cast(a, s);
-    r = cast_commit(c, bi, ver, s); if (r) return r;
-    K.casts++; K.rays += n;
-    if (block) *block = bi;
     return ART_OK;
+}
+// art_cast_rays' cast, which the queries of include/art_parity.h enqueue too.  *block (optional) receives the ring block whose event stands behind it.
+static int32_t cast_enqueue(ArtContext *c, const void *rays, uint32_t n, bool any, uint32_t cull, void *tuv, void *ids, void *hit, hipStream_t user, uint32_t *block) {
+    CastArgs a{}; RingSlot q;
+    int32_t r = query_begin(c, user, n, cull, tuv, ids, a, &q); if (r) return r;
+    a.rays = (const float4 *)rays; a.kind = any ? CastKind::Any : CastKind::Closest; a.hit = (uint8_t *)hit;
+    launch_cast(a, q.stream);
+    if (block) *block = q.block;
+    return cast_commit(c, q, n);
 }
 
-// a buffer of n records: null only when there are none (n = 0 touches nothing: a null buffer is one of no rays), and aligned; an output that may be null (not wanted): aligned
+// What the entry points ask of their descriptors, one text each.  A buffer of n records: null only when there are none (n = 0 touches nothing), and aligned; an optional output (null: not wanted): aligned
 static bool misaligned(const void *p, size_t align) { return ((uintptr_t)p & (align - 1)) != 0; }
-static bool bad(const void *p, size_t align, uint32_t n) { return (p == nullptr && n != 0u) || misaligned(p, align); }
-// what art_cast_rays and art_cast_rays_multi ask of the fields their descriptors share
+static int32_t invalid(const char *who, const std::string &what) { return fail(ART_E_INVALID, std::string(who) + ": " + what); }
+static int32_t check_null(const char *who, const void *c, const void *d) { return !c || !d ? invalid(who, "null argument") : ART_OK; }
+static int32_t check_flags(const char *who, uint32_t flags) { return flags != 0u ? invalid(who, "flags: must be 0") : ART_OK; }
+static int32_t check_cull(const char *who, uint32_t cull_mask) { return cull_mask > 0xFFu ? invalid(who, "cull_mask: above 0xFF") : ART_OK; }
+static int32_t check_n(const char *who, uint32_t n) { return n > ART_CAST_MAX_RAYS ? invalid(who, "n: above ART_CAST_MAX_RAYS") : ART_OK; }
+static int32_t check_buffer(const char *who, const char *name, const void *p, size_t align, uint32_t n, bool optional = false) {
+    if (!misaligned(p, align) && (optional || p || !n)) return ART_OK;
+    std::string what = optional ? "" : "null";
+    if (align > 1) what += (optional ? "not " : " or not ") + std::to_string(align) + "-byte aligned";
+    return invalid(who, std::string(name) + ": " + what);
+}
+// the fields the descriptors of the three casts of rays share
 static int32_t cast_check(const char *who, uint32_t flags, uint32_t cull_mask, uint32_t n, const void *rays_dev) {
-    if (flags != 0u) return fail(ART_E_INVALID, std::string(who) + ": flags: must be 0");
-    if (cull_mask > 0xFFu) return fail(ART_E_INVALID, std::string(who) + ": cull_mask: above 0xFF");
-    if (n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, std::string(who) + ": n: above ART_CAST_MAX_RAYS");
-    if (bad(rays_dev, 16, n)) return fail(ART_E_INVALID, std::string(who) + ": rays_dev: null or not 16-byte aligned");
-    return ART_OK;
+    int32_t r = check_flags(who, flags);
+    return r || (r = check_cull(who, cull_mask)) || (r = check_n(who, n)) ? r : check_buffer(who, "rays_dev", rays_dev, 16, n);
+}
+static int32_t check_records(const char *who, const char *tuv_name, const void *tuv_dev, const void *ids_dev, uint32_t n) {
+    const int32_t r = check_buffer(who, tuv_name, tuv_dev, 16, n);
+    return r ? r : check_buffer(who, "ids_dev", ids_dev, 8, n);
 }
 
 extern "C" {
 
 int32_t art_cast_rays(ArtContext *c, const ArtRayCast *d) {
-    if (!c || !d) return fail(ART_E_INVALID, "art_cast_rays: null argument");
-    if (d->kind != ART_CAST_CLOSEST && d->kind != ART_CAST_ANY) return fail(ART_E_INVALID, "art_cast_rays: kind: ART_CAST_CLOSEST or ART_CAST_ANY");
-    int32_t r = cast_check("art_cast_rays", d->flags, d->cull_mask, d->n, d->rays_dev); if (r) return r;
+    const char *who = "art_cast_rays"; int32_t r;
+    if ((r = check_null(who, c, d))) return r;
+    if (d->kind != ART_CAST_CLOSEST && d->kind != ART_CAST_ANY) return invalid(who, "kind: ART_CAST_CLOSEST or ART_CAST_ANY");
+    if ((r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev))) return r;
     const bool any = d->kind == ART_CAST_ANY;
     if (any) {
-        if (d->tuv_dev || d->ids_dev) return fail(ART_E_INVALID, "art_cast_rays: tuv_dev / ids_dev: must be NULL for ART_CAST_ANY");
-        if (bad(d->hit_dev, 1, d->n)) return fail(ART_E_INVALID, "art_cast_rays: hit_dev: null");
+        if (d->tuv_dev || d->ids_dev) return invalid(who, "tuv_dev / ids_dev: must be NULL for ART_CAST_ANY");
+        if ((r = check_buffer(who, "hit_dev", d->hit_dev, 1, d->n))) return r;
     } else {
-        if (d->hit_dev) return fail(ART_E_INVALID, "art_cast_rays: hit_dev: must be NULL for ART_CAST_CLOSEST");
-        if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_cast_rays: tuv_dev: null or not 16-byte aligned");
-        if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_cast_rays: ids_dev: null or not 8-byte aligned");
+        if (d->hit_dev) return invalid(who, "hit_dev: must be NULL for ART_CAST_CLOSEST");
+        if ((r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n))) return r;
     }
     if (!c->built) return fail(ART_E_STATE, "art_cast_rays: scene not built (art_scene_build)");
     if (d->n == 0u) return ART_OK;
@@ -138,85 +149,74 @@ int32_t art_cast_rays(ArtContext *c, const ArtRayCast *d) {
 }
 
 int32_t art_cast_rays_multi(ArtContext *c, const ArtRayCastMulti *d) {
-    if (!c || !d) return fail(ART_E_INVALID, "art_cast_rays_multi: null argument");
-    if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return fail(ART_E_INVALID, "art_cast_rays_multi: max_hits: 1 .. ART_CAST_MAX_HITS");
-    int32_t r = cast_check("art_cast_rays_multi", d->flags, d->cull_mask, d->n, d->rays_dev); if (r) return r;
-    if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_cast_rays_multi: tuv_dev: null or not 16-byte aligned");
-    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_cast_rays_multi: ids_dev: null or not 8-byte aligned");
+    const char *who = "art_cast_rays_multi"; int32_t r;
+    if ((r = check_null(who, c, d))) return r;
+    if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
+    if ((r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev)) || (r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n))) return r;
     if (!c->built) return fail(ART_E_STATE, "art_cast_rays_multi: scene not built (art_scene_build)");
     if (d->n == 0u) return ART_OK;
-    return cast_enqueue(c, d->rays_dev, d->n, false, d->cull_mask, d->tuv_dev, d->ids_dev, d->count_dev, (hipStream_t)d->hip_stream, nullptr, d->max_hits);
+    CastArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
+    a.rays = (const float4 *)d->rays_dev; a.kind = CastKind::Multi; a.max_hits = d->max_hits; a.count = (uint8_t *)d->count_dev;
+    launch_cast(a, q.stream);
+    return cast_commit(c, q, d->n);
 }
 
 // ---- the surface behind hit records (include/art.h: art_resolve_hits) ---------------------------------------------------------------------------
 // A resolve goes through the casts' ring: it claims a block (whose cursors it has no use for), holds the version it reads and leaves the block's event behind its
 // launch, so art_cast_sync, sync_all and scene_refresh wait for it where they wait for casts.  It is not counted as a cast: it traces nothing.
 int32_t art_resolve_hits(ArtContext *c, const ArtHitResolve *d) {
-    if (!c || !d) return fail(ART_E_INVALID, "art_resolve_hits: null argument");
-    if (d->flags != 0u) return fail(ART_E_INVALID, "art_resolve_hits: flags: must be 0");
-    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_resolve_hits: n: above ART_CAST_MAX_RAYS");
-    if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_resolve_hits: tuv_dev: null or not 16-byte aligned");
-    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_resolve_hits: ids_dev: null or not 8-byte aligned");
+    const char *who = "art_resolve_hits"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags)) || (r = check_n(who, d->n)) || (r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n))) return r;
     if (misaligned(d->pos_dev, 16) || misaligned(d->ng_dev, 16) || misaligned(d->ns_dev, 16) || misaligned(d->albedo_dev, 16) || misaligned(d->orm_dev, 16))
-        return fail(ART_E_INVALID, "art_resolve_hits: pos_dev / ng_dev / ns_dev / albedo_dev / orm_dev: not 16-byte aligned");
-    if (misaligned(d->uv_dev, 8)) return fail(ART_E_INVALID, "art_resolve_hits: uv_dev: not 8-byte aligned");
-    if (d->n != 0u && !d->pos_dev && !d->ng_dev && !d->ns_dev && !d->uv_dev && !d->albedo_dev && !d->orm_dev) return fail(ART_E_INVALID, "art_resolve_hits: no output buffer given");
+        return invalid(who, "pos_dev / ng_dev / ns_dev / albedo_dev / orm_dev: not 16-byte aligned");
+    if ((r = check_buffer(who, "uv_dev", d->uv_dev, 8, d->n, true))) return r;
+    if (d->n != 0u && !d->pos_dev && !d->ng_dev && !d->ns_dev && !d->uv_dev && !d->albedo_dev && !d->orm_dev) return invalid(who, "no output buffer given");
     if (!c->built) return fail(ART_E_STATE, "art_resolve_hits: scene not built, or changed since the build (art_scene_build)");
     if (d->n == 0u) return ART_OK;
-    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
-    int32_t r = cast_claim(c, (hipStream_t)d->hip_stream, &s, &ver, &bi); if (r) return r;
-    const AsPtrs as = as_ptrs(c, ver);
+    RingSlot q;
+    r = cast_claim(c, (hipStream_t)d->hip_stream, &q); if (r) return r;
+    const AsPtrs as = as_ptrs(c, q.version);
     ResolveArgs a{};
     a.tuv = (const float4 *)d->tuv_dev; a.ids = (const int2 *)d->ids_dev; a.n = d->n;
     a.n_prims = (uint32_t)c->h_dev_prims.size(); a.T = c->T;   // (after cast_claim: a rebuild the cost rule started made them anew, with the table)
     a.prims = as.prims; a.shade = as.shade; a.gid_leaf = c->bvh.gid_leaf; a.tex_pool = c->d_tex.p;
     a.pos = (float4 *)d->pos_dev; a.ng = (float4 *)d->ng_dev; a.ns = (float4 *)d->ns_dev; a.uv = (float2 *)d->uv_dev; a.albedo = (float4 *)d->albedo_dev; a.orm = (float4 *)d->orm_dev;
-    launch_resolve(a, s);
-    return cast_commit(c, bi, ver, s);
+    launch_resolve(a, q.stream);
+    return cast_commit(c, q, 0);
 }
 
 // ---- nearest surface points (include/art.h: art_closest_points) ---------------------------------------------------------------------------------
-// A batch of queries goes through the casts' ring like a cast -- claim, the block's cursors zeroed on its stream, the launch, commit -- and like a resolve it is not
-// counted as a cast: it traces no ray.
+// A batch of queries goes through the casts' ring like a cast, and like a resolve it is not counted as one: it traces no ray.
 int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
-    if (!c || !d) return fail(ART_E_INVALID, "art_closest_points: null argument");
-    if (d->flags != 0u) return fail(ART_E_INVALID, "art_closest_points: flags: must be 0");
-    if (d->reserved != 0u) return fail(ART_E_INVALID, "art_closest_points: reserved: must be 0");
-    if (d->cull_mask > 0xFFu) return fail(ART_E_INVALID, "art_closest_points: cull_mask: above 0xFF");
-    if (d->n > ART_CAST_MAX_RAYS) return fail(ART_E_INVALID, "art_closest_points: n: above ART_CAST_MAX_RAYS");
-    if (bad(d->points_dev, 16, d->n)) return fail(ART_E_INVALID, "art_closest_points: points_dev: null or not 16-byte aligned");
-    if (bad(d->duv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_closest_points: duv_dev: null or not 16-byte aligned");
-    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_closest_points: ids_dev: null or not 8-byte aligned");
-    if (misaligned(d->point_dev, 16)) return fail(ART_E_INVALID, "art_closest_points: point_dev: not 16-byte aligned");
+    const char *who = "art_closest_points"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
+    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
+    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "points_dev", d->points_dev, 16, d->n)) ||
+        (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) || (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true))) return r;
     if (!c->built) return fail(ART_E_STATE, "art_closest_points: scene not built, or changed since the build (art_scene_build)");
     if (d->n == 0u) return ART_OK;
-    hipStream_t s = nullptr; uint32_t ver = 0, bi = 0;
-    int32_t r = cast_claim(c, (hipStream_t)d->hip_stream, &s, &ver, &bi); if (r) return r;
-    uint32_t *cursors = c->cast.cursors + (size_t)bi * kCastCursorWords;
-    HIPC(hipMemsetAsync(cursors, 0, kCastCursorWords * 4, s));
-    const AsPtrs as = as_ptrs(c, ver);
-    ClosestArgs a{};
-    a.wide = as.wide; a.tris = as.tris; a.tri_prim = c->bvh.tri_prim; a.first_tri = c->d_first_tri.p;
-    a.points = (const float4 *)d->points_dev; a.n = d->n; a.duv = (float4 *)d->duv_dev; a.ids = (int2 *)d->ids_dev; a.point = (float4 *)d->point_dev; a.cursors = cursors;
-    a.tune = c->trace_tune();
-    a.filter = c->alpha_live || d->cull_mask == 0u;   // the casts' condition: while the scene has a mask or a cutoff (the leaf bits mark both), or the queries see nothing
-    a.alpha_bits = c->d_alpha_bits.p; a.shade = as.shade; a.prims = as.prims; a.cull = d->cull_mask;
-    launch_closest(a, s);
-    return cast_commit(c, bi, ver, s);
+    ClosestArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
+    a.points = (const float4 *)d->points_dev; a.point = (float4 *)d->point_dev;
+    launch_closest(a, q.stream);
+    return cast_commit(c, q, 0);
 }
 
 // ---- a ball along each ray (include/art.h: art_cast_spheres) -----------------------------------------------------------------------------------------
-// A cast like the others -- cast_enqueue: claim, cursors, launch, commit, counted in casts and rays -- with another kernel behind launch_cast.
+// A cast like the others, counted in casts and rays, with another kernel behind it.
 int32_t art_cast_spheres(ArtContext *c, const ArtSphereCast *d) {
-    if (!c || !d) return fail(ART_E_INVALID, "art_cast_spheres: null argument");
-    int32_t r = cast_check("art_cast_spheres", d->flags, d->cull_mask, d->n, d->rays_dev); if (r) return r;
-    if (!(d->radius >= 0.0f) || d->radius == INFINITY) return fail(ART_E_INVALID, "art_cast_spheres: radius: NaN, negative or infinite");
-    if (bad(d->tuv_dev, 16, d->n)) return fail(ART_E_INVALID, "art_cast_spheres: tuv_dev: null or not 16-byte aligned");
-    if (bad(d->ids_dev, 8, d->n)) return fail(ART_E_INVALID, "art_cast_spheres: ids_dev: null or not 8-byte aligned");
-    if (misaligned(d->point_dev, 16)) return fail(ART_E_INVALID, "art_cast_spheres: point_dev: not 16-byte aligned");
+    const char *who = "art_cast_spheres"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev))) return r;
+    if (!(d->radius >= 0.0f) || d->radius == INFINITY) return invalid(who, "radius: NaN, negative or infinite");
+    if ((r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n)) || (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true))) return r;
     if (!c->built) return fail(ART_E_STATE, "art_cast_spheres: scene not built, or changed since the build (art_scene_build)");
     if (d->n == 0u) return ART_OK;
-    return cast_enqueue(c, d->rays_dev, d->n, false, d->cull_mask, d->tuv_dev, d->ids_dev, d->point_dev, (hipStream_t)d->hip_stream, nullptr, 0, d->radius + 0.0f);   // (-0.0 + 0.0 is +0.0)
+    CastArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
+    a.rays = (const float4 *)d->rays_dev; a.kind = CastKind::Sweep; a.radius = d->radius + 0.0f; a.point = (float4 *)d->point_dev;   // (-0.0 + 0.0 is +0.0)
+    launch_cast(a, q.stream);
+    return cast_commit(c, q, d->n);
 }
 
 int32_t art_cast_sync(ArtContext *c) {

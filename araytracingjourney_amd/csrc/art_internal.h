@@ -292,32 +292,27 @@ constexpr uint32_t kAoTableEntriesPerSample = 64 * 64;
 void launch_ao_table(uint32_t spp, float4 *tab, hipStream_t s); // tab: spp * kAoTableEntriesPerSample float4
 // pix: 2 * n_local float4 of scratch (per-pixel origin | start node, normal | noise index); tab: launch_ao_table's; entry_search: start the rays below the root
 void launch_ao(const FrameArgs &f, uint32_t spp, float radius, uint8_t *occl, float4 *pix, const float4 *tab, bool entry_search, uint32_t *ao, const uint32_t *lut, hipStream_t s);
-// One cast of rays that sit in a device buffer (art_cast_rays; art_query_* are host wrappers over it): rays[2i] = o.xyz,tmin | rays[2i+1] = d.xyz,tmax.
-// Closest (any false): tuv[i] = t,u,v,0 and ids[i] = primitive, triangle in the primitive -- a miss is tmax,0,0,0 and -1,-1; any: hit[i] = 0 | 1.
-struct CastArgs {
-    const DevNode4 *wide; const DevTri *tris;           // the version of the structure the cast reads
+// What every query on the casts' ring reads, filled by art_cast.hip's query_begin for a claimed block
+struct QueryArgs {
+    const DevNode4 *wide; const DevTri *tris;           // the version of the structure the query reads
     const uint32_t *tri_prim, *first_tri;               // gid -> primitive (Lbvh::tri_prim); primitive -> its first gid (the build's table): the ids, on the device
-    const float4 *rays; uint32_t n; bool any;
-    float4 *tuv; int2 *ids; uint8_t *hit;
-    uint32_t *cursors;                                  // kCastCursorWords words, zeroed on the cast's stream in front of the launch
+    uint32_t n; float4 *tuv; int2 *ids;                 // n records: t,u,v,0 (a point query: d,u,v,0) and primitive, triangle in the primitive -- a miss is x,0,0,0 and -1,-1
+    uint32_t *cursors;                                  // kCastCursorWords words, zeroed on the query's stream in front of the launch
     TraceTune tune;
-    bool alpha; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool;   // alpha: FrameArgs' (the mask / alpha test)
-    uint32_t cull;                                      // the rays' cull mask
-    uint32_t max_hits; uint8_t *count;                  // art_cast_rays_multi: K > 0 -- tuv / ids hold K records a ray, ray-major; count (optional) a byte a ray.  0: the casts above
-    bool sweep; float radius; float4 *point;            // art_cast_spheres: a ball of this radius along each ray (any false, max_hits 0); tuv / ids as a closest cast's, point (optional) the contact point, w = 1 (a miss: zeros)
+    bool filter;                                        // the instances with the mask / alpha test (FrameArgs::alpha): while the scene needs them or the cull mask is 0 (such a query sees nothing, and no leaf bit says so)
+    const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; const uint32_t *tex_pool;
+    uint32_t cull;                                      // the queries' cull mask
 };
 constexpr uint32_t kCastCursorWords = 8 * 32;           // eight per-XCD cursors, a 128-byte line each
+// Rays in a device buffer, rays[2i] = o.xyz,tmin | rays[2i+1] = d.xyz,tmax (a miss record's x is tmax), and the fields each kind of cast reads beside them:
+//   Closest, Any  art_cast_rays (art_query_* are host wrappers over it): Any writes hit[i] = 0 | 1 and no records
+//   Multi         art_cast_rays_multi (3.6): tuv / ids hold max_hits records a ray, ray-major; count (optional) a byte a ray
+//   Sweep         art_cast_spheres (3.9): a ball of `radius` along each ray; point (optional) the contact point, w = 1 (a miss: zeros)
+enum class CastKind { Closest, Any, Multi, Sweep };
+struct CastArgs : QueryArgs { const float4 *rays; CastKind kind; uint8_t *hit; uint32_t max_hits; uint8_t *count; float radius; float4 *point; };
 void launch_cast(const CastArgs &c, hipStream_t s);
-// One batch of nearest-point queries (art_closest_points): points[i] = p.xyz, r; duv[i] = d,u,v,0 and ids[i] as a closest cast's -- a miss is r,0,0,0 and
-// -1,-1; point (optional) = the surface point, w = 1 (a miss: zeros).  filter: the instance with the visibility masks (CastArgs::alpha's condition).
-struct ClosestArgs {
-    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
-    const float4 *points; uint32_t n;
-    float4 *duv; int2 *ids; float4 *point;
-    uint32_t *cursors;                                  // a cast's cursor block, zeroed in front of the launch
-    TraceTune tune;
-    bool filter; const uint32_t *alpha_bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;
-};
+// Nearest-point queries (art_closest_points): points[i] = p.xyz, r; a miss record's x is r; point (optional) = the surface point, w = 1 (a miss: zeros)
+struct ClosestArgs : QueryArgs { const float4 *points; float4 *point; };
 void launch_closest(const ClosestArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).

@@ -1,14 +1,45 @@
 // art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest) and
-// swept spheres (k_sweep), each a Source or a candidate policy of art_walk.h's pooled loop, and their launchers.  art_cast.hip is their host side.
+// swept spheres (k_sweep), each a Source or a candidate policy of art_walk.h's pooled loop.  What they share stands once: at the top the ray read, the hit and miss
+// records, the contact point and the mask test; at the bottom the arguments' common fields and the launch.  art_cast.hip is their host side.
 #include "art_walk.h"
 
 namespace art {
 
-// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT), are READ -- two 16-byte loads a lane, 2 KB a wave in one
-// piece.  A dead ray (non-finite origin or direction, NaN tmax: TravBase::start's rule) gets its miss record there and then and never enters the pool.  One walk for every
-// context, whatever ArtTuning says.  Closest hits leave as t,u,v,0 and (primitive, triangle in the primitive): the walk carries the best candidate's gid, tri_prim names its
-// primitive and first_tri that primitive's first gid -- no triangle record, no host.  Any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's
-// record depends on the ray alone.
+// ---- what the queries share -----------------------------------------------------------------------------------------------------------------------------------
+// One ray of a cast's buffer: two 16-byte loads a lane (2 KB a wave in one piece), o.xyz tmin | d.xyz tmax.  False: a dead ray (non-finite origin or direction, NaN
+// tmax: TravBase::start's rule), which accepts nothing -- its source writes the miss record there and then, with tmax as given, and the ray never enters the pool.
+__device__ __forceinline__ bool read_ray(const float4 *rays, uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) {
+    const float4 r0 = rays[2 * (size_t)sidx], r1 = rays[2 * (size_t)sidx + 1];
+    o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
+    return ray_finite(o, d) && r1.w == r1.w;
+}
+// A record, on the device: t,u,v,0 and (primitive, triangle in the primitive) -- tri_prim names the gid's primitive (k_soup's table) and first_tri that primitive's first
+// gid; no triangle record, no host.  A miss: (x,0,0,0) and (-1,-1), x the range's end as the caller gave it.  K: anything with tuv, ids, tri_prim, first_tri.
+// (I: the index in its caller's own type, uint32_t or size_t: with a size_t parameter the compiler assigns the registers of k_cast, k_sweep and k_closest otherwise, and
+// k_cast gains an instruction)
+template <class K, class I> __device__ __forceinline__ void write_hit(const K &a, I at, uint32_t gid, float t, float u, float v) {
+    const uint32_t prim = a.tri_prim[gid];
+    a.tuv[at] = make_float4(t, u, v, 0.f);
+    a.ids[at] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
+}
+template <class K, class I> __device__ __forceinline__ void write_miss(const K &a, I at, float x) { a.tuv[at] = make_float4(x, 0.f, 0.f, 0.f); a.ids[at] = make_int2(-1, -1); }
+// the point u, v of the triangle at leaf position pos, from its record (v0 e1 e2), w = 1: what k_closest and k_sweep report beside a hit
+__device__ __forceinline__ float4 contact_point(const DevTri *tris, uint32_t pos, float u, float v) {
+    const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
+    const float4 ta = tq[0], tb = tq[1], tc = tq[2];
+    return make_float4(ta.x + (u * ta.w + v * tb.z), ta.y + (u * tb.x + v * tb.w), ta.z + (u * tb.y + v * tc.x), 1.0f);
+}
+// does a query with this cull mask see the triangle at leaf position pos?  The masks only -- no cutoff: the test of the walks that have no alpha_cut
+__device__ __forceinline__ bool leaf_visible(const uint32_t *bits, const DevShadeTri *shade, const DevPrim *prims, uint32_t cull, uint32_t pos) {
+    if (cull == 0u) return false;
+    if (!((bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
+    const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(shade + pos)[8].z);
+    return (prim_vis(prims[prim].masked) & cull) != 0u;
+}
+
+// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT), are READ.  One walk for every context, whatever ArtTuning
+// says.  Closest hits leave as records of the walk's best candidate; any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's record
+// depends on the ray alone.
 struct CastK {
     const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
     const float4 *rays; float4 *tuv; int2 *ids; uint8_t *hit;
@@ -23,23 +54,15 @@ template <bool ANY> struct CastSource {
     const CastK &a;
     template <class TRAV> __device__ __forceinline__ void init(TRAV &) const {}
     __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
-        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
-        const bool has = ray_finite(o, d) && r1.w == r1.w;
-        if (!has) {                // a dead ray accepts nothing: its miss record, without a walk
-            if (ANY) a.hit[sidx] = 0;
-            else { a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1); }
-        }
+        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
+        if (!has) { if (ANY) a.hit[sidx] = 0; else write_miss(a, sidx, e1); }   // a dead ray: its miss record, without a walk
         return has;
     }
     template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
     template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
         if (ANY) a.hit[slot] = tr.bpos != kNoHit ? 1 : 0;
-        else if (tr.bgid != kNoHit) {             // the ids, on the device: gid -> primitive (k_soup's table) -> triangle in the primitive
-            const uint32_t prim = a.tri_prim[tr.bgid];
-            a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
-            a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
-        } else { a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1); }
+        else if (tr.bgid != kNoHit) write_hit(a, slot, tr.bgid, tr.tbest, tr.bu, tr.bv);
+        else write_miss(a, slot, tr.r.tmax);
     }
 };
 template <bool ANY, bool ALPHA>
@@ -93,12 +116,10 @@ template <int KMAX> struct CastMultiSource {
     const CastMultiK &a;
     template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.bind(a.max_hits); }
     __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];
-        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
-        const bool has = ray_finite(o, d) && r1.w == r1.w;
-        if (!has) {                // a dead ray: K miss records with tmax as given, no walk
+        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
+        if (!has) {                // a dead ray: K miss records, no walk
             const size_t base = (size_t)sidx * a.max_hits;
-            for (uint32_t j = 0; j < a.max_hits; j++) { a.tuv[base + j] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[base + j] = make_int2(-1, -1); }
+            for (uint32_t j = 0; j < a.max_hits; j++) write_miss(a, base + j, e1);
             if (a.count) a.count[sidx] = 0;
         }
         return has;
@@ -107,12 +128,10 @@ template <int KMAX> struct CastMultiSource {
     template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
         const size_t base = (size_t)slot * tr.K;
         for (uint32_t j = 0; j < tr.K; j++) {
-            if (j < tr.cnt) {      // the ids as CastSource makes them
+            if (j < tr.cnt) {
                 const uint4 e = tr.list[j * kTraceBlock];
-                const uint32_t prim = a.tri_prim[e.w];
-                a.tuv[base + j] = make_float4(__uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z), 0.f);
-                a.ids[base + j] = make_int2((int)prim, (int)(e.w - a.first_tri[prim]));
-            } else { a.tuv[base + j] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[base + j] = make_int2(-1, -1); }
+                write_hit(a, base + j, e.w, __uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z));
+            } else write_miss(a, base + j, tr.r.tmax);
         }
         if (a.count) a.count[slot] = (uint8_t)tr.cnt;
     }
@@ -171,7 +190,7 @@ __device__ __forceinline__ float box_d2(V3 p, float lx, float ly, float lz, floa
 }
 struct ClosestK {
     const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
-    const float4 *points; float4 *duv; int2 *ids; float4 *point;   // point: may be null
+    const float4 *points; float4 *tuv; int2 *ids; float4 *point;   // tuv: d,u,v,0; point: may be null
     uint32_t total, chunk, refill, leaf_batch;
     uint32_t *cursors;        // a cast's cursor block
     const uint32_t *bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;   // FILTER instance only: AlphaView's leaf bits, records and table; the queries' cull mask
@@ -198,13 +217,6 @@ template <bool FILTER> struct TravPoint {
         }
         return true;
     }
-    __device__ __forceinline__ bool visible(const ClosestK &a, uint32_t pos) const {
-        if (!FILTER) return true;
-        if (a.cull == 0u) return false;
-        if (!((a.bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
-        const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(a.shade + pos)[8].z);
-        return (prim_vis(a.prims[prim].masked) & a.cull) != 0u;
-    }
     __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
         const uint32_t pos = (uint32_t)~cur;
         if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
@@ -216,7 +228,7 @@ template <bool FILTER> struct TravPoint {
         if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum: fmaxf would drop a NaN
             const float de = fmaxf(dt, bd);
             const uint32_t gid = __float_as_uint(td.w);
-            if ((de < limit || (de == limit && gid < bgid)) && visible(a, pos)) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; }
+            if ((de < limit || (de == limit && gid < bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; }
         }
         return pop(lds, ovf);
     }
@@ -289,7 +301,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                         tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
                         radius = q.w; slot = sidx; active = true;
                     } else {   // a non-finite point, a NaN or negative radius: the miss record, without a walk
-                        a.duv[sidx] = make_float4(q.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1);
+                        write_miss(a, sidx, q.w);
                         if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
                     }
                 }
@@ -306,17 +318,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
         if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
         if (done) {
             active = false;
-            if (tr.bgid != kNoHit) {   // the ids as CastSource::finish makes them; the point from the winning triangle's record
-                const uint32_t prim = a.tri_prim[tr.bgid];
-                a.duv[slot] = make_float4(sqrtf(tr.limit), tr.bu, tr.bv, 0.f);
-                a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
-                if (a.point) {
-                    const float4 *tq = reinterpret_cast<const float4 *>(a.tris + tr.bpos);
-                    const float4 ta = tq[0], tb = tq[1], tc = tq[2];
-                    a.point[slot] = make_float4(ta.x + (tr.bu * ta.w + tr.bv * tb.z), ta.y + (tr.bu * tb.x + tr.bv * tb.w), ta.z + (tr.bu * tb.y + tr.bv * tc.x), 1.0f);
-                }
+            if (tr.bgid != kNoHit) {
+                write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
+                if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
             } else {
-                a.duv[slot] = make_float4(radius, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1);
+                write_miss(a, slot, radius);
                 if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
@@ -373,17 +379,10 @@ __device__ __forceinline__ float tri_sweep(V3 w0, V3 d, V3 e1, V3 e2, float rho,
     ok = sweep_root(dd, dotp(w2, d), dotp(w2, w2) - rr, t); sweep_take(ok, t, 0.0f, 1.0f, tmin, tmax, bt, u, v);
     return bt;
 }
-// The candidate policy: TravBase's state, stack and tie rule; boxes inflated by rho.  FILTER: the visibility masks (k_closest's visible(); alpha cutoffs are not tested)
+// The candidate policy: TravBase's state, stack and tie rule; boxes inflated by rho.  FILTER: the visibility masks (leaf_visible; alpha cutoffs are not tested)
 template <int LDSN, bool FILTER> struct TravSweep : TravBase<false, kOvfStack4 + (kLdsStack - LDSN), LDSN, false> {
     using Nodes = const DevNode4 *;
     float rho;
-    __device__ __forceinline__ bool visible(const AlphaView &av, uint32_t pos) const {
-        if (!FILTER) return true;
-        if (av.cull == 0u) return false;
-        if (!((av.bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
-        const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(av.shade + pos)[8].z);
-        return (prim_vis(av.prims[prim].masked) & av.cull) != 0u;
-    }
     // the triangle's own box, inflated, against tbest first -- an exact cull: a candidate's t_eff is at least its box's entry and at least tmin -- then the eight features
     __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
         const uint32_t pos = (uint32_t)~this->cur;
@@ -398,7 +397,7 @@ template <int LDSN, bool FILTER> struct TravSweep : TravBase<false, kOvfStack4 +
             if (tt < INFINITY) {
                 const float teff = fmaxf(tt, te);
                 const uint32_t gid = __float_as_uint(td.w);
-                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && visible(av, pos)) { this->tbest = teff; this->bu = u; this->bv = v; this->bpos = pos; this->bgid = gid; }
+                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && (!FILTER || leaf_visible(av.bits, av.shade, av.prims, av.cull, pos))) { this->tbest = teff; this->bu = u; this->bv = v; this->bpos = pos; this->bgid = gid; }
             }
         }
         return this->pop(lds, ovf);
@@ -446,28 +445,20 @@ struct SweepSource {
     const SweepK &a;
     template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.rho = a.radius; }   // the same for every ray
     __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const float4 r0 = a.rays[2 * (size_t)sidx], r1 = a.rays[2 * (size_t)sidx + 1];   // o.xyz tmin | d.xyz tmax
-        o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
-        const bool has = ray_finite(o, d) && r1.w == r1.w;
-        if (!has) {                // a dead ray (CastSource's rule): its miss record, without a walk
-            a.tuv[sidx] = make_float4(r1.w, 0.f, 0.f, 0.f); a.ids[sidx] = make_int2(-1, -1);
+        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
+        if (!has) {                // a dead ray: its miss record, without a walk
+            write_miss(a, sidx, e1);
             if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         return has;
     }
     template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
     template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
-        if (tr.bgid != kNoHit) {   // the ids as CastSource::finish makes them; the contact point from the winning triangle's record
-            const uint32_t prim = a.tri_prim[tr.bgid];
-            a.tuv[slot] = make_float4(tr.tbest, tr.bu, tr.bv, 0.f);
-            a.ids[slot] = make_int2((int)prim, (int)(tr.bgid - a.first_tri[prim]));
-            if (a.point) {
-                const float4 *tq = reinterpret_cast<const float4 *>(a.tris + tr.bpos);
-                const float4 ta = tq[0], tb = tq[1], tc = tq[2];
-                a.point[slot] = make_float4(ta.x + (tr.bu * ta.w + tr.bv * tb.z), ta.y + (tr.bu * tb.x + tr.bv * tb.w), ta.z + (tr.bu * tb.y + tr.bv * tc.x), 1.0f);
-            }
+        if (tr.bgid != kNoHit) {
+            write_hit(a, slot, tr.bgid, tr.tbest, tr.bu, tr.bv);
+            if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
         } else {
-            a.tuv[slot] = make_float4(tr.r.tmax, 0.f, 0.f, 0.f); a.ids[slot] = make_int2(-1, -1);
+            write_miss(a, slot, tr.r.tmax);
             if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
@@ -478,43 +469,41 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
     pooled_trace<kCastLds, false, FILTER, SweepK, SweepSource, TravSweep<kCastLds, FILTER>>(a, SweepSource{a});
 }
 
-// rays in device buffers (art_cast_rays and, through it, the queries): {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernel has -- a cast is
-// throughput-bound like it -- with the context's ArtTuning overrides
-static const Tune kCastPreset = {256, kPoolTake, 2048, 8};
-void launch_cast(const CastArgs &c, hipStream_t s) {
-    if (!c.n) return;
-    const Tune t = tune_over(kCastPreset, c.tune);
-    CastK a{};
-    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.rays = c.rays; a.tuv = c.tuv; a.ids = c.ids; a.hit = c.hit;
+// The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
+// the context's ArtTuning overrides.  query_fill: the fields every kernel's arguments share; launch_query: one instance, chosen by its caller, on that shape.
+static Tune query_tune(const QueryArgs &c) { return tune_over(Tune{256, kPoolTake, 2048, 8}, c.tune); }
+template <class K> static K query_fill(const QueryArgs &c) {
+    const Tune t = query_tune(c);
+    K a{};
+    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.tuv = c.tuv; a.ids = c.ids;
     a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
-    a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
-    const uint32_t nb = persistent_blocks(c.n, t);
-    if (c.sweep) {      // a ball along each ray (art_cast_spheres): the filtered instance under the casts' condition -- it tests masks, never a cutoff
-        SweepK w{}; static_cast<CastK &>(w) = a; w.point = c.point; w.radius = c.radius;
-        if (c.alpha) k_sweep<true><<<nb, kTraceBlock, 0, s>>>(w); else k_sweep<false><<<nb, kTraceBlock, 0, s>>>(w);
-        return;
-    }
-    if (c.max_hits) {   // the first K hits: the instance with the smallest list that holds K
-        CastMultiK m{}; static_cast<CastK &>(m) = a; m.count = c.count; m.max_hits = c.max_hits;
-        if (c.max_hits <= 4u) { if (c.alpha) k_cast_multi<4, true><<<nb, kTraceBlock, 0, s>>>(m); else k_cast_multi<4, false><<<nb, kTraceBlock, 0, s>>>(m); }
-        else if (c.alpha) k_cast_multi<8, true><<<nb, kTraceBlock, 0, s>>>(m);
-        else k_cast_multi<8, false><<<nb, kTraceBlock, 0, s>>>(m);
-        return;
-    }
-    if (c.any) { if (c.alpha) k_cast<true, true><<<nb, kTraceBlock, 0, s>>>(a); else k_cast<true, false><<<nb, kTraceBlock, 0, s>>>(a); }
-    else if (c.alpha) k_cast<false, true><<<nb, kTraceBlock, 0, s>>>(a);
-    else k_cast<false, false><<<nb, kTraceBlock, 0, s>>>(a);
+    return a;
 }
-// nearest surface points (art_closest_points): the casts' launch shape -- as throughput-bound as they are -- with the context's ArtTuning overrides
+template <class K> static K cast_fill(const CastArgs &c) {
+    K a = query_fill<K>(c);
+    a.rays = c.rays; a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
+    return a;
+}
+template <class K> static void launch_query(void (*kernel)(K), const K &a, const QueryArgs &c, hipStream_t s) {
+    if (c.n) kernel<<<persistent_blocks(c.n, query_tune(c)), kTraceBlock, 0, s>>>(a);
+}
+
+void launch_cast(const CastArgs &c, hipStream_t s) {
+    if (c.kind == CastKind::Sweep) {          // the filtered instance tests masks, never a cutoff
+        SweepK a = cast_fill<SweepK>(c); a.point = c.point; a.radius = c.radius;
+        launch_query(c.filter ? k_sweep<true> : k_sweep<false>, a, c, s);
+    } else if (c.kind == CastKind::Multi) {   // the instance with the smallest list that holds K
+        CastMultiK a = cast_fill<CastMultiK>(c); a.count = c.count; a.max_hits = c.max_hits;
+        launch_query(c.max_hits <= 4u ? (c.filter ? k_cast_multi<4, true> : k_cast_multi<4, false>) : (c.filter ? k_cast_multi<8, true> : k_cast_multi<8, false>), a, c, s);
+    } else {
+        CastK a = cast_fill<CastK>(c); a.hit = c.hit;
+        launch_query(c.kind == CastKind::Any ? (c.filter ? k_cast<true, true> : k_cast<true, false>) : (c.filter ? k_cast<false, true> : k_cast<false, false>), a, c, s);
+    }
+}
 void launch_closest(const ClosestArgs &c, hipStream_t s) {
-    if (!c.n) return;
-    const Tune t = tune_over(kCastPreset, c.tune);
-    ClosestK a{};
-    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.points = c.points; a.duv = c.duv; a.ids = c.ids; a.point = c.point;
-    a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
+    ClosestK a = query_fill<ClosestK>(c); a.points = c.points; a.point = c.point;
     a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
-    const uint32_t nb = persistent_blocks(c.n, t);
-    if (c.filter) k_closest<true><<<nb, kTraceBlock, 0, s>>>(a); else k_closest<false><<<nb, kTraceBlock, 0, s>>>(a);
+    launch_query(c.filter ? k_closest<true> : k_closest<false>, a, c, s);
 }
 
 } // namespace art

@@ -677,44 +677,74 @@ class Renderer:
         p, s, a = _mask_value("primary", primary), _mask_value("shadow", shadow), _mask_value("ao", ao)
         check(self._L.art_set_ray_masks(self._ctx, p, s, a))
 
+    # ---- queries on device buffers: one tensor check, one output rule, one stream rule (the texts are the ones callers have always seen: hosts log them) ----
+    _RECORDS = (("tuv", "float32", (4,), 16), ("ids", "int32", (2,), 8))   # an output: name, dtype, the shape behind n, alignment
+    _POINT = ("point", "float32", (4,), 16)
+    _RESOLVE_OUTPUTS = dict(pos=4, ng=4, ns=4, uv=2, albedo=4, orm=4)   # name -> floats a record (the order of ArtHitResolve's fields)
+
+    def _query_device(self):
+        """this context's device index; created on "the current device": the one torch calls current (the same HIP runtime state), looked up once"""
+        if self._device < 0:
+            import torch
+            self._device = torch.cuda.current_device()
+        return self._device
+
+    def _on_device(self, t, dtype, align):
+        import torch
+        return isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self._query_device() and t.dtype == getattr(torch, dtype) and t.is_contiguous() and \
+            t.data_ptr() % align == 0
+
+    def _dev_tensor(self, t, name, dtype, tail_shape, align, n=None, exact=False):
+        """t, or ValueError: a contiguous, aligned tensor of that dtype on this context's device, of shape (any, *tail_shape) -- an input -- or (>= n, *tail_shape) -- an
+        output of at least n records -- or exactly tail_shape"""
+        import torch
+        dev = self._query_device()
+        if self._on_device(t, dtype, align) and (tuple(t.shape) == tail_shape if exact else
+                                                 t.dim() == 1 + len(tail_shape) and tuple(t.shape[1:]) == tail_shape and (n is None or t.shape[0] >= n)):
+            return t
+        if exact:
+            raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape {tail_shape}, {align}-byte aligned")
+        if n is not None:   # (n,) for no tail, (n, 4) for one, (n, K, 4,) for two
+            shape = "".join(f", {w}" for w in tail_shape) + ("," if len(tail_shape) != 1 else "")
+            raise ValueError(f"out: {name} must be a contiguous torch.{dtype} tensor on cuda:{dev} of shape (>= n{shape}), {align}-byte aligned")
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev):
+            raise ValueError(f"{name} must be a torch tensor on cuda:{dev}")
+        raise ValueError(f"{name} must be {dtype} of shape (n, {tail_shape[0]}), contiguous and {align}-byte aligned")
+
+    def _outputs(self, out, n, device, specs):
+        """the tensors a query writes, one per (name, dtype, shape behind n, alignment): the caller's, of at least n records each, or new ones"""
+        import torch
+        if out is None:
+            return tuple(torch.empty((n,) + tail, dtype=getattr(torch, dtype), device=device) for _, dtype, tail, _ in specs)
+        return tuple(self._dev_tensor(t, name, dtype, tail, align, n) for t, (name, dtype, tail, align) in zip(out, specs, strict=True))
+
+    @staticmethod
+    def _stream_handle(stream, device):
+        """the hipStream_t a query is enqueued on: `stream` (a torch stream or a raw handle), default torch's current stream on `device`.  torch's default stream is HIP's
+        null stream, handle 0 -- which the entry points read as "the context's cast stream": hipStreamLegacy (1) names the null stream itself"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(device)
+        return int(getattr(stream, "cuda_stream", stream)) or 1
+
     def cast_rays(self, rays, kind="closest", cull_mask=0xFF, out=None, stream=None):
         """Trace rays that sit on the device (art_cast_rays: the application's own traceRayEXT).  rays: a torch tensor on this context's device, float32, shape (n, 8) --
         o.xyz, tmin, d.xyz, tmax -- contiguous and 16-byte aligned.  kind "closest" returns (tuv, ids): (n, 4) float32 t,u,v,0 -- a miss is (tmax, 0, 0, 0) -- and (n, 2) int32
         (primitive, triangle in the primitive), -1,-1 for a miss; kind "any" returns hit: (n,) uint8.  out: the tensor(s) to write -- (tuv, ids) or hit, of at least n records,
         which must not overlap the rays -- instead of new ones.  The cast is enqueued on `stream` (a torch stream or a raw hipStream_t; default: torch's current stream) and
         the call returns: no host synchronisation, the results are ordered behind the cast on that stream like those of any torch operation."""
-        import torch
         m = _mask_value("cull_mask", cull_mask)
         if kind not in ("closest", "any"):
             raise ValueError("kind must be 'closest' or 'any'")
-        if self._device < 0:   # created on "the current device": the one torch calls current (the same HIP runtime state), looked up once
-            self._device = torch.cuda.current_device()
-        dev = self._device
-        if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device.index != dev:
-            raise ValueError(f"rays must be a torch tensor on cuda:{dev}")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.data_ptr() % 16:
-            raise ValueError("rays must be float32 of shape (n, 8), contiguous and 16-byte aligned")
-        n = rays.shape[0]
-
-        def _out(t, name, dtype, width, align):
-            ok = isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and \
-                t.shape[0] >= n and tuple(t.shape[1:]) == width
-            if not ok:
-                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n,{' ' + str(width[0]) if width else ''}), {align}-byte aligned")
-            return t
+        n = self._dev_tensor(rays, "rays", "float32", (8,), 16).shape[0]
         d = _lib.ArtRayCast(rays_dev=rays.data_ptr() or None, n=n, cull_mask=m, flags=0)
         if kind == "closest":
-            tuv, ids = out if out is not None else (torch.empty((n, 4), dtype=torch.float32, device=rays.device), torch.empty((n, 2), dtype=torch.int32, device=rays.device))
-            _out(tuv, "tuv", torch.float32, (4,), 16), _out(ids, "ids", torch.int32, (2,), 8)
-            d.kind, d.tuv_dev, d.ids_dev, res = _lib.ART_CAST_CLOSEST, tuv.data_ptr() or None, ids.data_ptr() or None, (tuv, ids)
+            res = tuv, ids = self._outputs(out, n, rays.device, self._RECORDS)
+            d.kind, d.tuv_dev, d.ids_dev = _lib.ART_CAST_CLOSEST, tuv.data_ptr() or None, ids.data_ptr() or None
         else:
-            hit = out if out is not None else torch.empty((n,), dtype=torch.uint8, device=rays.device)
-            _out(hit, "hit", torch.uint8, (), 1)
-            d.kind, d.hit_dev, res = _lib.ART_CAST_ANY, hit.data_ptr() or None, hit
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        # torch's default stream is HIP's null stream, handle 0 -- which art_cast_rays reads as "the context's cast stream": hipStreamLegacy (1) names the null stream itself
-        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1
+            res, = self._outputs(None if out is None else (out,), n, rays.device, (("hit", "uint8", (), 1),))
+            d.kind, d.hit_dev = _lib.ART_CAST_ANY, res.data_ptr() or None
+        d.hip_stream = self._stream_handle(stream, rays.device)
         check(self._L.art_cast_rays(self._ctx, C.byref(d)))
         return res
 
@@ -723,36 +753,16 @@ class Renderer:
         (primitive, triangle in the primitive) and (n,) uint8 -- record j of ray i is its j-th hit in ascending (t, global triangle id) while j < count[i], and the miss
         record (tmax, 0, 0, 0), (-1, -1) from there on.  out: (tuv, ids, count) to write instead of new ones, of at least n rays and exactly K records a ray, not overlapping
         the rays or each other.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
-        import torch
         m = _mask_value("cull_mask", cull_mask)
         k = int(max_hits)
         if k != max_hits or not 1 <= k <= _lib.ART_CAST_MAX_HITS:
             raise ValueError(f"max_hits must be an integer in 1..{_lib.ART_CAST_MAX_HITS}")
-        if self._device < 0:
-            self._device = torch.cuda.current_device()
-        dev = self._device
-        if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device.index != dev:
-            raise ValueError(f"rays must be a torch tensor on cuda:{dev}")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.data_ptr() % 16:
-            raise ValueError("rays must be float32 of shape (n, 8), contiguous and 16-byte aligned")
-        n = rays.shape[0]
-        if out is None:
-            out = (torch.empty((n, k, 4), dtype=torch.float32, device=rays.device), torch.empty((n, k, 2), dtype=torch.int32, device=rays.device),
-                   torch.empty((n,), dtype=torch.uint8, device=rays.device))
-        tuv, ids, count = out
-        for t, name, dtype, width, align in ((tuv, "tuv", torch.float32, (k, 4), 16), (ids, "ids", torch.int32, (k, 2), 8), (count, "count", torch.uint8, (), 1)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and
-                    t.shape[0] >= n and tuple(t.shape[1:]) == width):
-                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n,{''.join(' ' + str(w) + ',' for w in width)}), {align}-byte aligned")
+        n = self._dev_tensor(rays, "rays", "float32", (8,), 16).shape[0]
+        tuv, ids, count = self._outputs(out, n, rays.device, (("tuv", "float32", (k, 4), 16), ("ids", "int32", (k, 2), 8), ("count", "uint8", (), 1)))
         d = _lib.ArtRayCastMulti(rays_dev=rays.data_ptr() or None, tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, count_dev=count.data_ptr() or None,
-                                 n=n, max_hits=k, cull_mask=m, flags=0)
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+                                 n=n, max_hits=k, cull_mask=m, flags=0, hip_stream=self._stream_handle(stream, rays.device))
         check(self._L.art_cast_rays_multi(self._ctx, C.byref(d)))
         return tuv, ids, count
-
-    _RESOLVE_OUTPUTS = dict(pos=4, ng=4, ns=4, uv=2, albedo=4, orm=4)   # name -> floats a record (the order of ArtHitResolve's fields)
 
     def resolve_hits(self, tuv, ids, want=("pos", "ng", "ns", "uv", "albedo", "orm"), out=None, stream=None):
         """What the rays hit (art_resolve_hits): the surface attributes behind hit records.  tuv, ids: the tensors cast_rays (kind "closest") or cast_rays_multi returned --
@@ -768,36 +778,24 @@ class Renderer:
             a = r.resolve_hits(tuv, ids, want=("albedo",))["albedo"][..., 3]          # (n, 4): alpha of every surface crossed, 0 in the tail records
             through = torch.cumprod(1 - a, dim=1)[:, -1]                               # what is left of the ray behind its first four surfaces"""
         import torch
-        if self._device < 0:
-            self._device = torch.cuda.current_device()
-        dev = self._device
+        dev = self._query_device()
         want = tuple(want)
         if not want or len(set(want)) != len(want) or any(w not in self._RESOLVE_OUTPUTS for w in want):
             raise ValueError(f"want must name one or more of {tuple(self._RESOLVE_OUTPUTS)}, each once")
-        for t, name, dtype, width, align in ((tuv, "tuv", torch.float32, 4, 16), (ids, "ids", torch.int32, 2, 8)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.dim() in (2, 3) and t.shape[-1] == width and
-                    t.is_contiguous() and t.data_ptr() % align == 0):
-                raise ValueError(f"{name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (n, {width}) or (n, K, {width}), {align}-byte aligned")
+        for t, (name, dtype, (width,), align) in zip((tuv, ids), self._RECORDS):   # (n, w) or (n, K, w): a check of its own
+            if not (self._on_device(t, dtype, align) and t.dim() in (2, 3) and t.shape[-1] == width):
+                raise ValueError(f"{name} must be a contiguous torch.{dtype} tensor on cuda:{dev} of shape (n, {width}) or (n, K, {width}), {align}-byte aligned")
         lead = tuple(tuv.shape[:-1])
         if tuple(ids.shape[:-1]) != lead:
             raise ValueError("tuv and ids must hold the same records")
-        n = 1
-        for k in lead:
-            n *= k
         res = {}
         for name in want:
             width = self._RESOLVE_OUTPUTS[name]
             t = out[name] if out is not None and name in out else torch.empty(lead + (width,), dtype=torch.float32, device=tuv.device)
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == torch.float32 and t.is_contiguous() and
-                    tuple(t.shape) == lead + (width,) and t.data_ptr() % (4 * width) == 0):
-                raise ValueError(f"out: {name} must be a contiguous float32 tensor on cuda:{dev} of shape {lead + (width,)}, {4 * width}-byte aligned")
-            res[name] = t
-        d = _lib.ArtHitResolve(tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, n=n, flags=0)
+            res[name] = self._dev_tensor(t, name, "float32", lead + (width,), 4 * width, exact=True)
+        d = _lib.ArtHitResolve(tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, n=tuv.numel() // 4, flags=0, hip_stream=self._stream_handle(stream, tuv.device))
         for name, t in res.items():
             setattr(d, name + "_dev", t.data_ptr() or None)
-        if stream is None:
-            stream = torch.cuda.current_stream(tuv.device)
-        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
         check(self._L.art_resolve_hits(self._ctx, C.byref(d)))
         return res
 
@@ -813,29 +811,11 @@ class Renderer:
         point, a NaN or negative r) is the miss record: (r, 0, 0, 0), (-1, -1) and a point of zeros.  Alpha cutoffs are not tested; primitive masks are, against cull_mask.
         out: (duv, ids, point) to write instead of new ones, of at least n records, not overlapping the points or each other.  Enqueued on `stream` (default: torch's
         current stream) without host synchronisation, like cast_rays."""
-        import torch
         m = _mask_value("cull_mask", cull_mask)
-        if self._device < 0:
-            self._device = torch.cuda.current_device()
-        dev = self._device
-        if not isinstance(points, torch.Tensor) or not points.is_cuda or points.device.index != dev:
-            raise ValueError(f"points must be a torch tensor on cuda:{dev}")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.data_ptr() % 16:
-            raise ValueError("points must be float32 of shape (n, 4), contiguous and 16-byte aligned")
-        n = points.shape[0]
-        if out is None:
-            out = (torch.empty((n, 4), dtype=torch.float32, device=points.device), torch.empty((n, 2), dtype=torch.int32, device=points.device),
-                   torch.empty((n, 4), dtype=torch.float32, device=points.device))
-        duv, ids, point = out
-        for t, name, dtype, width, align in ((duv, "duv", torch.float32, (4,), 16), (ids, "ids", torch.int32, (2,), 8), (point, "point", torch.float32, (4,), 16)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and
-                    t.shape[0] >= n and tuple(t.shape[1:]) == width):
-                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n, {width[0]}), {align}-byte aligned")
+        n = self._dev_tensor(points, "points", "float32", (4,), 16).shape[0]
+        duv, ids, point = self._outputs(out, n, points.device, (("duv", "float32", (4,), 16), self._RECORDS[1], self._POINT))
         d = _lib.ArtPointQuery(points_dev=points.data_ptr() or None, duv_dev=duv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
-                               n=n, cull_mask=m, flags=0, reserved=0)
-        if stream is None:
-            stream = torch.cuda.current_stream(points.device)
-        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+                               n=n, cull_mask=m, flags=0, reserved=0, hip_stream=self._stream_handle(stream, points.device))
         check(self._L.art_closest_points(self._ctx, C.byref(d)))
         return duv, ids, point
 
@@ -853,32 +833,14 @@ class Renderer:
         point of zeros.  Alpha cutoffs are not tested; primitive masks are, against cull_mask.  out: (tuv, ids, point) to write instead of new ones, of at least n records,
         not overlapping the rays or each other.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
         import math
-        import torch
         m = _mask_value("cull_mask", cull_mask)
         radius = float(radius)
         if not (radius >= 0.0 and math.isfinite(radius)):
             raise ValueError("radius must be a finite number >= 0")
-        if self._device < 0:
-            self._device = torch.cuda.current_device()
-        dev = self._device
-        if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device.index != dev:
-            raise ValueError(f"rays must be a torch tensor on cuda:{dev}")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.data_ptr() % 16:
-            raise ValueError("rays must be float32 of shape (n, 8), contiguous and 16-byte aligned")
-        n = rays.shape[0]
-        if out is None:
-            out = (torch.empty((n, 4), dtype=torch.float32, device=rays.device), torch.empty((n, 2), dtype=torch.int32, device=rays.device),
-                   torch.empty((n, 4), dtype=torch.float32, device=rays.device))
-        tuv, ids, point = out
-        for t, name, dtype, width, align in ((tuv, "tuv", torch.float32, (4,), 16), (ids, "ids", torch.int32, (2,), 8), (point, "point", torch.float32, (4,), 16)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype and t.is_contiguous() and t.data_ptr() % align == 0 and
-                    t.shape[0] >= n and tuple(t.shape[1:]) == width):
-                raise ValueError(f"out: {name} must be a contiguous {dtype} tensor on cuda:{dev} of shape (>= n, {width[0]}), {align}-byte aligned")
+        n = self._dev_tensor(rays, "rays", "float32", (8,), 16).shape[0]
+        tuv, ids, point = self._outputs(out, n, rays.device, self._RECORDS + (self._POINT,))
         d = _lib.ArtSphereCast(rays_dev=rays.data_ptr() or None, tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
-                               n=n, cull_mask=m, flags=0, radius=radius)
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device)
-        d.hip_stream = int(getattr(stream, "cuda_stream", stream)) or 1   # (handle 0 is "the context's cast stream": cast_rays)
+                               n=n, cull_mask=m, flags=0, radius=radius, hip_stream=self._stream_handle(stream, rays.device))
         check(self._L.art_cast_spheres(self._ctx, C.byref(d)))
         return tuv, ids, point
 

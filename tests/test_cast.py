@@ -2,28 +2,16 @@
 (orc.Scene.trace_closest / trace_any over a 30-bit-Morton tree of its own): ids and the bits of t, u, v are equal, any-hit bytes are equal.  Scenes and rays are those
 of the query tests (tests/test_gpu_parity.py, tests/test_alpha.py)."""
 import ctypes as C
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 from helpers import random_rays
+from helpers import _dead_rays, _gcc_layout, _outward_rays, R, _tex_of_alpha as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATTERN = -0x5A5A5A5B   # what oversized output buffers are filled with (int32; as a float a NaN with a payload no tracer writes)
-
-
-@pytest.fixture(scope="module")
-def R():
-    from araytracingjourney_amd import renderer
-    return renderer
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    return t
 
 
 _REF = {}
@@ -58,10 +46,6 @@ def _same_any(got, want, what=""):
     assert np.array_equal(got.cpu().numpy(), want), what
 
 
-def _up(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,detail,n", [("sponza_like", 0.12, 20000), ("cornell", 1.0, 4096)])
 def test_casts_match_the_oracle_bitwise(R, torch, orc, get_scene, name, detail, n):
@@ -88,22 +72,6 @@ def test_casts_match_the_oracle_bitwise(R, torch, orc, get_scene, name, detail, 
         assert set(ref["ids"][:, 0].tolist()) == set(range(len(ref["scene"].primitives))) | {-1}   # every primitive is somebody's closest hit
     assert r.cast_counts() == dict(casts=4, rays=4 * n, host_waits=0)
     r.close()
-
-
-def _dead_rays(base):
-    """NaN direction, infinite origin, NaN tmax in turn"""
-    d = base.copy()
-    d[0::3, 4] = np.nan
-    d[1::3, 0] = np.inf
-    d[2::3, 7] = np.nan
-    return d
-
-
-def _outward_rays(base):
-    """from the sphere around the scene, away from it: nothing to hit"""
-    out = base[(np.arange(base.shape[0]) % 3) != 0].copy()   # (every third ray of random_rays starts inside the scene)
-    out[:, 4:7] = out[:, 0:3] / np.linalg.norm(out[:, 0:3], axis=1, keepdims=True)
-    return out
 
 
 @pytest.mark.gpu
@@ -195,16 +163,6 @@ def test_a_partly_dead_pool_filling_is_compacted(R, torch, orc, get_scene, refil
 
 
 # ---- the alpha card of tests/test_alpha.py (its construction, restated) ---------------------------------------------------------------------------------
-def _tex(alpha, rgb=(180, 150, 120)):
-    th, tw = alpha.shape
-    t = np.zeros((3, th, tw, 4), np.uint8)
-    t[0, ..., 0], t[0, ..., 1], t[0, ..., 2] = rgb
-    t[0, ..., 3] = alpha
-    t[1, ..., 0], t[1, ..., 1], t[1, ..., 2], t[1, ..., 3] = 255, 160, 0, 255
-    t[2, ..., 0], t[2, ..., 1], t[2, ..., 2], t[2, ..., 3] = 128, 128, 255, 255
-    return t
-
-
 def _card_scene(scenes, base, alpha):
     """Cornell and a horizontal card under its light"""
     mb = scenes.MeshBuilder()
@@ -515,15 +473,6 @@ def test_errors_change_nothing_and_enqueue_nothing(R, torch, get_scene):
     with pytest.raises(ValueError):
         r.cast_rays(rays, cull_mask=0x100)
     r.close()
-
-
-def _gcc_layout():
-    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "tools", "gen_rust_bindings.py"))
-    g = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(g)
-    structs = [s for s in g.parse(open(g.HDR).read())[2] if s[0] == "ArtRayCast"]
-    assert len(structs) == 1
-    return g.c_layout(structs), [f for f, _ in structs[0][2]]
 
 
 def test_the_ctypes_descriptor_is_the_headers():

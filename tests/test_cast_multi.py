@@ -4,29 +4,17 @@ The reference is the CPU oracle, one triangle at a time: an orc.Scene that holds
 its t_eff, u, v -- accept() and t_eff are structure-independent.  The table of all those answers (sparse: hits only), sorted by (t_eff, gid) within a ray
 and cut at K, is what the device must write, ids and bits.  The CPU tests below first check that table against the oracle's own whole-scene walks."""
 import ctypes as C
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 from helpers import random_rays
+from helpers import _dead_rays, _gcc_layout, _outward_rays, R, _tex_flat as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATTERN = -0x5A5A5A5B   # tests/test_cast.py's: what oversized output buffers are filled with
 N = 4096
-
-
-@pytest.fixture(scope="module")
-def R():
-    from araytracingjourney_amd import renderer
-    return renderer
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    return t
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------------------------
@@ -114,10 +102,6 @@ def _same(got, want, what=""):
         assert np.array_equal(count.cpu().numpy(), rcount), f"{what}: counts differ"
 
 
-def _up(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared references are read-only)
-
-
 # ---- without a GPU ------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,detail", [("cornell", 1.0), ("sponza_like", 0.05)])
 def test_the_table_reproduces_the_whole_scene_walks(orc, get_scene, name, detail):
@@ -138,15 +122,6 @@ def test_the_table_reproduces_the_whole_scene_walks(orc, get_scene, name, detail
         assert tied_rays(tab, N + 1, 8) >= 50 and int((per_ray > 3).sum()) >= 300
     else:
         assert int((per_ray > 8).sum()) >= 50
-
-
-def _gcc_layout(name):
-    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "tools", "gen_rust_bindings.py"))
-    g = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(g)
-    structs = [s for s in g.parse(open(g.HDR).read())[2] if s[0] == name]
-    assert len(structs) == 1
-    return g.c_layout(structs), [f for f, _ in structs[0][2]]
 
 
 def test_the_ctypes_descriptor_is_the_headers():
@@ -218,22 +193,6 @@ def test_sponza_full_lists_move_the_bound(R, torch, orc, get_scene):
     for K, g in got.items():
         _same(g, expected(tab, rays, K, keep), f"K = {K}")
     r.close()
-
-
-def _dead_rays(base):
-    """tests/test_cast.py's: NaN direction, infinite origin, NaN tmax in turn"""
-    d = base.copy()
-    d[0::3, 4] = np.nan
-    d[1::3, 0] = np.inf
-    d[2::3, 7] = np.nan
-    return d
-
-
-def _outward_rays(base):
-    """tests/test_cast.py's: from the sphere around the scene, away from it"""
-    out = base[(np.arange(base.shape[0]) % 3) != 0].copy()
-    out[:, 4:7] = out[:, 0:3] / np.linalg.norm(out[:, 0:3], axis=1, keepdims=True)
-    return out
 
 
 @pytest.mark.gpu
@@ -311,15 +270,6 @@ def test_ranges(R, torch, orc, get_scene):
         for K, g in got.items():
             _same(g, expected(t, rays, K), f"{what}, K = {K}")
     r.close()
-
-
-def _tex(alpha_value, tw=8, th=8):
-    """tests/test_alpha.py's three layers, alpha the same in every texel: no sampler is needed to know the alpha anywhere"""
-    t = np.zeros((3, th, tw, 4), np.uint8)
-    t[0, ..., 0], t[0, ..., 1], t[0, ..., 2], t[0, ..., 3] = 180, 150, 120, alpha_value
-    t[1, ..., 0], t[1, ..., 1], t[1, ..., 2], t[1, ..., 3] = 255, 160, 0, 255
-    t[2, ..., 0], t[2, ..., 1], t[2, ..., 2], t[2, ..., 3] = 128, 128, 255, 255
-    return t
 
 
 @pytest.mark.gpu

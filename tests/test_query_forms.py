@@ -40,6 +40,7 @@ import test_closest_points as tcp
 import test_sphere_cast as tsc
 import test_walk_edges as twe
 from helpers import chain_scene, degenerate_soup, dequantise, pending_on_first_descent_point, pending_on_first_descent_wide, random_rays
+from helpers import _host, R, torch, _up  # noqa: F401  (R, torch: module fixtures)
 
 PATTERN = -0x5A5A5A5B   # tests/test_cast.py's: what oversized output buffers are filled with
 RHO = 0.05
@@ -48,18 +49,6 @@ KS = (1, 4, 8)
 LDS_DEPTH = 8           # kCastLds and kClosestLds of art_query.hip: stack entries a lane keeps in LDS; deeper ones spill
 OUTPUTS = ("pos", "ng", "ns", "uv", "albedo", "orm")
 SIZES = (0, 1, 63, 64, 65, 127, 511, 513, 4097)
-
-
-@pytest.fixture(scope="module")
-def R():
-    from araytracingjourney_amd import renderer
-    return renderer
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    return t
 
 
 # ---- scenes, inputs and references: made once, shared, never written ------------------------------------------------------------------------------------------------
@@ -145,14 +134,6 @@ def _want_multi(c, K, n=None):
     if (K, n) not in memo:
         memo[(K, n)] = _freeze(tm.expected(c["tab"], c["rays"][:n], K, c["keep"] & (c["tab"]["ray"] < n)))
     return memo[(K, n)]
-
-
-def _up(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared references are read-only)
-
-
-def _host(got):
-    return tuple(t.cpu().numpy() for t in got)
 
 
 def _words(t):

@@ -8,7 +8,6 @@ better than half a unit in the last place of the output's magnitude (a constant 
 measurement: float32 cannot promise more.  Both figures per case are committed in tests/golden/resolve_margins.json (python tests/test_resolve.py --write-margins makes the file);
 a CPU test measures again and compares.  The records the CPU measures on are the oracle's closest hits -- the casts' records bit for bit (tests/test_cast.py)."""
 import ctypes as C
-import importlib.util
 import json
 import os
 import sys
@@ -17,6 +16,7 @@ import numpy as np
 import pytest
 
 from helpers import random_rays, seam_scene
+from helpers import _gcc_layout, R, torch, _up  # noqa: F401  (R, torch: module fixtures)
 import np_shading as nps
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,18 +25,6 @@ OUTPUTS = dict(pos=4, ng=4, ns=4, uv=2, albedo=4, orm=4)
 SHORT = 1e-3          # |interpolated normal|, |interpolated tangent| or |tangent after Gram-Schmidt| below this: the normalisation amplifies without bound, ns is not compared
 LEFT_OUT_CAP = 0.005  # at most this share of a case's hit records may be left out that way
 SENTINEL = -12345.5
-
-
-@pytest.fixture(scope="module")
-def R():
-    from araytracingjourney_amd import renderer
-    return renderer
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    return t
 
 
 # ---- the witness ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -271,15 +259,6 @@ def write_margins():
 
 
 # ---- without a GPU ----------------------------------------------------------------------------------------------------------------------------------------------
-def _gcc_layout(name):
-    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "tools", "gen_rust_bindings.py"))
-    g = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(g)
-    structs = [s for s in g.parse(open(g.HDR).read())[2] if s[0] == name]
-    assert len(structs) == 1
-    return g.c_layout(structs), [f for f, _ in structs[0][2]]
-
-
 def test_the_ctypes_descriptor_is_the_headers():
     """ArtHitResolve as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 80 bytes"""
     from araytracingjourney_amd import _lib
@@ -349,10 +328,6 @@ def test_the_committed_margins_are_what_the_witness_measures(orc, scenes, get_sc
 
 
 # ---- on the device ----------------------------------------------------------------------------------------------------------------------------------------------
-def _up(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared references are read-only)
-
-
 def _host(surf):
     return {k: v.cpu().numpy() for k, v in surf.items()}
 

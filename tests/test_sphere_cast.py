@@ -17,6 +17,7 @@ import pytest
 import np_closest as nc
 import np_sweep as ns
 from helpers import RANGES, SIMILARITIES, chain_scene, degenerate_soup, lattice_rays, lattice_scene, random_rays, similarity, with_ranges
+from helpers import _bits, _host, R, torch, _up  # noqa: F401  (R, torch: module fixtures)
 from test_closest_points import _card_scene, _gcc_layout, _hostile as _closest_hostile   # Cornell with two cards; gcc's layout of a header struct; its hostile scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,18 +26,6 @@ PATTERN = -0x5A5A5A5B   # tests/test_cast.py's: what oversized output buffers ar
 N = 4096
 RHO = 0.05
 SCENES = [("cornell", 1.0), ("sponza_like", 0.05)]
-
-
-@pytest.fixture(scope="module")
-def R():
-    from araytracingjourney_amd import renderer
-    return renderer
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    return t
 
 
 _REF = {}
@@ -56,10 +45,6 @@ def _ref(get_scene, name, detail):
     return _REF[key]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _same(got, want, what=""):
     """ids, the bits of t, u, v, a fourth word of 0, the bits of the point"""
     (tuv, ids, point), (rtuv, rids, rpoint) = got, want
@@ -69,14 +54,6 @@ def _same(got, want, what=""):
     assert not bad.any(), f"{what}: t, u, v of {int(bad.sum())} rays differ (first: {np.flatnonzero(bad)[:5]}: {tuv[bad][:2]} for {rtuv[bad][:2]})"
     assert not _bits(tuv)[:, 3].any(), f"{what}: the fourth word is not 0"
     assert np.array_equal(_bits(point), _bits(rpoint)), f"{what}: the points differ"
-
-
-def _up(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared references are read-only)
-
-
-def _host(got):
-    return tuple(t.cpu().numpy() for t in got)
 
 
 def _ask(r, torch, rays, rho, **kw):
