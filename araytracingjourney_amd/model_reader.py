@@ -8,8 +8,8 @@ import numpy as np
 from . import _lib
 from ._lib import ArtGlbCopyInfo
 
-VERTICES, TEX_COORDS, NORMALS, TANGENTS, INDICES = 1, 2, 4, 8, 16   # MeshAttributeType (model_reader.rs:6-12)
-ALBEDO, ORM, NORMAL, EMISSIVE = 1, 2, 4, 8                           # TextureType (model_reader.rs:14-19)
+VERTICES, TEX_COORDS, NORMALS, TANGENTS, INDICES = _lib.ART_ATTR_VERTICES, _lib.ART_ATTR_TEX_COORDS, _lib.ART_ATTR_NORMALS, _lib.ART_ATTR_TANGENTS, _lib.ART_ATTR_INDICES   # MeshAttributeType (model_reader.rs:6-12)
+ALBEDO, ORM, NORMAL, EMISSIVE = _lib.ART_TEX_ALBEDO, _lib.ART_TEX_ORM, _lib.ART_TEX_NORMAL, _lib.ART_TEX_EMISSIVE   # TextureType (model_reader.rs:14-19)
 COERCE_NONE, COERCE_R8G8B8A8, COERCE_B8G8R8A8, COERCE_B8G8R8 = 0, 1, 2, 3
 
 

@@ -293,7 +293,7 @@ class Model:
 
 
 # the named bits of include/art.h: a convention only, the library gives bits no meaning
-MASK_ALL, VIS_CAMERA, VIS_SHADOW, VIS_AO, VIS_QUERY = 0xFF, 1, 2, 4, 8
+MASK_ALL, VIS_CAMERA, VIS_SHADOW, VIS_AO, VIS_QUERY = _lib.ART_MASK_ALL, _lib.ART_VIS_CAMERA, _lib.ART_VIS_SHADOW, _lib.ART_VIS_AO, _lib.ART_VIS_QUERY
 
 
 def _mask_value(name, v):

@@ -1,10 +1,13 @@
-import importlib.util
+import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_bindings  # noqa: E402  (the parser of the headers and gcc's layout of their structs: the one the bindings are generated with)
 
 
 def oracle_for(orc, scene, n_lights=None, morton_bits=30):
@@ -43,7 +46,6 @@ def random_rays(n, seed, radius=2.5):
 
 def device_to_host(ptr, nbytes):
     """bytes at a raw device pointer (art_device_*) -> numpy uint8; the process's one HIP runtime (loaded by torch / libart)"""
-    import ctypes as C
     hip = C.CDLL("libamdhip64.so")
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     out = np.empty(nbytes, np.uint8)
@@ -380,11 +382,32 @@ def _tex_flat(alpha_value, tw=8, th=8):
     return t
 
 
-def _gcc_layout(name="ArtRayCast"):
-    """sizeof / offsetof of one descriptor of include/art.h as gcc compiles it, and its fields in order (tools/gen_rust_bindings.py)"""
-    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "tools", "gen_rust_bindings.py"))
-    g = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(g)
-    structs = [s for s in g.parse(open(g.HDR).read())[2] if s[0] == name]
-    assert len(structs) == 1
-    return g.c_layout(structs), [f for f, _ in structs[0][2]]
+def layout_mismatches(header, namespace, only=None):
+    """the structs the header at path `header` declares (all of them, or the one named `only`) against the ctypes classes of their names in `namespace`, gcc being the judge:
+    one line "Name: what differs" for every struct whose field names in order, sizeof, any offsetof or packedness is not the class's; [] when the binding is the header's"""
+    structs = [s for s in gen_bindings.parse(header)[2] if only in (None, s[0])]
+    assert structs, (header, only)
+    lay, bad = gen_bindings.c_layout(header, structs), []
+    for name, packed, fields in structs:
+        cls, names = getattr(namespace, name, None), [f for f, _, _ in fields]
+        if cls is None:
+            bad.append(f"{name}: no such class")
+        elif names != [n for n, _ in cls._fields_]:
+            bad.append(f"{name}: fields {[n for n, _ in cls._fields_]} are not the header's {names}")
+        elif C.sizeof(cls) != lay[name]:
+            bad.append(f"{name}: sizeof {C.sizeof(cls)} is not gcc's {lay[name]}")
+        elif bool(getattr(cls, "_pack_", 0)) != packed:
+            bad.append(f"{name}: packed in one, not in the other")
+        else:
+            bad += [f"{name}: offsetof {f} {getattr(cls, f).offset} is not gcc's {lay[name + '.' + f]}" for f in names if getattr(cls, f).offset != lay[name + "." + f]][:1]
+    return bad
+
+
+def _layout_is_the_headers(name, size, fields=None):
+    """_lib's ctypes class `name` is the struct of include/art.h as gcc compiles it, field by field (layout_mismatches), `size` bytes long, and its fields are `fields`
+    where given; returns the class"""
+    from araytracingjourney_amd import _lib
+    cls = getattr(_lib, name)
+    assert layout_mismatches(os.path.join(ROOT, "include", "art.h"), _lib, only=name) == []
+    assert C.sizeof(cls) == size and fields in (None, [n for n, _ in cls._fields_])
+    return cls

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import random_rays
-from helpers import _dead_rays, _gcc_layout, _outward_rays, R, _tex_of_alpha as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
+from helpers import _dead_rays, _layout_is_the_headers, _outward_rays, R, _tex_of_alpha as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATTERN = -0x5A5A5A5B   # what oversized output buffers are filled with (int32; as a float a NaN with a payload no tracer writes)
@@ -478,11 +478,7 @@ def test_errors_change_nothing_and_enqueue_nothing(R, torch, get_scene):
 def test_the_ctypes_descriptor_is_the_headers():
     """ArtRayCast as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field"""
     from araytracingjourney_amd import _lib
-    lay, fields = _gcc_layout()
-    assert fields == [n for n, _ in _lib.ArtRayCast._fields_]
-    assert C.sizeof(_lib.ArtRayCast) == lay["ArtRayCast"] == 56
-    for f in fields:
-        assert getattr(_lib.ArtRayCast, f).offset == lay["ArtRayCast." + f], f
+    _layout_is_the_headers("ArtRayCast", 56)
     hdr = open(os.path.join(ROOT, "include", "art.h")).read()
     for name in ("ART_CAST_CLOSEST", "ART_CAST_ANY", "ART_CAST_MAX_RAYS", "ART_CAST_POOL"):
         assert f"#define {name} {getattr(_lib, name)}u" in hdr, name

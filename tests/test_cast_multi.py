@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from helpers import random_rays
-from helpers import _dead_rays, _gcc_layout, _outward_rays, R, _tex_flat as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
+from helpers import _dead_rays, _layout_is_the_headers, _outward_rays, R, _tex_flat as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATTERN = -0x5A5A5A5B   # tests/test_cast.py's: what oversized output buffers are filled with
@@ -127,11 +127,7 @@ def test_the_table_reproduces_the_whole_scene_walks(orc, get_scene, name, detail
 def test_the_ctypes_descriptor_is_the_headers():
     """ArtRayCastMulti as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 56 bytes"""
     from araytracingjourney_amd import _lib
-    lay, fields = _gcc_layout("ArtRayCastMulti")
-    assert fields == [n for n, _ in _lib.ArtRayCastMulti._fields_] == ["rays_dev", "tuv_dev", "ids_dev", "count_dev", "hip_stream", "n", "max_hits", "cull_mask", "flags"]
-    assert C.sizeof(_lib.ArtRayCastMulti) == lay["ArtRayCastMulti"] == 56
-    for f in fields:
-        assert getattr(_lib.ArtRayCastMulti, f).offset == lay["ArtRayCastMulti." + f], f
+    _layout_is_the_headers("ArtRayCastMulti", 56, ["rays_dev", "tuv_dev", "ids_dev", "count_dev", "hip_stream", "n", "max_hits", "cull_mask", "flags"])
     assert f"#define ART_CAST_MAX_HITS {_lib.ART_CAST_MAX_HITS}u" in open(os.path.join(ROOT, "include", "art.h")).read() and _lib.ART_CAST_MAX_HITS == 8
 
 

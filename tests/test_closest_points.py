@@ -16,7 +16,7 @@ import pytest
 
 import np_closest as nc
 from helpers import SIMILARITIES, chain_scene, degenerate_soup, lattice_coords, lattice_scene, oracle_camera, oracle_for, random_rays, similarity
-from helpers import _bits, _gcc_layout, _host, R, _tex_flat as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
+from helpers import _bits, _layout_is_the_headers, _host, R, _tex_flat as _tex, torch, _up  # noqa: F401  (R, torch: module fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = os.path.join(ROOT, "tests", "golden", "closest_points.stats.json")
@@ -113,12 +113,7 @@ def test_the_brute_force_against_the_witness(get_scene, name, detail):
 
 def test_the_ctypes_descriptor_is_the_headers():
     """3: ArtPointQuery as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 56 bytes"""
-    from araytracingjourney_amd import _lib
-    lay, fields = _gcc_layout("ArtPointQuery")
-    assert fields == [n for n, _ in _lib.ArtPointQuery._fields_] == ["points_dev", "duv_dev", "ids_dev", "point_dev", "hip_stream", "n", "cull_mask", "flags", "reserved"]
-    assert C.sizeof(_lib.ArtPointQuery) == lay["ArtPointQuery"] == 56
-    for f in fields:
-        assert getattr(_lib.ArtPointQuery, f).offset == lay["ArtPointQuery." + f], f
+    _layout_is_the_headers("ArtPointQuery", 56, ["points_dev", "duv_dev", "ids_dev", "point_dev", "hip_stream", "n", "cull_mask", "flags", "reserved"])
 
 
 def test_presence():

@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import _layout_is_the_headers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -29,7 +31,7 @@ def test_mgpu_shard_rule_and_argument_errors():
     for fn in (L.art_mgpu_trace, L.art_mgpu_flush):
         assert fn(None) == _lib.ART_E_INVALID
     assert L.art_mgpu_destroy(None) == _lib.ART_OK
-    assert C.sizeof(_lib.ArtMgpuConfig) == 48 and C.sizeof(_lib.ArtLayout) == 40
+    assert _layout_is_the_headers("ArtMgpuConfig", 48) and _layout_is_the_headers("ArtLayout", 40)
 
 
 def _free_port():

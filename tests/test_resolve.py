@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from helpers import random_rays, seam_scene
-from helpers import _gcc_layout, R, torch, _up  # noqa: F401  (R, torch: module fixtures)
+from helpers import _layout_is_the_headers, R, torch, _up  # noqa: F401  (R, torch: module fixtures)
 import np_shading as nps
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -261,12 +261,7 @@ def write_margins():
 # ---- without a GPU ----------------------------------------------------------------------------------------------------------------------------------------------
 def test_the_ctypes_descriptor_is_the_headers():
     """ArtHitResolve as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 80 bytes"""
-    from araytracingjourney_amd import _lib
-    lay, fields = _gcc_layout("ArtHitResolve")
-    assert fields == [n for n, _ in _lib.ArtHitResolve._fields_] == ["tuv_dev", "ids_dev", "pos_dev", "ng_dev", "ns_dev", "uv_dev", "albedo_dev", "orm_dev", "hip_stream", "n", "flags"]
-    assert C.sizeof(_lib.ArtHitResolve) == lay["ArtHitResolve"] == 80
-    for f in fields:
-        assert getattr(_lib.ArtHitResolve, f).offset == lay["ArtHitResolve." + f], f
+    _layout_is_the_headers("ArtHitResolve", 80, ["tuv_dev", "ids_dev", "pos_dev", "ng_dev", "ns_dev", "uv_dev", "albedo_dev", "orm_dev", "hip_stream", "n", "flags"])
 
 
 def test_the_entry_point_is_exported_bound_and_wrapped():

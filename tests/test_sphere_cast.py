@@ -18,7 +18,7 @@ import np_closest as nc
 import np_sweep as ns
 from helpers import RANGES, SIMILARITIES, chain_scene, degenerate_soup, lattice_rays, lattice_scene, random_rays, similarity, with_ranges
 from helpers import _bits, _host, R, torch, _up  # noqa: F401  (R, torch: module fixtures)
-from test_closest_points import _card_scene, _gcc_layout, _hostile as _closest_hostile   # Cornell with two cards; gcc's layout of a header struct; its hostile scenes
+from test_closest_points import _card_scene, _layout_is_the_headers, _hostile as _closest_hostile   # Cornell with two cards; gcc's layout of a header struct; its hostile scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = os.path.join(ROOT, "tests", "golden", "sphere_cast.stats.json")
@@ -121,13 +121,8 @@ def test_the_conditions_the_gpu_tests_lean_on(get_scene):
 
 def test_the_ctypes_descriptor_is_the_headers():
     """4: ArtSphereCast as ctypes lays it out against sizeof / offsetof of include/art.h as gcc compiles it, field by field: 56 bytes"""
-    from araytracingjourney_amd import _lib
-    lay, fields = _gcc_layout("ArtSphereCast")
-    assert fields == [n for n, _ in _lib.ArtSphereCast._fields_] == ["rays_dev", "tuv_dev", "ids_dev", "point_dev", "hip_stream", "n", "cull_mask", "flags", "radius"]
-    assert C.sizeof(_lib.ArtSphereCast) == lay["ArtSphereCast"] == 56
-    for f in fields:
-        assert getattr(_lib.ArtSphereCast, f).offset == lay["ArtSphereCast." + f], f
-    assert _lib.ArtSphereCast._fields_[-1][1] is C.c_float
+    cls = _layout_is_the_headers("ArtSphereCast", 56, ["rays_dev", "tuv_dev", "ids_dev", "point_dev", "hip_stream", "n", "cull_mask", "flags", "radius"])
+    assert cls._fields_[-1][1] is C.c_float
 
 
 def test_presence():
