@@ -837,9 +837,9 @@ int32_t art_read_color_tiles(ArtContext *c, void *dst, size_t bytes) {
 }
 int32_t art_untile_gathered_frames(ArtContext *c, const void *gathered_dev, uint32_t shard_count, uint32_t shard_stride_tiles, uint32_t n_frames, void *frames_dev, void *hip_stream) {
     if (!c || !gathered_dev) return fail(ART_E_INVALID, "art_untile_gathered: null argument");
+    int32_t r = ensure_layout(c, "art_untile_gathered"); if (r) return r;   // (first: until the frame is laid out padded_tiles is 0 and the two checks below pass whatever they are given)
     if (shard_stride_tiles < c->padded_tiles) return fail(ART_E_INVALID, "art_untile_gathered: stride smaller than a shard's padded tile count");
     if (n_frames == 0 || (n_frames > 1 && (!frames_dev || (uint64_t)n_frames * c->padded_tiles > shard_stride_tiles))) return fail(ART_E_INVALID, "art_untile_gathered_frames: frames do not fit the shard stride (or no output given)");
-    int32_t r = ensure_layout(c, "art_untile_gathered"); if (r) return r;
     if (shard_count != (c->cfg.shard_count > 1 ? c->cfg.shard_count : 1)) return fail(ART_E_INVALID, "art_untile_gathered: shard_count differs from the context's");
     r = use_device(c); if (r) return r;
     hipStream_t us = hip_stream ? (hipStream_t)hip_stream : c->stream_of(c->last);
@@ -858,6 +858,7 @@ int32_t art_untile_gathered_strided(ArtContext *c, const void *gathered_dev, uin
 }
 int32_t art_untile_gathered(ArtContext *c, const void *gathered_dev, uint32_t shard_count, void *frame_dev, void *hip_stream) {
     if (!c) return fail(ART_E_INVALID, "art_untile_gathered: null argument");
+    int32_t r = ensure_layout(c, "art_untile_gathered"); if (r) return r;   // (padded_tiles is the stride: 0 until the frame is laid out)
     return art_untile_gathered_strided(c, gathered_dev, shard_count, c->padded_tiles, frame_dev, hip_stream);
 }
 

@@ -54,6 +54,45 @@ def device_to_host(ptr, nbytes):
     return out
 
 
+def host_to_device(ptr, array):
+    """the bytes of a numpy array to a raw device pointer (art_device_*): the caller has made sure nothing on the device still uses the buffer (Renderer.sync)"""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    a = np.ascontiguousarray(array)
+    rc = hip.hipMemcpy(C.c_void_p(ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, 1)   # hipMemcpyHostToDevice
+    assert rc == 0, f"hipMemcpy failed: {rc}"
+
+
+class MadeUpFrame:
+    """art_present on buffers of the test's making (tests/test_present_edges.py): a renderer with one frame in flight renders the Cornell box once at (w, h) -- which
+    lays the frame out and makes the context presentable -- optionally traces AO (the AO image has no device pointer: a test uses the values the frame has,
+    `self.ao`, None without AO); then present(color, normal, depth) overwrites the three outputs art_present reads through art_device_color / _normal / _depth
+    (arrays of [h, w, 4], [h, w, 4] and [h, w] float32, any of them None to leave what is there) and returns (packed colour, packed normal, packed depth, BGRA8)"""
+
+    def __init__(self, R, scene, w, h, ao_spp=None):
+        self.r = R.renderer_for_scene(scene, (w, h), frames_in_flight=1)
+        self.w, self.h = w, h
+        self.r.render_frame(sync=False)
+        if ao_spp:
+            self.r.trace_ao(ao_spp)
+        self.r.sync()
+        self.ao = self.r.read_ao() if ao_spp else None
+
+    def present(self, color=None, normal=None, depth=None):
+        r, w, h = self.r, self.w, self.h
+        r.sync()
+        for a, (ptr, nbytes), shape in ((color, r.device_color(), (h, w, 4)), (normal, r._dev("normal"), (h, w, 4)), (depth, r._dev("depth"), (h, w))):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float32)
+                assert a.shape == shape and a.nbytes == nbytes, (a.shape, shape, a.nbytes, nbytes)   # never past the buffer's end
+                host_to_device(ptr, a)
+        r.present()
+        return r.read_packed() + (r.read_present(),)
+
+    def close(self):
+        self.r.close()
+
+
 def seam_scene(scenes):
     """one quad whose uv run from -1.25 to 2.25 (and -0.75 to 1.75) under a 4 x 5 texture of unrelated texels: nearly every pixel's bilinear footprint sits on a texel boundary,
     a fifth of them on the REPEAT wrap (tests/test_oracle.py: against numpy in fp64; tests/test_gpu_parity.py: the GPU against the oracle)"""

@@ -385,23 +385,27 @@ def lpm_setup_709():
 
 
 def lpm_map_709(c, P):
-    """LpmMap (ffx_lpm.h:727-832) with shoulder, con, soft, con2, clip and scaleOnly all false"""
-    sat = lambda x: min(max(x, 0.0), 1.0)
-    R, G, B = c
-    rcp_max = 1.0 / max(R, G, B)
-    ratio = np.array([R * rcp_max, G * rcp_max, B * rcp_max]) ** P["saturation"]
-    lt = P["luma_t"]
-    luma = G * lt[1] + (R * lt[0] + B * lt[2])
-    luma = luma ** P["contrast"]
-    luma = luma / (luma * P["tone"][0] + P["tone"][1])
-    scale = sat(luma / float(ratio @ lt))
-    col = np.array([sat(x * scale) for x in ratio])
-    cap = -P["crosstalk"] * col + P["crosstalk"]
-    add = sat(luma - float(col @ lt))
-    t = add / float(cap @ lt)
-    col = np.array([sat(t * cap[k] + col[k]) for k in range(3)])
-    add = sat(luma - float(col @ lt))
-    return np.array([sat(add * P["rcp_luma_t"][k] + col[k]) for k in range(3)])
+    """LpmMap (ffx_lpm.h:727-832) with shoulder, con, soft, con2, clip and scaleOnly all false.
+    Total over finite colours with a positive maximum: the arithmetic is IEEE's (numpy float64 under errstate: x / 0 = +-Inf, 0 / 0 = NaN, never an exception) and
+    sat(NaN) = 0, which is what fminf(fmaxf(x, 0), 1) of both C restatements gives.  It matters from grey 256 (hdrMax) up: the colour saturates to 1, every cap is 0,
+    t = add / 0 = Inf, t * cap = NaN -> 0, and the second luma step brings the pixel back to white"""
+    sat = lambda x: 0.0 if x != x else min(max(float(x), 0.0), 1.0)
+    with np.errstate(all="ignore"):
+        R, G, B = (np.float64(x) for x in c)
+        rcp_max = np.float64(1.0) / max(R, G, B)
+        ratio = np.array([R * rcp_max, G * rcp_max, B * rcp_max]) ** P["saturation"]
+        lt = P["luma_t"]
+        luma = G * lt[1] + (R * lt[0] + B * lt[2])
+        luma = luma ** P["contrast"]
+        luma = luma / (luma * P["tone"][0] + P["tone"][1])
+        scale = sat(luma / np.float64(ratio @ lt))
+        col = np.array([sat(x * scale) for x in ratio])
+        cap = -P["crosstalk"] * col + P["crosstalk"]
+        add = np.float64(sat(luma - np.float64(col @ lt)))
+        t = add / np.float64(cap @ lt)
+        col = np.array([sat(t * cap[k] + col[k]) for k in range(3)])
+        add = sat(luma - np.float64(col @ lt))
+        return np.array([sat(add * P["rcp_luma_t"][k] + col[k]) for k in range(3)])
 
 
 def present_pixel(packed, ao, P):

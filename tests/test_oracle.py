@@ -601,7 +601,8 @@ def test_presentation_against_numpy_in_fp64(orc):
     """the last leg both hands wrote alike: AMD's LPM tone mapper, restated twice from ffx_lpm.h by the same hand (oracle and art_present.hip).
     tests/np_shading.py restates the presentation a third time, in float64 and from the other side: the control block from the reference's own Rust
     (vk_tonemap.rs:12-47, :122-230, with its z = 1 - x + y), LpmMap from ffx_lpm.h:727-832, the small-float read-back from the format's definition.  4 000 colours
-    from black over mid grey to 300 (saturated primaries, near-equal channels, every AO value): the oracle's 8-bit output is numpy's value rounded, or -- where
+    from black over mid grey to 300 (saturated primaries, near-equal channels, every AO value), and 240 greys and near-greys from 256 up to 64512, where LpmMap
+    divides by a zero cap: the oracle's 8-bit output is numpy's value rounded, or -- where
     numpy's value lies within 0.02 of a rounding boundary and float arithmetic may fall the other way -- its neighbour"""
     rng = np.random.default_rng(7)
     n = 4000
@@ -612,7 +613,17 @@ def test_presentation_against_numpy_in_fp64(orc):
     col[0, 50:100, :3] = mag[50:100, None]                          # greys
     col[0, 100:150, 1:3] = 0.0                                      # saturated red
     ao = rng.integers(0, 256, (1, n)).astype(np.uint32); ao[0, :200] = 255
+    # greys and near-greys from hdrMax = 256 up to 64512, the largest value all three channels hold: the colour saturates, LpmMap divides by a zero cap and the
+    # witness has to follow IEEE through it (np_shading.lpm_map_709).  Half of them under full AO, half under a random one
+    m = 240
+    hi = np.zeros((1, m, 4), np.float32)
+    g = np.concatenate([[256.0, 257.0, 300.0, 512.0, 1000.0, 32768.0, 64512.0], 256.0 * (64512.0 / 256.0) ** np.sort(rng.random(m // 2 - 7))])
+    hi[0, :m // 2, :3] = g[:, None]
+    hi[0, m // 2:, :3] = np.minimum(g[:, None] * (1.0 + 0.03 * (rng.random((m // 2, 3)) - 0.5)), 64512.0)
+    ao_hi = rng.integers(1, 256, (1, m)).astype(np.uint32); ao_hi[0, ::2] = 255
+    col, ao, n = np.concatenate([col, hi], 1), np.concatenate([ao, ao_hi], 1), n + m
     packed, bgra = orc.present(col, ao)
+    assert np.all(bgra[0, n - m:n - m // 2:2, :3] == 255)            # (full AO: white, not the black a NaN would leave)
     P = NP.lpm_setup_709()
     ctl = orc.lpm_control_block(False, 0.0, 256.0, 8.0, 0.25, 1.0, (0, 0, 0), (1.0, 0.5, 1.0 / 32.0)).view(np.float32)
     assert np.allclose(ctl[0:3], P["saturation"], rtol=1e-6) and np.isclose(ctl[3], P["contrast"]) and np.allclose(ctl[4:6], P["tone"], rtol=2e-5)

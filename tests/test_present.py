@@ -1,9 +1,41 @@
 """Output packing + LPM tonemap: the step right after the path.  CPU tests of the oracle restatement and of
-libart's host-side LpmSetup port (no GPU needed); the GPU comparison lives in test_gpu_parity.py."""
+libart's host-side LpmSetup port (no GPU needed), and the definition of the two small-float formats every packer is judged by.  The GPU comparisons: one natural frame
+in test_gpu_parity.py (test_packing_and_tonemap_match_oracle), every code, tie and special value of the packers and the tone mapper against the fp64 witness in
+test_present_edges.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+
+# ---- B10G11R11_UFLOAT_PACK32's two channel formats, from the format and not from the C: 5 exponent bits (bias 15), `mb` = 6 or 5 mantissa bits, no sign ------------------
+def ufloat_table(mb):
+    """the value of every finite code, in code order (1 984 codes for 6 mantissa bits, 992 for 5), float64 (exact): exponent field 0 is m / 2^mb * 2^-14, any other
+    (1 + m / 2^mb) * 2^(e - 15); exponent field 31 is Inf (m = 0) and NaN (the other codes)"""
+    code = np.arange(31 << mb)
+    e, m = code >> mb, code & ((1 << mb) - 1)
+    return np.where(e == 0, np.ldexp(m.astype(np.float64), -14 - mb), np.ldexp((m + (1 << mb)).astype(np.float64), e - 15 - mb))
+
+
+def ufloat_nan_code(code, mb):
+    code = np.asarray(code)
+    return ((code >> mb) == 31) & ((code & ((1 << mb) - 1)) != 0)
+
+
+def ufloat_encode(values, mb):
+    """float32 -> code: the nearest table entry, a tie to the even code; negatives (-0 and -Inf among them) to 0; +Inf to the Inf code; NaN of either sign to a NaN code
+    (this one: mantissa 1; ufloat_nan_code tells any).  Past the largest finite code the project's rule as it stands (test_present_edges.py pins it under its own
+    name): the Inf code counts as the table's next entry, 2^16, so a finite value from the midpoint between the largest finite value and 2^16 up becomes Inf"""
+    v = np.asarray(values, np.float32)
+    t = np.concatenate([ufloat_table(mb), [65536.0]])
+    mid = 0.5 * (t[:-1] + t[1:])                                       # exact: neighbours have at most mb + 1 bits each and exponents one apart at most
+    with np.errstate(invalid="ignore"):                                # (a signalling NaN on its way to float64)
+        x = v.astype(np.float64)
+        lo = np.searchsorted(mid, x, side="left")                      # mids below x: the code whose cell x lies in, the lower one on a tie
+        tie = mid[np.minimum(lo, len(mid) - 1)] == x
+    code = np.minimum(np.where(tie & (lo % 2 == 1), lo + 1, lo), len(t) - 1)
+    code = np.where(np.signbit(v), 0, code)
+    return np.where(np.isnan(v), (31 << mb) | 1, code).astype(np.uint32)
 
 
 def _values(n, seed):
