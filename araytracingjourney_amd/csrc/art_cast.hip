@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres; DESIGN.md 3.5 .. 3.9) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi; DESIGN.md 3.5 .. 3.10) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
 // entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -200,6 +200,24 @@ int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
     a.points = (const float4 *)d->points_dev; a.point = (float4 *)d->point_dev;
     launch_closest(a, q.stream);
+    return cast_commit(c, q, 0);
+}
+
+// ---- the K nearest triangles (include/art.h: art_closest_points_multi) -------------------------------------------------------------------------------
+// art_closest_points' path with K records a query: a block of the ring, counted as no cast.
+int32_t art_closest_points_multi(ArtContext *c, const ArtPointQueryMulti *d) {
+    const char *who = "art_closest_points_multi"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
+    if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
+    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "points_dev", d->points_dev, 16, d->n)) ||
+        (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) || (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true))) return r;
+    if (!c->built) return fail(ART_E_STATE, "art_closest_points_multi: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    ClosestMultiArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
+    a.points = (const float4 *)d->points_dev; a.point = (float4 *)d->point_dev; a.max_hits = d->max_hits; a.count = (uint8_t *)d->count_dev;
+    a.gid_leaf = c->bvh.gid_leaf;   // (after query_begin: a rebuild the cost rule started made the table anew)
+    launch_closest_multi(a, q.stream);
     return cast_commit(c, q, 0);
 }
 

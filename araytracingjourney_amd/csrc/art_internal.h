@@ -314,6 +314,10 @@ void launch_cast(const CastArgs &c, hipStream_t s);
 // Nearest-point queries (art_closest_points): points[i] = p.xyz, r; a miss record's x is r; point (optional) = the surface point, w = 1 (a miss: zeros)
 struct ClosestArgs : QueryArgs { const float4 *points; float4 *point; };
 void launch_closest(const ClosestArgs &c, hipStream_t s);
+// The K nearest triangles (art_closest_points_multi): tuv / ids / point hold max_hits records a query, query-major; count (optional) a byte a query;
+// gid_leaf: the structure's gid -> leaf table (Lbvh::gid_leaf), which a record's point is found through
+struct ClosestMultiArgs : ClosestArgs { uint32_t max_hits; uint8_t *count; const uint32_t *gid_leaf; };
+void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
 struct ResolveArgs {

@@ -1,5 +1,5 @@
-// art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest) and
-// swept spheres (k_sweep), each a Source or a candidate policy of art_walk.h's pooled loop.  What they share stands once: at the top the ray read, the hit and miss
+// art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest), the K nearest
+// triangles (k_closest_multi) and swept spheres (k_sweep), each a Source or a candidate policy of art_walk.h's pooled loop.  What they share stands once: at the top the ray read, the hit and miss
 // records, the contact point and the mask test; at the bottom the arguments' common fields and the launch.  art_cast.hip is their host side.
 #include "art_walk.h"
 
@@ -329,6 +329,123 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     }
 }
 
+// ---- the K nearest triangles (art_closest_points_multi) ------------------------------------------------------------------------------------------
+// TravPoint's walk with TravMulti's list in place of the single best: up to K entries (d2_eff, u, v, gid) a lane in ascending (d2_eff, gid), in LDS, [entry][lane], 16 bytes
+// an entry -- the insertion is ds_read / ds_write_b128 with the entry index in a register, nothing of it goes to scratch.  limit / bgid are the walk's LIMIT: (r*r, none)
+// until the list is full, the K-th entry's pair from then on.  TravPoint's push, pop and step_internal read nothing else, so they serve unchanged (inherited: TravPoint's
+// text, and with it k_closest's code, stays as it is): a child is skipped iff its box_d2 > limit -- strict, ties stay in play -- and a candidate enters iff it is below the
+// limit in the total order, which is TravPoint::step_leaf's comparison word for word (K = 1 IS that walk).  A triangle sits in one leaf and a leaf is visited at most once:
+// nothing arrives twice, nothing is checked.  Only a candidate that would enter is put to the mask test.  d2_tri, box_d2 and the point are the one copy above.
+// An entry keeps the gid (the tie rule needs it at every comparison) and not the leaf position, which only the point of a record needs: the finish finds it through the
+// structure's gid -> leaf table (Lbvh::gid_leaf, art_resolve_hits' table), one more load a record where a point is wanted and none in the walk.
+template <int KMAX, bool FILTER> struct TravPointMulti : TravPoint<FILTER> {
+    uint32_t K, cnt;   // K: 1..KMAX, wave-uniform; cnt: entries held, 0..K
+    uint4 *list;       // this lane's entry 0; entry j at list[j * kTraceBlock]
+    __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const float bd = box_d2(this->p, tc.y, tc.z, tc.w, td.x, td.y, td.z);
+        float u, v;
+        const float dt = tri_closest(this->p - mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), u, v);
+        if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum: fmaxf would drop a NaN
+            const float de = fmaxf(dt, bd);
+            const uint32_t gid = __float_as_uint(td.w);
+            if ((de < this->limit || (de == this->limit && gid < this->bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
+                uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
+                while (j > 0u) {                 // entries above the candidate move up one
+                    const uint4 e = list[(j - 1u) * kTraceBlock];
+                    const float pd = __uint_as_float(e.x);
+                    if (pd < de || (pd == de && e.w < gid)) break;
+                    list[j * kTraceBlock] = e; j--;
+                }
+                list[j * kTraceBlock] = make_uint4(__float_as_uint(de), __float_as_uint(u), __float_as_uint(v), gid);
+                cnt = min(cnt + 1u, K);
+                if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; this->limit = __uint_as_float(e.x); this->bgid = e.w; }   // full: the K-th entry is the limit
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+};
+struct ClosestMultiK : ClosestK { uint8_t *count; const uint32_t *gid_leaf; uint32_t max_hits; };   // tuv / ids / point: max_hits records a query, query-major; count: a byte a query, or null
+template <class I> __device__ __forceinline__ void write_point_miss(const ClosestMultiK &a, I at, float r) {
+    write_miss(a, at, r);
+    if (a.point) a.point[at] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// KMAX 4 | 8: the list is KMAX KB of LDS a wave on top of the stack's 4 KB, and LDS is what bounds the waves a CU holds: 20 waves with KMAX 4, 13 with
+// KMAX 8 -- five and three a SIMD, whose registers are the kernel's to use.  The loop is k_closest's, line for line, with K records where that has one.
+template <int KMAX, bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 5, 5))) void k_closest_multi(ClosestMultiK a) {
+    __shared__ int2 stack[kClosestLds * kTraceBlock];
+    __shared__ uint4 hits[KMAX * kTraceBlock];
+    int ovf[kClosestOvf];
+    int2 *lds = &stack[threadIdx.x];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t leaf_batch = a.leaf_batch;
+    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
+    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // HW_REG_XCC_ID: speed only
+    uint32_t shards_left = 8;
+    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
+    bool exhausted = false, active = false;
+    TravPointMulti<KMAX, FILTER> tr;
+    tr.sp = 0; tr.cur = 0;
+    tr.K = min(max(a.max_hits, 1u), (uint32_t)KMAX); tr.cnt = 0u; tr.list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+    const uint32_t K = tr.K;
+    float radius = 0.0f;
+    uint32_t slot = 0;
+    for (;;) {
+        const uint64_t idle = ballot64(!active);
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        if (n_idle >= a.refill) {
+            if (!exhausted && cur == end) {
+                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
+                if (got >= n_chunks) exhausted = true;
+                else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
+            }
+            if (!exhausted) {   // the idle lanes read the next queries of the chunk, one each
+                const uint32_t take = min(n_idle, end - cur);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (!active && rank < take) {
+                    const uint32_t sidx = cur + rank;
+                    const float4 q = a.points[sidx];
+                    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
+                    if (z == 0.0f && q.w == q.w && !(q.w < 0.0f)) {
+                        tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bgid = kNoHit; tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
+                        radius = q.w; slot = sidx; active = true;
+                    } else {   // a non-finite point, a NaN or negative radius: K miss records and the count, without a walk
+                        const size_t base = (size_t)sidx * K;
+                        for (uint32_t j = 0; j < K; j++) write_point_miss(a, base + j, q.w);
+                        if (a.count) a.count[sidx] = 0;
+                    }
+                }
+                cur += take;
+            } else if (n_idle == 64u) break;
+            if (ballot64(active) == 0ull) continue;
+        }
+        bool done = false;   // pooled_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
+#pragma unroll
+        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
+            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
+        const bool on_leaf = active && !done && tr.cur < 0;
+        const uint64_t lm = ballot64(on_leaf);
+        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
+        if (done) {
+            active = false;
+            const size_t base = (size_t)slot * K;
+            for (uint32_t j = 0; j < K; j++) {
+                if (j < tr.cnt) {
+                    const uint4 e = tr.list[j * kTraceBlock];
+                    const float u = __uint_as_float(e.y), v = __uint_as_float(e.z);
+                    write_hit(a, base + j, e.w, sqrtf(__uint_as_float(e.x)), u, v);
+                    if (a.point) a.point[base + j] = contact_point(a.tris, a.gid_leaf[e.w], u, v);
+                } else write_point_miss(a, base + j, radius);
+            }
+            if (a.count) a.count[slot] = (uint8_t)tr.cnt;
+        }
+    }
+}
+
 // ---- a ball along a ray (art_cast_spheres) --------------------------------------------------------------------------------------------------------
 // The rays are the casts' -- 32 bytes a ray, everything ray_init makes of them -- so the loop is pooled_trace with a fourth candidate policy.  The ball's radius is the
 // same for every ray of a launch: boxes grow by it (one subtraction / addition a plane, before the slab), and a triangle answers with the first time the ball's centre is
@@ -504,6 +621,11 @@ void launch_closest(const ClosestArgs &c, hipStream_t s) {
     ClosestK a = query_fill<ClosestK>(c); a.points = c.points; a.point = c.point;
     a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
     launch_query(c.filter ? k_closest<true> : k_closest<false>, a, c, s);
+}
+void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s) {   // the instance with the smallest list that holds K
+    ClosestMultiK a = query_fill<ClosestMultiK>(c); a.points = c.points; a.point = c.point; a.count = c.count; a.gid_leaf = c.gid_leaf; a.max_hits = c.max_hits;
+    a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    launch_query(c.max_hits <= 4u ? (c.filter ? k_closest_multi<4, true> : k_closest_multi<4, false>) : (c.filter ? k_closest_multi<8, true> : k_closest_multi<8, false>), a, c, s);
 }
 
 } // namespace art

@@ -288,6 +288,16 @@ public:
     static_assert(sizeof(ArtPointQuery) == 56, "ArtPointQuery is part of the ABI");
     static void closest_points(ArtContext *ctx, const ArtPointQuery &d) { check(art_closest_points(ctx, &d)); }
     void closest_points(const ArtPointQuery &d) { closest_points(ctx_, d); }
+    // the max_hits nearest triangles to each of n points: n x max_hits records of art_closest_points' kind, query-major, and (optionally) a count a query (art_closest_points_multi)
+    static ArtPointQueryMulti point_query_multi(const void *points_dev, uint32_t n, uint32_t max_hits, void *duv_dev, void *ids_dev, void *point_dev = nullptr, void *count_dev = nullptr,
+                                                void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtPointQueryMulti d{}; d.points_dev = points_dev; d.duv_dev = duv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.count_dev = count_dev; d.hip_stream = hip_stream;
+        d.n = n; d.max_hits = max_hits; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtPointQueryMulti) == 64, "ArtPointQueryMulti is part of the ABI");
+    static void closest_points_multi(ArtContext *ctx, const ArtPointQueryMulti &d) { check(art_closest_points_multi(ctx, &d)); }
+    void closest_points_multi(const ArtPointQueryMulti &d) { closest_points_multi(ctx_, d); }
     // where a ball of `radius` along each of n rays in device memory first touches the scene: records as a closest cast's and (optionally) n x float4 contact points (art_cast_spheres)
     static ArtSphereCast sphere_cast(const void *rays_dev, uint32_t n, float radius, void *tuv_dev, void *ids_dev, void *point_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
         ArtSphereCast d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask; d.radius = radius;

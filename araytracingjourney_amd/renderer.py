@@ -825,6 +825,31 @@ class Renderer:
         duv, ids, point = self.closest_points(points, cull_mask, stream=stream)
         return (duv, ids, point), self.resolve_hits(duv, ids, want, stream=stream)
 
+    def closest_points_multi(self, points, max_hits, cull_mask=0xFF, out=None, stream=None):
+        """The max_hits nearest triangles to each point (art_closest_points_multi).  points: as closest_points.  Returns (duv, ids, point, count): (n, K, 4) float32
+        d,u,v,0, (n, K, 2) int32 (primitive, triangle in the primitive), (n, K, 4) float32 the nearest point of that triangle, w = 1, and (n,) uint8 -- record j of query i
+        is its j-th nearest triangle in ascending (distance, global triangle id) while j < count[i], each closest_points' own record for that triangle, and the miss record
+        (r, 0, 0, 0), (-1, -1) and a point of zeros from there on.  The answers are triangles, not distinct points: those that share the nearest edge or vertex all appear.
+        out: (duv, ids, point, count) to write instead of new ones, of at least n queries and exactly K records a query, not overlapping the points or each other.
+        Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        m = _mask_value("cull_mask", cull_mask)
+        k = int(max_hits)
+        if k != max_hits or not 1 <= k <= _lib.ART_CAST_MAX_HITS:
+            raise ValueError(f"max_hits must be an integer in 1..{_lib.ART_CAST_MAX_HITS}")
+        n = self._dev_tensor(points, "points", "float32", (4,), 16).shape[0]
+        duv, ids, point, count = self._outputs(out, n, points.device, (("duv", "float32", (k, 4), 16), ("ids", "int32", (k, 2), 8), ("point", "float32", (k, 4), 16),
+                                                                       ("count", "uint8", (), 1)))
+        d = _lib.ArtPointQueryMulti(points_dev=points.data_ptr() or None, duv_dev=duv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
+                                    count_dev=count.data_ptr() or None, n=n, max_hits=k, cull_mask=m, flags=0, hip_stream=self._stream_handle(stream, points.device))
+        check(self._L.art_closest_points_multi(self._ctx, C.byref(d)))
+        return duv, ids, point, count
+
+    def closest_surface_multi(self, points, max_hits, cull_mask=0xFF, want=("pos", "ng", "ns", "uv", "albedo", "orm"), stream=None):
+        """closest_points_multi and one resolve of its n x K records on the same stream: ((duv, ids, point, count), surface dict of (n, K, w) tensors) -- the normal of
+        every face of a contact manifold.  Miss records resolve to zeros."""
+        duv, ids, point, count = self.closest_points_multi(points, max_hits, cull_mask, stream=stream)
+        return (duv, ids, point, count), self.resolve_hits(duv, ids, want, stream=stream)
+
     def cast_spheres(self, rays, radius, cull_mask=0xFF, out=None, stream=None):
         """Where a ball of `radius` moving along each ray first touches the scene (art_cast_spheres).  rays: cast_rays' tensor, float32 of shape (n, 8) -- o.xyz, tmin,
         d.xyz, tmax; the ball's centre is o + t*d -- contiguous and 16-byte aligned; radius: one finite float >= 0 for the whole call.  Returns (tuv, ids, point): (n, 4)

@@ -424,6 +424,38 @@ typedef struct ArtSphereCast {
     float radius;           /* of the ball, for every ray of the call: finite, >= 0 */
 } ArtSphereCast;            /* 56 bytes */
 int32_t art_cast_spheres(ArtContext *ctx, const ArtSphereCast *s);
+/* The K nearest triangles to a point (new functionality: an rtcPointQuery callback that collects instead of shrinking, PhysX's overlap that reports what
+ * it touches): every face a ball rests on for a contact manifold, the clearance against the second-nearest wall, neighbours for a distance field, snapping that chooses
+ * among candidates.  A query is art_closest_points' (p.xyz, r); the answer is up to max_hits records a query.
+ *  - Results: defined exactly and independent of the structure, with art_closest_points' formulas unchanged (d2_tri, box_d2, d2_eff = max of the two, the point).  Let A
+ *    be the query's candidates there: the triangles whose primitive's mask & cull_mask != 0 (tested first), with d2_tri and box_d2 finite and d2_eff <= r*r.  Records
+ *    0 .. c-1 of the query, c = min(|A|, max_hits), are the first c elements of A in ascending (d2_eff, global triangle id), each art_closest_points' own record for
+ *    that triangle: duv (sqrtf(d2_eff), u, v, 0), ids (primitive id, triangle in the primitive), point (v0 + (u*e1 + v*e2), 1).  Records c .. max_hits-1 are the miss
+ *    record -- (r as given, 0, 0, 0), (-1, -1), a point of zeros -- and count_dev[i] = c.  The answers are the K nearest TRIANGLES, not K distinct points: the triangles
+ *    that share the nearest edge or vertex all appear, at the same distance and with the same point, ordered by global id.  Every record is one art_resolve_hits takes
+ *    (n x max_hits of them, flattened).  With max_hits = 1 the records are art_closest_points', bit for bit.  A query's records depend on that query alone.
+ *  - A query with a non-finite p, a NaN r or r < 0 has c = 0 and max_hits miss records that carry r as given; r = +inf and -0.0 are legal.  Alpha cutoffs are NOT
+ *    tested, for art_closest_points' reason; visibility masks apply as for casts (cull_mask 0 sees nothing); a primitive that left the structure by residency is nowhere
+ *    and is never returned.
+ *  - Asynchrony and scene: art_closest_points', with no path of its own -- stream, no allocation or synchronisation on the steady path, the scene as of the call, the
+ *    version held, a block of the casts' ring (ART_CAST_POOL), the same fences.  art_cast_counts counts it in neither casts nor rays (it traces no ray); a host wait it
+ *    causes counts in host_waits.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null or misaligned points_dev / duv_dev (16 bytes) / ids_dev (8 bytes) --
+ *    with n = 0 null is fine; a misaligned point_dev; max_hits 0 or above ART_CAST_MAX_HITS; cull_mask above 0xFF; flags other than 0; n above ART_CAST_MAX_RAYS.
+ *    ART_E_STATE: the scene is not built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtPointQueryMulti {
+    const void *points_dev; /* n x 4 floats p.xyz, r; 16-byte aligned (ArtPointQuery's) */
+    void *duv_dev;          /* n x max_hits x 4 floats d,u,v,0, query-major: query i's record j at i*max_hits + j; 16-byte aligned */
+    void *ids_dev;          /* n x max_hits x 2 int32, same order; 8-byte aligned */
+    void *point_dev;        /* n x max_hits x float4, same order; 16-byte aligned.  May be NULL */
+    void *count_dev;        /* n x uint8: records that are answers, 0..max_hits.  May be NULL */
+    void *hip_stream;       /* as ArtRayCast */
+    uint32_t n;             /* 0 is legal: nothing is enqueued */
+    uint32_t max_hits;      /* K: 1..ART_CAST_MAX_HITS */
+    uint32_t cull_mask;     /* 0..0xFF */
+    uint32_t flags;         /* must be 0 */
+} ArtPointQueryMulti;       /* 64 bytes */
+int32_t art_closest_points_multi(ArtContext *ctx, const ArtPointQueryMulti *q);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
