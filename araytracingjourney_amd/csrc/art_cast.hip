@@ -118,7 +118,7 @@ static int32_t check_buffer(const char *who, const char *name, const void *p, si
     if (align > 1) what += (optional ? "not " : " or not ") + std::to_string(align) + "-byte aligned";
     return invalid(who, std::string(name) + ": " + what);
 }
-// the fields the descriptors of the three casts of rays share
+// the fields the descriptors of the three casts of rays share (cast_check), and those of the two point queries (point_check)
 static int32_t cast_check(const char *who, uint32_t flags, uint32_t cull_mask, uint32_t n, const void *rays_dev) {
     int32_t r = check_flags(who, flags);
     return r || (r = check_cull(who, cull_mask)) || (r = check_n(who, n)) ? r : check_buffer(who, "rays_dev", rays_dev, 16, n);
@@ -126,6 +126,10 @@ static int32_t cast_check(const char *who, uint32_t flags, uint32_t cull_mask, u
 static int32_t check_records(const char *who, const char *tuv_name, const void *tuv_dev, const void *ids_dev, uint32_t n) {
     const int32_t r = check_buffer(who, tuv_name, tuv_dev, 16, n);
     return r ? r : check_buffer(who, "ids_dev", ids_dev, 8, n);
+}
+template <class D> static int32_t point_check(const char *who, const D *d) {   // D: ArtPointQuery | ArtPointQueryMulti
+    int32_t r = check_cull(who, d->cull_mask);
+    return r || (r = check_n(who, d->n)) || (r = check_buffer(who, "points_dev", d->points_dev, 16, d->n)) || (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) ? r : check_buffer(who, "point_dev", d->point_dev, 16, d->n, true);
 }
 
 extern "C" {
@@ -191,9 +195,7 @@ int32_t art_resolve_hits(ArtContext *c, const ArtHitResolve *d) {
 int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
     const char *who = "art_closest_points"; int32_t r;
     if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
-    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
-    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "points_dev", d->points_dev, 16, d->n)) ||
-        (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) || (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true))) return r;
+    if ((r = d->reserved != 0u ? invalid(who, "reserved: must be 0") : point_check(who, d))) return r;
     if (!c->built) return fail(ART_E_STATE, "art_closest_points: scene not built, or changed since the build (art_scene_build)");
     if (d->n == 0u) return ART_OK;
     ClosestArgs a{}; RingSlot q;
@@ -208,9 +210,7 @@ int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
 int32_t art_closest_points_multi(ArtContext *c, const ArtPointQueryMulti *d) {
     const char *who = "art_closest_points_multi"; int32_t r;
     if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
-    if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
-    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "points_dev", d->points_dev, 16, d->n)) ||
-        (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) || (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true))) return r;
+    if ((r = d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS ? invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS") : point_check(who, d))) return r;
     if (!c->built) return fail(ART_E_STATE, "art_closest_points_multi: scene not built, or changed since the build (art_scene_build)");
     if (d->n == 0u) return ART_OK;
     ClosestMultiArgs a{}; RingSlot q;

@@ -1,6 +1,9 @@
 // art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest), the K nearest
-// triangles (k_closest_multi) and swept spheres (k_sweep), each a Source or a candidate policy of art_walk.h's pooled loop.  What they share stands once: at the top the ray read, the hit and miss
-// records, the contact point and the mask test; at the bottom the arguments' common fields and the launch.  art_cast.hip is their host side.
+// triangles (k_closest_multi) and swept spheres (k_sweep).  The casts and the sweep are Sources and candidate policies of art_walk.h's pooled loop; the two point queries have
+// a loop of their own, in two texts.  What the queries share stands once: at the top the ray read, the hit and miss records, the contact point and the mask test; the sorted
+// list of both K-walks (KList), which a walk fills through its leaf step's hook for a candidate's fate (step_leaf_take: one leaf step a walk); at the bottom the arguments'
+// common fields and the launch.  (The list and the leaf steps were copies once, kept apart so that no other kernel's code would move.  Compared instruction for instruction --
+// tools/kernel_diff.py -- none but k_closest_multi's does: profiles/README.md, "one list, one hook".)  art_cast.hip is their host side.
 #include "art_walk.h"
 
 namespace art {
@@ -23,11 +26,15 @@ template <class K, class I> __device__ __forceinline__ void write_hit(const K &a
     a.ids[at] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
 }
 template <class K, class I> __device__ __forceinline__ void write_miss(const K &a, I at, float x) { a.tuv[at] = make_float4(x, 0.f, 0.f, 0.f); a.ids[at] = make_int2(-1, -1); }
-// the point u, v of the triangle at leaf position pos, from its record (v0 e1 e2), w = 1: what k_closest and k_sweep report beside a hit
+// the point u, v of the triangle at leaf position pos, from its record (v0 e1 e2), w = 1: what the point queries and k_sweep report beside a hit; a miss: zeros (point: may be null)
 __device__ __forceinline__ float4 contact_point(const DevTri *tris, uint32_t pos, float u, float v) {
     const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
     const float4 ta = tq[0], tb = tq[1], tc = tq[2];
     return make_float4(ta.x + (u * ta.w + v * tb.z), ta.y + (u * tb.x + v * tb.w), ta.z + (u * tb.y + v * tc.x), 1.0f);
+}
+template <class K, class I> __device__ __forceinline__ void write_point_miss(const K &a, I at, float x) {
+    write_miss(a, at, x);
+    if (a.point) a.point[at] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 // does a query with this cull mask see the triangle at leaf position pos?  The masks only -- no cutoff: the test of the walks that have no alpha_cut
 __device__ __forceinline__ bool leaf_visible(const uint32_t *bits, const DevShadeTri *shade, const DevPrim *prims, uint32_t cull, uint32_t pos) {
@@ -68,46 +75,43 @@ template <bool ANY> struct CastSource {
 template <bool ANY, bool ALPHA>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) { pooled_trace<kCastLds, ANY, ALPHA>(a, CastSource<ANY>{a}); }
 
-// The first K hits of each ray, in order (art_cast_rays_multi): the third candidate policy.  The closest walk keeps ONE best candidate; this one keeps a list
-// of up to K entries (t_eff, u, v, gid) a lane in ascending (t_eff, gid) -- in LDS, [entry][lane] like the walk stack, 16 bytes an entry, so the insertion runs on ds_read /
-// ds_write_b128 with the entry index in a register and nothing goes to scratch.  tbest / bgid are the walk's LIMIT: (tmax, none) until the list is full, the K-th entry's pair
-// from then on -- every box test of Trav4 and the leaf's exact slab cull against it as they cull against the best candidate in the closest walk, and a candidate enters iff it
-// is below the limit in the total order, which is the closest walk's comparison, word for word (K = 1 IS the closest walk).  Every triangle sits in one leaf and a walk visits a
-// leaf at most once: no entry can arrive twice, nothing is checked.  Only a candidate that would enter is put to the mask / alpha test.  (step_leaf is TravBase's text up to
-// the candidate's fate: a hook inside TravBase for it would be a change to the code of k_cast and k_trace_ao, whose registers are pinned.)
-template <int KMAX, int LDSN, bool ALPHA> struct TravMulti : Trav4<false, LDSN, ALPHA> {
+// A lane's K best candidates, which both multi walks keep (TravMulti below, TravPointMulti): up to K entries (key, u, v, gid) in ascending (key, gid), the key a t_eff or a
+// d2_eff -- in LDS, [entry][lane] like the walk stack, 16 bytes an entry, so the insertion runs on ds_read / ds_write_b128 with the entry index in a register and nothing
+// goes to scratch.  A walk's best pair (tbest | limit, bgid) is its LIMIT: (the range's end, none) until the list is full, the K-th entry's pair from then on -- boxes and
+// leaves cull against it as they cull against the best candidate of a closest walk, and a candidate enters iff it is below the limit in the total order, which is that
+// walk's comparison (its step_leaf_take makes it: K = 1 IS the closest walk).  Every triangle sits in one leaf and a walk visits a leaf at most once: no entry can arrive
+// twice, nothing is checked.  Only a candidate that would enter is put to the mask / alpha test.
+struct KList {
     uint32_t K, cnt;   // K: 1..KMAX, wave-uniform; cnt: entries held, 0..K
     uint4 *list;       // this lane's entry 0; entry j at list[j * kTraceBlock]
+    // hits: the kernel's __shared__ uint4[kmax * kTraceBlock].  (It is declared where each kernel had it, not in here: with one array in here for both walks, k_closest_multi's
+    // instances with a list of 4 came out five and six instructions longer and 0.4 % slower on two legs of their probe -- profiles/README.md, "one list, one hook")
+    __device__ __forceinline__ void bind(uint4 *hits, uint32_t k, uint32_t kmax) {
+        K = min(max(k, 1u), kmax); cnt = 0u; list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+    }
+    // a candidate below the limit enters; limit / limit_gid: the walk's pair
+    __device__ __forceinline__ void enter(float key, float u, float v, uint32_t gid, float &limit, uint32_t &limit_gid) {
+        uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
+        while (j > 0u) {                 // entries above the candidate move up one
+            const uint4 p = list[(j - 1u) * kTraceBlock];
+            const float pk = __uint_as_float(p.x);
+            if (pk < key || (pk == key && p.w < gid)) break;
+            list[j * kTraceBlock] = p; j--;
+        }
+        list[j * kTraceBlock] = make_uint4(__float_as_uint(key), __float_as_uint(u), __float_as_uint(v), gid);
+        cnt = min(cnt + 1u, K);
+        if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; limit = __uint_as_float(e.x); limit_gid = e.w; }   // full: the K-th entry is the limit
+    }
+};
+// The first K hits of each ray, in order (art_cast_rays_multi): the third candidate policy.  The closest walk keeps ONE best candidate; this one hands it to
+// the list, through the hook TravBase::step_leaf_take has for a candidate's fate -- the leaf step, its slab cull and the box tests of Trav4 are the closest walk's own.
+template <int KMAX, int LDSN, bool ALPHA> struct TravMulti : Trav4<false, LDSN, ALPHA>, KList {
     __device__ __forceinline__ void bind(uint32_t k) {
         __shared__ uint4 hits[KMAX * kTraceBlock];
-        K = min(max(k, 1u), (uint32_t)KMAX); cnt = 0u; list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+        KList::bind(hits, k, KMAX);
     }
     __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
-        uint32_t pos = (uint32_t)~this->cur;
-        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // an absent child (TravBase::step_leaf)
-        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
-        float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];
-        asm volatile("" : "+v"(td.x), "+v"(td.y), "+v"(td.z), "+v"(td.w), "+v"(tc.y), "+v"(tc.z), "+v"(tc.w));
-        float te, t, u, v;
-        if (moller_trumbore(this->r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v)) {
-            if (slab(this->r, tc.y, tc.z, tc.w, td.x, td.y, td.z, this->tbest, te)) {
-                const float teff = fmaxf(t, te);
-                const uint32_t gid = __float_as_uint(td.w);
-                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && (!ALPHA || !alpha_cut(av, pos, u, v))) {
-                    uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
-                    while (j > 0u) {                 // entries above the candidate move up one
-                        const uint4 p = list[(j - 1u) * kTraceBlock];
-                        const float pt = __uint_as_float(p.x);
-                        if (pt < teff || (pt == teff && p.w < gid)) break;
-                        list[j * kTraceBlock] = p; j--;
-                    }
-                    list[j * kTraceBlock] = make_uint4(__float_as_uint(teff), __float_as_uint(u), __float_as_uint(v), gid);
-                    cnt = min(cnt + 1u, K);
-                    if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; this->tbest = __uint_as_float(e.x); this->bgid = e.w; }   // full: the K-th entry is the limit
-                }
-            }
-        }
-        return this->pop(lds, ovf);
+        return this->step_leaf_take(tris, lds, ovf, av, [this](float teff, float u, float v, uint32_t, uint32_t gid) { enter(teff, u, v, gid, this->tbest, this->bgid); });
     }
 };
 struct CastMultiK : CastK { uint8_t *count; uint32_t max_hits; };   // tuv / ids: max_hits records a ray, ray-major; count: a byte a ray, or null
@@ -217,9 +221,10 @@ template <bool FILTER> struct TravPoint {
         }
         return true;
     }
-    __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
+    // the triangle in `cur`; a candidate below (limit, bgid) that the masks let through goes to take(d2_eff, u, v, pos, gid): the best here, the list's in TravPointMulti
+    template <class TAKE> __device__ __forceinline__ bool step_leaf_take(const ClosestK &a, int2 *lds, int *ovf, const TAKE &take) {
         const uint32_t pos = (uint32_t)~cur;
-        if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
+        if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
         const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
         const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
         const float bd = box_d2(p, tc.y, tc.z, tc.w, td.x, td.y, td.z);
@@ -228,9 +233,12 @@ template <bool FILTER> struct TravPoint {
         if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum: fmaxf would drop a NaN
             const float de = fmaxf(dt, bd);
             const uint32_t gid = __float_as_uint(td.w);
-            if ((de < limit || (de == limit && gid < bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; }
+            if ((de < limit || (de == limit && gid < bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) take(de, u, v, pos, gid);
         }
         return pop(lds, ovf);
+    }
+    __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
+        return step_leaf_take(a, lds, ovf, [this](float de, float u, float v, uint32_t pos, uint32_t gid) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; });
     }
     __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
         const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
@@ -300,10 +308,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                     if (z == 0.0f && q.w == q.w && !(q.w < 0.0f)) {
                         tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
                         radius = q.w; slot = sidx; active = true;
-                    } else {   // a non-finite point, a NaN or negative radius: the miss record, without a walk
-                        write_miss(a, sidx, q.w);
-                        if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
+                    } else write_point_miss(a, sidx, q.w);   // a non-finite point, a NaN or negative radius: the miss record, without a walk
                 }
                 cur += take;
             } else if (n_idle == 64u) break;
@@ -321,60 +326,27 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
             if (tr.bgid != kNoHit) {
                 write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
                 if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
-            } else {
-                write_miss(a, slot, radius);
-                if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            } else write_point_miss(a, slot, radius);
         }
     }
 }
 
 // ---- the K nearest triangles (art_closest_points_multi) ------------------------------------------------------------------------------------------
-// TravPoint's walk with TravMulti's list in place of the single best: up to K entries (d2_eff, u, v, gid) a lane in ascending (d2_eff, gid), in LDS, [entry][lane], 16 bytes
-// an entry -- the insertion is ds_read / ds_write_b128 with the entry index in a register, nothing of it goes to scratch.  limit / bgid are the walk's LIMIT: (r*r, none)
-// until the list is full, the K-th entry's pair from then on.  TravPoint's push, pop and step_internal read nothing else, so they serve unchanged (inherited: TravPoint's
-// text, and with it k_closest's code, stays as it is): a child is skipped iff its box_d2 > limit -- strict, ties stay in play -- and a candidate enters iff it is below the
-// limit in the total order, which is TravPoint::step_leaf's comparison word for word (K = 1 IS that walk).  A triangle sits in one leaf and a leaf is visited at most once:
-// nothing arrives twice, nothing is checked.  Only a candidate that would enter is put to the mask test.  d2_tri, box_d2 and the point are the one copy above.
+// TravPoint's walk with the list (KList, keyed by d2_eff) in place of the single best, through TravPoint::step_leaf_take's hook; limit / bgid are the walk's LIMIT: (r*r, none)
+// until the list is full, the K-th entry's pair from then on.  TravPoint's push, pop and step_internal read nothing else of the candidate, so they serve as they are: a
+// child is skipped iff its box_d2 > limit -- strict, ties stay in play.  d2_tri, box_d2 and the point are the one copy above.
 // An entry keeps the gid (the tie rule needs it at every comparison) and not the leaf position, which only the point of a record needs: the finish finds it through the
 // structure's gid -> leaf table (Lbvh::gid_leaf, art_resolve_hits' table), one more load a record where a point is wanted and none in the walk.
-template <int KMAX, bool FILTER> struct TravPointMulti : TravPoint<FILTER> {
-    uint32_t K, cnt;   // K: 1..KMAX, wave-uniform; cnt: entries held, 0..K
-    uint4 *list;       // this lane's entry 0; entry j at list[j * kTraceBlock]
+template <bool FILTER> struct TravPointMulti : TravPoint<FILTER>, KList {
     __device__ __forceinline__ bool step_leaf(const ClosestK &a, int2 *lds, int *ovf) {
-        const uint32_t pos = (uint32_t)~this->cur;
-        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
-        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
-        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
-        const float bd = box_d2(this->p, tc.y, tc.z, tc.w, td.x, td.y, td.z);
-        float u, v;
-        const float dt = tri_closest(this->p - mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), u, v);
-        if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum: fmaxf would drop a NaN
-            const float de = fmaxf(dt, bd);
-            const uint32_t gid = __float_as_uint(td.w);
-            if ((de < this->limit || (de == this->limit && gid < this->bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
-                uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
-                while (j > 0u) {                 // entries above the candidate move up one
-                    const uint4 e = list[(j - 1u) * kTraceBlock];
-                    const float pd = __uint_as_float(e.x);
-                    if (pd < de || (pd == de && e.w < gid)) break;
-                    list[j * kTraceBlock] = e; j--;
-                }
-                list[j * kTraceBlock] = make_uint4(__float_as_uint(de), __float_as_uint(u), __float_as_uint(v), gid);
-                cnt = min(cnt + 1u, K);
-                if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; this->limit = __uint_as_float(e.x); this->bgid = e.w; }   // full: the K-th entry is the limit
-            }
-        }
-        return this->pop(lds, ovf);
+        return this->step_leaf_take(a, lds, ovf, [this](float de, float u, float v, uint32_t, uint32_t gid) { enter(de, u, v, gid, this->limit, this->bgid); });
     }
 };
 struct ClosestMultiK : ClosestK { uint8_t *count; const uint32_t *gid_leaf; uint32_t max_hits; };   // tuv / ids / point: max_hits records a query, query-major; count: a byte a query, or null
-template <class I> __device__ __forceinline__ void write_point_miss(const ClosestMultiK &a, I at, float r) {
-    write_miss(a, at, r);
-    if (a.point) a.point[at] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
 // KMAX 4 | 8: the list is KMAX KB of LDS a wave on top of the stack's 4 KB, and LDS is what bounds the waves a CU holds: 20 waves with KMAX 4, 13 with
-// KMAX 8 -- five and three a SIMD, whose registers are the kernel's to use.  The loop is k_closest's, line for line, with K records where that has one.
+// KMAX 8 -- five and three a SIMD, whose registers are the kernel's to use.  The loop is k_closest's, line for line, with K records where that has one: a second text.  (One loop
+// over a record policy was built and left k_closest's code unmoved; it was measured only in a build whose list array sat in KList, where a leg of this kernel's probe read
+// above the parent's runs in two calls, and by the rule set for it the fold went out.  Unmeasured on its own since -- profiles/README.md, "one list, one hook")
 template <int KMAX, bool FILTER>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 5, 5))) void k_closest_multi(ClosestMultiK a) {
     __shared__ int2 stack[kClosestLds * kTraceBlock];
@@ -388,9 +360,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMA
     uint32_t shards_left = 8;
     uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
     bool exhausted = false, active = false;
-    TravPointMulti<KMAX, FILTER> tr;
+    TravPointMulti<FILTER> tr;
     tr.sp = 0; tr.cur = 0;
-    tr.K = min(max(a.max_hits, 1u), (uint32_t)KMAX); tr.cnt = 0u; tr.list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+    tr.bind(hits, a.max_hits, KMAX);
     const uint32_t K = tr.K;
     float radius = 0.0f;
     uint32_t slot = 0;
@@ -563,10 +535,7 @@ struct SweepSource {
     template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.rho = a.radius; }   // the same for every ray
     __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
         const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
-        if (!has) {                // a dead ray: its miss record, without a walk
-            write_miss(a, sidx, e1);
-            if (a.point) a.point[sidx] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        if (!has) write_point_miss(a, sidx, e1);   // a dead ray: its miss record, without a walk
         return has;
     }
     template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
@@ -574,10 +543,7 @@ struct SweepSource {
         if (tr.bgid != kNoHit) {
             write_hit(a, slot, tr.bgid, tr.tbest, tr.bu, tr.bv);
             if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
-        } else {
-            write_miss(a, slot, tr.r.tmax);
-            if (a.point) a.point[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        } else write_point_miss(a, slot, tr.r.tmax);
     }
 };
 // 6 waves a SIMD: the eight-feature test holds 79 VGPRs without a spill; at 8 waves (64) the compiler spills two dozen of them to scratch, at 4 it uses no more than at 6
@@ -587,7 +553,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 }
 
 // The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
-// the context's ArtTuning overrides.  query_fill: the fields every kernel's arguments share; launch_query: one instance, chosen by its caller, on that shape.
+// the context's ArtTuning overrides.  query_fill: the fields every kernel's arguments share (cast_fill, closest_fill: with those of the casts, of the point queries);
+// launch_query: one instance, chosen by its caller, on that shape.
 static Tune query_tune(const QueryArgs &c) { return tune_over(Tune{256, kPoolTake, 2048, 8}, c.tune); }
 template <class K> static K query_fill(const QueryArgs &c) {
     const Tune t = query_tune(c);
@@ -599,6 +566,11 @@ template <class K> static K query_fill(const QueryArgs &c) {
 template <class K> static K cast_fill(const CastArgs &c) {
     K a = query_fill<K>(c);
     a.rays = c.rays; a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
+    return a;
+}
+template <class K> static K closest_fill(const ClosestArgs &c) {
+    K a = query_fill<K>(c);
+    a.points = c.points; a.point = c.point; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
     return a;
 }
 template <class K> static void launch_query(void (*kernel)(K), const K &a, const QueryArgs &c, hipStream_t s) {
@@ -618,13 +590,10 @@ void launch_cast(const CastArgs &c, hipStream_t s) {
     }
 }
 void launch_closest(const ClosestArgs &c, hipStream_t s) {
-    ClosestK a = query_fill<ClosestK>(c); a.points = c.points; a.point = c.point;
-    a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
-    launch_query(c.filter ? k_closest<true> : k_closest<false>, a, c, s);
+    launch_query(c.filter ? k_closest<true> : k_closest<false>, closest_fill<ClosestK>(c), c, s);
 }
 void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s) {   // the instance with the smallest list that holds K
-    ClosestMultiK a = query_fill<ClosestMultiK>(c); a.points = c.points; a.point = c.point; a.count = c.count; a.gid_leaf = c.gid_leaf; a.max_hits = c.max_hits;
-    a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    ClosestMultiK a = closest_fill<ClosestMultiK>(c); a.count = c.count; a.gid_leaf = c.gid_leaf; a.max_hits = c.max_hits;
     launch_query(c.max_hits <= 4u ? (c.filter ? k_closest_multi<4, true> : k_closest_multi<4, false>) : (c.filter ? k_closest_multi<8, true> : k_closest_multi<8, false>), a, c, s);
 }
 

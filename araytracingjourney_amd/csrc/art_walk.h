@@ -1,5 +1,6 @@
 // art_walk.h -- the per-ray walk: a lane's traversal state over the binary and the 4-wide quantised nodes (TravBase / Trav / Trav4), the per-XCD chunk cursors
-// (pop_chunk) and the pooled persistent-wave loop (pooled_trace).  Included by art_trace.hip (k_trace, k_trace_ao) and art_query.hip (the casts, k_closest, k_sweep).
+// (pop_chunk) and the pooled persistent-wave loop (pooled_trace).  Included by art_trace.hip (k_trace, k_trace_ao) and art_query.hip (the casts, the point queries, k_sweep).
+// TravBase has ONE leaf step, step_leaf_take, with a hook for what becomes of a closest candidate: step_leaf keeps it as the best, art_query.hip's TravMulti lists it.
 #pragma once
 #include "art_device.h"
 
@@ -33,8 +34,9 @@ template <bool ANY, int OVF, int LDSN = kLdsStack, bool ALPHA = false> struct Tr
         if (sp < LDSN) cur = lds[sp * kTraceBlock]; else cur = *(volatile int *)&ovf[sp - LDSN];
         return false;
     }
-    // accept() of DESIGN.md 1.1 for the triangle in `cur`: exact triangle-AABB slab, then Moeller-Trumbore (and with ALPHA the alpha test of DESIGN.md 3.2)
-    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+    // accept() of DESIGN.md 1.1 for the triangle in `cur`: exact triangle-AABB slab, then Moeller-Trumbore (and with ALPHA the alpha test of DESIGN.md 3.2).  What becomes of a
+    // closest candidate that is below (tbest, bgid) is the caller's: take(t_eff, u, v, pos, gid) -- step_leaf keeps it as the best, TravMulti (art_query.hip) enters it in its list
+    template <class TAKE> __device__ __forceinline__ bool step_leaf_take(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av, const TAKE &take) {
         uint32_t pos = (uint32_t)~cur;
         // the reference of an ABSENT child of a 4-wide node (kAbsentChild: no leaf sits at position 2^31 - 1).  Its inverted box is left before it is entered by every
         // ray with a sign on every axis -- but a node scaled down to a point (a one-triangle tree, a node whose children were all masked) gives near == far on all three
@@ -53,11 +55,14 @@ template <bool ANY, int OVF, int LDSN = kLdsStack, bool ALPHA = false> struct Tr
                     float teff = fmaxf(t, te);
                     uint32_t gid = __float_as_uint(td.w);
                     // (only a candidate that would win is tested: a cut one that would lose changes nothing)
-                    if ((teff < tbest || (teff == tbest && gid < bgid)) && (!ALPHA || !alpha_cut(av, pos, u, v))) { tbest = teff; bu = u; bv = v; bpos = pos; bgid = gid; }
+                    if ((teff < tbest || (teff == tbest && gid < bgid)) && (!ALPHA || !alpha_cut(av, pos, u, v))) take(teff, u, v, pos, gid);
                 }
             }
         }
         return pop(lds, ovf);
+    }
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+        return step_leaf_take(tris, lds, ovf, av, [this](float teff, float u, float v, uint32_t pos, uint32_t gid) { tbest = teff; bu = u; bv = v; bpos = pos; bgid = gid; });
     }
     // two children with hit flags / entry distances: continue with the nearer, stack the farther
     __device__ __forceinline__ bool descend2(bool h0, bool h1, float te0, float te1, int c0, int c1, int *lds, int *ovf) {
