@@ -22,14 +22,17 @@ hipError_t art::acquire_stream(int device, hipStream_t *out) {
     {
         std::lock_guard<std::mutex> lock(g_stream_mutex);
         for (size_t i = 0; i < g_free_streams.size(); i++)
-            if (g_free_streams[i].first == device) { *out = g_free_streams[i].second; g_free_streams.erase(g_free_streams.begin() + (long)i); return hipSuccess; }
+            if (g_free_streams[i].first == device) { *out = g_free_streams[i].second; g_free_streams.erase(g_free_streams.begin() + (long)i); live_add(kLivePooled, -1); live_add(kLiveStreams, 1); return hipSuccess; }
     }
-    return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+    hipError_t e = hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+    if (e == hipSuccess) live_add(kLiveStreams, 1); else *out = nullptr;
+    return e;
 }
 void art::release_stream(int device, hipStream_t s) {
     (void)hipStreamSynchronize(s);
     std::lock_guard<std::mutex> lock(g_stream_mutex);
     g_free_streams.push_back({device, s});
+    live_add(kLiveStreams, -1); live_add(kLivePooled, 1);
 }
 
 int32_t art::use_device(ArtContext *c) {
@@ -272,14 +275,14 @@ int32_t art_create(const ArtConfig *cfg, ArtContext **out) {
     c->F = cfg->frames_in_flight == 0 ? 1 : cfg->frames_in_flight;
     hipError_t e = hipSetDevice(dev);
     for (uint32_t k = 0; k < c->F && e == hipSuccess; k++) {
-        e = acquire_stream(c->device, &c->slot[k].own);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->slot[k].done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreate(&c->slot[k].ao_ev[0]);
-        if (e == hipSuccess) e = hipEventCreate(&c->slot[k].ao_ev[1]);
+        e = c->slot[k].own.acquire(c->device);
+        if (e == hipSuccess) e = c->slot[k].done.create(hipEventDisableTiming);
+        if (e == hipSuccess) e = c->slot[k].ao_ev[0].create();
+        if (e == hipSuccess) e = c->slot[k].ao_ev[1].create();
     }
     for (int f = 0; f < ArtContext::kRing && e == hipSuccess; f++)
-        for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventCreate(&c->ev[f][i]);
-    if (e != hipSuccess) { (void)art_destroy(c); return hipfail(e, "art_create"); } // releases the streams and events created so far
+        for (int i = 0; i < 5 && e == hipSuccess; i++) e = c->ev[f][i].create();
+    if (e != hipSuccess) { (void)art_destroy(c); return hipfail(e, "art_create"); } // the handles made so far go with the context
     c->W = cfg->width; c->H = cfg->height;
     // the fused packet frame is the default at every ring depth (one frame at a time: 0.575 ms against 0.669 ms for the staged per-ray
     // kernels, profiles/README.md r1h); art_set_tuning selects the other forms
@@ -293,23 +296,12 @@ int32_t art_create(const ArtConfig *cfg, ArtContext **out) {
 int32_t art_destroy(ArtContext *c) {
     if (!c) return ART_OK;
     (void)hipSetDevice(c->device);
+    // everything the context put on the GPU is waited for, then every member releases what it owns (art_context.h: who owns what)
     for (uint32_t k = 0; k < c->F; k++) if (c->stream_of(k)) (void)hipStreamSynchronize(c->stream_of(k));
     drop_graphs(c);
-    cast_release(c);   // (waits for the casts on callers' streams too)
-    for (uint32_t i = 0; i < c->n_refit_streams; i++) if (c->refit_stream[i]) { (void)hipStreamSynchronize(c->refit_stream[i]); (void)hipStreamDestroy(c->refit_stream[i]); }
-    as_release(c);
-    lbvh_free(c->bvh); c->arena.release();
-    c->d_verts.release(); c->d_indices.release(); c->d_tex.release(); c->d_prims.release(); c->d_first_tri.release(); c->d_ao_tab.release();
-    c->d_tile_list.release(); c->d_tile_xy.release(); c->d_tile_slot.release(); c->d_block_order.release(); c->d_hints.release(); c->plan.release();
-    for (uint32_t k = 0; k < kMaxFrames; k++) {
-        c->slot[k].release();
-        if (c->slot[k].done) (void)hipEventDestroy(c->slot[k].done);
-        for (int i = 0; i < 2; i++) if (c->slot[k].ao_ev[i]) (void)hipEventDestroy(c->slot[k].ao_ev[i]);
-        if (c->slot[k].own) release_stream(c->device, c->slot[k].own);
-    }
-    for (int f = 0; f < ArtContext::kRing; f++)
-        for (int i = 0; i < 5; i++) if (c->ev[f][i]) (void)hipEventDestroy(c->ev[f][i]);
-    for (int i = 0; i < 2; i++) if (c->mark[i]) (void)hipEventDestroy(c->mark[i]);
+    (void)cast_sync(c);   // (the casts on callers' streams too)
+    for (uint32_t i = 0; i < c->n_refit_streams; i++) (void)hipStreamSynchronize(c->refit_stream[i]);
+    if (c->plan.plan_stream) (void)hipStreamSynchronize(c->plan.plan_stream);
     delete c;
     return ART_OK;
 }
@@ -517,16 +509,12 @@ static int32_t lights_upload(ArtContext *c, FrameSlot &S, hipStream_t s) {
     if (n <= (size_t)kMaxLights || S.lights_epoch == c->lights_epoch) return ART_OK;
     const size_t m = n - kMaxLights;
     if (S.lights_ev_set) HIPC(hipEventSynchronize(S.lights_ev));   // the upload that read the staging copy last
-    if (S.h_lights_cap < m) {
-        if (S.h_lights_more) (void)hipHostFree(S.h_lights_more);
-        S.h_lights_more = nullptr; S.h_lights_cap = 0;
-        HIPC(hipHostMalloc((void **)&S.h_lights_more, m * sizeof(ArtLight), hipHostMallocDefault)); S.h_lights_cap = m;
-    }
+    HIPC(S.h_lights_more.ensure(m));
     if (S.d_lights_more.n < m) { HIPC(hipStreamSynchronize(s)); HIPC(S.d_lights_more.ensure(m)); }   // (frames of this slot still read the old table)
-    std::memcpy(S.h_lights_more, c->lights.data() + kMaxLights, m * sizeof(ArtLight));
-    for (size_t i = 0; i < m; i++) directional_constants(S.h_lights_more[i]);
-    HIPC(hipMemcpyAsync(S.d_lights_more.p, S.h_lights_more, m * sizeof(ArtLight), hipMemcpyHostToDevice, s));
-    if (!S.lights_ev) HIPC(hipEventCreateWithFlags(&S.lights_ev, hipEventDisableTiming));
+    std::memcpy(S.h_lights_more.p, c->lights.data() + kMaxLights, m * sizeof(ArtLight));
+    for (size_t i = 0; i < m; i++) directional_constants(S.h_lights_more.p[i]);
+    HIPC(hipMemcpyAsync(S.d_lights_more.p, S.h_lights_more.p, m * sizeof(ArtLight), hipMemcpyHostToDevice, s));
+    HIPC(S.lights_ev.create(hipEventDisableTiming));
     HIPC(hipEventRecord(S.lights_ev, s)); S.lights_ev_set = true;
     S.lights_epoch = c->lights_epoch;
     return ART_OK;
@@ -557,7 +545,7 @@ int32_t art_trace(ArtContext *c) {
     if (c->tiled()) a.color_tiles = S.tiles_for(c->frame_no, c->F); // alternates when a pair of buffers is bound
     const bool fused = c->fused_frame();
     if (c->B > 1 && !fused) return fail(ART_E_STATE, "art_trace: several frames per launch need the default fused frame");
-    hipEvent_t *ev = c->ev[c->frame_no % ArtContext::kRing];
+    const Event *ev = c->ev[c->frame_no % ArtContext::kRing];
     c->ev_fused[c->frame_no % ArtContext::kRing] = fused;
     auto submitted = [&]() { S.ao_valid = false; S.presented = false; c->last = k; c->frame_no++; c->traced = true; return ART_OK; };   // the frame is in slot k's queue
     if (c->graph_mode && !fused && S.ext_ring_n < 2) { // a fused frame is a single launch: nothing for a graph to save; alternating tile buffers change a kernel argument
@@ -819,7 +807,7 @@ int32_t art_collect_timings(ArtContext *c, float sums_ms[5], uint32_t *n_frames)
     if (c->frame_no - from > (uint64_t)ArtContext::kRing) from = c->frame_no - ArtContext::kRing;
     for (int k = 0; k < 5; k++) sums_ms[k] = 0.f;
     for (uint64_t f = from; f < c->frame_no; f++) {
-        hipEvent_t *ev = c->ev[f % ArtContext::kRing];
+        const Event *ev = c->ev[f % ArtContext::kRing];
         float ms = 0;
         if (c->ev_fused[f % ArtContext::kRing]) { HIPC(hipEventElapsedTime(&ms, ev[0], ev[4])); sums_ms[0] += ms; sums_ms[4] += ms; continue; } // one launch: booked on the first stage
         for (int k = 0; k < 4; k++) { HIPC(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); sums_ms[k] += ms; }
@@ -875,7 +863,7 @@ int32_t art_timestamp_mark(ArtContext *c, uint32_t which) {
     if (!c || which > 1) return fail(ART_E_INVALID, "art_timestamp_mark: mark 0 or 1");
     if (!c->traced) return fail(ART_E_STATE, "art_timestamp_mark: nothing traced yet");
     int32_t r = use_device(c); if (r) return r;
-    if (!c->mark[which]) HIPC(hipEventCreate(&c->mark[which]));
+    HIPC(c->mark[which].create());
     HIPC(hipEventRecord(c->mark[which], c->stream_of(c->last)));
     return ART_OK;
 }
@@ -921,7 +909,7 @@ int32_t art_get_stats(ArtContext *c, ArtStats *out) {
         if (c->ao_spp && c->slot[c->last].ao_valid) { float ams = 0; if (hipEventElapsedTime(&ams, c->slot[c->last].ao_ev[0], c->slot[c->last].ao_ev[1]) == hipSuccess) c->stats.ao_ms = ams; } // (only a slot whose latest frame had its AO pass has recorded these events: asking others leaves an error behind for the next hipGetLastError)
         float ms = 0;
         if (c->frame_no) {
-            hipEvent_t *ev = c->ev[(c->frame_no - 1) % ArtContext::kRing];
+            const Event *ev = c->ev[(c->frame_no - 1) % ArtContext::kRing];
             if (hipEventElapsedTime(&ms, ev[0], ev[4]) == hipSuccess) c->stats.frame_ms = ms;
             if (c->ev_fused[(c->frame_no - 1) % ArtContext::kRing]) { c->stats.trace_primary_ms = c->stats.frame_ms; c->stats.shade_ms = c->stats.trace_shadow_ms = c->stats.accumulate_ms = 0.f; }
             else {
@@ -1016,13 +1004,12 @@ int32_t art_parity_math_sweep(ArtContext *c, uint32_t which, uint32_t first_bits
     int32_t r = use_device(c); if (r) return r;
     r = sync_all(c); if (r) return r;
     math_sweep_guard(guard);
-    unsigned long long *d = nullptr, h[3] = {0ull, ~0ull, 0ull};
-    HIPC(hipMalloc(&d, sizeof h));
-    hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { launch_math_sweep(which, first_bits, count, stride, d, nullptr); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    hipFree(d);
-    HIPC(e);
+    unsigned long long h[3] = {0ull, ~0ull, 0ull};
+    DevBuf<unsigned long long> d;
+    HIPC(d.ensure(3));
+    HIPC(hipMemcpy(d.p, h, sizeof h, hipMemcpyHostToDevice));
+    launch_math_sweep(which, first_bits, count, stride, d.p, nullptr); HIPC(hipGetLastError());
+    HIPC(hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost));
     *mismatches = h[0]; *fast_lanes = h[2];
     if (h[0]) *first_bad_bits = first_bits + (uint32_t)h[1] * stride;
     return ART_OK;
@@ -1035,16 +1022,22 @@ int32_t art_parity_radiance_sweep(ArtContext *c, uint32_t which, uint32_t first_
     if (which > 1 || count > (1ull << 32)) return fail(ART_E_INVALID, "art_parity_radiance_sweep: which 0..1, at most 2^32 patterns");
     int32_t r = use_device(c); if (r) return r;
     r = sync_all(c); if (r) return r;
-    unsigned long long *d = nullptr, h[3] = {0ull, 0ull, ~0ull};
-    HIPC(hipMalloc(&d, sizeof h));
-    hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { launch_radiance_sweep(which, first_bits, count, stride, numerator, d, nullptr); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    hipFree(d);
-    HIPC(e);
+    unsigned long long h[3] = {0ull, 0ull, ~0ull};
+    DevBuf<unsigned long long> d;
+    HIPC(d.ensure(3));
+    HIPC(hipMemcpy(d.p, h, sizeof h, hipMemcpyHostToDevice));
+    launch_radiance_sweep(which, first_bits, count, stride, numerator, d.p, nullptr); HIPC(hipGetLastError());
+    HIPC(hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost));
     *max_ulps = (uint32_t)(h[0] >> 32); *class_mismatches = h[1];
     if (h[0]) *worst_bits = first_bits + (uint32_t)h[0] * stride;
     if (h[1]) *first_class_bits = first_bits + (uint32_t)h[2] * stride;
+    return ART_OK;
+}
+
+// what libart holds in this process right now (include/art_parity.h): the counters the handles of art_own.h and the stream pool above keep
+int32_t art_parity_live_resources(uint64_t out[5]) {
+    if (!out) return fail(ART_E_INVALID, "art_parity_live_resources: null argument");
+    for (int i = 0; i < 5; i++) out[i] = g_live[i].load(std::memory_order_relaxed);
     return ART_OK;
 }
 

@@ -346,10 +346,12 @@ static hipError_t wide_build_host(Lbvh &l, uint32_t T, hipStream_t s) {
     }
     l.n_wide = (uint32_t)wide.size();
     levels.push_back(l.n_wide); l.wide_levels = levels;
-    HIPQ(hipMalloc(&l.wide, wide.size() * sizeof(DevNode4)));
-    HIPQ(hipMemcpy(l.wide, wide.data(), wide.size() * sizeof(DevNode4), hipMemcpyHostToDevice));
-    HIPQ(hipMalloc(&l.widef, widef.size() * sizeof(DevNodeW)));
-    HIPQ(hipMemcpy(l.widef, widef.data(), widef.size() * sizeof(DevNodeW), hipMemcpyHostToDevice));
+    DevBuf<DevNode4> d_wide; DevBuf<DevNodeW> d_widef;   // both records or neither: the tree takes them at the end
+    HIPQ(d_wide.ensure(wide.size()));
+    HIPQ(hipMemcpy(d_wide.p, wide.data(), wide.size() * sizeof(DevNode4), hipMemcpyHostToDevice));
+    HIPQ(d_widef.ensure(widef.size()));
+    HIPQ(hipMemcpy(d_widef.p, widef.data(), widef.size() * sizeof(DevNodeW), hipMemcpyHostToDevice));
+    l.wide = std::move(d_wide); l.widef = std::move(d_widef);
     return hipSuccess;
 }
 
@@ -470,46 +472,40 @@ hipError_t wide_build(Lbvh &l, uint32_t T, hipStream_t s, bool on_host) {
     DevNode4 *wide = nullptr; DevNodeW *widef = nullptr;
     std::vector<uint32_t> levels; // first node of every level (breadth-first numbering: a level is contiguous), then n_wide
     Arena own; Arena &A = l.arena ? *l.arena : own;
-    auto body = [&]() -> hipError_t {
-        HIPQ(rocprim::exclusive_scan(nullptr, tmp_bytes, cnt, offs, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), s));
-        HIPQ(A.reserve(3 * Arena::pad((size_t)cap * 4) + Arena::pad((size_t)cap * 16) + 2 * Arena::pad(((size_t)cap + 1) * 4) + Arena::pad((size_t)cap * sizeof(DevNode4)) + Arena::pad((size_t)cap * sizeof(DevNodeW)) + Arena::pad(tmp_bytes ? tmp_bytes : 16)));
-        front[0] = A.take<int32_t>(cap); front[1] = A.take<int32_t>(cap); cand = A.take<int32_t>((size_t)cap * 4);
-        meta = A.take<uint32_t>(cap); cnt = A.take<uint32_t>((size_t)cap + 1); offs = A.take<uint32_t>((size_t)cap + 1);
-        wide = A.take<DevNode4>(cap); widef = A.take<DevNodeW>(cap);
-        tmp = A.take<char>(tmp_bytes ? tmp_bytes : 16);
-        const int32_t root = NI ? 0 : ~0;
-        HIPQ(hipMemcpyAsync(front[0], &root, 4, hipMemcpyHostToDevice, s));
-        uint32_t first = 0, n = 1; int cur = 0;
-        while (n) {
-            if (first + n > cap) return hipErrorInvalidValue; // (cannot happen: see cap)
-            const uint32_t g = (n + 255) / 256;
-            k_wide_expand<<<g, 256, 0, s>>>(in, front[cur], n, cand, meta, cnt);
-            HIPQ(hipMemsetAsync(cnt + n, 0, 4, s));                                  // the scan's last element = the level's total
-            size_t tb = tmp_bytes;
-            HIPQ(rocprim::exclusive_scan(tmp, tb, cnt, offs, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
-            k_wide_emit<<<g, 256, 0, s>>>(in, n, first, cand, meta, offs, wide, widef, front[cur ^ 1]);
-            uint32_t n_next = 0;
-            HIPQ(hipMemcpyAsync(&n_next, offs + n, 4, hipMemcpyDeviceToHost, s));
-            HIPQ(hipStreamSynchronize(s));
-            levels.push_back(first);
-            first += n; n = n_next; cur ^= 1;
-        }
-        HIPQ(hipGetLastError());
-        l.n_wide = first;
-        levels.push_back(first); l.wide_levels = levels;
-        return hipSuccess;
-    };
-    hipError_t e = body();
-    if (e == hipSuccess) { // the work arrays are sized for the worst case (NI nodes); a 4-wide collapse of a binary tree has about a third of that
-        e = hipMalloc(&l.wide, (size_t)l.n_wide * sizeof(DevNode4));
-        if (e == hipSuccess) e = hipMalloc(&l.widef, (size_t)l.n_wide * sizeof(DevNodeW));
-        if (e == hipSuccess) e = hipMemcpyAsync(l.wide, wide, (size_t)l.n_wide * sizeof(DevNode4), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(l.widef, widef, (size_t)l.n_wide * sizeof(DevNodeW), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { hipFree(l.wide); hipFree(l.widef); l.wide = nullptr; l.widef = nullptr; l.n_wide = 0; }
+    HIPQ(rocprim::exclusive_scan(nullptr, tmp_bytes, cnt, offs, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), s));
+    HIPQ(A.reserve(3 * Arena::pad((size_t)cap * 4) + Arena::pad((size_t)cap * 16) + 2 * Arena::pad(((size_t)cap + 1) * 4) + Arena::pad((size_t)cap * sizeof(DevNode4)) + Arena::pad((size_t)cap * sizeof(DevNodeW)) + Arena::pad(tmp_bytes ? tmp_bytes : 16)));
+    front[0] = A.take<int32_t>(cap); front[1] = A.take<int32_t>(cap); cand = A.take<int32_t>((size_t)cap * 4);
+    meta = A.take<uint32_t>(cap); cnt = A.take<uint32_t>((size_t)cap + 1); offs = A.take<uint32_t>((size_t)cap + 1);
+    wide = A.take<DevNode4>(cap); widef = A.take<DevNodeW>(cap);
+    tmp = A.take<char>(tmp_bytes ? tmp_bytes : 16);
+    const int32_t root = NI ? 0 : ~0;
+    HIPQ(hipMemcpyAsync(front[0], &root, 4, hipMemcpyHostToDevice, s));
+    uint32_t first = 0, n = 1; int cur = 0;
+    while (n) {
+        if (first + n > cap) return hipErrorInvalidValue; // (cannot happen: see cap)
+        const uint32_t g = (n + 255) / 256;
+        k_wide_expand<<<g, 256, 0, s>>>(in, front[cur], n, cand, meta, cnt);
+        HIPQ(hipMemsetAsync(cnt + n, 0, 4, s));                                  // the scan's last element = the level's total
+        size_t tb = tmp_bytes;
+        HIPQ(rocprim::exclusive_scan(tmp, tb, cnt, offs, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
+        k_wide_emit<<<g, 256, 0, s>>>(in, n, first, cand, meta, offs, wide, widef, front[cur ^ 1]);
+        uint32_t n_next = 0;
+        HIPQ(hipMemcpyAsync(&n_next, offs + n, 4, hipMemcpyDeviceToHost, s));
+        HIPQ(hipStreamSynchronize(s));
+        levels.push_back(first);
+        first += n; n = n_next; cur ^= 1;
     }
-    own.release();
-    return e;
+    HIPQ(hipGetLastError());
+    levels.push_back(first);
+    // the work arrays are sized for the worst case (NI nodes); a 4-wide collapse of a binary tree has about a third of that.  Both records or neither: the tree takes them at the end
+    const uint32_t n_wide = levels.back();
+    DevBuf<DevNode4> d_wide; DevBuf<DevNodeW> d_widef;
+    HIPQ(d_wide.ensure(n_wide)); HIPQ(d_widef.ensure(n_wide));
+    HIPQ(hipMemcpyAsync(d_wide.p, wide, (size_t)n_wide * sizeof(DevNode4), hipMemcpyDeviceToDevice, s));
+    HIPQ(hipMemcpyAsync(d_widef.p, widef, (size_t)n_wide * sizeof(DevNodeW), hipMemcpyDeviceToDevice, s));
+    HIPQ(hipStreamSynchronize(s));
+    l.wide = std::move(d_wide); l.widef = std::move(d_widef); l.n_wide = n_wide; l.wide_levels = levels;
+    return hipSuccess;
 }
 
 // ---- refit: a model moved (VkModel::set_model_matrix, vk_model.rs:461-466; the reference rebuilds its TLAS every frame for this, renderer.rs:637-651) ------
@@ -762,9 +758,14 @@ hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s) {
     constexpr uint32_t kBatchNodes = 768;
     const std::vector<uint32_t> &levels = l.wide_levels;
     const uint32_t NW = l.n_wide, n_levels = (uint32_t)levels.size() - 1;
+    // Everything is made in locals and moved into the tree at the very end: a failure on the way leaves the tree's lists as they were (complete, or absent)
+    DevBuf<uint32_t> d_leaf_parent, d_node_parent, d_sub_nodes, d_sub_leaves, d_sub_off;
+    HIPQ(d_leaf_parent.ensure(T)); HIPQ(d_node_parent.ensure(NW));   // who holds whom in the 4-wide tree: the marks of a refit go up along it
+    launch_wide_parents(NW, l.widef, d_leaf_parent.p, d_node_parent.p, s);
+    HIPQ(hipGetLastError());
     std::vector<uint32_t> node_parent(NW), leaf_parent(T);
     HIPQ(hipStreamSynchronize(s));
-    HIPQ(hipMemcpy(node_parent.data(), l.node_parent, (size_t)NW * 4, hipMemcpyDeviceToHost)); HIPQ(hipMemcpy(leaf_parent.data(), l.leaf_parent, (size_t)T * 4, hipMemcpyDeviceToHost));
+    HIPQ(hipMemcpy(node_parent.data(), d_node_parent.p, (size_t)NW * 4, hipMemcpyDeviceToHost)); HIPQ(hipMemcpy(leaf_parent.data(), d_leaf_parent.p, (size_t)T * 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> size(NW, 1);
     for (uint32_t w = NW; w-- > 1;) size[node_parent[w]] += size[w];
     // batch_of: ~0 = the crown; roots in index order fill batches
@@ -802,31 +803,33 @@ hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s) {
         std::vector<uint32_t> at(cnt.begin(), cnt.end() - 1);
         for (uint32_t p = 0; p < T; p++) sub_leaves[at[slot(leaf_parent[p])]++] = p;
     }
+    std::vector<uint32_t> batch_prim_off, batch_prim_ids;
     {   // which primitives have triangles in which batch (the crown always runs): the leaf's primitive is tri_prim[leaf_gid[p]], gathered on the device
         std::vector<uint32_t> tp(T);
-        uint32_t *d_lp = nullptr;
-        HIPQ(hipMalloc(&d_lp, (size_t)T * 4));
-        k_leaf_prims<<<(T + 255) / 256, 256, 0, s>>>(T, l.leaf_gid, l.tri_prim, d_lp);
-        hipError_t ec = hipMemcpyAsync(tp.data(), d_lp, (size_t)T * 4, hipMemcpyDeviceToHost, s);   // (on the kernel's own stream: the context's streams do not wait for the null stream or it for them)
-        if (ec == hipSuccess) ec = hipStreamSynchronize(s);
-        hipFree(d_lp);
-        HIPQ(ec);
+        DevBuf<uint32_t> d_lp;
+        HIPQ(d_lp.ensure(T));
+        k_leaf_prims<<<(T + 255) / 256, 256, 0, s>>>(T, l.leaf_gid, l.tri_prim, d_lp.p);
+        HIPQ(hipMemcpyAsync(tp.data(), d_lp.p, (size_t)T * 4, hipMemcpyDeviceToHost, s));   // (on the kernel's own stream: the context's streams do not wait for the null stream or it for them)
+        HIPQ(hipStreamSynchronize(s));
         uint32_t n_prims = 0;
         for (uint32_t g = 0; g < T; g++) n_prims = std::max(n_prims, tp[g] + 1u);
         std::vector<uint32_t> seen(n_prims, 0u);   // seen[primitive] = batch + 1 of the last batch it was listed for (the leaf lists are batch by batch: one pass)
-        l.batch_prim_off.assign(1, 0u); l.batch_prim_ids.clear();
+        batch_prim_off.assign(1, 0u);
         for (uint32_t b = 0; b < nb; b++) {
             for (uint32_t i = off[nb1 + 1 + b]; i < off[nb1 + 2 + b]; i++) {
                 const uint32_t pr = tp[sub_leaves[i]];
-                if (seen[pr] != b + 1u) { seen[pr] = b + 1u; l.batch_prim_ids.push_back(pr); }
+                if (seen[pr] != b + 1u) { seen[pr] = b + 1u; batch_prim_ids.push_back(pr); }
             }
-            l.batch_prim_off.push_back((uint32_t)l.batch_prim_ids.size());
+            batch_prim_off.push_back((uint32_t)batch_prim_ids.size());
         }
     }
-    hipFree(l.sub_nodes); hipFree(l.sub_leaves); hipFree(l.sub_off); l.sub_nodes = l.sub_leaves = l.sub_off = nullptr;
-    HIPQ(hipMalloc(&l.sub_nodes, (size_t)NW * 4)); HIPQ(hipMalloc(&l.sub_leaves, (size_t)T * 4)); HIPQ(hipMalloc(&l.sub_off, off.size() * 4));
-    HIPQ(hipMemcpy(l.sub_nodes, sub_nodes.data(), (size_t)NW * 4, hipMemcpyHostToDevice)); HIPQ(hipMemcpy(l.sub_leaves, sub_leaves.data(), (size_t)T * 4, hipMemcpyHostToDevice));
-    HIPQ(hipMemcpy(l.sub_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    HIPQ(d_sub_nodes.ensure(NW)); HIPQ(d_sub_leaves.ensure(T)); HIPQ(d_sub_off.ensure(off.size()));
+    HIPQ(hipMemcpy(d_sub_nodes.p, sub_nodes.data(), (size_t)NW * 4, hipMemcpyHostToDevice)); HIPQ(hipMemcpy(d_sub_leaves.p, sub_leaves.data(), (size_t)T * 4, hipMemcpyHostToDevice));
+    HIPQ(hipMemcpy(d_sub_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    // all of them exist: the tree takes them (and lets go of what it had)
+    l.leaf_parent = std::move(d_leaf_parent); l.node_parent = std::move(d_node_parent);
+    l.sub_nodes = std::move(d_sub_nodes); l.sub_leaves = std::move(d_sub_leaves); l.sub_off = std::move(d_sub_off);
+    l.batch_prim_off = std::move(batch_prim_off); l.batch_prim_ids = std::move(batch_prim_ids);
     l.sub_batches = nb; l.sub_levels = n_levels;
     if (l.log & 1u) {
         uint32_t crown = 0, big = 0; for (uint32_t w = 0; w < NW; w++) crown += batch_of[w] == ~0u;
@@ -857,49 +860,36 @@ __global__ __launch_bounds__(256) void k_parents(uint32_t NI, const int32_t *__r
 hipError_t binary_refit(Lbvh &l, uint32_t T, const DevTri *tris, hipStream_t s) {
     const uint32_t NI = T > 1 ? T - 1 : 0, B = 256, GT = (T + B - 1) / B;
     k_leaf_boxes<<<GT, B, 0, s>>>(T, tris, l.leaf_lo, l.leaf_hi);
-    int32_t *parent_int = nullptr, *parent_leaf = nullptr; uint32_t *arrive = nullptr;
-    auto body = [&]() -> hipError_t {
-        if (NI) {
-            HIPQ(hipMalloc(&parent_int, (size_t)NI * 4)); HIPQ(hipMalloc(&parent_leaf, (size_t)T * 4)); HIPQ(hipMalloc(&arrive, (size_t)NI * 4));
-            for (int tree = 0; tree < 2; tree++) {
-                const int32_t *child = tree == 0 ? l.child : l.trav_child;
-                float *nlo = tree == 0 ? l.node_lo : l.trav_lo, *nhi = tree == 0 ? l.node_hi : l.trav_hi;
-                if (!child) continue;
-                HIPQ(hipMemsetAsync(arrive, 0, (size_t)NI * 4, s));
-                k_parents<<<(NI + B - 1) / B, B, 0, s>>>(NI, child, parent_int, parent_leaf);
-                k_refit<<<GT, B, 0, s>>>(T, child, parent_int, parent_leaf, l.leaf_lo, l.leaf_hi, nlo, nhi, arrive);
-            }
+    DevBuf<int32_t> parent_int, parent_leaf; DevBuf<uint32_t> arrive;   // (freed on every way out, behind the synchronisation on the good one)
+    if (NI) {
+        HIPQ(parent_int.ensure(NI)); HIPQ(parent_leaf.ensure(T)); HIPQ(arrive.ensure(NI));
+        for (int tree = 0; tree < 2; tree++) {
+            const int32_t *child = tree == 0 ? l.child : l.trav_child;
+            float *nlo = tree == 0 ? l.node_lo : l.trav_lo, *nhi = tree == 0 ? l.node_hi : l.trav_hi;
+            if (!child) continue;
+            HIPQ(hipMemsetAsync(arrive.p, 0, (size_t)NI * 4, s));
+            k_parents<<<(NI + B - 1) / B, B, 0, s>>>(NI, child, parent_int.p, parent_leaf.p);
+            k_refit<<<GT, B, 0, s>>>(T, child, parent_int.p, parent_leaf.p, l.leaf_lo, l.leaf_hi, nlo, nhi, arrive.p);
         }
-        const uint32_t NN = NI ? NI : 1;
-        if (l.trav_child) k_emit_nodes<<<(NN + B - 1) / B, B, 0, s>>>(T, l.trav_child, l.trav_lo, l.trav_hi, l.leaf_lo, l.leaf_hi, l.nodes);
-        else k_emit_nodes<<<(NN + B - 1) / B, B, 0, s>>>(T, l.child, l.node_lo, l.node_hi, l.leaf_lo, l.leaf_hi, l.nodes);
-        HIPQ(hipGetLastError());
-        HIPQ(hipStreamSynchronize(s));
-        l.canon_boxes = true;
-        return hipSuccess;
-    };
-    hipError_t e = body();
-    hipFree(parent_int); hipFree(parent_leaf); hipFree(arrive);
-    return e;
+    }
+    const uint32_t NN = NI ? NI : 1;
+    if (l.trav_child) k_emit_nodes<<<(NN + B - 1) / B, B, 0, s>>>(T, l.trav_child, l.trav_lo, l.trav_hi, l.leaf_lo, l.leaf_hi, l.nodes);
+    else k_emit_nodes<<<(NN + B - 1) / B, B, 0, s>>>(T, l.child, l.node_lo, l.node_hi, l.leaf_lo, l.leaf_hi, l.nodes);
+    HIPQ(hipGetLastError());
+    HIPQ(hipStreamSynchronize(s));
+    l.canon_boxes = true;
+    return hipSuccess;
 }
 
 __global__ void k_build_noop() {}
 void build_prewarm(hipStream_t s) { k_build_noop<<<1, 1, 0, s>>>(); }
 
-void lbvh_free(Lbvh &l) {
-    hipFree(l.wide); hipFree(l.widef); hipFree(l.leaf_parent); hipFree(l.node_parent);
-    hipFree(l.sub_nodes); hipFree(l.sub_leaves); hipFree(l.sub_off);
-    if (l.trav_child != l.res_trav_child) { hipFree(l.trav_child); hipFree(l.trav_lo); hipFree(l.trav_hi); }   // (allocations of their own: no room was reserved)
-    hipFree(l.block);   // leaf_gid .. shade_tris, cbounds, res_trav_*, gid_leaf
-    l = Lbvh{};
-}
 hipError_t lbvh_claim_trav(Lbvh &l, uint32_t NI) {
     if (l.trav_child) return hipSuccess;
     if (l.res_trav_child) { l.trav_child = l.res_trav_child; l.trav_lo = l.res_trav_lo; l.trav_hi = l.res_trav_hi; return hipSuccess; }
-    hipError_t e = hipMalloc(&l.trav_child, (size_t)NI * 8);
-    if (e == hipSuccess) e = hipMalloc(&l.trav_lo, (size_t)NI * 12);
-    if (e == hipSuccess) e = hipMalloc(&l.trav_hi, (size_t)NI * 12);
-    return e;
+    HIPQ(l.own_trav_child.ensure((size_t)NI * 2)); HIPQ(l.own_trav_lo.ensure((size_t)NI * 3)); HIPQ(l.own_trav_hi.ensure((size_t)NI * 3));
+    l.trav_child = l.own_trav_child.p; l.trav_lo = l.own_trav_lo.p; l.trav_hi = l.own_trav_hi.p;   // (the views only once all three exist)
+    return hipSuccess;
 }
 
 hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node_boxes) {
@@ -915,7 +905,6 @@ hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node
     int32_t *parent_int = nullptr, *parent_leaf = nullptr;
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
-    hipError_t err = hipSuccess;
     auto body = [&]() -> hipError_t {
         // the temporaries: one reservation of the context's arena (the sort's own scratch included)
         HIPQ(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in, out.keys, gid_in, out.leaf_gid, T, 0, 64, s));
@@ -928,8 +917,8 @@ hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node
             const size_t sizes[16] = {(size_t)T * 4, (size_t)T * 8, (size_t)NI * 8, (size_t)NI * 12, (size_t)NI * 12, (size_t)T * 12, (size_t)T * 12, (size_t)T * sizeof(DevTri), (size_t)NI * sizeof(DevNode),
                                       (size_t)T * 4, (size_t)T * sizeof(DevShadeTri), 32, (size_t)NI * 8, (size_t)NI * 12, (size_t)NI * 12, (size_t)T * 4};
             size_t total = 0; for (size_t b : sizes) total += Arena::pad(b);
-            HIPQ(hipMalloc(&out.block, total));
-            char *p = out.block; auto cut = [&](size_t bytes) { char *q = p; p += Arena::pad(bytes); return q; };
+            HIPQ(out.block.ensure(total));
+            char *p = out.block.p; auto cut = [&](size_t bytes) { char *q = p; p += Arena::pad(bytes); return q; };
             out.leaf_gid = (uint32_t *)cut(sizes[0]); out.keys = (uint64_t *)cut(sizes[1]); out.child = (int32_t *)cut(sizes[2]); out.node_lo = (float *)cut(sizes[3]); out.node_hi = (float *)cut(sizes[4]);
             out.leaf_lo = (float *)cut(sizes[5]); out.leaf_hi = (float *)cut(sizes[6]); out.tris = (DevTri *)cut(sizes[7]); out.nodes = (DevNode *)cut(sizes[8]); out.tri_prim = (uint32_t *)cut(sizes[9]);
             out.shade_tris = (DevShadeTri *)cut(sizes[10]); out.cbounds = (uint32_t *)cut(sizes[11]);
@@ -955,9 +944,8 @@ hipError_t lbvh_build(const BuildInputs &in, Lbvh &out, hipStream_t s, bool node
         HIPQ(hipStreamSynchronize(s));
         return hipSuccess;
     };
-    err = body();
-    own.release();
-    if (err != hipSuccess) lbvh_free(out);
+    const hipError_t err = body();
+    if (err != hipSuccess) out = Lbvh{};
     return err;
 }
 

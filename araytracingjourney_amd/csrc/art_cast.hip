@@ -7,14 +7,10 @@
 static int32_t cast_setup(ArtContext *c) {
     CastState &K = c->cast;
     if (K.stream) return ART_OK;
-    uint32_t *cur = nullptr;
-    HIPC(hipMalloc(&cur, (size_t)ART_CAST_POOL * kCastCursorWords * 4));
-    hipError_t e = hipSuccess;
-    for (CastBlock &b : K.block) if (e == hipSuccess && !b.ev) e = hipEventCreateWithFlags(&b.ev, hipEventDisableTiming);
-    hipStream_t s = nullptr;
-    if (e == hipSuccess) e = acquire_stream(c->device, &s);
-    if (e != hipSuccess) { (void)hipFree(cur); return hipfail(e, "art_cast_rays: the cast stream, cursor blocks and events"); }   // (events made so far stay: art_destroy)
-    K.cursors = cur; K.stream = s;
+    hipError_t e = K.cursors.ensure((size_t)ART_CAST_POOL * kCastCursorWords);
+    for (CastBlock &b : K.block) if (e == hipSuccess) e = b.ev.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = K.stream.acquire(c->device);   // (last: what was made before a failure is kept by its handle and found again by the next attempt)
+    if (e != hipSuccess) return hipfail(e, "art_cast_rays: the cast stream, cursor blocks and events");
     return ART_OK;
 }
 // every cast enqueued so far has finished, on whichever stream it runs
@@ -42,14 +38,6 @@ int32_t art::cast_wait_version(ArtContext *c, uint32_t version) {
     if (waited) c->cast.host_waits++;
     return ART_OK;
 }
-void art::cast_release(ArtContext *c) {
-    CastState &K = c->cast;
-    (void)cast_wait_all(c);   // casts on callers' streams too
-    for (CastBlock &b : K.block) if (b.ev) (void)hipEventDestroy(b.ev);
-    if (K.cursors) (void)hipFree(K.cursors);
-    K.q_rays.release(); K.q_out.release();
-    if (K.stream) release_stream(c->device, K.stream);
-}
 // The host side every enqueue on the ring shares -- a query's and a resolve's (art_resolve_hits traces nothing, but it reads a version of the scene and has to be waited
 // for like a cast).  cast_claim: the scene as of the call, the stream, the version to read (an event wait on that stream while its refit may still run) and the next ring
 // block, free.  cast_commit: the block's event behind what the caller launched, the version it holds, and its rays in the counts of casts (0: it traces none).
@@ -60,7 +48,7 @@ static int32_t cast_claim(ArtContext *c, hipStream_t user, RingSlot *q) {
     CastState &K = c->cast;
     if (c->xform_dirty) { r = scene_refresh(c, ~0u, K.stream); if (r) return r; }   // the scene as of the call: the refit in front of the cast (past the cost threshold: a rebuild)
     r = ensure_wide(c, true); if (r) return r;
-    hipStream_t s = user ? user : K.stream;
+    hipStream_t s = user ? user : K.stream.p;
     const uint32_t ver = c->as_cur;
     r = as_wait_ready(c, ver, s, ~0u); if (r) return r;   // the refit that wrote this version may still run: an event wait on the cast's stream, nothing on the host
     const uint32_t bi = K.next % ART_CAST_POOL;

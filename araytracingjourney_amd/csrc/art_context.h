@@ -27,22 +27,9 @@ struct HostPrim {
     uint32_t vis = 0xFFu;     // visibility mask (art_scene_set_primitive_mask; 0xFF: every ray sees it)
 };
 
-template <class T> struct DevBuf {
-    T *p = nullptr; size_t n = 0;
-    hipError_t ensure(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) n = count ? count : 1;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
-// one frame in flight: its own stream and per-frame buffers, like the reference's FrameData ring (renderer.rs:135, :300-318)
+// one frame in flight: its own stream and per-frame buffers, like the reference's FrameData ring (renderer.rs:135, :300-318).  Everything it holds is a handle (art_own.h)
 struct FrameSlot {
-    hipStream_t own = nullptr;
+    PoolStream own;
     DevBuf<uint32_t> d_counters, d_shadow_bits;
     DevBuf<float4> d_hits, d_contrib, d_shadow_rays, d_color, d_normal, d_color_tiles;
     DevBuf<float> d_depth;
@@ -51,9 +38,9 @@ struct FrameSlot {
     DevBuf<uint32_t> d_wave_cost;      // fused frame: packet steps of each wave of the slot's last launch (feedback for the wave plan)
     // more than 16 lights: records 16.. in a table of the slot's own (frames in flight on other slots keep theirs), uploaded on the slot's stream when the list changed since the
     // slot's last upload; the pinned staging copy is rewritten only once the upload that read it has finished
-    DevBuf<ArtLight> d_lights_more; ArtLight *h_lights_more = nullptr; size_t h_lights_cap = 0; hipEvent_t lights_ev = nullptr; bool lights_ev_set = false; uint64_t lights_epoch = 0;
+    DevBuf<ArtLight> d_lights_more; Pinned<ArtLight> h_lights_more; Event lights_ev; bool lights_ev_set = false; uint64_t lights_epoch = 0;
     DevBuf<uint32_t> d_pix_more;       // fused frame, more than 16 lights: shadow rays of lights 16.. per pixel
-    DevBuf<uint32_t> d_pcolor, d_pnormal, d_bgra; DevBuf<uint16_t> d_pdepth; bool presented = false; hipEvent_t ao_ev[2] = {nullptr, nullptr};
+    DevBuf<uint32_t> d_pcolor, d_pnormal, d_bgra; DevBuf<uint16_t> d_pdepth; bool presented = false; Event ao_ev[2];
     hipEvent_t done_alias = nullptr;   // the latest frame's completion is this ring event (fused frames: one record less per frame) instead of `done`
     float4 *ext_tiles = nullptr; size_t ext_tiles_bytes = 0; // caller-owned gather source (art_bind_color_tiles)
     static constexpr uint32_t kTileRing = kTileRingMax;
@@ -61,18 +48,12 @@ struct FrameSlot {
     float4 *tiles_of_last = nullptr;   // where the slot's most recent frame wrote its tiles
     float4 *tiles_for(uint64_t frame_no, uint32_t F) { float4 *t = ext_tiles ? (ext_ring_n > 1 ? ext_ring[(frame_no / F) % ext_ring_n] : ext_tiles) : d_color_tiles.p; tiles_of_last = t; return t; }
     float4 *last_tiles() const { return tiles_of_last ? tiles_of_last : (ext_tiles ? ext_tiles : d_color_tiles.p); }
-    hipEvent_t done = nullptr;       // recorded after the slot's last frame
+    Event done;                      // recorded after the slot's last frame
     hipGraphExec_t graph = nullptr;  // the frame's launch sequence captured once (graph mode); dropped whenever an input changes
     void *wait_event = nullptr;      // external event the slot's next frame must wait for (art_wait_external_event)
     uint32_t as_version = 0;         // which version of the acceleration structure the slot's latest frame read (art_trace_ao and the read-backs follow it)
     bool alpha = false;              // ... and whether it ran the instances with the alpha test (art_trace_ao follows it too)
     uint32_t ray_masks = kRayMasksAll; // ... and the cull masks of its rays (art_set_ray_masks; art_trace_ao casts its rays with the frame's AO mask)
-    void release() {
-        d_counters.release(); d_shadow_bits.release(); d_hits.release(); d_contrib.release(); d_shadow_rays.release();
-        d_color.release(); d_normal.release(); d_color_tiles.release(); d_depth.release(); d_occl.release(); d_ao.release(); d_ao_pix.release(); d_wave_cost.release(); d_lights_more.release(); d_pix_more.release();
-        if (h_lights_more) (void)hipHostFree(h_lights_more); h_lights_more = nullptr; h_lights_cap = 0;
-        if (lights_ev) (void)hipEventDestroy(lights_ev); lights_ev = nullptr; lights_ev_set = false; d_pcolor.release(); d_pnormal.release(); d_bgra.release(); d_pdepth.release();
-    }
 };
 constexpr uint32_t kMaxFrames = kMaxFrameSlots;
 
@@ -96,28 +77,22 @@ struct WavePlan {
     // host thread through 32 640 blocks, table down -- 0.3-0.9 ms inside an art_trace call now and then, ten frames' time; tools/camera_leg_probe.py, profiles/README.md round 4.)
     DevBuf<uint2> d_items[2]; uint32_t n_items[2] = {0, 0}; int cur = 0;
     DevBuf<uint8_t> d_level, d_level_tmp; DevBuf<uint32_t> d_worst;
-    uint32_t *h_result = nullptr, *dh_result = nullptr;   // pinned: PlanArgs::result
+    Pinned<uint32_t> result;           // pinned: PlanArgs::result
     uint32_t split1 = 0, split2 = 0;   // blocks the current table deals to four / sixteen waves
-    hipEvent_t retire[2][kMaxFrames] = {}; bool retire_set[2] = {false, false}; // recorded on every frame stream when table i was left: it may be rewritten once they have all fired
+    Event retire[2][kMaxFrames]; bool retire_set[2] = {false, false}; // recorded on every frame stream when table i was left: it may be rewritten once they have all fired
     uint32_t cap = 0;                  // items a table (and the cost buffers) hold
-    hipEvent_t cost_ready = nullptr; bool pending = false; int pending_table = 0;   // behind the sampled frame's k_plan
-    hipStream_t plan_stream = nullptr; // k_plan runs here, behind the sampled frame's completion event: one workgroup for ~0.1 ms -- on the frame's own stream the slot's next frame stood behind it (5-10 % of a 20-frame burst)
+    Event cost_ready; bool pending = false; int pending_table = 0;   // behind the sampled frame's k_plan
+    Stream plan_stream;                // k_plan runs here, behind the sampled frame's completion event: one workgroup for ~0.1 ms -- on the frame's own stream the slot's next frame stood behind it (5-10 % of a 20-frame burst)
     uint64_t next_sample = 0; uint32_t interval = 1;
     uint64_t last_sample = 0;          // the frame that was sampled last
     bool moved_since_poll = false;     // the view or the lights changed since the last plan came back: a new table is no reason to look again at once (the next one would differ too)
     uint32_t replans = 0;
-    void release() {
-        d_items[0].release(); d_items[1].release(); d_level.release(); d_level_tmp.release(); d_worst.release();
-        if (h_result) (void)hipHostFree(h_result); h_result = nullptr; dh_result = nullptr;
-        if (cost_ready) (void)hipEventDestroy(cost_ready); cost_ready = nullptr;
-        if (plan_stream) { (void)hipStreamSynchronize(plan_stream); (void)hipStreamDestroy(plan_stream); } plan_stream = nullptr;
-        for (int i = 0; i < 2; i++) for (uint32_t k = 0; k < kMaxFrames; k++) if (retire[i][k]) { (void)hipEventDestroy(retire[i][k]); retire[i][k] = nullptr; }
-    }
 };
 
 // One version of what a frame reads of the acceleration structure.  A static scene has none (the build's arrays are read directly); the first
 // art_scene_set_model_matrix makes a small ring of them: a refit writes the NEXT version while frames in flight still read the older ones, like the
 // reference's per-frame TLAS (one VkTlasBuilder per FrameData, renderer.rs:300-318, :637-651).  Version 0 is the build's own arrays.
+// A version owns its event and nothing else: its arrays are views into the context's blocks (as_block, as_pinned, shade_block, stage_*) or, version 0's, into the tree.
 constexpr uint32_t kMaxAsVersions = 24;
 struct AsVersion {
     DevTri *tris = nullptr; DevNodeW *widef = nullptr; DevNode4 *wide = nullptr; DevPrim *prims = nullptr;
@@ -131,7 +106,7 @@ struct AsVersion {
     double *acc = nullptr;               // 4 doubles of device scratch of the refit's last launch: zero between refits
     uint64_t used[kMaxFrameSlots] = {};  // frame number + 1 of the newest launch on each ring slot that read this version (0: none)
     bool aux[kMaxFrameSlots] = {};       // art_trace_ao / art_present ran behind that frame on the slot's stream
-    hipEvent_t ready = nullptr; bool ready_known = true; uint32_t ready_slot = 0; // the refit that wrote it: recorded on ring slot ready_slot's stream
+    Event ready; bool ready_known = true; uint32_t ready_slot = 0; // the refit that wrote it: recorded on ring slot ready_slot's stream
     bool result_pending = false;         // h_result is that refit's once `ready` has fired
     uint64_t epoch = 0;                  // which refit wrote it (0: the build)
     // Deformed meshes (art_scene_set_vertices): the version's own shading records (the build's array until the context first deforms a built primitive: version 0
@@ -146,15 +121,18 @@ struct AsVersion {
 // free again once it has fired (a ring that is lapped waits for it on the host: CastState::host_waits), the version of the structure the cast reads may be rewritten once it
 // has fired (scene_refresh), and art_cast_sync / sync_all wait for the events of all blocks.  (One event per VERSION behind "the latest cast that reads it" would not do: casts
 // on two callers' streams are not ordered, so the latest says nothing about the one before.)
-struct CastBlock { hipEvent_t ev = nullptr; bool set = false; uint32_t version = 0; };
+struct CastBlock { Event ev; bool set = false; uint32_t version = 0; };
 struct CastState {
-    hipStream_t stream = nullptr;              // made by the first cast: casts with hip_stream NULL, the queries, and the refit a cast finds pending when the context has no refit streams
-    uint32_t *cursors = nullptr;               // ART_CAST_POOL * kCastCursorWords words, one allocation
+    PoolStream stream;                         // made by the first cast (last of all: it is what says the ring is set up): casts with hip_stream NULL, the queries, and the refit a cast finds pending when the context has no refit streams
+    DevBuf<uint32_t> cursors;                  // ART_CAST_POOL * kCastCursorWords words, one allocation
     CastBlock block[ART_CAST_POOL]; uint32_t next = 0;
     uint64_t casts = 0, rays = 0, host_waits = 0;
     DevBuf<float4> q_rays; DevBuf<uint8_t> q_out;   // art_query_*: the rays and the records of one query at a time on the device; they only grow
 };
 
+// Who owns what: every device buffer, pinned block, event and stream below is a handle (art_own.h) that its destructor releases; raw pointers are views or the caller's.
+// art_destroy waits for every stream of the context and for the casts on callers' streams BEFORE `delete`, so no destructor frees what the GPU still uses.  Members go in reverse
+// order of declaration, and a block is declared before whatever points into it: the arena before the tree that borrows it, the versions' blocks before the versions.
 struct ArtContext {
     ArtConfig cfg{};
     int device = 0;
@@ -178,26 +156,26 @@ struct ArtContext {
     // device scene
     DevBuf<float> d_verts; DevBuf<uint8_t> d_indices; DevBuf<uint32_t> d_tex; DevBuf<DevPrim> d_prims; DevBuf<uint32_t> d_first_tri;
     std::vector<uint32_t> h_first_tri; // first global triangle id of every primitive slot (ascending): gid -> (primitive, triangle) on the host
-    Lbvh bvh{};
     Arena arena;              // the build phases' scratch, kept from build to build (art_internal.h)
+    Lbvh bvh{};
     std::vector<uint8_t> uploaded;   // which primitives' vertices / indices / texels are on the device, at the offsets a build over exactly this set computes (empty: nothing): a
                               // build over the same set -- the rebuild behind the refit's cost rule, a change of tuning -- uploads only the primitive table
     uint32_t T = 0;
     // moving models (art_scene_set_model_matrix): versions of the structure, the primitive table as the next refit will upload it
-    std::vector<AsVersion> as; uint32_t as_cur = 0; bool xform_dirty = false;
-    void *as_block = nullptr, *as_pinned = nullptr;   // ONE device allocation and ONE pinned one behind all the versions (six + three per version before).  versions_ms is something else: the refit streams' creation (a
+    DevBuf<char> as_block; Pinned<char> as_pinned;    // ONE device allocation and ONE pinned one behind all the versions (six + three per version before).  versions_ms is something else: the refit streams' creation (a
                                                       // high-priority hardware queue each: 4-10 ms apiece) and the refit's work lists (host, 9 ms for config 2) -- ArtTuning.log bit 0 prints the parts
     // Refits run on streams of their own, one per ring slot (up to four): the refit in front of frame n of slot k then overlaps frame n - F, which still runs on that slot's
     // stream, instead of queueing behind it -- the slot's chain is frame, frame, frame with the refits beside it, and the frame waits for its refit's event.  (On the frame's
     // own stream a slot's cycle was refit + frame: a model moving every frame cost the ring a third of its depth, profiles/README.md round 4.)
-    hipStream_t refit_stream[4] = {nullptr, nullptr, nullptr, nullptr}; uint32_t n_refit_streams = 0;
+    Stream refit_stream[4]; uint32_t n_refit_streams = 0;
     std::vector<DevPrim> h_dev_prims;          // host copy of d_prims (build order), matrices kept current
     std::vector<uint64_t> prim_moved;          // per primitive: the refit (as_epoch numbering) that first shows its latest move; 0: where the build put it
     std::vector<uint64_t> prim_deformed;       // per primitive: the refit that first shows its latest vertices (art_scene_set_vertices); 0: the build's
     std::vector<int64_t> deform_off;           // per primitive: first vertex of its slot in every version's staging (-1: never deformed since the build)
     size_t deform_verts = 0;                   // vertices of a version's staging (the sum of the deformed primitives' counts)
-    void *shade_block = nullptr;               // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
-    void *stage_block = nullptr, *stage_pinned = nullptr;   // every version's staging of replaced vertices: device, pinned
+    DevBuf<char> shade_block;                  // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
+    DevBuf<char> stage_block; Pinned<char> stage_pinned;    // every version's staging of replaced vertices: device, pinned
+    std::vector<AsVersion> as; uint32_t as_cur = 0; bool xform_dirty = false;   // (views into the five blocks above)
     int64_t masked_tris = 0;                   // triangles of primitives disabled since the build (still in the arrays, written "nowhere")
     // alpha-masked primitives: the cutoffs travel in the versioned primitive table (DevPrim::cutoff), so a change is a refit over no batch, like a
     // primitive that is disabled; alpha_bits marks the leaves whose primitive may have a cutoff (made by the build, bits added in front of the refit that first shows a
@@ -228,10 +206,10 @@ struct ArtContext {
     bool shadow_hints = true;       // ArtTuning.shadow_hints = 1 turns them off: the frames get a null table
     size_t hint_words() const { return (size_t)(n_local / 64u) * kHintLights * 4u; }
     static constexpr int kRing = 128;          // per-frame stage events kept for art_collect_timings
-    hipEvent_t ev[kRing][5] = {};
+    Event ev[kRing][5];
     bool ev_fused[kRing] = {};                 // the frame was one launch: only ev[0] and ev[4] were recorded
     uint64_t frame_no = 0, collected_upto = 0;
-    hipEvent_t mark[2] = {nullptr, nullptr};   // art_timestamp_mark
+    Event mark[2];                             // art_timestamp_mark
     bool traced = false;
     bool force_sample = false; // art_sample_wave_steps: the next fused frame counts its waves' steps whatever the plan's cadence
     bool graph_mode = false; // replay a captured hipGraph per slot instead of 5 launches + 6 event records (host-bound multi-GPU runs)
@@ -243,7 +221,7 @@ struct ArtContext {
     size_t tiles_bytes() const { return (size_t)padded_tiles * kTilePixels * tile_px_bytes(); } // one frame's compact tile buffer
     bool fused_frame() const { return fused && kind_primary == 8 && kind_shadow == 8; } // the frame is one launch of packet walks: no staged records, no counters
     TraceTune trace_tune() const { return TraceTune{tuning.trace_chunk, tuning.trace_refill, tuning.trace_blocks, tuning.trace_leaf_batch}; } // the per-ray tracers' knobs (frames and casts)
-    hipStream_t stream_of(uint32_t k) const { return (ext_stream && F == 1) ? ext_stream : slot[k].own; }
+    hipStream_t stream_of(uint32_t k) const { return (ext_stream && F == 1) ? ext_stream : slot[k].own.p; }
     hipStream_t main_stream() const { return stream_of(0); }
 };
 
@@ -252,14 +230,12 @@ struct AsPtrs { const DevTri *tris; const DevNodeW *widef; const DevNode4 *wide;
 
 namespace art {
 // ---- art_api.hip ----
-hipError_t acquire_stream(int device, hipStream_t *out);   // frame and cast streams come from a pool kept for the life of the process
-void release_stream(int device, hipStream_t s);
 int32_t use_device(ArtContext *c);
 void drop_graphs(ArtContext *c);
 int32_t sync_all(ArtContext *c);                           // every stream of the context, the casts on callers' streams included
 // ---- art_scene.hip ----
 AsPtrs as_ptrs(const ArtContext *c, uint32_t v);
-void as_release(ArtContext *c);
+void as_release(ArtContext *c);                            // the versions go (the caller synchronised); the tree and its work lists stay
 // Launches on `stream` read version v: ordered behind the refit that wrote it, by an event wait while that refit may still run.  own_slot: the ring slot whose stream
 // `stream` is -- a refit recorded on that slot's stream orders the launch by itself -- or ~0u for a stream that no ring slot owns (casts; scene_refresh writes
 // ready_slot the same way).
@@ -282,6 +258,5 @@ void plan_rewind(ArtContext *c);                                         // ring
 int32_t cast_sync(ArtContext *c);                                        // sync_all's part: every cast enqueued so far, on whichever stream, and the cast stream
 int32_t cast_wait_version(ArtContext *c, uint32_t version);              // scene_refresh's part: the casts that still read the version about to be rewritten
 int32_t cast_drain(ArtContext *c);                                       // art_scene_clear's part: outstanding casts read the scene that goes away
-void cast_release(ArtContext *c);                                        // art_destroy's part
 }
 #pragma GCC visibility pop

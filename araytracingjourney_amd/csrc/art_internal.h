@@ -9,6 +9,7 @@
 #include <utility>
 #include "../../include/art.h"
 #include "../../include/art_parity.h"
+#include "art_own.h"
 
 namespace art {
 
@@ -89,22 +90,18 @@ struct BuildInputs {
 // hipMalloc / hipFree their three dozen temporaries one by one -- 40 us apiece with the GPU idle in between: 2.1 of the 6.8 ms a rebuild of config 2 took.
 // A phase reserves what it needs (nothing of an earlier phase is live: every phase ends with a stream synchronisation), then takes its pieces.
 struct Arena {
-    char *base = nullptr; size_t cap = 0, off = 0;
+    DevBuf<char> mem; size_t off = 0;
     uint64_t generation = 0;   // bumped by every reserve(): a pointer taken in an earlier phase is stale (take_checked in sanitizer / debug builds)
     static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     hipError_t reserve(size_t bytes) {
         off = 0; generation++;
-        if (bytes <= cap) return hipSuccess;
-        if (base) (void)hipFree(base);
-        base = nullptr; cap = 0;
-        hipError_t e = hipMalloc(&base, bytes + bytes / 8);   // (some room: the next scene is rarely the same size to the byte)
-        if (e == hipSuccess) cap = bytes + bytes / 8;
-        return e;
+        if (bytes <= mem.n && mem.p) return hipSuccess;
+        return mem.ensure(bytes + bytes / 8);   // (some room: the next scene is rarely the same size to the byte)
     }
-    template <class T> T *take(size_t n) { T *p = reinterpret_cast<T *>(base + off); off += pad(n * sizeof(T)); return p; }   // the caller reserved the sum of pad(...)
-    void release() { if (base) (void)hipFree(base); base = nullptr; cap = 0; off = 0; }
+    template <class T> T *take(size_t n) { T *p = reinterpret_cast<T *>(mem.p + off); off += pad(n * sizeof(T)); return p; }   // the caller reserved the sum of pad(...)
+    void release() { mem.release(); off = 0; }
 };
-struct Lbvh {               // canonical binary LBVH, device arrays
+struct Lbvh {               // canonical binary LBVH, device arrays: it owns the DevBuf members, the plain pointers are views into `block`; `l = Lbvh{}` frees a tree
     Arena *arena = nullptr; // host: the context's scratch for the build phases (not owned; null: a phase allocates and frees its own)
     uint32_t *leaf_gid;     // [T]
     uint64_t *keys;         // [T]
@@ -115,23 +112,24 @@ struct Lbvh {               // canonical binary LBVH, device arrays
     DevNode *nodes;         // [max(T-1,1)]
     uint32_t *tri_prim;     // [T] gid -> primitive
     uint32_t *gid_leaf;     // [T] gid -> position in leaf order, the inverse of leaf_gid (art_resolve_hits: a hit record names its triangle by gid; the shading records are in leaf order)
-    DevNode4 *wide;         // [n_wide] collapsed + quantised traversal structure
-    DevNodeW *widef;        // [n_wide] the same topology with float boxes (packet walk)
+    DevBuf<DevNode4> wide;  // [n_wide] collapsed + quantised traversal structure
+    DevBuf<DevNodeW> widef; // [n_wide] the same topology with float boxes (packet walk)
     uint32_t n_wide;
     bool canon_boxes = false;          // host: node_lo / node_hi of the canonical tree hold its boxes (else: not computed yet, binary_refit does it on demand)
     uint32_t log = 0;                  // host: ArtTuning.log of the context that builds (bit 0: build phase times to stderr)
     std::vector<uint32_t> wide_levels; // host: first wide node of every level of the collapse (breadth-first numbering), then n_wide -- the refit goes through them bottom-up
     DevShadeTri *shade_tris; // [T] leaf order
-    uint32_t *leaf_parent;  // [T] the 4-wide node that holds a leaf, [n_wide] the one that holds a node (root: ~0): made with the first refit (launch_wide_parents), else null
-    uint32_t *node_parent;
+    DevBuf<uint32_t> leaf_parent;  // [T] the 4-wide node that holds a leaf, [n_wide] the one that holds a node (root: ~0): made with the first refit (launch_wide_parents), else null
+    DevBuf<uint32_t> node_parent;
     // the refit's work lists (refit_lists_build, made with the parents): the tree below its top levels is cut into batches of neighbouring subtrees, one workgroup each
-    uint32_t *sub_nodes = nullptr, *sub_leaves = nullptr, *sub_off = nullptr;   // device: batch b's nodes (deepest level first) / leaves; batch nb = the crown above the batches; sub_off: see k_refit_sub
+    DevBuf<uint32_t> sub_nodes, sub_leaves, sub_off;   // device: batch b's nodes (deepest level first) / leaves; batch nb = the crown above the batches; sub_off: see k_refit_sub
     uint32_t sub_batches = 0, sub_levels = 0;                                     // host: batches (without the crown); levels of the tree
     std::vector<uint32_t> batch_prim_off, batch_prim_ids;                         // host: the primitives whose triangles lie in batch b: ids [off[b], off[b + 1]) -- a refit launches the batches that hold a primitive that moved
     int32_t *trav_child;    // [2*(T-1)] topology of the traversal nodes when it is not the canonical one (sah_build), else null
     float *trav_lo, *trav_hi; // [(T-1)*3]
-    char *block = nullptr;  // host: ONE allocation behind the arrays lbvh_build makes (leaf_gid .. shade_tris, cbounds) and room for the traversal tree's three (res_trav_*): two dozen
-                            // hipMalloc per build were 0.6-1 ms inside build_ms; lbvh_free frees the block, never its pieces
+    DevBuf<int32_t> own_trav_child; DevBuf<float> own_trav_lo, own_trav_hi;   // ... when they are allocations of their own (lbvh_claim_trav); empty when trav_* are the room reserved in the block
+    DevBuf<char> block;     // host: ONE allocation behind the arrays lbvh_build makes (leaf_gid .. shade_tris, cbounds) and room for the traversal tree's three (res_trav_*): two dozen
+                            // hipMalloc per build were 0.6-1 ms inside build_ms; the pieces are views into it
     int32_t *res_trav_child = nullptr; float *res_trav_lo = nullptr, *res_trav_hi = nullptr;   // in the block, for whichever builder makes a traversal tree (trav_* stay null until one does)
     uint32_t *cbounds;      // [6] the bounds of the triangle-box centroids the Morton keys were made over, as order-preserving keys (lo xyz, hi xyz): the root domain of the SAH bins
 };
@@ -171,12 +169,11 @@ constexpr uint8_t kTouchRegather = 2u;         // RefitArgs::touched: the primit
 constexpr uint32_t kFoldRequantNodes = 400000;   // trees of this many 4-wide nodes and more: the refit's workgroups make the quantised records and the cost themselves (art_build.hip launch_refit)
 void launch_refit(const RefitArgs &r, hipStream_t s);
 void launch_wide_parents(uint32_t n_wide, const DevNodeW *widef, uint32_t *leaf_parent, uint32_t *node_parent, hipStream_t s);
-hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s);   // after launch_wide_parents (synchronises: a one-off of the scene's first version ring)
+hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s);   // the parents (launch_wide_parents) and the work lists: all of them into l, or on a failure none (synchronises: a one-off of the scene's first version ring)
 void launch_wide_cost(uint32_t n_wide, const DevNodeW *widef, DevNode4 *wide /*null: cost only*/, double *acc, double *result, hipStream_t s);
 hipError_t binary_refit(Lbvh &l, uint32_t T, const DevTri *tris, hipStream_t s);
 struct TraceTune { uint32_t chunk, refill, blocks, leaf_batch; }; // overrides of the persistent per-ray tracer's presets (ArtTuning.trace_chunk / trace_refill / trace_blocks; 0 = the preset): they travel with every launch
-void lbvh_free(Lbvh &l);
-// the traversal tree's arrays: the room lbvh_build reserved for them, else allocations of their own (lbvh_free tells which by the block)
+// the traversal tree's arrays: the room lbvh_build reserved for them, else allocations of their own (Lbvh::own_trav_*)
 hipError_t lbvh_claim_trav(Lbvh &l, uint32_t NI);
 
 // float32 -> unsigned small float (5 exponent bits, MB mantissa bits), round to nearest even; negatives -> 0, overflow -> +Inf

@@ -77,15 +77,15 @@ struct ArtMgpu {
     uint32_t F = 1, B = 1, GB = 1, NBUF = 4, G = 1;   // ring slots, frames per launch, launches per gather, tile buffers per slot, shards of the frame
     bool renders = true, root = false;                 // root: this rank assembles frames (rank 0; every rank with spread roots)
     bool spread = false; uint32_t nf_cap = 0;          // ART_MGPU_ROOT_SPREAD; frames of one group a rank can be the root of
-    char *stage = nullptr;                             // spread roots over the host exchange: one frame's tiles of every rank, as the hook leaves them
+    DevBuf<char> stage;                                // spread roots over the host exchange: one frame's tiles of every rank, as the hook leaves them
     size_t slot_bytes = 0, frame_bytes = 0;            // compact tiles of one launch (B frames); one assembled frame
-    char *tiles = nullptr;                             // [NBUF][F][slot_bytes]
-    char *gathered = nullptr;                          // a root: [world][GB][slot_bytes] (spread: [world][nf_cap][one frame's tiles]), one group at a time
-    char *frames = nullptr;                            // a root: [GB * B][frame_bytes] (spread: [nf_cap]), the group un-tiled last
-    hipStream_t xs = nullptr;                          // the exchange: gathers + un-tiles, in submission order
+    DevBuf<char> tiles;                                // [NBUF][F][slot_bytes]
+    DevBuf<char> gathered;                             // a root: [world][GB][slot_bytes] (spread: [world][nf_cap][one frame's tiles]), one group at a time
+    DevBuf<char> frames;                               // a root: [GB * B][frame_bytes] (spread: [nf_cap]), the group un-tiled last
+    Stream xs;                                         // the exchange: gathers + un-tiles, in submission order
     SlotState state[kTileRingMax][kMaxFrameSlots] = {};
     uint32_t ev_of[kTileRingMax][kMaxFrameSlots] = {};
-    std::vector<hipEvent_t> events; uint32_t next_event = 0; // one per exchange, shared by the group's slots; reused long after every slot of it was re-assigned
+    std::vector<Event> events; uint32_t next_event = 0; // one per exchange, shared by the group's slots; reused long after every slot of it was re-assigned
     std::deque<Group> fifo;                            // groups whose frames may still be running
     uint64_t traced = 0, gathers = 0;                  // launches traced through this object; exchanges submitted
     uint32_t pend_k0 = 0, pend_n = 0;
@@ -117,7 +117,7 @@ int32_t run_exchange_spread(ArtMgpu *m, const Group &g, const char *send) {
             if (q == r) for (uint32_t p = 0; p < W && rc == 0; p++) rc = rccl().Recv(m->gathered + ((size_t)p * m->nf_cap + mine) * ftb, ftb, kNcclUint8, (int)p, m->comm, m->xs);
             if (rc != 0) break;
         } else {
-            int32_t hr = m->cfg.exchange(m->cfg.exchange_user, send + (size_t)j * ftb, ftb, q == r ? m->stage : nullptr, q, m->xs);
+            int32_t hr = m->cfg.exchange(m->cfg.exchange_user, send + (size_t)j * ftb, ftb, q == r ? m->stage.p : nullptr, q, m->xs);
             if (hr != 0) return mg_fail(ART_E_HIP, "art_mgpu: the host exchange function failed (" + std::to_string(hr) + ")");
             if (q == r) { // the hook leaves [rank][ftb]; the un-tile wants a rank's frames of the group back to back
                 MGH(hipMemcpy2DAsync(m->gathered + (size_t)mine * ftb, (size_t)m->nf_cap * ftb, m->stage, ftb, ftb, W, hipMemcpyDeviceToDevice, m->xs));
@@ -143,11 +143,11 @@ int32_t run_exchange(ArtMgpu *m, const Group &g) {
     const size_t bytes = (size_t)g.n * m->slot_bytes;
     if (m->spread) MGA(run_exchange_spread(m, g, send));
     else if (m->cfg.transport == ART_MGPU_RCCL) {
-        int rc = rccl().Gather(send, m->root ? m->gathered : nullptr, bytes, kNcclUint8, 0, m->comm, m->xs);
+        int rc = rccl().Gather(send, m->root ? m->gathered.p : nullptr, bytes, kNcclUint8, 0, m->comm, m->xs);
         if (rc != 0) return mg_fail(ART_E_HIP, std::string("ncclGather: ") + rccl().GetErrorString(rc));
     } else {
         if (m->root) MGH(hipStreamSynchronize(m->xs)); // the un-tile of the previous group may still read `gathered`, and a hook need not order its writes behind xs (a blocking copy on the null stream does not)
-        int32_t rc = m->cfg.exchange(m->cfg.exchange_user, send, bytes, m->root ? m->gathered : nullptr, 0u, m->xs);
+        int32_t rc = m->cfg.exchange(m->cfg.exchange_user, send, bytes, m->root ? m->gathered.p : nullptr, 0u, m->xs);
         if (rc != 0) return mg_fail(ART_E_HIP, "art_mgpu: the host exchange function failed (" + std::to_string(rc) + ")");
     }
     if (m->root && !m->spread) { // rank r's block holds the group's launches back to back: a frame's shards are n * B * padded tiles apart; with a dedicated compositor shard s came from rank s + 1
@@ -230,10 +230,7 @@ int32_t art_mgpu_destroy(ArtMgpu *m) {
     if (!m) return ART_OK;
     if (m->ctx) { (void)art_sync(m->ctx); for (uint32_t k = 0; k < m->F; k++) (void)art_bind_color_tiles(m->ctx, k, nullptr, 0); }
     if (m->xs) (void)hipStreamSynchronize(m->xs);
-    if (m->comm) (void)rccl().CommDestroy(m->comm);
-    for (hipEvent_t e : m->events) (void)hipEventDestroy(e);
-    if (m->xs) (void)hipStreamDestroy(m->xs);
-    (void)hipFree(m->tiles); (void)hipFree(m->gathered); (void)hipFree(m->frames); (void)hipFree(m->stage);
+    if (m->comm) (void)rccl().CommDestroy(m->comm);   // the communicator first: its explicit teardown; then the members, in reverse order of declaration -- events, stream, buffers
     delete m;
     return ART_OK;
 }
@@ -267,16 +264,16 @@ int32_t art_mgpu_create(ArtContext *ctx, const ArtMgpuConfig *cfg, const uint8_t
     m->renders = !(cfg->compositor == ART_MGPU_DEDICATED && cfg->rank == 0);
     m->slot_bytes = (size_t)m->B * m->lay.tiles_padded * m->lay.tile_bytes;
     m->frame_bytes = (size_t)m->lay.width * m->lay.height * (m->lay.tile_bytes == 4u * kTilePixels ? 4u : 16u);   // the assembled frame: B10G11R11 words, or RGBA32F (the tiles carry RGB; alpha is the constant 1)
-    hipError_t e = hipMalloc(&m->tiles, (size_t)m->NBUF * m->F * m->slot_bytes);
+    hipError_t e = m->tiles.ensure((size_t)m->NBUF * m->F * m->slot_bytes);
     if (e == hipSuccess) e = hipMemset(m->tiles, 0, (size_t)m->NBUF * m->F * m->slot_bytes);
     const size_t n_frames_kept = m->spread ? m->nf_cap : (size_t)m->GB * m->B;
-    if (e == hipSuccess && m->root) e = hipMalloc(&m->gathered, m->spread ? (size_t)cfg->world * m->nf_cap * (m->slot_bytes / m->B) : (size_t)cfg->world * m->GB * m->slot_bytes);
-    if (e == hipSuccess && m->root) e = hipMalloc(&m->frames, n_frames_kept * m->frame_bytes);
+    if (e == hipSuccess && m->root) e = m->gathered.ensure(m->spread ? (size_t)cfg->world * m->nf_cap * (m->slot_bytes / m->B) : (size_t)cfg->world * m->GB * m->slot_bytes);
+    if (e == hipSuccess && m->root) e = m->frames.ensure(n_frames_kept * m->frame_bytes);
     if (e == hipSuccess && m->root) e = hipMemset(m->frames, 0, n_frames_kept * m->frame_bytes);
-    if (e == hipSuccess && m->spread && cfg->transport == ART_MGPU_HOST_EXCHANGE) e = hipMalloc(&m->stage, (size_t)cfg->world * (m->slot_bytes / m->B));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->xs, hipStreamNonBlocking);
-    m->events.assign((size_t)m->NBUF * m->F + 8, nullptr);
-    for (size_t i = 0; i < m->events.size() && e == hipSuccess; i++) e = hipEventCreateWithFlags(&m->events[i], hipEventDisableTiming);
+    if (e == hipSuccess && m->spread && cfg->transport == ART_MGPU_HOST_EXCHANGE) e = m->stage.ensure((size_t)cfg->world * (m->slot_bytes / m->B));
+    if (e == hipSuccess) e = m->xs.create();
+    m->events.resize((size_t)m->NBUF * m->F + 8);
+    for (size_t i = 0; i < m->events.size() && e == hipSuccess; i++) e = m->events[i].create(hipEventDisableTiming);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return bail(mg_fail(ART_E_HIP, std::string("art_mgpu_create: ") + hipGetErrorString(e)));
     if (cfg->transport == ART_MGPU_RCCL) {

@@ -40,10 +40,10 @@ int32_t art::plan_reset(ArtContext *c, const std::vector<uint32_t> &order) {
     P.n_items[0] = (uint32_t)first.size(); P.cur = 0; P.split1 = P.split2 = 0;
     HIPC(P.d_level.ensure(n64 ? n64 : 1)); HIPC(P.d_level_tmp.ensure(n64 ? n64 : 1)); HIPC(P.d_worst.ensure(n64 ? n64 : 1));
     HIPC(hipMemset(P.d_level.p, 0, n64 ? n64 : 1)); HIPC(hipMemset(P.d_worst.p, 0, (size_t)(n64 ? n64 : 1) * 4));
-    if (!P.h_result) { HIPC(hipHostMalloc((void **)&P.h_result, 32, hipHostMallocDefault)); HIPC(hipHostGetDevicePointer((void **)&P.dh_result, P.h_result, 0)); }
-    std::memset(P.h_result, 0, 32);
-    if (!P.cost_ready) HIPC(hipEventCreateWithFlags(&P.cost_ready, hipEventDisableTiming));
-    if (!P.plan_stream) { int lo = 0, hi = 0; HIPC(hipDeviceGetStreamPriorityRange(&lo, &hi)); HIPC(hipStreamCreateWithPriority(&P.plan_stream, hipStreamNonBlocking, lo)); }   // (the least urgent: nothing waits for it)
+    HIPC(P.result.ensure(8));
+    std::memset(P.result.p, 0, 32);
+    HIPC(P.cost_ready.create(hipEventDisableTiming));
+    if (!P.plan_stream) { int lo = 0, hi = 0; HIPC(hipDeviceGetStreamPriorityRange(&lo, &hi)); HIPC(P.plan_stream.create(lo)); }   // (the least urgent: nothing waits for it)
     else HIPC(hipStreamSynchronize(P.plan_stream));
     P.pending = false; P.next_sample = c->frame_no; P.interval = 1; P.replans = 0; P.last_sample = c->frame_no;
     return ART_OK;
@@ -73,7 +73,7 @@ int32_t art::plan_launch(ArtContext *c, const FrameArgs &a, hipEvent_t frame_don
     pa.items_out = P.d_items[P.cur ^ 1].p; pa.cap = P.cap;
     constexpr float kWaveSlots = 256.0f * 32.0f; // CUs x waves per CU
     pa.share = P.alpha * (float)c->B * (float)P.in_flight / kWaveSlots;   // (the counts are one frame's; a launch traces B frames)
-    pa.min_steps = P.min_steps; pa.fixed_steps = P.fixed_steps; pa.result = P.dh_result;
+    pa.min_steps = P.min_steps; pa.fixed_steps = P.fixed_steps; pa.result = P.result.d;
     launch_plan(pa, s);
     HIPC(hipEventRecord(P.cost_ready, s));
     P.pending = true; P.pending_table = P.cur; P.last_sample = c->frame_no;
@@ -98,12 +98,12 @@ int32_t art::plan_poll(ArtContext *c) {
     WavePlan &P = c->plan;
     if (!P.pending || hipEventQuery(P.cost_ready) != hipSuccess) return ART_OK;
     P.pending = false;
-    const uint32_t *res = P.h_result;
+    const uint32_t *res = P.result.p;
     const int verbose = (c->tuning.log & 4u) ? 2 : ((c->tuning.log & 2u) ? 1 : 0);
     if (verbose > 1) std::fprintf(stderr, "[art] plan poll at frame %llu: table %d sampled, %s, slowest wave %u steps, target %u, interval %u\n", (unsigned long long)c->frame_no, P.pending_table, res[1] ? "a new table" : "the table stays", res[5], res[4], P.interval);
     if (res[1]) {
         for (uint32_t k = 0; k < c->F; k++) {
-            if (!P.retire[P.cur][k]) HIPC(hipEventCreateWithFlags(&P.retire[P.cur][k], hipEventDisableTiming));
+            HIPC(P.retire[P.cur][k].create(hipEventDisableTiming));
             HIPC(hipEventRecord(P.retire[P.cur][k], c->stream_of(k)));
         }
         P.retire_set[P.cur] = true;

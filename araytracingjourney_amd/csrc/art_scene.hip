@@ -24,14 +24,13 @@ static void affine_inverse(const float *m, float *o) { // row-major 3x4
 int32_t art::ensure_wide(ArtContext *c, bool needed) {
     if (!needed || c->bvh.wide) return ART_OK;
     int32_t r = sync_all(c); if (r) return r;
-    hipEvent_t e0, e1; float ms = 0;
-    HIPC(hipEventCreate(&e0)); HIPC(hipEventCreate(&e1));
+    Event e0, e1; float ms = 0;
+    HIPC(e0.create()); HIPC(e1.create());
     HIPC(hipEventRecord(e0, c->main_stream()));
     hipError_t e = wide_build(c->bvh, c->T, c->main_stream(), c->wide_on_host);
     if (e == hipSuccess) e = hipEventRecord(e1, c->main_stream());
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (e != hipSuccess) return hipfail(e, "wide_build");
     c->stats.build_ms += ms;
     return ART_OK;
@@ -52,16 +51,9 @@ AsPtrs art::as_ptrs(const ArtContext *c, uint32_t v) {
 static uint64_t as_epoch_of(const ArtContext *c, uint32_t v) { return c->as.empty() ? 0 : c->as[v].epoch; }
 // everything that reads them has finished (the caller synchronised)
 void art::as_release(ArtContext *c) {
-    for (AsVersion &V : c->as) {
-        if (V.ready) (void)hipEventDestroy(V.ready);
-    }
-    (void)hipFree(c->as_block); c->as_block = nullptr;                         // every version's device arrays
-    if (c->as_pinned) (void)hipHostFree(c->as_pinned); c->as_pinned = nullptr; // every version's staging memory
-    if (c->shade_block) (void)hipFree(c->shade_block); c->shade_block = nullptr;           // the versions' shading records
-    if (c->stage_block) (void)hipFree(c->stage_block); c->stage_block = nullptr;           // the staging of replaced vertices
-    if (c->stage_pinned) (void)hipHostFree(c->stage_pinned); c->stage_pinned = nullptr;
+    c->as.clear(); c->as_cur = 0;   // (their events) -- then the blocks they pointed into: device arrays, staging memory, shading records, staging of replaced vertices
+    c->as_block.release(); c->as_pinned.release(); c->shade_block.release(); c->stage_block.release(); c->stage_pinned.release();
     c->deform_verts = 0; std::fill(c->deform_off.begin(), c->deform_off.end(), (int64_t)-1);
-    c->as.clear(); c->as_cur = 0;
 }
 // the first move of a built scene: the ring of versions (ArtTuning.as_versions; default 4: one more than the reference's frames in flight, renderer.rs:135 -- measured on
 // config 2 with a model of 164 k triangles moving every frame, 16 ring slots: 0.70 / 0.38 / 0.28 / 0.25 / 0.26 ms per frame with 1 / 2 / 3 / 4 / 8 versions), every one a copy of
@@ -77,7 +69,7 @@ static int32_t as_create(ArtContext *c) {
     //  arrays once more: 42 MB for config 2, 450 MB for config 4.)
     const uint32_t K = c->tuning.as_versions ? std::min(c->tuning.as_versions, kMaxAsVersions) : std::min(std::max(2u * c->F, 4u), kMaxAsVersions);
     const size_t np = c->h_dev_prims.size(), T = c->T, NW = c->bvh.n_wide;
-    c->as.assign(K, AsVersion{});
+    c->as.clear(); c->as.resize(K);
     hipStream_t s = c->main_stream();
     double t_sec[6] = {0, 0, 0, 0, 0, 0};
     auto lap = [&, last = std::chrono::steady_clock::now()](int i) mutable { const auto n = std::chrono::steady_clock::now(); t_sec[i] += std::chrono::duration<double, std::milli>(n - last).count(); last = n; };
@@ -85,15 +77,12 @@ static int32_t as_create(ArtContext *c) {
         const uint32_t want = c->tuning.refit_streams == 0xFFFFFFFFu ? 0u : (c->tuning.refit_streams ? std::min(c->tuning.refit_streams, 4u) : std::min(c->F, 4u));
         while (c->n_refit_streams < want) {   // (kept for the life of the context)
             int lo = 0, hi = 0; HIPC(hipDeviceGetStreamPriorityRange(&lo, &hi));   // hi: the numerically smallest = the most urgent: a refit is a handful of small launches a whole frame waits for
-            HIPC(hipStreamCreateWithPriority(&c->refit_stream[c->n_refit_streams], hipStreamNonBlocking, hi)); c->n_refit_streams++;
+            HIPC(c->refit_stream[c->n_refit_streams].create(hi)); c->n_refit_streams++;
         }
-        while (c->n_refit_streams > want) { c->n_refit_streams--; (void)hipStreamSynchronize(c->refit_stream[c->n_refit_streams]); (void)hipStreamDestroy(c->refit_stream[c->n_refit_streams]); c->refit_stream[c->n_refit_streams] = nullptr; }
+        while (c->n_refit_streams > want) c->refit_stream[--c->n_refit_streams].release();   // (waits for it first)
         lap(0);
-        if (!c->bvh.leaf_parent) { // who holds whom in the 4-wide tree: the marks of a refit go up along it
-            HIPC(hipMalloc(&c->bvh.leaf_parent, T * 4)); HIPC(hipMalloc(&c->bvh.node_parent, NW * 4));
-            launch_wide_parents(c->bvh.n_wide, c->bvh.widef, c->bvh.leaf_parent, c->bvh.node_parent, s);
-            HIPC(hipGetLastError());
-            hipError_t e = refit_lists_build(c->bvh, c->T, s);   // the refit's work lists (a workgroup per batch of subtrees)
+        if (!c->bvh.sub_off) { // the parents in the 4-wide tree and the refit's work lists (a workgroup per batch of subtrees): all there or none (refit_lists_build)
+            hipError_t e = refit_lists_build(c->bvh, c->T, s);
             if (e != hipSuccess) return hipfail(e, "refit_lists_build");
         }
         lap(1);
@@ -102,11 +91,10 @@ static int32_t as_create(ArtContext *c) {
         const size_t nbat = c->bvh.sub_batches ? c->bvh.sub_batches : 1;
         const size_t dev_owned = pad(T * sizeof(DevTri)) + pad(NW * sizeof(DevNodeW)) + pad(NW * sizeof(DevNode4)) + pad(np * sizeof(DevPrim)), dev_every = pad(NW * 4) + pad(32) + pad(nbat * 8);
         const size_t pin_every = pad(np * sizeof(DevPrim)) + pad(np) + pad(32) + pad(nbat * 4);
-        HIPC(hipMalloc(&c->as_block, (K - 1) * dev_owned + K * dev_every));
-        HIPC(hipHostMalloc(&c->as_pinned, K * pin_every, hipHostMallocDefault));
+        HIPC(c->as_block.ensure((K - 1) * dev_owned + K * dev_every));
+        HIPC(c->as_pinned.ensure(K * pin_every));
         lap(2);
-        char *dp = (char *)c->as_block, *hp = (char *)c->as_pinned, *dhp = nullptr;
-        HIPC(hipHostGetDevicePointer((void **)&dhp, c->as_pinned, 0));
+        char *dp = c->as_block.p, *hp = c->as_pinned.p, *dhp = c->as_pinned.d;
         auto carve = [&](char *&p, size_t n) { char *q = p; p += pad(n); return q; };
         for (uint32_t v = 0; v < K; v++) { // (everything on the context's first stream, asynchronously: one wait at the end)
             AsVersion &V = c->as[v];
@@ -120,11 +108,11 @@ static int32_t as_create(ArtContext *c) {
             }
             V.mark = (uint32_t *)carve(dp, NW * 4); V.acc = (double *)carve(dp, 32); V.batch_cost = (double *)carve(dp, nbat * 8);
             HIPC(hipMemsetAsync(V.mark, 0, NW * 4, s)); HIPC(hipMemsetAsync(V.acc, 0, 32, s));
-            const size_t off = (size_t)(hp - (char *)c->as_pinned);
+            const size_t off = (size_t)(hp - c->as_pinned.p);
             V.h_prims = (DevPrim *)carve(hp, np * sizeof(DevPrim)); V.h_touched = (uint8_t *)carve(hp, np); V.h_result = (double *)carve(hp, 32);
             V.dh_prims = (DevPrim *)(dhp + off); V.dh_touched = (uint8_t *)(dhp + off + pad(np * sizeof(DevPrim))); V.dh_result = (double *)(dhp + off + pad(np * sizeof(DevPrim)) + pad(np));
             V.h_dirty = (uint32_t *)carve(hp, nbat * 4); V.dh_dirty = (uint32_t *)(dhp + off + pad(np * sizeof(DevPrim)) + pad(np) + pad(32));
-            HIPC(hipEventCreateWithFlags(&V.ready, hipEventDisableTiming));
+            HIPC(V.ready.create(hipEventDisableTiming));
         }
         lap(3);
         AsVersion &V0 = c->as[0];
@@ -417,26 +405,24 @@ static int32_t deform_prepare(ArtContext *c, uint32_t id) {
     auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
     if (need_shade) {   // versions 1 .. K-1: copies of the build's records (nothing has written any version's yet); version 0 keeps aliasing them
         const size_t each = pad((size_t)c->T * sizeof(DevShadeTri));
-        void *blk = nullptr;
-        hipError_t e = hipMalloc(&blk, (K - 1) * each);
+        DevBuf<char> blk;   // (the context takes it once the copies are in it)
+        hipError_t e = blk.ensure((K - 1) * each);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(ART_E_NOMEM, std::string("art_scene_set_vertices: the versions' shading records: ") + hipGetErrorString(e)); }
         hipStream_t s = c->main_stream();
-        for (uint32_t v = 1; v < K && e == hipSuccess; v++) e = hipMemcpyAsync((char *)blk + (v - 1) * each, c->bvh.shade_tris, (size_t)c->T * sizeof(DevShadeTri), hipMemcpyDeviceToDevice, s);
+        for (uint32_t v = 1; v < K && e == hipSuccess; v++) e = hipMemcpyAsync(blk.p + (v - 1) * each, c->bvh.shade_tris, (size_t)c->T * sizeof(DevShadeTri), hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { (void)hipFree(blk); return hipfail(e, "art_scene_set_vertices: copies of the shading records"); }
-        c->shade_block = blk;
-        for (uint32_t v = 1; v < K; v++) c->as[v].shade = (DevShadeTri *)((char *)blk + (v - 1) * each);
+        if (e != hipSuccess) return hipfail(e, "art_scene_set_vertices: copies of the shading records");
+        c->shade_block = std::move(blk);
+        for (uint32_t v = 1; v < K; v++) c->as[v].shade = (DevShadeTri *)(c->shade_block.p + (v - 1) * each);
     }
     if (need_stage) {   // a larger staging for every version; what the old one held is not needed (a refit writes a version's staging in full for what it regathers)
         const size_t nv = c->deform_verts + c->prims[id].verts.size(), each = pad(nv * sizeof(ArtVertex));
-        void *dblk = nullptr, *hblk = nullptr;
-        hipError_t e = hipMalloc(&dblk, K * each);
-        if (e == hipSuccess) { e = hipHostMalloc(&hblk, K * each, hipHostMallocDefault); if (e != hipSuccess) { (void)hipFree(dblk); dblk = nullptr; } }
+        DevBuf<char> dblk; Pinned<char> hblk;   // (both or neither: the context keeps the old ones until then)
+        hipError_t e = dblk.ensure(K * each);
+        if (e == hipSuccess) e = hblk.ensure(K * each);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(ART_E_NOMEM, std::string("art_scene_set_vertices: staging of the vertices: ") + hipGetErrorString(e)); }
-        if (c->stage_block) (void)hipFree(c->stage_block);
-        if (c->stage_pinned) (void)hipHostFree(c->stage_pinned);
-        c->stage_block = dblk; c->stage_pinned = hblk;
-        for (uint32_t v = 0; v < K; v++) { c->as[v].d_stage = (float *)((char *)dblk + v * each); c->as[v].h_stage = (ArtVertex *)((char *)hblk + v * each); }
+        c->stage_block = std::move(dblk); c->stage_pinned = std::move(hblk);
+        for (uint32_t v = 0; v < K; v++) { c->as[v].d_stage = (float *)(c->stage_block.p + v * each); c->as[v].h_stage = (ArtVertex *)(c->stage_pinned.p + v * each); }
         c->deform_off[id] = (int64_t)c->deform_verts; c->deform_verts = nv;
     }
     return ART_OK;
@@ -471,7 +457,7 @@ int32_t art_scene_build(ArtContext *c) {
     int32_t r = use_device(c); if (r) return r;
     r = sync_all(c); if (r) return r;
     as_release(c); c->xform_dirty = false; c->as_epoch = 0; c->binary_epoch = 0; c->refit_cost_ratio = 1.0f; // the versions were copies of the tree that goes away
-    lbvh_free(c->bvh); c->bvh.arena = &c->arena; c->built = false; drop_graphs(c);
+    c->bvh = Lbvh{}; c->bvh.arena = &c->arena; c->built = false; drop_graphs(c);
     // Only enabled primitives are uploaded and instanced (get_acceleration_structure_instance returns None unless the model is in
     // the Device state, vk_model.rs:360-372).  Ids keep their meaning: a disabled primitive stays in the table with zero triangles.
     // With nothing enabled the tree is one zero-area triangle that no ray can hit (an empty TLAS: every ray misses).
@@ -528,28 +514,27 @@ int32_t art_scene_build(ArtContext *c) {
     c->prim_moved.assign(dp.size(), 0); c->prim_deformed.assign(dp.size(), 0); c->deform_off.assign(dp.size(), -1);
     c->T = T;
     BuildInputs in{c->d_prims.p, (uint32_t)dp.size(), c->d_first_tri.p, T, c->cfg.morton_bits};
-    hipEvent_t e0, e1;
-    HIPC(hipEventCreate(&e0)); HIPC(hipEventCreate(&e1));
+    Event e0, e1;
+    HIPC(e0.create()); HIPC(e1.create());
     HIPC(hipEventRecord(e0, c->main_stream()));
     const bool own_tree = c->fast_trace && T >= 3;   // a PREFER_FAST_TRACE build makes its own tree over the leaves: the canonical tree's boxes are computed only when asked for (art_get_lbvh)
     hipError_t e = lbvh_build(in, c->bvh, c->main_stream(), !own_tree);
     c->bvh.log = c->tuning.log;
-    if (e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return hipfail(e, "lbvh_build"); }
+    if (e != hipSuccess) return hipfail(e, "lbvh_build");
     if (c->fast_trace) { // PREFER_FAST_TRACE (vk_model.rs:968): the traversal nodes get a SAH-driven topology over the same leaves
         bool done = false;
         if (c->tree_builder == 3) { // the binned SAH on the device
             e = sah_build_device(c->bvh, T, c->main_stream());
-            if (e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return hipfail(e, "sah_build_device"); }
+            if (e != hipSuccess) return hipfail(e, "sah_build_device");
             done = true;
         }
         if (!done) {
             e = sah_build(c->bvh, T, c->main_stream());
-            if (e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return hipfail(e, "sah_build"); }
+            if (e != hipSuccess) return hipfail(e, "sah_build");
         }
     }
     HIPC(hipEventRecord(e1, c->main_stream())); HIPC(hipEventSynchronize(e1));
     float ms = 0; HIPC(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     c->stats.build_ms = ms; c->stats.num_triangles = T; c->stats.num_primitives = (uint32_t)dp.size(); c->stats.num_nodes = c->kind_primary == 4 ? c->bvh.n_wide : (T > 1 ? T - 1 : 1);
     {   // the leaf bits of the alpha test, from zero (on the first stream, then waited for: the frames run on every ring slot's stream)
         const size_t nw = ((size_t)T + 31) / 32;

@@ -670,6 +670,14 @@ class Renderer:
         check(self._L.art_parity_radiance_sweep(self._ctx, which, first_bits, count, stride, numerator, C.byref(ulps), C.byref(worst), C.byref(bad), C.byref(first)))
         return dict(max_ulps=ulps.value, worst_bits=worst.value if ulps.value else None, class_mismatches=bad.value, first_class_bits=first.value if bad.value else None)
 
+    @staticmethod
+    def live_resources():
+        """art_parity_live_resources: what libart holds in this process right now -> dict(device, pinned, events, streams (in use by contexts and MultiGpu objects),
+        pooled (streams parked for the next context)).  A context that was closed has given back everything but its pooled streams."""
+        out = (C.c_uint64 * 5)()
+        check(_lib.load().art_parity_live_resources(out))
+        return dict(zip(("device", "pinned", "events", "streams", "pooled"), (int(v) for v in out)))
+
     def set_ray_masks(self, primary=0xFF, shadow=0xFF, ao=0xFF):
         """the cull masks of the rays trace() (primary, shadow) and trace_ao() (ao) cast (Vulkan: traceRayEXT's cullMask; the reference hard-codes 0xFF,
         raytrace.rgen.glsl:92,169): a ray sees a primitive iff its mask (Model.set_mask) shares a bit with the ray's.  Per-launch state like the camera: a

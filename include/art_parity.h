@@ -145,6 +145,9 @@ int32_t art_collect_timings(ArtContext *ctx, float sums_ms[5], uint32_t *n_frame
  * items[2*i] = 8x8 pixel block (local pixel id / 64), items[2*i+1] = mask over its sixteen 2x2 cells (0: an idle wave), steps[i] = packet steps
  * (nodes + triangles visited, all walks of the wave).  *n = waves of the launch; at most cap are copied.  (tools/step_hist.py) */
 int32_t art_sample_wave_steps(ArtContext *ctx, uint32_t *items, uint32_t *steps, uint32_t cap, uint32_t *n);
+/* what libart holds in this process right now: out[0] device allocations, [1] pinned allocations, [2] events,
+ * [3] streams in use by contexts and ArtMgpu objects, [4] streams parked in the process-wide pool.  No context needed; never fails with out non-NULL. */
+int32_t art_parity_live_resources(uint64_t out[5]);
 
 
 /* groups of launches of an ArtMgpu whose exchange has not been submitted yet (their frames may still run) and launches of the group that is still open.
