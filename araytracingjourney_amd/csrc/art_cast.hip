@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi; DESIGN.md 3.5 .. 3.10) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes; DESIGN.md 3.5 .. 3.11) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
 // entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -206,6 +206,33 @@ int32_t art_closest_points_multi(ArtContext *c, const ArtPointQueryMulti *d) {
     a.points = (const float4 *)d->points_dev; a.point = (float4 *)d->point_dev; a.max_hits = d->max_hits; a.count = (uint8_t *)d->count_dev;
     a.gid_leaf = c->bvh.gid_leaf;   // (after query_begin: a rebuild the cost rule started made the table anew)
     launch_closest_multi(a, q.stream);
+    return cast_commit(c, q, 0);
+}
+
+// ---- the triangles that touch a box (include/art.h: art_overlap_boxes) ---------------------------------------------------------------------------------
+// art_closest_points' path with boxes for points: a block of the ring, counted as no cast.  Which outputs a kind has is checked here; the rest is the family's.
+int32_t art_overlap_boxes(ArtContext *c, const ArtBoxQuery *d) {
+    const char *who = "art_overlap_boxes"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
+    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
+    if (d->kind != ART_OVERLAP_ANY && d->kind != ART_OVERLAP_LIST) return invalid(who, "kind: ART_OVERLAP_ANY or ART_OVERLAP_LIST");
+    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "boxes_dev", d->boxes_dev, 16, d->n))) return r;
+    const bool any = d->kind == ART_OVERLAP_ANY;
+    if (any) {
+        if (d->ids_dev || d->count_dev) return invalid(who, "ids_dev / count_dev: must be NULL for ART_OVERLAP_ANY");
+        if (d->max_hits != 0u) return invalid(who, "max_hits: must be 0 for ART_OVERLAP_ANY");
+        if ((r = check_buffer(who, "hit_dev", d->hit_dev, 1, d->n))) return r;
+    } else {
+        if (d->hit_dev) return invalid(who, "hit_dev: must be NULL for ART_OVERLAP_LIST");
+        if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
+        if ((r = check_buffer(who, "ids_dev", d->ids_dev, 8, d->n)) || (r = check_buffer(who, "count_dev", d->count_dev, 4, d->n, true))) return r;
+    }
+    if (!c->built) return fail(ART_E_STATE, "art_overlap_boxes: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    OverlapArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, nullptr, d->ids_dev, a, &q); if (r) return r;
+    a.boxes = (const float4 *)d->boxes_dev; a.any = any; a.hit = (uint8_t *)d->hit_dev; a.count = (uint32_t *)d->count_dev; a.max_hits = d->max_hits;
+    launch_overlap(a, q.stream);
     return cast_commit(c, q, 0);
 }
 

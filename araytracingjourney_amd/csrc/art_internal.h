@@ -315,6 +315,10 @@ void launch_closest(const ClosestArgs &c, hipStream_t s);
 // gid_leaf: the structure's gid -> leaf table (Lbvh::gid_leaf), which a record's point is found through
 struct ClosestMultiArgs : ClosestArgs { uint32_t max_hits; uint8_t *count; const uint32_t *gid_leaf; };
 void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s);
+// The triangles that touch a box (art_overlap_boxes): boxes[2i] = lo.xyz,- | boxes[2i+1] = hi.xyz,-.  any: hit[i] = 0 | 1 and nothing else; otherwise ids
+// hold max_hits records a box, box-major ((-1,-1) behind the candidates), and count (optional) every candidate of the box, uncapped.  tuv is not used
+struct OverlapArgs : QueryArgs { const float4 *boxes; bool any; uint8_t *hit; uint32_t *count; uint32_t max_hits; };
+void launch_overlap(const OverlapArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
 struct ResolveArgs {

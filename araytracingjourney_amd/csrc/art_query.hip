@@ -1,5 +1,5 @@
 // art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest), the K nearest
-// triangles (k_closest_multi) and swept spheres (k_sweep).  The casts and the sweep are Sources and candidate policies of art_walk.h's pooled loop; the two point queries have
+// triangles (k_closest_multi), swept spheres (k_sweep) and the triangles that touch a box (k_overlap, whose loop is k_closest's in a third text).  The casts and the sweep are Sources and candidate policies of art_walk.h's pooled loop; the two point queries have
 // a loop of their own, in two texts.  What the queries share stands once: at the top the ray read, the hit and miss records, the contact point and the mask test; the sorted
 // list of both K-walks (KList), which a walk fills through its leaf step's hook for a candidate's fate (step_leaf_take: one leaf step a walk); at the bottom the arguments'
 // common fields and the launch.  (The list and the leaf steps were copies once, kept apart so that no other kernel's code would move.  Compared instruction for instruction --
@@ -552,6 +552,193 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
     pooled_trace<kCastLds, false, FILTER, SweepK, SweepSource, TravSweep<kCastLds, FILTER>>(a, SweepSource{a});
 }
 
+// ---- the triangles that touch a box (art_overlap_boxes) -----------------------------------------------------------------------------------------------
+// A query is a closed world-axis box lo.xyz, - | hi.xyz, -: two 16-byte loads a lane, nothing a pool would save, so the loop is k_closest's (pop_chunk, the idle lanes of a
+// wave read the next queries of its chunk, pooled_trace's step block).  Nothing orders or shrinks: a child is skipped iff its decoded box misses the query box by comparison
+// or is inverted (absent, masked), and the stack holds references alone -- eight a lane in LDS, deeper ones in scratch.  ANY ends at the first candidate; LIST visits every
+// leaf whose box meets the query, counts every candidate and keeps the KMAX smallest gids in ascending order in LDS, [entry][lane], 4 bytes an entry: 2 KB of stack and
+// 2 KB of list a wave, so LDS bounds nothing (40 waves fit a CU's 160 KB, more than its 32 slots) and one list size serves every K.
+// No fmaf in the leaf test: tests/np_overlap.py restates every operation in numpy float32.
+struct OverlapK {
+    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
+    const float4 *boxes; float4 *tuv; int2 *ids; uint8_t *hit; uint32_t *count;   // tuv: not used (query_fill's); ids: max_hits records a box, box-major (LIST); hit: a byte a box (ANY); count: may be null
+    uint32_t total, chunk, refill, leaf_batch;
+    uint32_t *cursors;        // a cast's cursor block
+    const uint32_t *bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;   // FILTER instance only, as ClosestK's
+    uint32_t max_hits;
+};
+constexpr int kOverlapLds = 8;                                     // stack references a lane in LDS
+constexpr int kOverlapOvf = kOvfStack4 + (kLdsStack - kOverlapLds);   // Trav4's bound on pending siblings holds for any walk of the tree
+// one axis of condition 4: p0, p1, p2 the three vertices' projections, rad the box's; min and max by comparisons, so a NaN separates nothing
+__device__ __forceinline__ bool axis_separates(float p0, float p1, float p2, float rad) {
+    float mn = p0, mx = p0;
+    mn = p1 < mn ? p1 : mn; mx = p1 > mx ? p1 : mx;
+    mn = p2 < mn ? p2 : mn; mx = p2 > mx ? p2 : mx;
+    return (mn > rad) | (mx < -rad);
+}
+// the three axes e_x, e_y, e_z x f for one edge f: p_m = a_m[j'] * f[i] - a_m[i] * f[j'], rad = h[i] * |f[j']| + h[j'] * |f[i]|, (i, j') = (y, z), (z, x), (x, y)
+__device__ __forceinline__ bool edge_separates(V3 a0, V3 a1, V3 a2, V3 h, V3 f) {
+    const float ax = fabsf(f.x), ay = fabsf(f.y), az = fabsf(f.z);
+    const bool sx = axis_separates(a0.z * f.y - a0.y * f.z, a1.z * f.y - a1.y * f.z, a2.z * f.y - a2.y * f.z, h.y * az + h.z * ay);
+    const bool sy = axis_separates(a0.x * f.z - a0.z * f.x, a1.x * f.z - a1.z * f.x, a2.x * f.z - a2.z * f.x, h.z * ax + h.x * az);
+    const bool sz = axis_separates(a0.y * f.x - a0.x * f.y, a1.y * f.x - a1.x * f.y, a2.y * f.x - a2.x * f.y, h.x * ay + h.y * ax);
+    return sx | sy | sz;
+}
+// conditions 3 and 4 of DESIGN.md 3.11 (Akenine-Moeller's test) for a triangle v0 e1 e2 against the box lo, hi
+__device__ __forceinline__ bool tri_box_overlap(V3 v0, V3 e1, V3 e2, V3 lo, V3 hi) {
+    const V3 c = mk(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z);
+    const V3 h = mk(0.5f * hi.x - 0.5f * lo.x, 0.5f * hi.y - 0.5f * lo.y, 0.5f * hi.z - 0.5f * lo.z);
+    const V3 a0 = v0 - c, a1 = mk(a0.x + e1.x, a0.y + e1.y, a0.z + e1.z), a2 = mk(a0.x + e2.x, a0.y + e2.y, a0.z + e2.z);
+    const V3 n = crossp(e1, e2);
+    if (fabsf(dotp(n, a0)) > (h.x * fabsf(n.x) + h.y * fabsf(n.y)) + h.z * fabsf(n.z)) return false;
+    const V3 f1 = e2 - e1, f2 = mk(-e2.x, -e2.y, -e2.z);
+    const bool s0 = edge_separates(a0, a1, a2, h, e1), s1 = edge_separates(a0, a1, a2, h, f1), s2 = edge_separates(a0, a1, a2, h, f2);
+    return !(s0 | s1 | s2);
+}
+template <bool ANY, bool FILTER> struct TravBox {
+    V3 lo, hi;
+    uint32_t cnt, K;     // cnt: candidates so far, uncapped (ANY: 0 | 1); K: 1..the kernel's KMAX, wave-uniform (LIST)
+    uint32_t *list;      // LIST: this lane's entry 0; entry j at list[j * kTraceBlock], the min(cnt, K) smallest gids in ascending order
+    int cur, sp;
+    __device__ __forceinline__ void push(int ref, int *lds, int *ovf) {
+        if (sp < kOverlapLds) lds[sp * kTraceBlock] = ref; else if (sp < kOverlapLds + kOverlapOvf) *(volatile int *)&ovf[sp - kOverlapLds] = ref;   // (volatile: TravBase::push)
+        sp = min(sp + 1, kOverlapLds + kOverlapOvf);
+    }
+    // the next reference; true: none left, the query is finished
+    __device__ __forceinline__ bool pop(int *lds, int *ovf) {
+        if (sp == 0) return true;
+        sp--;
+        if (sp < kOverlapLds) cur = lds[sp * kTraceBlock]; else cur = *(volatile int *)&ovf[sp - kOverlapLds];
+        return false;
+    }
+    // a candidate's gid into the list: it enters while the list is short, or below the K-th entry, which leaves.  (A leaf is visited at most once: no gid arrives twice)
+    __device__ __forceinline__ void enter(uint32_t gid) {
+        if (cnt >= K && !(gid < list[(K - 1u) * kTraceBlock])) return;
+        uint32_t j = min(cnt, K - 1u);
+        while (j > 0u) {   // entries above the candidate move up one
+            const uint32_t p = list[(j - 1u) * kTraceBlock];
+            if (p < gid) break;
+            list[j * kTraceBlock] = p; j--;
+        }
+        list[j * kTraceBlock] = gid;
+    }
+    // the triangle in `cur`: conditions 1 and 2 on its own box, then the separating axes, then the masks; ANY is finished by its first candidate
+    __device__ __forceinline__ bool step_leaf(const OverlapK &a, int *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~cur;
+        if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const bool meets = (tc.y < 3.0e38f) & (tc.y <= hi.x) & (lo.x <= td.x) & (tc.z <= hi.y) & (lo.y <= td.y) & (tc.w <= hi.z) & (lo.z <= td.z);
+        if (meets && tri_box_overlap(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), lo, hi) &&
+            (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
+            if (ANY) { cnt = 1u; return true; }
+            enter(__float_as_uint(td.w));
+            cnt++;
+        }
+        return pop(lds, ovf);
+    }
+    // TravPoint::step_internal's decode, then four box-against-box tests.  A child is skipped iff a comparison says its box misses the query's, or its box is inverted
+    // (255 / 0: absent or masked); on with the first that stays, the others wait.  (The order is speed only: nothing here shrinks)
+    __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int *lds, int *ovf) {
+        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
+        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
+        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
+        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
+        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
+        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        bool h[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t lxq = (b.x >> (8 * i)) & 255u, hxq = (b.w >> (8 * i)) & 255u;
+            const float lx = fmaf((float)lxq, sx, ox), hx = fmaf((float)hxq, sx, ox);
+            const float ly = fmaf((float)((b.y >> (8 * i)) & 255u), sy, oy), hy = fmaf((float)((c.x >> (8 * i)) & 255u), sy, oy);
+            const float lz = fmaf((float)((b.z >> (8 * i)) & 255u), sz, oz), hz = fmaf((float)((c.y >> (8 * i)) & 255u), sz, oz);
+            h[i] = (lxq <= hxq) & !((lx > hi.x) | (lo.x > hx) | (ly > hi.y) | (lo.y > hy) | (lz > hi.z) | (lo.z > hz));
+        }
+        int first = kAbsentChild;
+#pragma unroll
+        for (int i = 3; i >= 0; i--) {
+            if (h[i]) { if (first != kAbsentChild) push(first, lds, ovf); first = refs[i]; }
+        }
+        if (first == kAbsentChild) return pop(lds, ovf);
+        cur = first;
+        return false;
+    }
+};
+// (waves_per_eu 8: the leaf test holds its operands in 64 VGPRs without a spill -- DESIGN.md 3.11's table)
+template <bool ANY, int KMAX, bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_overlap(OverlapK a) {
+    __shared__ int stack[kOverlapLds * kTraceBlock];
+    __shared__ uint32_t gids[(ANY ? 1 : KMAX) * kTraceBlock];
+    int ovf[kOverlapOvf];
+    int *lds = &stack[threadIdx.x];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t leaf_batch = a.leaf_batch;
+    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
+    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // HW_REG_XCC_ID: speed only
+    uint32_t shards_left = 8;
+    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
+    bool exhausted = false, active = false;
+    TravBox<ANY, FILTER> tr;
+    tr.sp = 0; tr.cur = 0; tr.cnt = 0u;
+    tr.K = ANY ? 1u : min(max(a.max_hits, 1u), (uint32_t)KMAX);   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+    tr.list = &gids[threadIdx.x];
+    const uint32_t K = tr.K;
+    uint32_t slot = 0;
+    for (;;) {
+        const uint64_t idle = ballot64(!active);
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        if (n_idle >= a.refill) {
+            if (!exhausted && cur == end) {
+                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
+                if (got >= n_chunks) exhausted = true;
+                else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
+            }
+            if (!exhausted) {   // the idle lanes read the next queries of the chunk, one each
+                const uint32_t take = min(n_idle, end - cur);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (!active && rank < take) {
+                    const uint32_t sidx = cur + rank;
+                    const float4 q0 = a.boxes[2 * (size_t)sidx], q1 = a.boxes[2 * (size_t)sidx + 1];
+                    const float z = ((0.0f * q0.x + 0.0f * q0.y) + 0.0f * q0.z) + ((0.0f * q1.x + 0.0f * q1.y) + 0.0f * q1.z);   // 0 for six finite coordinates, NaN otherwise
+                    if (z == 0.0f && q0.x <= q1.x && q0.y <= q1.y && q0.z <= q1.z) {
+                        tr.lo = mk(q0.x, q0.y, q0.z); tr.hi = mk(q1.x, q1.y, q1.z); tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
+                        slot = sidx; active = true;
+                    } else if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate, lo > hi on an axis): its answer, without a walk
+                    else {
+                        const size_t base = (size_t)sidx * K;
+                        for (uint32_t j = 0; j < K; j++) a.ids[base + j] = make_int2(-1, -1);
+                        if (a.count) a.count[sidx] = 0u;
+                    }
+                }
+                cur += take;
+            } else if (n_idle == 64u) break;
+            if (ballot64(active) == 0ull) continue;
+        }
+        bool done = false;   // pooled_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
+#pragma unroll
+        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
+            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
+        const bool on_leaf = active && !done && tr.cur < 0;
+        const uint64_t lm = ballot64(on_leaf);
+        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
+        if (done) {
+            active = false;
+            if (ANY) a.hit[slot] = (uint8_t)tr.cnt;
+            else {
+                const size_t base = (size_t)slot * K;
+                for (uint32_t j = 0; j < K; j++) {
+                    if (j < tr.cnt) {
+                        const uint32_t gid = tr.list[j * kTraceBlock], prim = a.tri_prim[gid];
+                        a.ids[base + j] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
+                    } else a.ids[base + j] = make_int2(-1, -1);
+                }
+                if (a.count) a.count[slot] = tr.cnt;
+            }
+        }
+    }
+}
+
 // The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
 // the context's ArtTuning overrides.  query_fill: the fields every kernel's arguments share (cast_fill, closest_fill: with those of the casts, of the point queries);
 // launch_query: one instance, chosen by its caller, on that shape.
@@ -595,6 +782,13 @@ void launch_closest(const ClosestArgs &c, hipStream_t s) {
 void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s) {   // the instance with the smallest list that holds K
     ClosestMultiK a = closest_fill<ClosestMultiK>(c); a.count = c.count; a.gid_leaf = c.gid_leaf; a.max_hits = c.max_hits;
     launch_query(c.max_hits <= 4u ? (c.filter ? k_closest_multi<4, true> : k_closest_multi<4, false>) : (c.filter ? k_closest_multi<8, true> : k_closest_multi<8, false>), a, c, s);
+}
+void launch_overlap(const OverlapArgs &c, hipStream_t s) {   // one list size: ART_CAST_MAX_HITS gids a lane are 2 KB of LDS a wave, which bounds nothing
+    static_assert(ART_CAST_MAX_HITS == 8u, "k_overlap's list");
+    OverlapK a = query_fill<OverlapK>(c);
+    a.boxes = c.boxes; a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    if (c.any) launch_query(c.filter ? k_overlap<true, 0, true> : k_overlap<true, 0, false>, a, c, s);
+    else launch_query(c.filter ? k_overlap<false, 8, true> : k_overlap<false, 8, false>, a, c, s);
 }
 
 } // namespace art

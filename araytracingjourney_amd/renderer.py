@@ -858,6 +858,69 @@ class Renderer:
         duv, ids, point, count = self.closest_points_multi(points, max_hits, cull_mask, stream=stream)
         return (duv, ids, point, count), self.resolve_hits(duv, ids, want, stream=stream)
 
+    def overlap_boxes(self, boxes, kind="list", max_hits=8, cull_mask=0xFF, out=None, stream=None):
+        """The triangles that touch each box (art_overlap_boxes).  boxes: a torch tensor on this context's device, float32, shape (n, 8) -- lo.xyz, -, hi.xyz, - (words 3
+        and 7 are not read) -- contiguous and 16-byte aligned; a box is closed, and touching counts.  kind "list" returns (ids, count): (n, K, 2) int32 (primitive, triangle
+        in the primitive) of the K = max_hits overlapping triangles with the smallest global ids, in ascending order, (-1, -1) behind them, and (n,) int32 the number of ALL
+        overlapping triangles of the box, not capped by K (a uint32 on the device, handed out as the int32 torch has every operation for: a count never reaches 2^31).  kind "any" returns hit:
+        (n,) uint8, 1 where some triangle overlaps; max_hits is not used.  A box with a non-finite coordinate or lo > hi on an axis overlaps nothing.  Alpha cutoffs are not
+        tested; primitive masks are, against cull_mask.  out: (ids, count) or hit to write instead of new ones, of at least n boxes and exactly K records a box, not
+        overlapping the boxes or each other.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        m = _mask_value("cull_mask", cull_mask)
+        if kind not in ("list", "any"):
+            raise ValueError("kind must be 'list' or 'any'")
+        k = 0
+        if kind == "list":
+            k = int(max_hits)
+            if k != max_hits or not 1 <= k <= _lib.ART_CAST_MAX_HITS:
+                raise ValueError(f"max_hits must be an integer in 1..{_lib.ART_CAST_MAX_HITS}")
+        n = self._dev_tensor(boxes, "boxes", "float32", (8,), 16).shape[0]
+        d = _lib.ArtBoxQuery(boxes_dev=boxes.data_ptr() or None, n=n, max_hits=k, cull_mask=m, flags=0, reserved=0)
+        if kind == "list":
+            res = ids, count = self._outputs(out, n, boxes.device, (("ids", "int32", (k, 2), 8), ("count", "int32", (), 4)))
+            d.kind, d.ids_dev, d.count_dev = _lib.ART_OVERLAP_LIST, ids.data_ptr() or None, count.data_ptr() or None
+        else:
+            res, = self._outputs(None if out is None else (out,), n, boxes.device, (("hit", "uint8", (), 1),))
+            d.kind, d.hit_dev = _lib.ART_OVERLAP_ANY, res.data_ptr() or None
+        d.hip_stream = self._stream_handle(stream, boxes.device)
+        check(self._L.art_overlap_boxes(self._ctx, C.byref(d)))
+        return res
+
+    def voxelize(self, origin, cell, dims, cull_mask=0xFF, stream=None):
+        """An occupancy grid of the scene: a uint8 tensor [nx, ny, nz] on this context's device, 1 where some triangle touches the cell (overlap_boxes, kind "any").
+        origin: the grid's low corner (3 floats); cell: the cells' edge (one float, or 3); dims: (nx, ny, nz).  Cell (i, j, k) is the closed box lo = origin + idx * cell,
+        hi = origin + (idx + 1) * cell, made on the device in float32 -- one product, one sum -- so neighbours share their faces bit for bit and a triangle in a shared face
+        belongs to both.  Enqueued on `stream` (default: torch's current stream) without host synchronisation."""
+        import torch
+        m = _mask_value("cull_mask", cull_mask)
+        dims = tuple(int(x) for x in dims)
+        if len(dims) != 3 or any(x < 0 for x in dims):
+            raise ValueError("dims must be three integers >= 0")
+        dev = torch.device("cuda", self._query_device())
+        org = np.asarray(origin, np.float32).reshape(-1)
+        cel = np.asarray(cell, np.float32).reshape(-1)
+        if org.size != 3 or cel.size not in (1, 3) or not (np.isfinite(org).all() and np.isfinite(cel).all() and (cel > 0).all()):
+            raise ValueError("origin must be three finite floats and cell one or three finite floats > 0")
+        cel = np.broadcast_to(cel, (3,))
+        n = dims[0] * dims[1] * dims[2]
+        if n > _lib.ART_CAST_MAX_RAYS:
+            raise ValueError("dims: more than ART_CAST_MAX_RAYS cells")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        elif not hasattr(stream, "cuda_stream"):
+            stream = torch.cuda.ExternalStream(int(stream), device=dev)
+        with torch.cuda.stream(stream):
+            boxes = torch.zeros(dims + (8,), dtype=torch.float32, device=dev)
+            for axis in range(3):
+                shape = [1, 1, 1]
+                shape[axis] = dims[axis]
+                idx = torch.arange(dims[axis] + 1, dtype=torch.float32, device=dev)
+                plane = idx * float(cel[axis]) + float(org[axis])   # (a product and a sum in float32, two kernels: the planes both neighbours read)
+                boxes[..., axis] = plane[:-1].reshape(shape)
+                boxes[..., 4 + axis] = plane[1:].reshape(shape)
+            hit = self.overlap_boxes(boxes.reshape(n, 8), "any", cull_mask=m, stream=stream)
+        return hit.reshape(dims)
+
     def cast_spheres(self, rays, radius, cull_mask=0xFF, out=None, stream=None):
         """Where a ball of `radius` moving along each ray first touches the scene (art_cast_spheres).  rays: cast_rays' tensor, float32 of shape (n, 8) -- o.xyz, tmin,
         d.xyz, tmax; the ball's centre is o + t*d -- contiguous and 16-byte aligned; radius: one finite float >= 0 for the whole call.  Returns (tuv, ids, point): (n, 4)

@@ -456,6 +456,42 @@ typedef struct ArtPointQueryMulti {
     uint32_t flags;         /* must be 0 */
 } ArtPointQueryMulti;       /* 64 bytes */
 int32_t art_closest_points_multi(ArtContext *ctx, const ArtPointQueryMulti *q);
+/* The triangles that touch a box (new functionality: PhysX's overlap with a box geometry, Unity's OverlapBox / CheckBox -- the reference has no call
+ * for it): an occupancy grid of the scene (a voxelisation, which rays parallel to a surface miss and a ball round the cell overstates), trigger volumes, broad-phase
+ * candidates for a box-shaped body, the triangles of a region for a baker or a learned model.  A query is a closed world-axis box [lo, hi].
+ *  - Results: defined exactly and independent of the structure.  A triangle with global id g and record v0, e1, e2, tlo, thi (its own box) OVERLAPS the box iff (1) tlo.x <
+ *    3.0e38 (a primitive that left the structure by residency is nowhere and is never returned); (2) the boxes meet: on every axis tlo <= hi and lo <= thi, comparisons
+ *    only; (3) the triangle's plane does not separate and (4) none of the nine axes e_k x f_j does -- Akenine-Moeller's test about c = 0.5*lo + 0.5*hi with h = 0.5*hi -
+ *    0.5*lo, DESIGN.md 3.11's formulas in fp32 without fused operations, sums of three as (a + b) + c; a comparison with a NaN is false, so such an axis separates nothing;
+ *    a zero-area triangle goes through the same formulas.  Touching counts: a triangle in the face two boxes share belongs to both.  The candidates are the overlapping
+ *    triangles whose primitive's mask & cull_mask != 0 (cull_mask 0 sees nothing); alpha cutoffs are NOT tested, for art_closest_points' reason.
+ *  - ART_OVERLAP_ANY: hit_dev[i] = 1 iff the box has a candidate, else 0; the walk ends at the first one.  ART_OVERLAP_LIST: count_dev[i] (optional) = the number of
+ *    candidates, all of them, not capped by max_hits; records 0 .. c-1 of the box, c = min(count, max_hits), are (primitive id, triangle in the primitive) of the
+ *    candidates in ascending g; records c .. max_hits-1 are (-1, -1).  A box with a non-finite coordinate or with lo > hi on any axis is dead: hit 0, count 0, miss
+ *    records, no walk.  lo == hi is legal (a point, a segment, a rectangle).  Words 3 and 7 of a box are not read.  A box's answer depends on that box alone.
+ *  - Asynchrony and scene: art_closest_points', with no path of its own -- stream, no allocation or synchronisation on the steady path, the scene as of the call, the
+ *    version held, a block of the casts' ring (ART_CAST_POOL), the same fences.  art_cast_counts counts it in neither casts nor rays (it traces no ray); a host wait it
+ *    causes counts in host_waits.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; flags or reserved other than 0; a kind that is neither; cull_mask above
+ *    0xFF; n above ART_CAST_MAX_RAYS; a null or misaligned boxes_dev (16 bytes; with n = 0 null is fine); ANY: ids_dev or count_dev given, max_hits other than 0, a null
+ *    hit_dev; LIST: hit_dev given, max_hits 0 or above ART_CAST_MAX_HITS, a null or misaligned ids_dev (8 bytes), a misaligned count_dev (4 bytes).  ART_E_STATE: the
+ *    scene is not built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+#define ART_OVERLAP_ANY 0u
+#define ART_OVERLAP_LIST 1u
+typedef struct ArtBoxQuery {
+    const void *boxes_dev;  /* n x 8 floats: lo.xyz, -, hi.xyz, - (words 3 and 7 are not read); 16-byte aligned */
+    void *hit_dev;          /* ANY: n x uint8, 1 = some triangle overlaps the box.  LIST: must be NULL */
+    void *ids_dev;          /* LIST: n x max_hits x 2 int32 (primitive id, triangle in the primitive), box-major: box i's record j at i*max_hits + j; 8-byte aligned.  ANY: must be NULL */
+    void *count_dev;        /* LIST: n x uint32: ALL overlapping triangles of the box, not capped by max_hits; 4-byte aligned.  May be NULL.  ANY: must be NULL */
+    void *hip_stream;       /* as ArtRayCast */
+    uint32_t n;             /* 0 is legal: nothing is enqueued */
+    uint32_t kind;          /* ART_OVERLAP_ANY | ART_OVERLAP_LIST */
+    uint32_t max_hits;      /* LIST: K, 1..ART_CAST_MAX_HITS.  ANY: must be 0 */
+    uint32_t cull_mask;     /* 0..0xFF; 0 sees nothing */
+    uint32_t flags;         /* must be 0 */
+    uint32_t reserved;      /* must be 0 */
+} ArtBoxQuery;              /* 64 bytes */
+int32_t art_overlap_boxes(ArtContext *ctx, const ArtBoxQuery *q);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
