@@ -205,8 +205,7 @@ int32_t art::ring_rewind(ArtContext *c) {
     int32_t r = use_device(c); if (r) return r;
     r = sync_all(c); if (r) return r;
     c->frame_no = 0; c->collected_upto = 0; c->last = 0;
-    plan_rewind(c);
-    return ART_OK;
+    return plan_rewind(c);
 }
 
 static int32_t read_back(ArtContext *c, const void *src, size_t have, void *dst, size_t bytes, const char *who) {

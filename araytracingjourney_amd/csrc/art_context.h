@@ -253,7 +253,7 @@ int32_t plan_launch(ArtContext *c, const FrameArgs &a, hipEvent_t frame_done);
 void plan_hint_moved(ArtContext *c);
 void plan_hint_built(ArtContext *c);                                     // a new scene: the heavy blocks are elsewhere
 int32_t plan_sync(ArtContext *c);                                        // sync_all's part: a plan behind a sampled frame
-void plan_rewind(ArtContext *c);                                         // ring_rewind's part (everything is synchronised)
+int32_t plan_rewind(ArtContext *c);                                      // ring_rewind's part (everything is synchronised): a landed plan is adopted, not dropped
 // ---- art_cast.hip (every use of CastState / CastBlock is there) ----
 int32_t cast_sync(ArtContext *c);                                        // sync_all's part: every cast enqueued so far, on whichever stream, and the cast stream
 int32_t cast_wait_version(ArtContext *c, uint32_t version);              // scene_refresh's part: the casts that still read the version about to be rewritten

@@ -519,9 +519,10 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
 // Rounds 1-3 made it on the host: the step counts of a sampled frame travelled up, one thread went through 32 640 blocks and built the next table (0.3-0.9 ms inside an
 // art_trace call every few frames once the camera moves: frames are 0.16 ms), the table travelled down.  One workgroup does the same in ~20 us behind the sampled frame on
 // that frame's stream; the host only learns "a new table of n items is ready" from pinned memory once the event behind this launch has fired.
-// Table layout (what plan_build_items made): the split blocks' parts first -- sixteen cells each, then four quadrants each: the long poles start first -- padded to whole groups
-// of four, then every 256-pixel block of the launch order as four 8x8 items (mask 0: an idle wave where the block is split); finally the deal that keeps the four waves of
-// launch block 8g + x on XCD x (workgroup j runs on XCD j % 8): position 32g + 4x + k goes to 32g + 8k + x.
+// Table layout (what plan_build_items made): the split blocks' parts first -- sixteen cells each, then four quadrants each: the long poles start first -- padded with idle
+// waves to whole groups of 32, then every 256-pixel block of the launch order as four 8x8 items (mask 0: an idle wave where the block is split); finally the deal that keeps
+// the four waves of launch block 8g + x on XCD x (workgroup j runs on XCD j % 8): position 32g + 4x + k goes to 32g + 8k + x.  (Whole groups of 32, not of four: the parts are
+// a multiple of four as they are, and the deal's groups must be the launch order's own -- behind 4 s items, s not a multiple of 8, launch block L sat on XCD (L + s) % 8.)
 __device__ __forceinline__ uint32_t plan_block_sum(uint32_t v, uint32_t *sh) {   // sum over the 1024 threads, in every thread (sh: 16 words)
     for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
     __syncthreads();
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(1024) void k_plan(PlanArgs p) {
             n1 += lv == 1u; n2 += lv == 2u; u += lv > old; d += lv < old; sp += old != 0u; wmax = max(wmax, w);
         }
         N1 = plan_block_sum(n1, sh); N2 = plan_block_sum(n2, sh); ups = plan_block_sum(u, sh); downs = plan_block_sum(d, sh); split = plan_block_sum(sp, sh);
-        if (p.n64 + (p.n64 & 3u) + 4u * N1 + 16u * N2 + 4u <= p.cap) break;
+        if (p.n64 + (p.n64 & 3u) + 4u * N1 + 16u * N2 + 32u <= p.cap) break;   // (the padding is at most 28 items)
         if (attempt == 7) { N1 = N2 = ups = downs = 0; for (uint32_t b = b0; b < b1; b++) p.level_tmp[b] = p.level[b]; n1 = n2 = 0; }   // (never seen: no target fits -- the plan stays)
     }
     for (int off = 32; off >= 1; off >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, off));
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(1024) void k_plan(PlanArgs p) {
     __syncthreads();
     uint32_t base2 = 0, base1 = 0;
     for (uint32_t i = 0; i < tid; i++) { base2 += sc2[i]; base1 += sc1[i]; }   // (1024 LDS reads a thread: a microsecond)
-    const uint32_t heavy = 16u * N2 + 4u * N1, heavy_pad = (heavy + 3u) & ~3u, total = heavy_pad + p.n256 * 4u;
+    const uint32_t heavy = 16u * N2 + 4u * N1, heavy_pad = (heavy + 31u) & ~31u, total = heavy_pad + p.n256 * 4u;
     for (uint32_t b = b0; b < b1; b++) {
         const uint32_t lv = p.level_tmp[b];
         p.level[b] = (uint8_t)lv;

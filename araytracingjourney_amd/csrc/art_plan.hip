@@ -123,8 +123,13 @@ int32_t art::plan_sync(ArtContext *c) {
     if (P.plan_stream && P.pending) { for (uint32_t k = 0; k < c->F; k++) HIPC(hipStreamSynchronize(c->stream_of(k))); HIPC(hipStreamSynchronize(P.plan_stream)); }
     return ART_OK;
 }
-// the ring starts again at frame 0 (a sample in flight has landed: everything is synchronised)
-void art::plan_rewind(ArtContext *c) { c->plan.next_sample = 0; c->plan.pending = false; c->plan.last_sample = 0; }
+// the ring starts again at frame 0.  Everything is synchronised, so a sample in flight has landed: its table is adopted like any other (k_plan committed the levels with
+// it; dropping the result would leave them a table ahead of the host)
+int32_t art::plan_rewind(ArtContext *c) {
+    int32_t r = plan_poll(c); if (r) return r;
+    c->plan.next_sample = 0; c->plan.pending = false; c->plan.last_sample = 0;
+    return ART_OK;
+}
 
 extern "C" {
 
@@ -145,7 +150,66 @@ int32_t art_sample_wave_steps(ArtContext *c, uint32_t *items, uint32_t *steps, u
     const uint32_t m = std::min(*n, cap);
     if (items && m) HIPC(hipMemcpy(items, P.d_items[P.pending_table].p, (size_t)m * 8, hipMemcpyDeviceToHost));
     if (steps && m) HIPC(hipMemcpy(steps, c->slot[c->last].d_wave_cost.p, (size_t)m * 4, hipMemcpyDeviceToHost));
-    if (!P.enabled) P.pending = false;   // nobody polls a plan that is switched off (k_plan ran all the same: its table is not adopted)
+    if (!P.enabled) {   // nobody polls a plan that is switched off (k_plan ran all the same: its table is not adopted)
+        P.pending = false;
+        // ... and k_plan commits the levels together with the table it writes: a switched-off plan runs the first table for as long as its layout lives, all blocks level 0
+        if (P.result.p[1]) { HIPC(hipMemset(P.d_level.p, 0, P.d_level.n)); HIPC(hipDeviceSynchronize()); }
+    }
+    return ART_OK;
+}
+
+// k_plan on made-up buffers (include/art_parity.h): every index the kernel makes from its inputs is checked here first
+int32_t art_parity_plan(ArtContext *c, uint32_t n256, const uint32_t *order, const uint32_t *items_in, uint32_t n_items_in, const uint32_t *cost, const uint8_t *level_in,
+                        const uint32_t *worst_in, uint32_t cap, float share, uint32_t min_steps, uint32_t fixed_steps, uint32_t *items_out, uint8_t *level_out,
+                        uint32_t *worst_out, uint32_t result[8]) {
+    if (!c || !order || !level_in || !worst_in || !items_out || !level_out || !worst_out || !result || (n_items_in && (!items_in || !cost)))
+        return fail(ART_E_INVALID, "art_parity_plan: null argument");
+    if (n256 < 1 || n256 > (1u << 16) || n_items_in > (1u << 22) || cap < 1 || cap > (1u << 22)) return fail(ART_E_INVALID, "art_parity_plan: n256 1..2^16, at most 2^22 items, cap 1..2^22");
+    const uint32_t n64 = 4 * n256;
+    std::vector<uint8_t> seen(n256, 0);
+    for (uint32_t i = 0; i < n256; i++) { if (order[i] >= n256 || seen[order[i]]) return fail(ART_E_INVALID, "art_parity_plan: order is not a permutation of the 256-pixel blocks"); seen[order[i]] = 1; }
+    for (uint32_t i = 0; i < n_items_in; i++) if (items_in[2 * i] >= n64) return fail(ART_E_INVALID, "art_parity_plan: an item's block is not below n64");
+    for (uint32_t b = 0; b < n64; b++) if (level_in[b] > 2) return fail(ART_E_INVALID, "art_parity_plan: a level above 2");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    DevBuf<uint2> d_in, d_out; DevBuf<uint32_t> d_cost, d_worst, d_order; DevBuf<uint8_t> d_level, d_tmp; Pinned<uint32_t> res;
+    HIPC(d_in.ensure(n_items_in)); HIPC(d_cost.ensure(n_items_in)); HIPC(d_out.ensure(cap)); HIPC(d_worst.ensure(n64)); HIPC(d_order.ensure(n256));
+    HIPC(d_level.ensure(n64)); HIPC(d_tmp.ensure(n64)); HIPC(res.ensure(8));
+    if (n_items_in) { HIPC(hipMemcpy(d_in.p, items_in, (size_t)n_items_in * 8, hipMemcpyHostToDevice)); HIPC(hipMemcpy(d_cost.p, cost, (size_t)n_items_in * 4, hipMemcpyHostToDevice)); }
+    HIPC(hipMemcpy(d_order.p, order, (size_t)n256 * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_level.p, level_in, n64, hipMemcpyHostToDevice)); HIPC(hipMemcpy(d_worst.p, worst_in, (size_t)n64 * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_out.p, 0xFF, (size_t)cap * 8)); HIPC(hipMemset(d_tmp.p, 0xFF, n64));
+    std::memcpy(res.p, result, 32);
+    HIPC(hipDeviceSynchronize());   // (the copies and clears above ran on the null stream)
+    PlanArgs pa{};
+    pa.items_in = d_in.p; pa.n_items_in = n_items_in; pa.cost = d_cost.p;
+    pa.level = d_level.p; pa.level_tmp = d_tmp.p; pa.n64 = n64; pa.worst = d_worst.p;
+    pa.order = d_order.p; pa.n256 = n256; pa.items_out = d_out.p; pa.cap = cap;
+    pa.share = share; pa.min_steps = min_steps; pa.fixed_steps = fixed_steps; pa.result = res.d;
+    launch_plan(pa, nullptr); HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(items_out, d_out.p, (size_t)cap * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(level_out, d_level.p, n64, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(worst_out, d_worst.p, (size_t)n64 * 4, hipMemcpyDeviceToHost));
+    std::memcpy(result, res.p, 32);
+    return ART_OK;
+}
+
+int32_t art_read_wave_plan(ArtContext *c, uint8_t *level, size_t n64, uint32_t *items, uint32_t cap, uint32_t *n_items, uint32_t result[8], uint32_t state[4]) {
+    if (!c) return fail(ART_E_INVALID, "art_read_wave_plan: null context");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    if (!c->frame_ready) return fail(ART_E_STATE, "art_read_wave_plan: no frame layout yet (art_trace)");
+    WavePlan &P = c->plan;
+    if (P.enabled) { r = plan_poll(c); if (r) return r; }   // a plan that has landed takes effect first
+    if (level) {
+        if (n64 != c->n_local / 64) return fail(ART_E_INVALID, "art_read_wave_plan: size mismatch");
+        if (n64) HIPC(hipMemcpy(level, P.d_level.p, n64, hipMemcpyDeviceToHost));
+    }
+    const uint32_t n = P.n_items[P.cur], m = std::min(n, cap);
+    if (n_items) *n_items = n;
+    if (items && m) HIPC(hipMemcpy(items, P.d_items[P.cur].p, (size_t)m * 8, hipMemcpyDeviceToHost));
+    if (result) std::memcpy(result, P.result.p, 32);
+    if (state) { state[0] = (uint32_t)P.cur; state[1] = P.pending ? 1u : 0u; state[2] = P.replans; state[3] = P.cap; }
     return ART_OK;
 }
 

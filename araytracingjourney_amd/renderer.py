@@ -678,6 +678,41 @@ class Renderer:
         check(_lib.load().art_parity_live_resources(out))
         return dict(zip(("device", "pinned", "events", "streams", "pooled"), (int(v) for v in out)))
 
+    PLAN_UNWRITTEN = 0xFFFFFFFF   # what art_parity_plan leaves in every word of items_out the kernel did not write
+
+    def parity_plan(self, order, items_in, cost, level_in, worst_in, cap, share, min_steps, fixed_steps, result_in=None):
+        """art_parity_plan: one launch of k_plan on made-up buffers -> (items_out [cap, 2] uint32, level_out [n64] uint8, worst_out [n64] uint32, result [8] uint32);
+        result_in: the eight words the kernel's result starts from (zeros)"""
+        order, cost, worst_in = (np.ascontiguousarray(a, np.uint32) for a in (order, cost, worst_in))
+        items_in, level_in = np.ascontiguousarray(items_in, np.uint32).reshape(-1, 2), np.ascontiguousarray(level_in, np.uint8)
+        n256 = order.size
+        if level_in.size != 4 * n256 or worst_in.size != 4 * n256 or cost.size != items_in.shape[0]:
+            raise ValueError("parity_plan: level_in and worst_in hold 4 * len(order) entries, cost one per item")
+        items_out, level_out, worst_out = np.zeros((max(int(cap), 1), 2), np.uint32), np.zeros(4 * n256, np.uint8), np.zeros(4 * n256, np.uint32)
+        result = np.zeros(8, np.uint32) if result_in is None else np.array(result_in, np.uint32)
+        assert result.size == 8
+        check(self._L.art_parity_plan(self._ctx, n256, _ptr(order), _ptr(items_in), items_in.shape[0], _ptr(cost), _ptr(level_in), _ptr(worst_in), int(cap), float(share),
+                                      int(min_steps), int(fixed_steps), _ptr(items_out), _ptr(level_out), _ptr(worst_out), _ptr(result)))
+        return items_out, level_out, worst_out, result
+
+    def read_wave_plan(self):
+        """art_read_wave_plan: the context's wave plan as it stands (a landed plan is adopted first) -> dict(level [n64] uint8, items [n, 2] uint32 -- the table the next
+        frame runs --, result [8] uint32, cur, pending, replans, cap)"""
+        n, state, result = C.c_uint32(), (C.c_uint32 * 4)(), np.zeros(8, np.uint32)
+        check(self._L.art_read_wave_plan(self._ctx, None, 0, None, 0, C.byref(n), None, state))
+        level, items = np.zeros(self.layout()["tiles_owned"] * 16, np.uint8), np.zeros((n.value, 2), np.uint32)
+        check(self._L.art_read_wave_plan(self._ctx, _ptr(level), level.size, _ptr(items), n.value, C.byref(n), _ptr(result), state))
+        assert n.value == items.shape[0]
+        return dict(level=level, items=items, result=result, cur=state[0], pending=bool(state[1]), replans=state[2], cap=state[3])
+
+    def sample_wave_steps(self):
+        """art_sample_wave_steps: one frame with the step-counting instance -> (items [n, 2] uint32: the table that launch ran, steps [n] uint32: what its waves counted)"""
+        cap = self.layout()["tiles_owned"] * 16 * 2 + 64
+        items, steps, n = np.zeros((cap, 2), np.uint32), np.zeros(cap, np.uint32), C.c_uint32()
+        check(self._L.art_sample_wave_steps(self._ctx, _ptr(items), _ptr(steps), cap, C.byref(n)))
+        assert n.value <= cap
+        return items[:n.value].copy(), steps[:n.value].copy()
+
     def set_ray_masks(self, primary=0xFF, shadow=0xFF, ao=0xFF):
         """the cull masks of the rays trace() (primary, shadow) and trace_ao() (ao) cast (Vulkan: traceRayEXT's cullMask; the reference hard-codes 0xFF,
         raytrace.rgen.glsl:92,169): a ray sees a primitive iff its mask (Model.set_mask) shares a bit with the ray's.  Per-launch state like the camera: a

@@ -145,6 +145,23 @@ int32_t art_collect_timings(ArtContext *ctx, float sums_ms[5], uint32_t *n_frame
  * items[2*i] = 8x8 pixel block (local pixel id / 64), items[2*i+1] = mask over its sixteen 2x2 cells (0: an idle wave), steps[i] = packet steps
  * (nodes + triangles visited, all walks of the wave).  *n = waves of the launch; at most cap are copied.  (tools/step_hist.py) */
 int32_t art_sample_wave_steps(ArtContext *ctx, uint32_t *items, uint32_t *steps, uint32_t cap, uint32_t *n);
+/* the wave plan's kernel (k_plan) on buffers of the caller's making, all in host memory (tests/test_wave_plan.py compares it with tests/np_plan.py bit for bit): one launch
+ * of what runs behind a sampled frame.  In: the launch order order[n256] of the 256-pixel blocks, the sampled table items_in[2 * n_items_in] (8x8 block, cell mask) with
+ * what its waves counted cost[n_items_in], every 8x8 block's level level_in[n64] (0 | 1 | 2) and scratch word worst_in[n64] (zero between launches in a context),
+ * n64 = 4 * n256; a table holds cap items; the target is fixed_steps, or max(min_steps, share * steps of the table) when that is 0.  Out: items_out[2 * cap], every word
+ * 0xFFFFFFFF where the kernel wrote nothing; level_out[n64], worst_out[n64]; result[8] -- the words of PlanArgs::result ([0] items of the new table, [1] 1 = a new table was
+ * written, [2] blocks in four, [3] blocks in sixteen, [4] the target, [5] the slowest wave) -- goes in as the caller filled it and comes back with the words the kernel
+ * wrote changed.  CONTRACT (checked, ART_E_INVALID otherwise: the kernel indexes with them): 1 <= n256 <= 2^16, order is a permutation of 0 .. n256 - 1, every item's block
+ * is below n64, every level is at most 2, n_items_in <= 2^22, 1 <= cap <= 2^22.  The context only names the device.  Takes its buffers for the call and gives them back
+ * (art_parity_live_resources is what it was); synchronises. */
+int32_t art_parity_plan(ArtContext *ctx, uint32_t n256, const uint32_t *order, const uint32_t *items_in, uint32_t n_items_in, const uint32_t *cost, const uint8_t *level_in,
+                        const uint32_t *worst_in, uint32_t cap, float share, uint32_t min_steps, uint32_t fixed_steps, uint32_t *items_out, uint8_t *level_out,
+                        uint32_t *worst_out, uint32_t result[8]);
+/* a context's wave plan as it stands.  Synchronises, and a plan that has landed behind a sampled frame is adopted first, as the next art_trace would adopt it.  level[n64]: every
+ * 8x8 block's level on the device (n64 = local pixels / 64, ART_E_INVALID otherwise); items[2 * i], i < min(*n_items, cap): the table the next frame runs, *n_items its length;
+ * result[8]: the pinned words of the latest k_plan; state[4]: which of the two tables is the current one, 1 while a sample is in flight, tables adopted since the frame was
+ * laid out, items a table can hold.  Any pointer but ctx may be NULL.  Needs the frame layout of a first art_trace (ART_E_STATE). */
+int32_t art_read_wave_plan(ArtContext *ctx, uint8_t *level, size_t n64, uint32_t *items, uint32_t cap, uint32_t *n_items, uint32_t result[8], uint32_t state[4]);
 /* what libart holds in this process right now: out[0] device allocations, [1] pinned allocations, [2] events,
  * [3] streams in use by contexts and ArtMgpu objects, [4] streams parked in the process-wide pool.  No context needed; never fails with out non-NULL. */
 int32_t art_parity_live_resources(uint64_t out[5]);
