@@ -1,9 +1,10 @@
 // art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest), the K nearest
-// triangles (k_closest_multi), swept spheres (k_sweep) and the triangles that touch a box (k_overlap, whose loop is k_closest's in a third text).  The casts and the sweep are Sources and candidate policies of art_walk.h's pooled loop; the two point queries have
-// a loop of their own, in two texts.  What the queries share stands once: at the top the ray read, the hit and miss records, the contact point and the mask test; the sorted
-// list of both K-walks (KList), which a walk fills through its leaf step's hook for a candidate's fate (step_leaf_take: one leaf step a walk); at the bottom the arguments'
-// common fields and the launch.  (The list and the leaf steps were copies once, kept apart so that no other kernel's code would move.  Compared instruction for instruction --
-// tools/kernel_diff.py -- none but k_closest_multi's does: profiles/README.md, "one list, one hook".)  art_cast.hip is their host side.
+// triangles (k_closest_multi), swept spheres (k_sweep) and the triangles that touch a box (k_overlap).  The casts and the sweep are Sources and candidate policies of
+// art_walk.h's pooled loop; the point and box queries, which have no ray to pool, are Sinks and walks of one loop of their own (point_trace).  What the queries share stands
+// once: at the top the ray read, the hit and miss records, the contact point, the mask test and the 4-wide node's decode (load_node4); the sorted list of both K-walks
+// (KList), which a walk fills through its leaf step's hook for a candidate's fate (step_leaf_take: one leaf step a walk); at the bottom the arguments' common fields and
+// the launch.  (The list, the leaf steps and the loop were copies once, kept apart so that no other kernel's code would move.  Compared instruction for instruction --
+// tools/kernel_diff.py -- what moves is in profiles/README.md, "one list, one hook" and "one point loop".)  art_cast.hip is their host side.
 #include "art_walk.h"
 
 namespace art {
@@ -42,6 +43,17 @@ __device__ __forceinline__ bool leaf_visible(const uint32_t *bits, const DevShad
     if (!((bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
     const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(shade + pos)[8].z);
     return (prim_vis(prims[prim].masked) & cull) != 0u;
+}
+// A 4-wide node as the queries' own walks (TravPoint, TravSweep, TravBox) take it apart: four bytes a plane, child i's in bits 8i.. of b (lo.x lo.y lo.z hi.x) and c
+// (hi.y hi.z); the origin and the power-of-two scales that decode them (plane = byte * s + o); the four references.  It is Trav4::step_internal's decode, which stays
+// with the kernels of the frame.  What a walk makes of a child's box is its own.  (c: the two words in use, not the uint4 -- handed on whole, k_sweep loads all four)
+struct Node4 { uint4 b; uint2 c; float ox, oy, oz, sx, sy, sz; int refs[4]; };
+__device__ __forceinline__ Node4 load_node4(const DevNode4 *__restrict__ wide, int cur) {
+    const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
+    uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
+    asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
+    return {b, make_uint2(c.x, c.y), __uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z),
+            __uint_as_float((a.w & 255u) << 23), __uint_as_float(((a.w >> 8) & 255u) << 23), __uint_as_float(((a.w >> 16) & 255u) << 23), {(int)d.x, (int)d.y, (int)d.z, (int)d.w}};
 }
 
 // Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT), are READ.  One walk for every context, whatever ArtTuning
@@ -149,10 +161,10 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMA
 
 // ---- nearest surface points (art_closest_points) ------------------------------------------------------------------------------------------------
 // A query is a point and a radius, not a ray: the pooled loop's ray fields (inv, ood, tmin / tmax, the slab of every policy) have no meaning for it, and a query is ONE
-// 16-byte load -- nothing a pool would save.  So the walk has a loop of its own: the idle lanes of a wave read the next queries of its chunk directly (pop_chunk and the
-// cursor block are the casts').  Stack entries are pairs (reference, the child's box_d2): `limit` only ever falls, and an entry whose box has fallen behind it by the time
-// it is popped is dropped without a fetch.  Eight pairs a lane in LDS (4 KB a wave: 40 waves fit a CU's 160 KB, more than its 32 slots); deeper entries spill to scratch
-// as references alone.
+// 16-byte load -- nothing a pool would save.  So the walk has a loop of its own (point_trace below, which the K nearest and the box query run too): the idle lanes of a
+// wave read the next queries of its chunk directly (pop_chunk and the cursor block are the casts').  Stack entries are pairs (reference, the child's box_d2): `limit`
+// only ever falls, and an entry whose box has fallen behind it by the time it is popped is dropped without a fetch.  Eight pairs a lane in LDS (4 KB a wave: 40 waves
+// fit a CU's 160 KB, more than its 32 slots); deeper entries spill to scratch as references alone.
 // No fmaf in anything that decides a record: d2_tri, box_d2 of a triangle and the point are restated by numpy float32 bit for bit (tests/np_closest.py).
 __device__ __forceinline__ float dotp(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 crossp(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
@@ -200,7 +212,7 @@ struct ClosestK {
     const uint32_t *bits; const DevShadeTri *shade; const DevPrim *prims; uint32_t cull;   // FILTER instance only: AlphaView's leaf bits, records and table; the queries' cull mask
 };
 constexpr int kClosestLds = 8;                                     // stack pairs a lane in LDS
-constexpr int kClosestOvf = kOvfStack4 + (kLdsStack - kClosestLds);   // Trav4's bound on pending siblings holds for any walk of the tree
+constexpr int kQueryOvf = kOvfStack4 + (kLdsStack - kClosestLds);     // the scratch stack of point_trace's walks: Trav4's bound on pending siblings holds for any walk of the tree
 template <bool FILTER> struct TravPoint {
     V3 p;
     float limit, bu, bv;     // limit: r*r, then the best candidate's d2_eff
@@ -208,8 +220,8 @@ template <bool FILTER> struct TravPoint {
     int cur, sp;
     // (a spilled entry is the reference alone, TravBase's: pairs there would double the scratch every wave slot of the device reserves; it is visited unasked)
     __device__ __forceinline__ void push(int ref, float d2, int2 *lds, int *ovf) {
-        if (sp < kClosestLds) lds[sp * kTraceBlock] = make_int2(ref, __float_as_int(d2)); else if (sp < kClosestLds + kClosestOvf) *(volatile int *)&ovf[sp - kClosestLds] = ref;   // (volatile: TravBase::push)
-        sp = min(sp + 1, kClosestLds + kClosestOvf);
+        if (sp < kClosestLds) lds[sp * kTraceBlock] = make_int2(ref, __float_as_int(d2)); else if (sp < kClosestLds + kQueryOvf) *(volatile int *)&ovf[sp - kClosestLds] = ref;   // (volatile: TravBase::push)
+        sp = min(sp + 1, kClosestLds + kQueryOvf);
     }
     // the next entry whose box is still within the limit; true: none left, the query is finished
     __device__ __forceinline__ bool pop(int2 *lds, int *ovf) {
@@ -241,12 +253,7 @@ template <bool FILTER> struct TravPoint {
         return step_leaf_take(a, lds, ovf, [this](float de, float u, float v, uint32_t pos, uint32_t gid) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; });
     }
     __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
-        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
-        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
-        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
-        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
-        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
-        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, cur);
         float d2[4]; bool h[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -273,11 +280,19 @@ template <bool FILTER> struct TravPoint {
         return false;
     }
 };
-template <bool FILTER>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_closest(ClosestK a) {
-    __shared__ int2 stack[kClosestLds * kTraceBlock];
-    int ovf[kClosestOvf];
-    int2 *lds = &stack[threadIdx.x];
+// The wave loop of the point and box queries (k_closest, k_closest_multi, k_overlap): a wave takes a chunk from the cursor block, its idle lanes read the next queries of
+// the chunk, one each, and every lane walks its own by pooled_trace's step block.  TRAV: the walk -- push, pop, step_internal(wide, lds, ovf), step_leaf(a, lds, ovf) over
+// stack entries of its own kind (STACK).  stack: the kernel's __shared__ array, kTraceBlock entries a level.  What else differs between the queries is their Sink:
+//   init(tr) -> K                  once per lane, before the loop: what the walk keeps for the whole launch.  K: the records a query gets (wave-uniform; 1 where it is one)
+//   begin(tr, sidx, K, radius)     reads query sidx.  A live one: the walk's start state, and radius for the finish -> true.  A dead one: its complete answer, written
+//                                  there and then -> false, and it takes no lane
+//   finish(tr, slot, K, radius)    the finished query's records
+// (The __shared__ arrays stay where each kernel declares them; the walk, K and radius are the loop's own locals, handed to the hooks.  What this form moves in the kernels'
+// code -- register names, six to eight instructions a point kernel in the path that starts a query, no resource figure -- is in profiles/README.md, "one point loop")
+template <class TRAV, class ARGS, class STACK, class SINK>
+__device__ __forceinline__ void point_trace(const ARGS &a, STACK *stack, const SINK &sink) {
+    int ovf[kQueryOvf];
+    STACK *lds = &stack[threadIdx.x];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t leaf_batch = a.leaf_batch;
     const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
@@ -285,8 +300,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     uint32_t shards_left = 8;
     uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
     bool exhausted = false, active = false;
-    TravPoint<FILTER> tr;
+    TRAV tr;
     tr.sp = 0; tr.cur = 0;
+    const uint32_t K = sink.init(tr);
     float radius = 0.0f;
     uint32_t slot = 0;
     for (;;) {
@@ -303,12 +319,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                 if (!active && rank < take) {
                     const uint32_t sidx = cur + rank;
-                    const float4 q = a.points[sidx];
-                    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
-                    if (z == 0.0f && q.w == q.w && !(q.w < 0.0f)) {
-                        tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
-                        radius = q.w; slot = sidx; active = true;
-                    } else write_point_miss(a, sidx, q.w);   // a non-finite point, a NaN or negative radius: the miss record, without a walk
+                    if (sink.begin(tr, sidx, K, radius)) { slot = sidx; active = true; }
                 }
                 cur += take;
             } else if (n_idle == 64u) break;
@@ -321,14 +332,39 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
         const bool on_leaf = active && !done && tr.cur < 0;
         const uint64_t lm = ballot64(on_leaf);
         if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
-        if (done) {
-            active = false;
-            if (tr.bgid != kNoHit) {
-                write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
-                if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
-            } else write_point_miss(a, slot, radius);
-        }
+        if (done) { active = false; sink.finish(tr, slot, K, radius); }
     }
+}
+// a point query: xyz and the radius in w.  False: a dead one (a non-finite point, a NaN or negative radius), which gets its miss records without a walk
+__device__ __forceinline__ bool read_point(const float4 *points, uint32_t sidx, float4 &q) {
+    q = points[sidx];
+    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
+    return z == 0.0f && q.w == q.w && !(q.w < 0.0f);
+}
+struct ClosestSink {
+    const ClosestK &a;
+    template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &) const { return 1u; }
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t, float &radius) const {
+        float4 q;
+        if (read_point(a.points, sidx, q)) {
+            tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
+            radius = q.w;
+            return true;
+        }
+        write_point_miss(a, sidx, q.w);
+        return false;
+    }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t, float radius) const {
+        if (tr.bgid != kNoHit) {
+            write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
+            if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
+        } else write_point_miss(a, slot, radius);
+    }
+};
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_closest(ClosestK a) {
+    __shared__ int2 stack[kClosestLds * kTraceBlock];
+    point_trace<TravPoint<FILTER>>(a, stack, ClosestSink{a});
 }
 
 // ---- the K nearest triangles (art_closest_points_multi) ------------------------------------------------------------------------------------------
@@ -344,78 +380,42 @@ template <bool FILTER> struct TravPointMulti : TravPoint<FILTER>, KList {
 };
 struct ClosestMultiK : ClosestK { uint8_t *count; const uint32_t *gid_leaf; uint32_t max_hits; };   // tuv / ids / point: max_hits records a query, query-major; count: a byte a query, or null
 // KMAX 4 | 8: the list is KMAX KB of LDS a wave on top of the stack's 4 KB, and LDS is what bounds the waves a CU holds: 20 waves with KMAX 4, 13 with
-// KMAX 8 -- five and three a SIMD, whose registers are the kernel's to use.  The loop is k_closest's, line for line, with K records where that has one: a second text.  (One loop
-// over a record policy was built and left k_closest's code unmoved; it was measured only in a build whose list array sat in KList, where a leg of this kernel's probe read
-// above the parent's runs in two calls, and by the rule set for it the fold went out.  Unmeasured on its own since -- profiles/README.md, "one list, one hook")
+// KMAX 8 -- five and three a SIMD, whose registers are the kernel's to use.  The loop is point_trace, with K records where k_closest has one.  (The list's array is the
+// kernel's and comes to the sink as a pointer: declared in KList it cost two legs of this kernel's probe 0.4 % -- profiles/README.md, "one list, one hook")
+template <int KMAX> struct ClosestMultiSink {
+    const ClosestMultiK &a;
+    uint4 *hits;   // the kernel's __shared__ list array
+    template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &tr) const { tr.bind(hits, a.max_hits, KMAX); return tr.K; }
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &radius) const {
+        float4 q;
+        if (read_point(a.points, sidx, q)) {
+            tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bgid = kNoHit; tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
+            radius = q.w;
+            return true;
+        }
+        const size_t base = (size_t)sidx * K;   // K miss records and the count
+        for (uint32_t j = 0; j < K; j++) write_point_miss(a, base + j, q.w);
+        if (a.count) a.count[sidx] = 0;
+        return false;
+    }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t K, float radius) const {
+        const size_t base = (size_t)slot * K;
+        for (uint32_t j = 0; j < K; j++) {
+            if (j < tr.cnt) {
+                const uint4 e = tr.list[j * kTraceBlock];
+                const float u = __uint_as_float(e.y), v = __uint_as_float(e.z);
+                write_hit(a, base + j, e.w, sqrtf(__uint_as_float(e.x)), u, v);
+                if (a.point) a.point[base + j] = contact_point(a.tris, a.gid_leaf[e.w], u, v);
+            } else write_point_miss(a, base + j, radius);
+        }
+        if (a.count) a.count[slot] = (uint8_t)tr.cnt;
+    }
+};
 template <int KMAX, bool FILTER>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 5, 5))) void k_closest_multi(ClosestMultiK a) {
     __shared__ int2 stack[kClosestLds * kTraceBlock];
     __shared__ uint4 hits[KMAX * kTraceBlock];
-    int ovf[kClosestOvf];
-    int2 *lds = &stack[threadIdx.x];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t leaf_batch = a.leaf_batch;
-    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
-    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // HW_REG_XCC_ID: speed only
-    uint32_t shards_left = 8;
-    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
-    bool exhausted = false, active = false;
-    TravPointMulti<FILTER> tr;
-    tr.sp = 0; tr.cur = 0;
-    tr.bind(hits, a.max_hits, KMAX);
-    const uint32_t K = tr.K;
-    float radius = 0.0f;
-    uint32_t slot = 0;
-    for (;;) {
-        const uint64_t idle = ballot64(!active);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (n_idle >= a.refill) {
-            if (!exhausted && cur == end) {
-                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
-                if (got >= n_chunks) exhausted = true;
-                else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
-            }
-            if (!exhausted) {   // the idle lanes read the next queries of the chunk, one each
-                const uint32_t take = min(n_idle, end - cur);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (!active && rank < take) {
-                    const uint32_t sidx = cur + rank;
-                    const float4 q = a.points[sidx];
-                    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
-                    if (z == 0.0f && q.w == q.w && !(q.w < 0.0f)) {
-                        tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bgid = kNoHit; tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
-                        radius = q.w; slot = sidx; active = true;
-                    } else {   // a non-finite point, a NaN or negative radius: K miss records and the count, without a walk
-                        const size_t base = (size_t)sidx * K;
-                        for (uint32_t j = 0; j < K; j++) write_point_miss(a, base + j, q.w);
-                        if (a.count) a.count[sidx] = 0;
-                    }
-                }
-                cur += take;
-            } else if (n_idle == 64u) break;
-            if (ballot64(active) == 0ull) continue;
-        }
-        bool done = false;   // pooled_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
-#pragma unroll
-        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
-            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
-        const bool on_leaf = active && !done && tr.cur < 0;
-        const uint64_t lm = ballot64(on_leaf);
-        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
-        if (done) {
-            active = false;
-            const size_t base = (size_t)slot * K;
-            for (uint32_t j = 0; j < K; j++) {
-                if (j < tr.cnt) {
-                    const uint4 e = tr.list[j * kTraceBlock];
-                    const float u = __uint_as_float(e.y), v = __uint_as_float(e.z);
-                    write_hit(a, base + j, e.w, sqrtf(__uint_as_float(e.x)), u, v);
-                    if (a.point) a.point[base + j] = contact_point(a.tris, a.gid_leaf[e.w], u, v);
-                } else write_point_miss(a, base + j, radius);
-            }
-            if (a.count) a.count[slot] = (uint8_t)tr.cnt;
-        }
-    }
+    point_trace<TravPointMulti<FILTER>>(a, stack, ClosestMultiSink<KMAX>{a, hits});
 }
 
 // ---- a ball along a ray (art_cast_spheres) --------------------------------------------------------------------------------------------------------
@@ -494,12 +494,7 @@ template <int LDSN, bool FILTER> struct TravSweep : TravBase<false, kOvfStack4 +
     // Trav4's sign-selected slab with each child's near plane moved out and its far plane moved out by rho.  An absent child or a masked subtree carries an inverted byte box
     // (255 / 0): "left before it is entered" no longer holds once the planes have moved, so it is skipped by TravPoint's explicit test
     __device__ __forceinline__ bool step_internal(Nodes wide, int *lds, int *ovf) {
-        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + this->cur);
-        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
-        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
-        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
-        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
-        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, this->cur);
         float te[4]; bool h[4];
         const Ray &r = this->r;
         const bool ngx = r.inv.x < 0.0f, ngy = r.inv.y < 0.0f, ngz = r.inv.z < 0.0f;
@@ -553,8 +548,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 }
 
 // ---- the triangles that touch a box (art_overlap_boxes) -----------------------------------------------------------------------------------------------
-// A query is a closed world-axis box lo.xyz, - | hi.xyz, -: two 16-byte loads a lane, nothing a pool would save, so the loop is k_closest's (pop_chunk, the idle lanes of a
-// wave read the next queries of its chunk, pooled_trace's step block).  Nothing orders or shrinks: a child is skipped iff its decoded box misses the query box by comparison
+// A query is a closed world-axis box lo.xyz, - | hi.xyz, -: two 16-byte loads a lane, nothing a pool would save, so the loop is the point queries' (point_trace: the idle
+// lanes of a wave read the next queries of its chunk).  Nothing orders or shrinks: a child is skipped iff its decoded box misses the query box by comparison
 // or is inverted (absent, masked), and the stack holds references alone -- eight a lane in LDS, deeper ones in scratch.  ANY ends at the first candidate; LIST visits every
 // leaf whose box meets the query, counts every candidate and keeps the KMAX smallest gids in ascending order in LDS, [entry][lane], 4 bytes an entry: 2 KB of stack and
 // 2 KB of list a wave, so LDS bounds nothing (40 waves fit a CU's 160 KB, more than its 32 slots) and one list size serves every K.
@@ -568,7 +563,7 @@ struct OverlapK {
     uint32_t max_hits;
 };
 constexpr int kOverlapLds = 8;                                     // stack references a lane in LDS
-constexpr int kOverlapOvf = kOvfStack4 + (kLdsStack - kOverlapLds);   // Trav4's bound on pending siblings holds for any walk of the tree
+static_assert(kOverlapLds == kClosestLds, "kQueryOvf: the loop's scratch stack is what is left of Trav4's bound behind either LDS part");
 // one axis of condition 4: p0, p1, p2 the three vertices' projections, rad the box's; min and max by comparisons, so a NaN separates nothing
 __device__ __forceinline__ bool axis_separates(float p0, float p1, float p2, float rad) {
     float mn = p0, mx = p0;
@@ -601,8 +596,8 @@ template <bool ANY, bool FILTER> struct TravBox {
     uint32_t *list;      // LIST: this lane's entry 0; entry j at list[j * kTraceBlock], the min(cnt, K) smallest gids in ascending order
     int cur, sp;
     __device__ __forceinline__ void push(int ref, int *lds, int *ovf) {
-        if (sp < kOverlapLds) lds[sp * kTraceBlock] = ref; else if (sp < kOverlapLds + kOverlapOvf) *(volatile int *)&ovf[sp - kOverlapLds] = ref;   // (volatile: TravBase::push)
-        sp = min(sp + 1, kOverlapLds + kOverlapOvf);
+        if (sp < kOverlapLds) lds[sp * kTraceBlock] = ref; else if (sp < kOverlapLds + kQueryOvf) *(volatile int *)&ovf[sp - kOverlapLds] = ref;   // (volatile: TravBase::push)
+        sp = min(sp + 1, kOverlapLds + kQueryOvf);
     }
     // the next reference; true: none left, the query is finished
     __device__ __forceinline__ bool pop(int *lds, int *ovf) {
@@ -637,15 +632,10 @@ template <bool ANY, bool FILTER> struct TravBox {
         }
         return pop(lds, ovf);
     }
-    // TravPoint::step_internal's decode, then four box-against-box tests.  A child is skipped iff a comparison says its box misses the query's, or its box is inverted
+    // Four box-against-box tests.  A child is skipped iff a comparison says its box misses the query's, or its box is inverted
     // (255 / 0: absent or masked); on with the first that stays, the others wait.  (The order is speed only: nothing here shrinks)
     __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int *lds, int *ovf) {
-        const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
-        uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
-        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
-        const float ox = __uint_as_float(a.x), oy = __uint_as_float(a.y), oz = __uint_as_float(a.z);
-        const float sx = __uint_as_float((a.w & 255u) << 23), sy = __uint_as_float(((a.w >> 8) & 255u) << 23), sz = __uint_as_float(((a.w >> 16) & 255u) << 23);
-        const int refs[4] = {(int)d.x, (int)d.y, (int)d.z, (int)d.w};
+        const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, cur);
         bool h[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -665,78 +655,50 @@ template <bool ANY, bool FILTER> struct TravBox {
         return false;
     }
 };
+template <bool ANY, int KMAX> struct OverlapSink {
+    const OverlapK &a;
+    uint32_t *gids;   // the kernel's __shared__ list array
+    template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &tr) const {
+        tr.cnt = 0u;
+        tr.K = ANY ? 1u : min(max(a.max_hits, 1u), (uint32_t)KMAX);   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
+        tr.list = &gids[threadIdx.x];
+        return tr.K;
+    }
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &) const {
+        const float4 q0 = a.boxes[2 * (size_t)sidx], q1 = a.boxes[2 * (size_t)sidx + 1];
+        const float z = ((0.0f * q0.x + 0.0f * q0.y) + 0.0f * q0.z) + ((0.0f * q1.x + 0.0f * q1.y) + 0.0f * q1.z);   // 0 for six finite coordinates, NaN otherwise
+        if (z == 0.0f && q0.x <= q1.x && q0.y <= q1.y && q0.z <= q1.z) {
+            tr.lo = mk(q0.x, q0.y, q0.z); tr.hi = mk(q1.x, q1.y, q1.z); tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
+            return true;
+        }
+        if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate, lo > hi on an axis): its answer, without a walk
+        else {
+            const size_t base = (size_t)sidx * K;
+            for (uint32_t j = 0; j < K; j++) a.ids[base + j] = make_int2(-1, -1);
+            if (a.count) a.count[sidx] = 0u;
+        }
+        return false;
+    }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t K, float) const {
+        if (ANY) a.hit[slot] = (uint8_t)tr.cnt;
+        else {
+            const size_t base = (size_t)slot * K;
+            for (uint32_t j = 0; j < K; j++) {
+                if (j < tr.cnt) {
+                    const uint32_t gid = tr.list[j * kTraceBlock], prim = a.tri_prim[gid];
+                    a.ids[base + j] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
+                } else a.ids[base + j] = make_int2(-1, -1);
+            }
+            if (a.count) a.count[slot] = tr.cnt;
+        }
+    }
+};
 // (waves_per_eu 8: the leaf test holds its operands in 64 VGPRs without a spill -- DESIGN.md 3.11's table)
 template <bool ANY, int KMAX, bool FILTER>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_overlap(OverlapK a) {
     __shared__ int stack[kOverlapLds * kTraceBlock];
     __shared__ uint32_t gids[(ANY ? 1 : KMAX) * kTraceBlock];
-    int ovf[kOverlapOvf];
-    int *lds = &stack[threadIdx.x];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t leaf_batch = a.leaf_batch;
-    const uint32_t n_chunks = (a.total + a.chunk - 1) / a.chunk;   // (pooled_trace's bounds: total <= ART_CAST_MAX_RAYS)
-    uint32_t shard = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;   // HW_REG_XCC_ID: speed only
-    uint32_t shards_left = 8;
-    uint32_t cur = 0, end = 0;   // wave-uniform: the unread part of this wave's chunk
-    bool exhausted = false, active = false;
-    TravBox<ANY, FILTER> tr;
-    tr.sp = 0; tr.cur = 0; tr.cnt = 0u;
-    tr.K = ANY ? 1u : min(max(a.max_hits, 1u), (uint32_t)KMAX);   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
-    tr.list = &gids[threadIdx.x];
-    const uint32_t K = tr.K;
-    uint32_t slot = 0;
-    for (;;) {
-        const uint64_t idle = ballot64(!active);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (n_idle >= a.refill) {
-            if (!exhausted && cur == end) {
-                const uint32_t got = pop_chunk(a.cursors, n_chunks, lane, shard, shards_left);
-                if (got >= n_chunks) exhausted = true;
-                else { cur = got * a.chunk; end = min(cur + a.chunk, a.total); }
-            }
-            if (!exhausted) {   // the idle lanes read the next queries of the chunk, one each
-                const uint32_t take = min(n_idle, end - cur);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (!active && rank < take) {
-                    const uint32_t sidx = cur + rank;
-                    const float4 q0 = a.boxes[2 * (size_t)sidx], q1 = a.boxes[2 * (size_t)sidx + 1];
-                    const float z = ((0.0f * q0.x + 0.0f * q0.y) + 0.0f * q0.z) + ((0.0f * q1.x + 0.0f * q1.y) + 0.0f * q1.z);   // 0 for six finite coordinates, NaN otherwise
-                    if (z == 0.0f && q0.x <= q1.x && q0.y <= q1.y && q0.z <= q1.z) {
-                        tr.lo = mk(q0.x, q0.y, q0.z); tr.hi = mk(q1.x, q1.y, q1.z); tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
-                        slot = sidx; active = true;
-                    } else if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate, lo > hi on an axis): its answer, without a walk
-                    else {
-                        const size_t base = (size_t)sidx * K;
-                        for (uint32_t j = 0; j < K; j++) a.ids[base + j] = make_int2(-1, -1);
-                        if (a.count) a.count[sidx] = 0u;
-                    }
-                }
-                cur += take;
-            } else if (n_idle == 64u) break;
-            if (ballot64(active) == 0ull) continue;
-        }
-        bool done = false;   // pooled_trace's step block: node steps, then the triangle tests once enough lanes wait on one (or nobody can move without it)
-#pragma unroll
-        for (int rep_ = 0; rep_ < ART_NODE_REPS; rep_++)
-            if (active && !done && tr.cur >= 0) done = tr.step_internal(a.wide, lds, ovf);
-        const bool on_leaf = active && !done && tr.cur < 0;
-        const uint64_t lm = ballot64(on_leaf);
-        if (lm != 0ull && ((uint32_t)__popcll(lm) >= leaf_batch || ballot64(active && !done && tr.cur >= 0) == 0ull)) { if (on_leaf) done = tr.step_leaf(a, lds, ovf); }
-        if (done) {
-            active = false;
-            if (ANY) a.hit[slot] = (uint8_t)tr.cnt;
-            else {
-                const size_t base = (size_t)slot * K;
-                for (uint32_t j = 0; j < K; j++) {
-                    if (j < tr.cnt) {
-                        const uint32_t gid = tr.list[j * kTraceBlock], prim = a.tri_prim[gid];
-                        a.ids[base + j] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
-                    } else a.ids[base + j] = make_int2(-1, -1);
-                }
-                if (a.count) a.count[slot] = tr.cnt;
-            }
-        }
-    }
+    point_trace<TravBox<ANY, FILTER>>(a, stack, OverlapSink<ANY, KMAX>{a, gids});
 }
 
 // The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
