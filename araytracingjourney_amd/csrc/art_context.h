@@ -100,7 +100,7 @@ struct AsVersion {
     // Pinned host memory the refit's kernels read and write IN PLACE (no copies in front of or behind the launches): the primitive table as of this refit, a byte per
     // primitive (moved since this version was written), and the refit's result (cost sum, root half-area, start / end device stamps).  d*: the device's addresses of the same.
     DevPrim *h_prims = nullptr, *dh_prims = nullptr; uint8_t *h_touched = nullptr, *dh_touched = nullptr; double *h_result = nullptr, *dh_result = nullptr;
-    uint32_t *mark = nullptr;            // per 4-wide node (art_build.hip k_retri): all zero between refits
+    uint32_t *mark = nullptr;            // per 4-wide node (art_refit.hip retri_one): all zero between refits
     uint32_t *h_dirty = nullptr, *dh_dirty = nullptr;   // pinned: the batches this refit runs (those that hold a primitive that moved since the version was written)
     double *batch_cost = nullptr; bool cost_cached = false;   // device: every batch's share of this version's cost (large trees); valid once a refit has run all batches
     double *acc = nullptr;               // 4 doubles of device scratch of the refit's last launch: zero between refits

@@ -112,7 +112,7 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, ON
             // 4-wide node, float boxes (128 B, two scalar loads).  Its children were sorted at build time along the axis `ax` their centroids spread
             // most on, so the packet's front-to-back order is 0,1,2,3 or 3,2,1,0 by the sign of its rays' direction on that axis -- no per-lane
             // distances, no votes.  (Order only steers the culling: the answer is order-independent)  Absent children carry a
-            // point box out at 3e38, which no ray passes (art_build.hip).  Measured against the binary walk (profiles/README.md r2): scalar
+            // point box out at 3e38, which no ray passes (art_wide.hip).  Measured against the binary walk (profiles/README.md r2): scalar
             // instructions -43 %, vector instructions +9 % (all four boxes of a node are tested, also below a child the binary walk would have
             // culled), half the dependent node fetches: config 2 +1 %, config 3 +8 %, config 4 +11 % rays/s.  The default since round 2
             // (ArtTuning.packet_wide = 2 selects the binary walk).

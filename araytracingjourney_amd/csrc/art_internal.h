@@ -81,7 +81,8 @@ constexpr uint32_t kTileRingMax = 8;    // caller-owned compact tile buffers per
 int32_t ring_rewind(ArtContext *ctx);   // art_api.hip: waits for every frame in flight, then the next art_trace is launch 0 again (ring slot 0, first tile buffer)
 void set_last_error(const char *msg);   // art_api.hip: the thread's art_last_error() string, for entry points that live in other files
 
-// ---- launch wrappers (art_build.hip / art_trace.hip, art_frame.hip, art_query.hip, art_sweeps.hip, art_present.hip) ---------------------------------------------------------
+// ---- launch wrappers (art_build.hip, art_wide.hip, art_refit.hip / art_trace.hip, art_frame.hip, art_query.hip, art_sweeps.hip, art_present.hip) ----------------------------
+#define HIPQ(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)   // the builders' early return of a hipError_t
 struct BuildInputs {
     const DevPrim *prims; uint32_t n_prims; const uint32_t *prim_first_tri; // device
     uint32_t T; uint32_t morton_bits;
@@ -101,6 +102,7 @@ struct Arena {
     template <class T> T *take(size_t n) { T *p = reinterpret_cast<T *>(mem.p + off); off += pad(n * sizeof(T)); return p; }   // the caller reserved the sum of pad(...)
     void release() { mem.release(); off = 0; }
 };
+struct WalkTree { int32_t *child; float *lo, *hi; };   // Lbvh::walk_tree()
 struct Lbvh {               // canonical binary LBVH, device arrays: it owns the DevBuf members, the plain pointers are views into `block`; `l = Lbvh{}` frees a tree
     Arena *arena = nullptr; // host: the context's scratch for the build phases (not owned; null: a phase allocates and frees its own)
     uint32_t *leaf_gid;     // [T]
@@ -127,6 +129,7 @@ struct Lbvh {               // canonical binary LBVH, device arrays: it owns the
     std::vector<uint32_t> batch_prim_off, batch_prim_ids;                         // host: the primitives whose triangles lie in batch b: ids [off[b], off[b + 1]) -- a refit launches the batches that hold a primitive that moved
     int32_t *trav_child;    // [2*(T-1)] topology of the traversal nodes when it is not the canonical one (sah_build), else null
     float *trav_lo, *trav_hi; // [(T-1)*3]
+    WalkTree walk_tree() const { return trav_child ? WalkTree{trav_child, trav_lo, trav_hi} : WalkTree{child, node_lo, node_hi}; }   // the binary tree the walks use: what the 4-wide collapse and the node records are made from
     DevBuf<int32_t> own_trav_child; DevBuf<float> own_trav_lo, own_trav_hi;   // ... when they are allocations of their own (lbvh_claim_trav); empty when trav_* are the room reserved in the block
     DevBuf<char> block;     // host: ONE allocation behind the arrays lbvh_build makes (leaf_gid .. shade_tris, cbounds) and room for the traversal tree's three (res_trav_*): two dozen
                             // hipMalloc per build were 0.6-1 ms inside build_ms; the pieces are views into it
@@ -144,12 +147,13 @@ hipError_t wide_build(Lbvh &l, uint32_t T, hipStream_t s, bool on_host = false);
 hipError_t sah_build(Lbvh &l, uint32_t T, hipStream_t s);
 // the binned SAH of sah_build, level by level on the device (art_sahdev.hip)
 hipError_t sah_build_device(Lbvh &l, uint32_t T, hipStream_t s);
-void launch_emit_nodes(Lbvh &l, uint32_t T, hipStream_t s);
+void launch_emit_nodes(Lbvh &l, uint32_t T, hipStream_t s);   // art_build.hip: l.nodes from l.walk_tree() and the leaf boxes
 // an empty launch from the translation unit of each builder: the runtime loads a unit's code object at its first launch (10-20 ms a process used to pay inside its first
-// art_scene_build); art_create pays it instead
-void build_prewarm(hipStream_t s);   // art_build.hip (LBVH, 4-wide collapse, refit, rocPRIM's sort and scans)
+// art_scene_build, and the refit's unit inside the first moved frame); art_create pays it instead
+void build_prewarm(hipStream_t s);   // art_build.hip (LBVH, rocPRIM's sort), and through the next two art_wide.hip (4-wide collapse, rocPRIM's scan) and art_refit.hip
+void wide_prewarm(hipStream_t s); void refit_prewarm(hipStream_t s);
 void sah_prewarm(hipStream_t s);     // art_sahdev.hip
-// refit after a model moved (art_build.hip): the triangle records of a version of the acceleration structure from the shading records and that version's
+// refit after a model moved (art_refit.hip; binary_refit: art_build.hip): the triangle records of a version of the acceleration structure from the shading records and that version's
 // primitive table; its 4-wide nodes bottom-up, level by level (l.wide_levels); the tree's surface-area cost (2 doubles: sum of child half-areas, root half-area);
 // the binary trees and node records from a version's triangles (on demand, synchronises)
 // prims_host / touched: PINNED host memory the kernels read in place (the version's staging copies: one byte per primitive -- whose triangles to make again, 1 moved,
@@ -166,7 +170,7 @@ struct RefitArgs {
     bool fold;                                 // the quantised records and the cost in the refit's own workgroups (large trees: kFoldRequantNodes / ArtTuning.refit_fold_nodes)
 };
 constexpr uint8_t kTouchRegather = 2u;         // RefitArgs::touched: the primitive's vertices were replaced (bit 0: it moved)
-constexpr uint32_t kFoldRequantNodes = 400000;   // trees of this many 4-wide nodes and more: the refit's workgroups make the quantised records and the cost themselves (art_build.hip launch_refit)
+constexpr uint32_t kFoldRequantNodes = 400000;   // trees of this many 4-wide nodes and more: the refit's workgroups make the quantised records and the cost themselves (art_refit.hip launch_refit)
 void launch_refit(const RefitArgs &r, hipStream_t s);
 void launch_wide_parents(uint32_t n_wide, const DevNodeW *widef, uint32_t *leaf_parent, uint32_t *node_parent, hipStream_t s);
 hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s);   // the parents (launch_wide_parents) and the work lists: all of them into l, or on a failure none (synchronises: a one-off of the scene's first version ring)

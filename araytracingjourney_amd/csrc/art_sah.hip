@@ -17,8 +17,6 @@
 namespace art {
 namespace {
 
-#define HIPS(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 constexpr int kBins = 32;
 
 struct Box3 {
@@ -220,9 +218,9 @@ hipError_t sah_build(Lbvh &l, uint32_t T, hipStream_t s) {
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     auto t0 = now();
     std::vector<float> llo((size_t)T * 3), lhi((size_t)T * 3);
-    HIPS(hipStreamSynchronize(s));
-    HIPS(hipMemcpy(llo.data(), l.leaf_lo, (size_t)T * 12, hipMemcpyDeviceToHost));
-    HIPS(hipMemcpy(lhi.data(), l.leaf_hi, (size_t)T * 12, hipMemcpyDeviceToHost));
+    HIPQ(hipStreamSynchronize(s));
+    HIPQ(hipMemcpy(llo.data(), l.leaf_lo, (size_t)T * 12, hipMemcpyDeviceToHost));
+    HIPQ(hipMemcpy(lhi.data(), l.leaf_hi, (size_t)T * 12, hipMemcpyDeviceToHost));
     auto t1 = now();
     Builder B; B.llo = llo.data(); B.lhi = lhi.data();
     unsigned hw = std::thread::hardware_concurrency();
@@ -250,11 +248,11 @@ hipError_t sah_build(Lbvh &l, uint32_t T, hipStream_t s) {
         for (auto &th : pool) th.join();
     }
     auto t3 = now();
-    HIPS(hipMemcpy(l.nodes, nodes.data(), (size_t)NI * sizeof(DevNode), hipMemcpyHostToDevice));
-    HIPS(lbvh_claim_trav(l, NI));
-    HIPS(hipMemcpy(l.trav_child, B.child.data(), (size_t)NI * 8, hipMemcpyHostToDevice));
-    HIPS(hipMemcpy(l.trav_lo, B.nlo.data(), (size_t)NI * 12, hipMemcpyHostToDevice));
-    HIPS(hipMemcpy(l.trav_hi, B.nhi.data(), (size_t)NI * 12, hipMemcpyHostToDevice));
+    HIPQ(hipMemcpy(l.nodes, nodes.data(), (size_t)NI * sizeof(DevNode), hipMemcpyHostToDevice));
+    HIPQ(lbvh_claim_trav(l, NI));
+    HIPQ(hipMemcpy(l.trav_child, B.child.data(), (size_t)NI * 8, hipMemcpyHostToDevice));
+    HIPQ(hipMemcpy(l.trav_lo, B.nlo.data(), (size_t)NI * 12, hipMemcpyHostToDevice));
+    HIPQ(hipMemcpy(l.trav_hi, B.nhi.data(), (size_t)NI * 12, hipMemcpyHostToDevice));
     if (log) std::fprintf(stderr, "[art] sah_build %u leaves: wait + read-back %.1f ms, build %.1f, node records %.1f, upload %.1f\n", T, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
     return hipSuccess;
 }

@@ -24,8 +24,6 @@
 namespace art {
 namespace {
 
-#define HIPQ(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 #ifndef ART_SAH_BINS
 #define ART_SAH_BINS 64
 #endif

@@ -1,5 +1,5 @@
 // art_scene.hip -- the scene behind include/art.h: the primitive table and its setters, art_scene_build, the ring of versions of the acceleration structure (refit,
-// deformation), the trees the non-default walks read on demand, and the tree read-outs of the parity surface.  Host code only; the kernels are art_build.hip's.
+// deformation), the trees the non-default walks read on demand, and the tree read-outs of the parity surface.  Host code only; the kernels are art_build.hip's (LBVH), art_wide.hip's (4-wide collapse) and art_refit.hip's (refit).
 #include "art_context.h"
 #include <chrono>
 #include <cmath>

@@ -107,7 +107,7 @@ template <bool ANY, int LDSN = kLdsStack, bool ALPHA = false> struct Trav4 : Tra
         float te[4]; bool h[4];
         // The slab with the entry plane of each axis chosen by the lane's direction sign -- ONE select per axis picks the word that holds the four children's near
         // planes, one the far planes -- instead of min / max of both planes per child: fma is monotone in the plane coordinate, so min(t0, t1) IS the near plane's
-        // t for a box with lo <= hi, bit for bit (the packet walks' octant trick, per lane).  An absent child carries an inverted box (art_build.hip): whatever the
+        // t for a box with lo <= hi, bit for bit (the packet walks' octant trick, per lane).  An absent child carries an inverted box (art_records.h wide_quantise): whatever the
         // signs it is left before it is entered, so no valid-mask test.  33 -> 22 vector instructions a child; config 5 16 440 -> 16 980 Mray/s (profiles/README.md round 3).
         const Ray &r = this->r;
         const bool ngx = r.inv.x < 0.0f, ngy = r.inv.y < 0.0f, ngz = r.inv.z < 0.0f;

@@ -102,6 +102,15 @@ def _render(R, sc, extent, tuning, cutoffs=None, disabled=(), before_build=False
     return r
 
 
+def _render_outputs(R, sc, extent, tuning, rays, **kw):
+    """_outputs of a context made for them, which is closed again (a Renderer and its models refer to each other: unclosed, it keeps its context until a garbage collection)"""
+    r = _render(R, sc, extent, tuning, **kw)
+    try:
+        return _outputs(r, rays)
+    finally:
+        r.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", list(FORMS))
 def test_a_card_cut_everywhere_is_a_disabled_card(R, get_scene, scenes, form):
@@ -111,12 +120,12 @@ def test_a_card_cut_everywhere_is_a_disabled_card(R, get_scene, scenes, form):
     card = len(sc.primitives) - 1
     rays = random_rays(2048, 5, radius=0.9)
     t = FORMS[form]
-    cut = _outputs(_render(R, sc, (64, 64), t, cutoffs={card: 0.5}), rays)
-    off = _outputs(_render(R, sc, (64, 64), t, disabled=[card]), rays)
+    cut = _render_outputs(R, sc, (64, 64), t, rays, cutoffs={card: 0.5})
+    off = _render_outputs(R, sc, (64, 64), t, rays, disabled=[card])
     _assert_equal(cut, off, f"{form}: cut card vs disabled card")
-    cut_b = _outputs(_render(R, sc, (64, 64), t, cutoffs={card: 0.5}, before_build=True), rays)
+    cut_b = _render_outputs(R, sc, (64, 64), t, rays, cutoffs={card: 0.5}, before_build=True)
     _assert_equal(cut_b, off, f"{form}: cutoff set before the build vs disabled card")
-    opaque = _outputs(_render(R, sc, (64, 64), t), rays)
+    opaque = _render_outputs(R, sc, (64, 64), t, rays)
     assert not np.array_equal(opaque["depth"], off["depth"]) and not np.array_equal(opaque["shadow_bits"], off["shadow_bits"]), "the card is neither seen nor casting shadows"
     assert (opaque["q_ids"] != off["q_ids"]).any() and not np.array_equal(opaque["ao"], off["ao"])
 
@@ -130,14 +139,16 @@ def test_nothing_cut_is_the_opaque_scene(R, get_scene, scenes, form):
     full = _scene(get_scene("cornell"), [_ceiling_card(scenes, np.full((8, 8), 255, np.uint8))])
     zero = _scene(get_scene("cornell"), [_ceiling_card(scenes, np.zeros((8, 8), np.uint8))])
     card = len(full.primitives) - 1
-    ref = _outputs(_render(R, full, (64, 64), t), rays)
-    _assert_equal(_outputs(_render(R, full, (64, 64), t, cutoffs={card: 0.5}), rays), ref, f"{form}: alpha 255, cutoff 0.5")
-    _assert_equal(_outputs(_render(R, full, (64, 64), t, cutoffs={card: 1.0}), rays), ref, f"{form}: alpha 255, cutoff 1")
-    ref0 = _outputs(_render(R, zero, (64, 64), t), rays)
+    ref = _render_outputs(R, full, (64, 64), t, rays)
+    _assert_equal(_render_outputs(R, full, (64, 64), t, rays, cutoffs={card: 0.5}), ref, f"{form}: alpha 255, cutoff 0.5")
+    _assert_equal(_render_outputs(R, full, (64, 64), t, rays, cutoffs={card: 1.0}), ref, f"{form}: alpha 255, cutoff 1")
+    ref0 = _render_outputs(R, zero, (64, 64), t, rays)
     r = _render(R, zero, (64, 64), t, cutoffs={card: 0.5})
     r.models_mut()[0].set_alpha_cutoff(card, 0.0)   # back to opaque: the next frame
     r.trace()
-    _assert_equal(_outputs(r, rays), ref0, f"{form}: cutoff back to 0")
+    got = _outputs(r, rays)
+    r.close()
+    _assert_equal(got, ref0, f"{form}: cutoff back to 0")
 
 
 def _card_alpha(tw=16, th=16):
@@ -177,6 +188,7 @@ def test_partial_cut_against_numpy(R, get_scene, scenes, form):
     cam = sc.camera
     view, view_inv, proj, proj_inv = nps.camera_matrices(cam["pos"], cam["dir"], w / h, cam["fovy"], cam["znear"], cam["zfar"])
     ls = [nps.light_from_record(x) for x in r._lights.copy_lights_shader_data()[0][:len(lights)]]
+    r.close()
     v0, e1, e2 = tris[:, 0], tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]
 
     def candidates(o, d, tmin, tmax):
@@ -278,8 +290,10 @@ def test_cutoffs_change_without_a_build_with_sixteen_frames_in_flight(R, get_sce
         fresh_sc = S.Scene("x", list(base.primitives) + [P(v_i, card0.indices, card0.tex, mm_i)], sc.camera, sc.lights)
         f = _render(R, fresh_sc, (w, h), {}, cutoffs={ci: c} if c > 0 else None)
         f.sync()
-        assert np.array_equal(outs[k][1].view(np.uint32), f.read_depth().view(np.uint32)), f"frame {k}: depth"
-        assert np.array_equal(outs[k][0].view(np.uint32), f.read_color().view(np.uint32)), f"frame {k}: colour"
+        f_depth, f_color = f.read_depth(), f.read_color()
+        f.close()
+        assert np.array_equal(outs[k][1].view(np.uint32), f_depth.view(np.uint32)), f"frame {k}: depth"
+        assert np.array_equal(outs[k][0].view(np.uint32), f_color.view(np.uint32)), f"frame {k}: colour"
     # residency: the card out (a disabled primitive) and back in keeps its cutoff
     m.set_alpha_cutoff(0, 0.5)
     r.trace(); r.sync(); want = r.read_depth().copy()
@@ -287,6 +301,7 @@ def test_cutoffs_change_without_a_build_with_sixteen_frames_in_flight(R, get_sce
     r._L.art_scene_set_primitive_enabled(r._ctx, m.primitive_ids[0], 1); r.trace(); r.sync()
     assert np.array_equal(r.read_depth().view(np.uint32), want.view(np.uint32)), "residency out and in lost the mask"
     assert r.stats()["rebuilds"] == st0["rebuilds"] and not r.needs_build()
+    r.close()
 
 
 @pytest.mark.gpu
@@ -301,7 +316,9 @@ def test_config2_banners_masked(R, get_scene):
     def frame(tuning, masked=True):
         r = _render(R, sc, (w, h), tuning, cutoffs={i: 0.5 for i in BANNERS} if masked else None)
         r.sync()
-        return r.read_hits()[1], r.read_depth(), r.read_color(), r.read_shadow_bits()
+        out = r.read_hits()[1], r.read_depth(), r.read_color(), r.read_shadow_bits()
+        r.close()
+        return out
     ref = frame({})
     for name in ("fused-binary", "per-ray", "per-ray-wide"):
         got = frame(FORMS[name])
@@ -331,6 +348,7 @@ def test_bad_calls_change_nothing(R, get_scene, scenes):
     r.trace(); r.sync()
     assert np.array_equal(r.read_color().view(np.uint32), want.view(np.uint32))
     assert r.stats()["rebuilds"] == 0
+    r.close()
 
 
 def _mask_glb(path, prims, cutoff=0.4, blend_first=False):

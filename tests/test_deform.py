@@ -126,6 +126,51 @@ def test_cornell_last_primitive_deforms_every_frame(R, orc, get_scene, dynamic):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("fold", [0, 1], ids=["requant-launch", "requant-folded"])
+def test_u32_and_u16_indices_in_one_table(R, orc, get_scene, scenes, fold):
+    """the Cornell box whose moving primitive carries its indices as uint32 and the others as uint16 (both widths of the one index fetch, in the build's kernels and in
+    the refit's gather): the frame as built, two deformed frames, a moved one, one without the primitive and one with it back -- each the oracle's over the same primitives"""
+    from araytracingjourney_amd._lib import check
+    base = get_scene("cornell")
+    movers = [len(base.primitives) - 1]
+    P = type(base.primitives[0])
+    prims = [P(p.verts, p.indices.astype(np.uint32), p.tex, p.model) if j in movers else p for j, p in enumerate(base.primitives)]
+    assert prims[movers[0]].indices.dtype == np.uint32 and all(p.indices.dtype == np.uint16 for p in prims[:-1])
+    sc = scenes.Scene(base.name, prims, base.camera, base.lights)
+    w, h, F = 64, 64, 2
+    lights = sc.lights[:1]
+    r, model = _setup(R, sc, movers, (w, h), lights, frames_in_flight=F, tuning=dict(refit_fold_nodes=fold))
+    state = _State(sc, movers)
+
+    def enable(on):
+        for pid in model.primitive_ids:
+            check(r._L.art_scene_set_primitive_enabled(r._ctx, pid, 1 if on else 0))
+        state.enabled = on
+
+    def moved():
+        m = _pose(prims[movers[0]].model, 3); model.set_model_matrix(m); state.model = m
+
+    steps = [("built", lambda: None), ("deformed 0", lambda: _deform(model, state, 0)), ("deformed 1", lambda: _deform(model, state, 1)), ("moved", moved),
+             ("disabled", lambda: enable(False)), ("enabled again", lambda: enable(True))]
+    wrong = []
+    for k in range(0, len(steps), F):   # two frames in flight, then both against the oracle
+        got = []
+        for what, edit in steps[k:k + F]:
+            edit()
+            r.trace()
+            got.append((what, state.prims(), _grab(r)))
+        r.sync()
+        for what, ps, ptr in got:
+            try:
+                _check(orc, sc, ps, ptr, w, h, lights, what)
+            except AssertionError as e:   # (every step is looked at: a wrong fetch in the build alone would hide the gather's and the move's)
+                wrong.append(str(e).splitlines()[0])
+    assert not wrong, wrong
+    assert r.stats()["refits"] == len(steps) - 1 and r.stats()["rebuilds"] == 0
+    r.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("versions", [3, 1, 8])
 def test_two_primitives_deform_with_sixteen_frames_in_flight(R, orc, get_scene, scenes, versions):
     """sponza_like's two displaced spheres deformed before each of 16 frames launched without a host sync: every frame the oracle's, 16 refits, no rebuild"""

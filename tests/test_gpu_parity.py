@@ -791,8 +791,10 @@ def test_api_state_and_argument_errors(R, get_scene):
     assert r._L.art_get_wide_nodes(r._ctx, small.ctypes.data, None, 1, C.byref(n)) == _lib.ART_E_INVALID and n.value > 1   # buffer too small: the count is still reported
     p = sc.primitives[0]
     bad = p.indices.copy(); bad[0] = p.verts.shape[0]  # index out of range is rejected on the host, never reaches a kernel
+    tiny = R.Renderer((8, 8))
     with pytest.raises(_lib.ArtError) as e:
-        R.Renderer((8, 8)).add_model([type(p)(p.verts, bad, p.tex, p.model)])
+        tiny.add_model([type(p)(p.verts, bad, p.tex, p.model)])
+    tiny.close()
     assert "index out of range" in str(e.value)
     cfg = _lib.ArtConfig(device=99, width=8, height=8)
     ctx = C.c_void_p()
@@ -1524,6 +1526,8 @@ def test_packing_and_tonemap_match_oracle(R, orc, get_scene):
     r.render_frame(sync=False)                                                     # no AO for this frame: ao = 255
     r.present()
     assert np.abs(r.read_present().astype(int) - orc.present(r.read_color())[1].astype(int)).max() <= 1
+    unpresented = R.renderer_for_scene(sc, (32, 32))
     with pytest.raises(Exception):
-        R.renderer_for_scene(sc, (32, 32)).read_present()
+        unpresented.read_present()
+    unpresented.close()
     r.close()

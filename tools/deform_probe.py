@@ -21,8 +21,8 @@ a = ap.parse_args()
 
 
 def regs():
-    """VGPRs / SGPR and VGPR spills / waves per SIMD of k_refit_sub<true> and <false>, as the compiler reports them for the code object of art_build.hip"""
-    src = os.path.join(ROOT, "araytracingjourney_amd", "csrc", "art_build.hip")
+    """VGPRs / SGPR and VGPR spills / waves per SIMD of k_refit_sub<true> and <false>, as the compiler reports them for the code object of art_refit.hip"""
+    src = os.path.join(ROOT, "araytracingjourney_amd", "csrc", "art_refit.hip")
     out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17",
                           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull], capture_output=True, text=True, timeout=600).stderr
     res, cur = {}, None

@@ -5,7 +5,8 @@
 Every kernel in the gfx950 code objects of either library (kernel_resources.code_objects) is disassembled with llvm-objdump and compared by mangled name: the instruction
 stream, and the resource figures kernel_resources() reads.  A stream is what is left of a kernel's disassembly without addresses and encodings; branch operands are
 offsets already, and an address made from the program counter (s_getpc_b64, then s_add_u32 / s_addc_u32 with the distance) is replaced by the symbol it lands on, so a
-kernel may sit anywhere in its code object, beside any neighbours.  Prints the kernels that differ or exist on one side only and exits 1 if there are any.  No GPU is needed."""
+kernel may sit anywhere in its code object, beside any neighbours; a kernel with a copy in several code objects (a rocPRIM template, once per unit that calls it) is
+compared as the set of its distinct streams, so a unit more or less that calls it changes nothing.  Prints the kernels that differ or exist on one side only and exits 1 if there are any.  No GPU is needed."""
 import bisect
 import os
 import re
@@ -44,7 +45,8 @@ def streams(path):
             for line in text.splitlines():
                 m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
                 if m:
-                    cur, end, pc_of = funcs.setdefault(m.group(1), []), end_of.get(m.group(1), 0), {}
+                    cur, end, pc_of = [], end_of.get(m.group(1), 0), {}
+                    funcs.setdefault(m.group(1), []).append(cur)   # (a library template's kernel has a copy in every unit that uses it)
                     continue
                 m = re.match(r"^\s+(\S.*?)\s*//\s*([0-9A-Fa-f]+):", line)
                 if cur is None or not m:
@@ -65,7 +67,7 @@ def streams(path):
                     ins = re.sub(r", (0x[0-9a-f]+|-?\d+)$", ", <high>", ins)
                     pc_of = {}
                 cur.append(ins)
-    return funcs
+    return {name: sorted(set(map(tuple, copies))) for name, copies in funcs.items()}
 
 
 def main():
@@ -86,13 +88,16 @@ def main():
         a, b = str_old.get(name, []), str_new.get(name, [])
         if not a or not b:
             why.append("no disassembly found")
+        elif a != b and (len(a) > 1 or len(b) > 1):
+            why.append(f"its copies in several code objects: {len(a)} -> {len(b)} distinct streams")
         elif a != b:
+            a, b = a[0], b[0]
             at = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
             why.append(f"stream {len(a)} -> {len(b)} instructions, first difference at {at}: {a[at] if at < len(a) else '(end)'} | {b[at] if at < len(b) else '(end)'}")
         if why:
             print(f"differs: {name}: " + "; ".join(why))
             bad += 1
-    n_ins = sum(len(str_new.get(k, [])) for k in res_new)
+    n_ins = sum(len(s) for k in res_new for s in str_new.get(k, []))
     print(f"{len(res_old)} kernels in the old library, {len(res_new)} in the new, {n_ins} instructions compared: {bad} differ")
     sys.exit(1 if bad else 0)
 
