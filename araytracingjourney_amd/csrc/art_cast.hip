@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes; DESIGN.md 3.5 .. 3.11) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings; DESIGN.md 3.5 .. 3.12) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
 // entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -248,6 +248,22 @@ int32_t art_cast_spheres(ArtContext *c, const ArtSphereCast *d) {
     CastArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
     a.rays = (const float4 *)d->rays_dev; a.kind = CastKind::Sweep; a.radius = d->radius + 0.0f; a.point = (float4 *)d->point_dev;   // (-0.0 + 0.0 is +0.0)
+    launch_cast(a, q.stream);
+    return cast_commit(c, q, d->n);
+}
+
+// ---- the surfaces each ray enters and leaves (include/art.h: art_cast_crossings) ----------------------------------------------------------------------
+// A cast like the others, counted in casts and rays; its one output is the pair of counts (no tuv / ids records).
+int32_t art_cast_crossings(ArtContext *c, const ArtRayCrossings *d) {
+    const char *who = "art_cast_crossings"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev))) return r;
+    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
+    if ((r = check_buffer(who, "cross_dev", d->cross_dev, 8, d->n))) return r;
+    if (!c->built) return fail(ART_E_STATE, "art_cast_crossings: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    CastArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, nullptr, nullptr, a, &q); if (r) return r;
+    a.rays = (const float4 *)d->rays_dev; a.kind = CastKind::Crossings; a.cross = (uint2 *)d->cross_dev;
     launch_cast(a, q.stream);
     return cast_commit(c, q, d->n);
 }

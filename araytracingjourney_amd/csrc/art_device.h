@@ -214,6 +214,24 @@ __device__ __forceinline__ bool moller_trumbore(const Ray &r, V3 v0, V3 e1, V3 e
     t = tt; u = uu; v = vv;
     return true;
 }
+// moller_trumbore, expression for expression, which also hands out its det = dot3(e1, cross3(d, e2)) = -d . (e1 x e2): > 0 the ray goes against the winding normal,
+// < 0 along it (art_cast_crossings, DESIGN.md 3.12: the sign of a crossing comes from the evaluation that accepts it)
+__device__ __forceinline__ bool moller_trumbore_det(const Ray &r, V3 v0, V3 e1, V3 e2, float &t, float &u, float &v, float &det_out) {
+    V3 p = cross3(r.d, e2);
+    float det = dot3(e1, p);
+    if (det == 0.0f) return false;
+    float inv = 1.0f / det;
+    V3 tv = r.o - v0;
+    float uu = dot3(tv, p) * inv;
+    if (!(uu >= -ART_BARY_EPS && uu <= 1.0f + ART_BARY_EPS)) return false;
+    V3 q = cross3(tv, e1);
+    float vv = dot3(r.d, q) * inv;
+    if (!(vv >= -ART_BARY_EPS && uu + vv <= 1.0f + ART_BARY_EPS)) return false;
+    float tt = dot3(e2, q) * inv;
+    if (!(tt > r.tmin && tt < r.tmax)) return false;
+    t = tt; u = uu; v = vv; det_out = det;
+    return true;
+}
 
 // the same arithmetic without the early exits: in a packet some lane nearly always survives each test, so the wave pays for
 // every stage anyway and the exits only add exec-mask bookkeeping (det == 0 lanes compute inf/NaN that the flag discards)

@@ -309,8 +309,9 @@ constexpr uint32_t kCastCursorWords = 8 * 32;           // eight per-XCD cursors
 //   Closest, Any  art_cast_rays (art_query_* are host wrappers over it): Any writes hit[i] = 0 | 1 and no records
 //   Multi         art_cast_rays_multi (3.6): tuv / ids hold max_hits records a ray, ray-major; count (optional) a byte a ray
 //   Sweep         art_cast_spheres (3.9): a ball of `radius` along each ray; point (optional) the contact point, w = 1 (a miss: zeros)
-enum class CastKind { Closest, Any, Multi, Sweep };
-struct CastArgs : QueryArgs { const float4 *rays; CastKind kind; uint8_t *hit; uint32_t max_hits; uint8_t *count; float radius; float4 *point; };
+//   Crossings     art_cast_crossings (3.12): cross holds (entries, exits) a ray, uncapped; tuv / ids are not used
+enum class CastKind { Closest, Any, Multi, Sweep, Crossings };
+struct CastArgs : QueryArgs { const float4 *rays; CastKind kind; uint8_t *hit; uint32_t max_hits; uint8_t *count; float radius; float4 *point; uint2 *cross; };
 void launch_cast(const CastArgs &c, hipStream_t s);
 // Nearest-point queries (art_closest_points): points[i] = p.xyz, r; a miss record's x is r; point (optional) = the surface point, w = 1 (a miss: zeros)
 struct ClosestArgs : QueryArgs { const float4 *points; float4 *point; };

@@ -1,4 +1,4 @@
-// art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), nearest surface points (k_closest), the K nearest
+// art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), the crossings of each ray (k_cross), nearest surface points (k_closest), the K nearest
 // triangles (k_closest_multi), swept spheres (k_sweep) and the triangles that touch a box (k_overlap).  The casts and the sweep are Sources and candidate policies of
 // art_walk.h's pooled loop; the point and box queries, which have no ray to pool, are Sinks and walks of one loop of their own (point_trace).  What the queries share stands
 // once: at the top the ray read, the hit and miss records, the contact point, the mask test and the 4-wide node's decode (load_node4); the sorted list of both K-walks
@@ -157,6 +157,46 @@ template <int KMAX> struct CastMultiSource {
 template <int KMAX, bool ALPHA>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 4, 4))) void k_cast_multi(CastMultiK a) {
     pooled_trace<kCastLds, false, ALPHA, CastMultiK, CastMultiSource<KMAX>, TravMulti<KMAX, kCastLds, ALPHA>>(a, CastMultiSource<KMAX>{a});
+}
+
+// The surfaces each ray enters and leaves (art_cast_crossings): the fourth candidate policy.  Nothing orders or shrinks: tbest stays the range's end for
+// the whole walk, so Trav4's box tests and the triangle's slab cull against [tmin, tmax] alone and every triangle accept() takes is met once.  Two counters a lane, no list:
+// LDS is the walk stack and the pool, as k_cast's.  The leaf step is a sibling of TravBase::step_leaf_take -- that one's hook has no det -- around moller_trumbore_det,
+// whose det is the one that accepted the candidate.  EVERY candidate is put to the mask / alpha test (each one counts; there is no "would win").
+template <int LDSN, bool ALPHA> struct TravCross : Trav4<false, LDSN, ALPHA> {
+    uint32_t n_in, n_out;   // det > 0: against the winding normal, an entry; det < 0: along it, an exit
+    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
+        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
+        float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        asm volatile("" : "+v"(td.x), "+v"(td.y), "+v"(td.z), "+v"(td.w), "+v"(tc.y), "+v"(tc.z), "+v"(tc.w));   // the box arrives with the vertices (TravBase::step_leaf_take)
+        float te, t, u, v, det;
+        if (moller_trumbore_det(this->r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v, det)) {
+            if (slab(this->r, tc.y, tc.z, tc.w, td.x, td.y, td.z, this->tbest, te)) {
+                if (!ALPHA || !alpha_cut(av, pos, u, v)) { if (det > 0.0f) n_in++; else n_out++; }   // (alpha_cut: the masks first, then the cutoff)
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+};
+struct CrossK : CastK { uint2 *cross; };   // cross: (entries, exits) a ray; tuv / ids / hit are not used
+struct CrossSource {
+    static constexpr int kFields = 12;   // CastSource's
+    const CrossK &a;
+    template <class TRAV> __device__ __forceinline__ void init(TRAV &) const {}
+    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
+        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
+        if (!has) a.cross[sidx] = make_uint2(0u, 0u);   // a dead ray crosses nothing: its record, without a walk
+        return has;
+    }
+    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; tr.n_in = 0u; tr.n_out = 0u; }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const { a.cross[slot] = make_uint2(tr.n_in, tr.n_out); }
+};
+// (waves_per_eu 8: k_cast's walk with two counters for the best candidate's five fields -- DESIGN.md 3.12's table has the compiler's figures)
+template <bool ALPHA>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cross(CrossK a) {
+    pooled_trace<kCastLds, false, ALPHA, CrossK, CrossSource, TravCross<kCastLds, ALPHA>>(a, CrossSource{a});
 }
 
 // ---- nearest surface points (art_closest_points) ------------------------------------------------------------------------------------------------
@@ -730,6 +770,9 @@ void launch_cast(const CastArgs &c, hipStream_t s) {
     if (c.kind == CastKind::Sweep) {          // the filtered instance tests masks, never a cutoff
         SweepK a = cast_fill<SweepK>(c); a.point = c.point; a.radius = c.radius;
         launch_query(c.filter ? k_sweep<true> : k_sweep<false>, a, c, s);
+    } else if (c.kind == CastKind::Crossings) {
+        CrossK a = cast_fill<CrossK>(c); a.cross = c.cross;
+        launch_query(c.filter ? k_cross<true> : k_cross<false>, a, c, s);
     } else if (c.kind == CastKind::Multi) {   // the instance with the smallest list that holds K
         CastMultiK a = cast_fill<CastMultiK>(c); a.count = c.count; a.max_hits = c.max_hits;
         launch_query(c.max_hits <= 4u ? (c.filter ? k_cast_multi<4, true> : k_cast_multi<4, false>) : (c.filter ? k_cast_multi<8, true> : k_cast_multi<8, false>), a, c, s);

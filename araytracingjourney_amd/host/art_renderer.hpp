@@ -319,6 +319,14 @@ public:
     static_assert(sizeof(ArtSphereCast) == 56, "ArtSphereCast is part of the ABI");
     static void cast_spheres(ArtContext *ctx, const ArtSphereCast &d) { check(art_cast_spheres(ctx, &d)); }
     void cast_spheres(const ArtSphereCast &d) { cast_spheres(ctx_, d); }
+    // how many surfaces each of n rays in device memory enters and leaves over its whole range: n x (entries, exits) uint32, uncapped (art_cast_crossings)
+    static ArtRayCrossings crossings_cast(const void *rays_dev, uint32_t n, void *cross_dev, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtRayCrossings d{}; d.rays_dev = rays_dev; d.cross_dev = cross_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtRayCrossings) == 40, "ArtRayCrossings is part of the ABI");
+    static void cast_crossings(ArtContext *ctx, const ArtRayCrossings &d) { check(art_cast_crossings(ctx, &d)); }
+    void cast_crossings(const ArtRayCrossings &d) { cast_crossings(ctx_, d); }
     void cast_sync() { check(art_cast_sync(ctx_)); }
     struct CastCounts { uint64_t casts, rays, host_waits; };
     CastCounts cast_counts() { CastCounts c{}; check(art_cast_counts(ctx_, &c.casts, &c.rays, &c.host_waits)); return c; }

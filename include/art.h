@@ -321,6 +321,34 @@ typedef struct ArtRayCastMulti {
     uint32_t flags;        /* must be 0 */
 } ArtRayCastMulti;        /* 56 bytes */
 int32_t art_cast_rays_multi(ArtContext *ctx, const ArtRayCastMulti *cast);
+/* The surfaces each ray enters and leaves: how many triangles the ray crosses over its whole range, uncapped, and in which direction it crosses each --
+ * what "is this point inside the mesh?", a signed distance, a solid voxelisation and a thickness count are made of.
+ *  - Results: for a ray let A be art_cast_rays_multi's set: the triangles accept() takes (the triangle's own slab, then Moeller-Trumbore with
+ *    tmin < t < tmax) that the visibility masks do not discard (primitive's mask & cull_mask != 0; tested first) and the alpha cutoff does not cut.  EVERY member of A is
+ *    alpha-tested: every candidate counts, there is no "would win".  For a member of A let det = dot3(e1, cross3(d, e2)), d the ray's direction as given, e1 and e2 the
+ *    triangle's world-space edges, dot3 and cross3 in their fmaf forms: the det Moeller-Trumbore itself forms (accept() has excluded det == 0).  The crossing is an
+ *    ENTRY iff det > 0 and an EXIT iff det < 0: det = -d . (e1 x e2), so an entry goes against the winding normal ng of art_resolve_hits and an exit along it.
+ *    Orientation is that of the world-space vertices: a mirroring model matrix swaps entries and exits, as it flips ng.  cross_dev[i] = (#entries, #exits), neither
+ *    capped.  A ray with a non-finite origin or direction or a NaN tmax has (0, 0); tmax = +inf is legal.  A primitive that left the structure by residency is nowhere
+ *    and is never counted.  A ray's record depends on that ray alone and on no property of the tree.
+ *  - Exact, not topological: two triangles that share an edge BOTH accept a ray through that edge (the 1e-6 edge fattening of DESIGN.md 1.1 that makes closest hits
+ *    watertight), so such a ray counts both.  A caller who wants inside / outside votes over several rays: the Python Renderer.points_inside does, with three.
+ *  - Everything else is art_cast_rays's: asynchronous on hip_stream (NULL: the context's cast stream), the scene as of the call with the refit in front of the cast and the
+ *    version held until the cast finishes, the same ring of ART_CAST_POOL cursor blocks and the same host waits; art_cast_counts counts it in casts and rays, art_cast_sync,
+ *    art_sync, art_scene_build and the others wait for it.  (Not through art_mgpu_*.)
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; a null or misaligned rays_dev (16 bytes) or cross_dev (8 bytes) (with n = 0
+ *    a null buffer is one of no rays); cull_mask above 0xFF; flags or reserved other than 0; n above ART_CAST_MAX_RAYS.  ART_E_STATE: the scene is not built, or
+ *    art_scene_needs_build.  cross_dev must not overlap the rays: the caller's contract, not checked. */
+typedef struct ArtRayCrossings {
+    const void *rays_dev;  /* n x 8 floats o.xyz,tmin,d.xyz,tmax, as ArtRayCast; 16-byte aligned */
+    void *cross_dev;       /* n x 2 uint32: (entries, exits); 8-byte aligned */
+    void *hip_stream;      /* as ArtRayCast: NULL = the context's cast stream */
+    uint32_t n;            /* 0 is legal: nothing is enqueued */
+    uint32_t cull_mask;    /* 0..0xFF; 0 sees nothing */
+    uint32_t flags;        /* must be 0 */
+    uint32_t reserved;     /* must be 0 */
+} ArtRayCrossings;         /* 40 bytes */
+int32_t art_cast_crossings(ArtContext *ctx, const ArtRayCrossings *cast);
 /* every cast enqueued so far has finished (those on callers' streams included) */
 int32_t art_cast_sync(ArtContext *ctx);
 /* since art_create: casts enqueued (n > 0), their rays, and the times art_cast_rays (or a refit in front of a frame) waited on the host for a cast.  Any pointer may be NULL. */
