@@ -112,6 +112,41 @@ def seam_scene(scenes):
                         [dict(kind="point", pos=(0.3, -0.2, -0.3), color=(6.0, 5.0, 4.0), falloff=4.0, casts_shadows=False)])
 
 
+def check_tree_arrays(lb, tr, same_as_karras_allowed=False):
+    """_check_traversal_tree on arrays: lb the canonical LBVH (leaf_gid, child, leaf_lo, leaf_hi), tr a traversal tree over its leaves (child, node_lo, node_hi) --
+    a device's (get_lbvh, get_traversal_tree) or a model's (tests/np_sah.py)"""
+    T = lb["leaf_gid"].size
+    child = tr["child"]
+    assert child.shape == (T - 1, 2)
+    if not same_as_karras_allowed:
+        assert not np.array_equal(child, lb["child"])                                    # a different topology than Karras'
+    leaves = ~child[child < 0]
+    assert np.array_equal(np.sort(leaves), np.arange(T))                                 # each leaf exactly once
+    inner = child[child >= 0]
+    assert np.array_equal(np.sort(inner), np.arange(1, T - 1))                           # each node but the root has exactly one parent
+    def boxes(ref):
+        lo = np.where((ref < 0)[:, None], lb["leaf_lo"][np.where(ref < 0, ~ref, 0)], tr["node_lo"][np.where(ref < 0, 0, ref)])
+        hi = np.where((ref < 0)[:, None], lb["leaf_hi"][np.where(ref < 0, ~ref, 0)], tr["node_hi"][np.where(ref < 0, 0, ref)])
+        return lo, hi
+    l0, h0 = boxes(child[:, 0]); l1, h1 = boxes(child[:, 1])
+    assert np.array_equal(np.minimum(l0, l1).view(np.uint32), tr["node_lo"].view(np.uint32))
+    assert np.array_equal(np.maximum(h0, h1).view(np.uint32), tr["node_hi"].view(np.uint32))
+    depth = np.zeros(T - 1, np.int32)                                                    # pre-order layout: parents come before children
+    for n in range(T - 1):
+        for c in child[n]:
+            if c >= 0:
+                assert c > n
+                depth[c] = depth[n] + 1
+    assert depth.max() + 1 <= 80
+    return T
+
+
+def _check_traversal_tree(r, same_as_karras_allowed=False):
+    """every leaf of the canonical LBVH hangs in the traversal tree exactly once, every node box is the exact min/max union of its children's boxes, the root is node 0
+    (pre-order: parents before children), the depth stays inside the walks' stacks"""
+    return check_tree_arrays(r.get_lbvh(), r.get_traversal_tree(), same_as_karras_allowed)
+
+
 # ---- hostile inputs for the walks (tests/test_walk_edges.py): one generator per hazard ---------------------------------------------------------------------------
 # the similarities every scene is run at: (scale, offset).  Powers of two and offsets of a few thousand: no intermediate of the slab test, of Moeller-Trumbore or of the
 # shading leaves float32's normal range (extreme scales, where the products go denormal or overflow, are left out on purpose)

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_radiance_close, radiance_margin, record_margin
-from helpers import degenerate_soup, oracle_camera, oracle_for, random_rays
+from helpers import _check_traversal_tree, degenerate_soup, oracle_camera, oracle_for, random_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -607,36 +607,6 @@ def test_residency_only_device_models_are_traced(R, get_scene):
     st = both.stats()
     assert st["hit_pixels"] == 0 and st["shadow_rays"] == 0 and np.all(both.read_depth() == 10000.0)
     both.close(); only.close()
-
-
-def _check_traversal_tree(r, same_as_karras_allowed=False):
-    """every leaf of the canonical LBVH hangs in the traversal tree exactly once, every node box is the exact min/max union of its children's boxes, the root is node 0
-    (pre-order: parents before children), the depth stays inside the walks' stacks"""
-    lb, tr = r.get_lbvh(), r.get_traversal_tree()
-    T = lb["leaf_gid"].size
-    child = tr["child"]
-    assert child.shape == (T - 1, 2)
-    if not same_as_karras_allowed:
-        assert not np.array_equal(child, lb["child"])                                    # a different topology than Karras'
-    leaves = ~child[child < 0]
-    assert np.array_equal(np.sort(leaves), np.arange(T))                                 # each leaf exactly once
-    inner = child[child >= 0]
-    assert np.array_equal(np.sort(inner), np.arange(1, T - 1))                           # each node but the root has exactly one parent
-    def boxes(ref):
-        lo = np.where((ref < 0)[:, None], lb["leaf_lo"][np.where(ref < 0, ~ref, 0)], tr["node_lo"][np.where(ref < 0, 0, ref)])
-        hi = np.where((ref < 0)[:, None], lb["leaf_hi"][np.where(ref < 0, ~ref, 0)], tr["node_hi"][np.where(ref < 0, 0, ref)])
-        return lo, hi
-    l0, h0 = boxes(child[:, 0]); l1, h1 = boxes(child[:, 1])
-    assert np.array_equal(np.minimum(l0, l1).view(np.uint32), tr["node_lo"].view(np.uint32))
-    assert np.array_equal(np.maximum(h0, h1).view(np.uint32), tr["node_hi"].view(np.uint32))
-    depth = np.zeros(T - 1, np.int32)                                                    # pre-order layout: parents come before children
-    for n in range(T - 1):
-        for c in child[n]:
-            if c >= 0:
-                assert c > n
-                depth[c] = depth[n] + 1
-    assert depth.max() + 1 <= 80
-    return T
 
 
 @pytest.mark.parametrize("builder", ["sah-device", "sah-host"])
