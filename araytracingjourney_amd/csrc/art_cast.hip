@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings; DESIGN.md 3.5 .. 3.12) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings, art_overlap_triangles; DESIGN.md 3.5 .. 3.13) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
 // entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -119,6 +119,31 @@ template <class D> static int32_t point_check(const char *who, const D *d) {   /
     int32_t r = check_cull(who, d->cull_mask);
     return r || (r = check_n(who, d->n)) || (r = check_buffer(who, "points_dev", d->points_dev, 16, d->n)) || (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) ? r : check_buffer(who, "point_dev", d->point_dev, 16, d->n, true);
 }
+// the two overlap queries' descriptors (overlap_check -- D: ArtBoxQuery | ArtTriQuery; in_name / in_dev: its buffer of queries; which outputs a kind has) and what their launches share (overlap_begin)
+template <class D> static int32_t overlap_check(const char *who, ArtContext *c, const D *d, const char *in_name, const void *in_dev) {
+    int32_t r;
+    if ((r = check_flags(who, d->flags))) return r;
+    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
+    if (d->kind != ART_OVERLAP_ANY && d->kind != ART_OVERLAP_LIST) return invalid(who, "kind: ART_OVERLAP_ANY or ART_OVERLAP_LIST");
+    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, in_name, in_dev, 16, d->n))) return r;
+    if (d->kind == ART_OVERLAP_ANY) {
+        if (d->ids_dev || d->count_dev) return invalid(who, "ids_dev / count_dev: must be NULL for ART_OVERLAP_ANY");
+        if (d->max_hits != 0u) return invalid(who, "max_hits: must be 0 for ART_OVERLAP_ANY");
+        if ((r = check_buffer(who, "hit_dev", d->hit_dev, 1, d->n))) return r;
+    } else {
+        if (d->hit_dev) return invalid(who, "hit_dev: must be NULL for ART_OVERLAP_LIST");
+        if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
+        if ((r = check_buffer(who, "ids_dev", d->ids_dev, 8, d->n)) || (r = check_buffer(who, "count_dev", d->count_dev, 4, d->n, true))) return r;
+    }
+    if (!c->built) return fail(ART_E_STATE, std::string(who) + ": scene not built, or changed since the build (art_scene_build)");
+    return ART_OK;
+}
+// a block of the ring for a checked descriptor of n > 0 queries, and the outputs both kinds of query share
+template <class D> static int32_t overlap_begin(ArtContext *c, const D *d, OverlapArgs &a, RingSlot *q) {
+    const int32_t r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, nullptr, d->ids_dev, a, q); if (r) return r;
+    a.any = d->kind == ART_OVERLAP_ANY; a.hit = (uint8_t *)d->hit_dev; a.count = (uint32_t *)d->count_dev; a.max_hits = d->max_hits;
+    return ART_OK;
+}
 
 extern "C" {
 
@@ -209,30 +234,27 @@ int32_t art_closest_points_multi(ArtContext *c, const ArtPointQueryMulti *d) {
     return cast_commit(c, q, 0);
 }
 
-// ---- the triangles that touch a box (include/art.h: art_overlap_boxes) ---------------------------------------------------------------------------------
-// art_closest_points' path with boxes for points: a block of the ring, counted as no cast.  Which outputs a kind has is checked here; the rest is the family's.
+// ---- the triangles that touch a box or a triangle (include/art.h: art_overlap_boxes, art_overlap_triangles) -----------------------------------
+// art_closest_points' path with boxes or triangles for points: a block of the ring, counted as no cast.  Which outputs a kind has is checked once for both
+// (overlap_check above); the rest is the family's.
 int32_t art_overlap_boxes(ArtContext *c, const ArtBoxQuery *d) {
     const char *who = "art_overlap_boxes"; int32_t r;
-    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
-    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
-    if (d->kind != ART_OVERLAP_ANY && d->kind != ART_OVERLAP_LIST) return invalid(who, "kind: ART_OVERLAP_ANY or ART_OVERLAP_LIST");
-    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "boxes_dev", d->boxes_dev, 16, d->n))) return r;
-    const bool any = d->kind == ART_OVERLAP_ANY;
-    if (any) {
-        if (d->ids_dev || d->count_dev) return invalid(who, "ids_dev / count_dev: must be NULL for ART_OVERLAP_ANY");
-        if (d->max_hits != 0u) return invalid(who, "max_hits: must be 0 for ART_OVERLAP_ANY");
-        if ((r = check_buffer(who, "hit_dev", d->hit_dev, 1, d->n))) return r;
-    } else {
-        if (d->hit_dev) return invalid(who, "hit_dev: must be NULL for ART_OVERLAP_LIST");
-        if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
-        if ((r = check_buffer(who, "ids_dev", d->ids_dev, 8, d->n)) || (r = check_buffer(who, "count_dev", d->count_dev, 4, d->n, true))) return r;
-    }
-    if (!c->built) return fail(ART_E_STATE, "art_overlap_boxes: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_null(who, c, d)) || (r = overlap_check(who, c, d, "boxes_dev", d->boxes_dev))) return r;
     if (d->n == 0u) return ART_OK;
     OverlapArgs a{}; RingSlot q;
-    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, nullptr, d->ids_dev, a, &q); if (r) return r;
-    a.boxes = (const float4 *)d->boxes_dev; a.any = any; a.hit = (uint8_t *)d->hit_dev; a.count = (uint32_t *)d->count_dev; a.max_hits = d->max_hits;
+    r = overlap_begin(c, d, a, &q); if (r) return r;
+    a.boxes = (const float4 *)d->boxes_dev;
     launch_overlap(a, q.stream);
+    return cast_commit(c, q, 0);
+}
+int32_t art_overlap_triangles(ArtContext *c, const ArtTriQuery *d) {
+    const char *who = "art_overlap_triangles"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = overlap_check(who, c, d, "tris_dev", d->tris_dev))) return r;
+    if (d->n == 0u) return ART_OK;
+    TriOverlapArgs a{}; RingSlot q;
+    r = overlap_begin(c, d, a, &q); if (r) return r;
+    a.qtris = (const float4 *)d->tris_dev;
+    launch_tri_overlap(a, q.stream);
     return cast_commit(c, q, 0);
 }
 

@@ -324,6 +324,9 @@ void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s);
 // hold max_hits records a box, box-major ((-1,-1) behind the candidates), and count (optional) every candidate of the box, uncapped.  tuv is not used
 struct OverlapArgs : QueryArgs { const float4 *boxes; bool any; uint8_t *hit; uint32_t *count; uint32_t max_hits; };
 void launch_overlap(const OverlapArgs &c, hipStream_t s);
+// The triangles that touch a triangle (art_overlap_triangles): qtris[3i .. 3i+2] = q0.xyz,- | q1.xyz,- | q2.xyz,-; the outputs are OverlapArgs' (boxes is not used)
+struct TriOverlapArgs : OverlapArgs { const float4 *qtris; };
+void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
 struct ResolveArgs {

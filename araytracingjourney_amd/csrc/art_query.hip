@@ -1,6 +1,6 @@
 // art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), the crossings of each ray (k_cross), nearest surface points (k_closest), the K nearest
-// triangles (k_closest_multi), swept spheres (k_sweep) and the triangles that touch a box (k_overlap).  The casts and the sweep are Sources and candidate policies of
-// art_walk.h's pooled loop; the point and box queries, which have no ray to pool, are Sinks and walks of one loop of their own (point_trace).  What the queries share stands
+// triangles (k_closest_multi), swept spheres (k_sweep), the triangles that touch a box (k_overlap) and those that touch a triangle (k_overlap_tris).  The casts and the sweep
+// are Sources and candidate policies of art_walk.h's pooled loop; the point, box and triangle queries, which have no ray to pool, are Sinks and walks of one loop of their own (point_trace).  What the queries share stands
 // once: at the top the ray read, the hit and miss records, the contact point, the mask test and the 4-wide node's decode (load_node4); the sorted list of both K-walks
 // (KList), which a walk fills through its leaf step's hook for a candidate's fate (step_leaf_take: one leaf step a walk); at the bottom the arguments' common fields and
 // the launch.  (The list, the leaf steps and the loop were copies once, kept apart so that no other kernel's code would move.  Compared instruction for instruction --
@@ -741,6 +741,98 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     point_trace<TravBox<ANY, FILTER>>(a, stack, OverlapSink<ANY, KMAX>{a, gids});
 }
 
+// ---- the triangles that touch a triangle (art_overlap_triangles) ---------------------------------------------------------------------------------------
+// A query is a triangle q0.xyz, - | q1.xyz, - | q2.xyz, -: three 16-byte loads a lane, and the loop, the node step against the query's own box [qlo, qhi], the stack, the
+// list and the finish are the box query's (TravBox, OverlapSink) as they stand; what is this query's own are the two hooks -- the fetch (TriSink::begin) and the leaf step
+// (TravTri::step_leaf): the triangle's box against [qlo, qhi], then the 17 separating axes of two triangles.  The query's vertices stay in registers beside qlo / qhi
+// and the a_m = q_m - v0 are formed at each leaf (DESIGN.md 3.13's table).
+// No fmaf in the leaf test: tests/np_tri_overlap.py restates every operation in numpy float32.
+struct TriOverlapK : OverlapK { const float4 *qtris; };   // boxes: not used
+// one axis x of condition 3: the scene triangle's projections 0, x.e1, x.e2 against the query's x.a0, x.a1, x.a2; min and max by comparisons, so a NaN separates nothing
+__device__ __forceinline__ bool tri_axis_separates(V3 x, V3 e1, V3 e2, V3 a0, V3 a1, V3 a2) {
+    const float t1 = dotp(x, e1), t2 = dotp(x, e2), p0 = dotp(x, a0), p1 = dotp(x, a1), p2 = dotp(x, a2);
+    float tmn = 0.0f, tmx = 0.0f, qmn = p0, qmx = p0;
+    tmn = t1 < tmn ? t1 : tmn; tmx = t1 > tmx ? t1 : tmx;
+    tmn = t2 < tmn ? t2 : tmn; tmx = t2 > tmx ? t2 : tmx;
+    qmn = p1 < qmn ? p1 : qmn; qmx = p1 > qmx ? p1 : qmx;
+    qmn = p2 < qmn ? p2 : qmn; qmx = p2 > qmx ? p2 : qmx;
+    return (tmn > qmx) | (tmx < qmn);
+}
+// condition 3 of DESIGN.md 3.13 for a triangle v0 e1 e2 against the query q0 q1 q2: the two normals, the nine edge pairs, the six in-plane axes -- a conjunction, left
+// at the first group that separates
+__device__ __forceinline__ bool tri_tri_overlap(V3 v0, V3 e1, V3 e2, V3 q0, V3 q1, V3 q2) {
+    const V3 a0 = q0 - v0, a1 = q1 - v0, a2 = q2 - v0;
+    const V3 f[3] = {e1, e2 - e1, mk(-e2.x, -e2.y, -e2.z)}, g[3] = {a1 - a0, a2 - a1, a0 - a2};
+    const V3 n = crossp(e1, e2), m = crossp(g[0], g[1]);
+    if (tri_axis_separates(n, e1, e2, a0, a1, a2) || tri_axis_separates(m, e1, e2, a0, a1, a2)) return false;
+    bool s = false;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) s |= tri_axis_separates(crossp(f[i], g[j]), e1, e2, a0, a1, a2);
+    }
+    if (s) return false;
+#pragma unroll
+    for (int i = 0; i < 3; i++) s |= tri_axis_separates(crossp(n, f[i]), e1, e2, a0, a1, a2);
+#pragma unroll
+    for (int j = 0; j < 3; j++) s |= tri_axis_separates(crossp(m, g[j]), e1, e2, a0, a1, a2);
+    return !s;
+}
+// TravBox with the query's vertices beside its box (lo, hi: qlo, qhi) and a leaf step of its own; push, pop, enter and step_internal are TravBox's
+template <bool ANY, bool FILTER> struct TravTri : TravBox<ANY, FILTER> {
+    V3 q0, q1, q2;
+    // the triangle in `cur`: conditions 1 and 2 on its own box, then the separating axes, then the masks; ANY is finished by its first candidate
+    __device__ __forceinline__ bool step_leaf(const TriOverlapK &a, int *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const V3 &lo = this->lo, &hi = this->hi;
+        const bool meets = (tc.y < 3.0e38f) & (tc.y <= hi.x) & (lo.x <= td.x) & (tc.z <= hi.y) & (lo.y <= td.y) & (tc.w <= hi.z) & (lo.z <= td.z);
+        if (meets && tri_tri_overlap(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), q0, q1, q2) &&
+            (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
+            if (ANY) { this->cnt = 1u; return true; }
+            this->enter(__float_as_uint(td.w));
+            this->cnt++;
+        }
+        return this->pop(lds, ovf);
+    }
+};
+// OverlapSink with the fetch of a triangle: init and finish are the box query's
+template <bool ANY, int KMAX> struct TriSink : OverlapSink<ANY, KMAX> {
+    const float4 *qtris;
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &) const {
+        const float4 r0 = qtris[3 * (size_t)sidx], r1 = qtris[3 * (size_t)sidx + 1], r2 = qtris[3 * (size_t)sidx + 2];
+        const float z = (((0.0f * r0.x + 0.0f * r0.y) + 0.0f * r0.z) + ((0.0f * r1.x + 0.0f * r1.y) + 0.0f * r1.z)) + ((0.0f * r2.x + 0.0f * r2.y) + 0.0f * r2.z);   // 0 for nine finite coordinates, NaN otherwise
+        if (z == 0.0f) {
+            V3 mn = mk(r0.x, r0.y, r0.z), mx = mn;   // qlo, qhi: two selects an axis from the first vertex
+            mn.x = r1.x < mn.x ? r1.x : mn.x; mn.y = r1.y < mn.y ? r1.y : mn.y; mn.z = r1.z < mn.z ? r1.z : mn.z;
+            mx.x = r1.x > mx.x ? r1.x : mx.x; mx.y = r1.y > mx.y ? r1.y : mx.y; mx.z = r1.z > mx.z ? r1.z : mx.z;
+            mn.x = r2.x < mn.x ? r2.x : mn.x; mn.y = r2.y < mn.y ? r2.y : mn.y; mn.z = r2.z < mn.z ? r2.z : mn.z;
+            mx.x = r2.x > mx.x ? r2.x : mx.x; mx.y = r2.y > mx.y ? r2.y : mx.y; mx.z = r2.z > mx.z ? r2.z : mx.z;
+            tr.q0 = mk(r0.x, r0.y, r0.z); tr.q1 = mk(r1.x, r1.y, r1.z); tr.q2 = mk(r2.x, r2.y, r2.z);
+            tr.lo = mn; tr.hi = mx; tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
+            return true;
+        }
+        const OverlapK &a = this->a;
+        if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate): its answer, without a walk
+        else {
+            const size_t base = (size_t)sidx * K;
+            for (uint32_t j = 0; j < K; j++) a.ids[base + j] = make_int2(-1, -1);
+            if (a.count) a.count[sidx] = 0u;
+        }
+        return false;
+    }
+};
+// (waves_per_eu: ANY holds the 17 axes' operands in 64 VGPRs without a spill; LIST, with the list's state beside them, spills two of them at 8 waves and uses
+// 75 / 76 without a spill at 6, no more at 5 or 4 -- DESIGN.md 3.13's table)
+template <bool ANY, int KMAX, bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(ANY ? 8 : 6, ANY ? 8 : 6))) void k_overlap_tris(TriOverlapK a) {
+    __shared__ int stack[kOverlapLds * kTraceBlock];
+    __shared__ uint32_t gids[(ANY ? 1 : KMAX) * kTraceBlock];
+    point_trace<TravTri<ANY, FILTER>>(a, stack, TriSink<ANY, KMAX>{{a, gids}, a.qtris});
+}
+
 // The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
 // the context's ArtTuning overrides.  query_fill: the fields every kernel's arguments share (cast_fill, closest_fill: with those of the casts, of the point queries);
 // launch_query: one instance, chosen by its caller, on that shape.
@@ -794,6 +886,12 @@ void launch_overlap(const OverlapArgs &c, hipStream_t s) {   // one list size: A
     a.boxes = c.boxes; a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
     if (c.any) launch_query(c.filter ? k_overlap<true, 0, true> : k_overlap<true, 0, false>, a, c, s);
     else launch_query(c.filter ? k_overlap<false, 8, true> : k_overlap<false, 8, false>, a, c, s);
+}
+void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s) {   // launch_overlap's instances and list size
+    TriOverlapK a = query_fill<TriOverlapK>(c);
+    a.qtris = c.qtris; a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    if (c.any) launch_query(c.filter ? k_overlap_tris<true, 0, true> : k_overlap_tris<true, 0, false>, a, c, s);
+    else launch_query(c.filter ? k_overlap_tris<false, 8, true> : k_overlap_tris<false, 8, false>, a, c, s);
 }
 
 } // namespace art

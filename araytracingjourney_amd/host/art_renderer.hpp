@@ -311,6 +311,19 @@ public:
     static_assert(sizeof(ArtBoxQuery) == 64, "ArtBoxQuery is part of the ABI");
     static void overlap_boxes(ArtContext *ctx, const ArtBoxQuery &d) { check(art_overlap_boxes(ctx, &d)); }
     void overlap_boxes(const ArtBoxQuery &d) { overlap_boxes(ctx_, d); }
+    // the scene triangles that touch each of n query triangles (q0.xyz, -, q1.xyz, -, q2.xyz, -) in device memory: a byte a query (any_collision), or max_hits id pairs a
+    // query in ascending global id and (optionally) a uint32 count of all of them (list_collision) (art_overlap_triangles)
+    static ArtTriQuery any_collision(const void *tris_dev, uint32_t n, void *hit_dev, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtTriQuery d{}; d.tris_dev = tris_dev; d.hit_dev = hit_dev; d.hip_stream = hip_stream; d.n = n; d.kind = ART_OVERLAP_ANY; d.cull_mask = cull_mask;
+        return d;
+    }
+    static ArtTriQuery list_collision(const void *tris_dev, uint32_t n, uint32_t max_hits, void *ids_dev, void *count_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
+        ArtTriQuery d{}; d.tris_dev = tris_dev; d.ids_dev = ids_dev; d.count_dev = count_dev; d.hip_stream = hip_stream; d.n = n; d.kind = ART_OVERLAP_LIST; d.max_hits = max_hits; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtTriQuery) == 64, "ArtTriQuery is part of the ABI");
+    static void overlap_triangles(ArtContext *ctx, const ArtTriQuery &d) { check(art_overlap_triangles(ctx, &d)); }
+    void overlap_triangles(const ArtTriQuery &d) { overlap_triangles(ctx_, d); }
     // where a ball of `radius` along each of n rays in device memory first touches the scene: records as a closest cast's and (optionally) n x float4 contact points (art_cast_spheres)
     static ArtSphereCast sphere_cast(const void *rays_dev, uint32_t n, float radius, void *tuv_dev, void *ids_dev, void *point_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
         ArtSphereCast d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask; d.radius = radius;

@@ -901,6 +901,10 @@ class Renderer:
         (n,) uint8, 1 where some triangle overlaps; max_hits is not used.  A box with a non-finite coordinate or lo > hi on an axis overlaps nothing.  Alpha cutoffs are not
         tested; primitive masks are, against cull_mask.  out: (ids, count) or hit to write instead of new ones, of at least n boxes and exactly K records a box, not
         overlapping the boxes or each other.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        return self._overlap(self._L.art_overlap_boxes, _lib.ArtBoxQuery, "boxes_dev", boxes, "boxes", 8, kind, max_hits, cull_mask, out, stream)
+
+    def _overlap(self, entry, desc, field, queries, name, width, kind, max_hits, cull_mask, out, stream):
+        """overlap_boxes and overlap_triangles behind their docstrings: the checks, the outputs and the call -- the two descriptors differ in their first field's name"""
         m = _mask_value("cull_mask", cull_mask)
         if kind not in ("list", "any"):
             raise ValueError("kind must be 'list' or 'any'")
@@ -909,17 +913,71 @@ class Renderer:
             k = int(max_hits)
             if k != max_hits or not 1 <= k <= _lib.ART_CAST_MAX_HITS:
                 raise ValueError(f"max_hits must be an integer in 1..{_lib.ART_CAST_MAX_HITS}")
-        n = self._dev_tensor(boxes, "boxes", "float32", (8,), 16).shape[0]
-        d = _lib.ArtBoxQuery(boxes_dev=boxes.data_ptr() or None, n=n, max_hits=k, cull_mask=m, flags=0, reserved=0)
+        n = self._dev_tensor(queries, name, "float32", (width,), 16).shape[0]
+        d = desc(n=n, max_hits=k, cull_mask=m, flags=0, reserved=0)
+        setattr(d, field, queries.data_ptr() or None)
         if kind == "list":
-            res = ids, count = self._outputs(out, n, boxes.device, (("ids", "int32", (k, 2), 8), ("count", "int32", (), 4)))
+            res = ids, count = self._outputs(out, n, queries.device, (("ids", "int32", (k, 2), 8), ("count", "int32", (), 4)))
             d.kind, d.ids_dev, d.count_dev = _lib.ART_OVERLAP_LIST, ids.data_ptr() or None, count.data_ptr() or None
         else:
-            res, = self._outputs(None if out is None else (out,), n, boxes.device, (("hit", "uint8", (), 1),))
+            res, = self._outputs(None if out is None else (out,), n, queries.device, (("hit", "uint8", (), 1),))
             d.kind, d.hit_dev = _lib.ART_OVERLAP_ANY, res.data_ptr() or None
-        d.hip_stream = self._stream_handle(stream, boxes.device)
-        check(self._L.art_overlap_boxes(self._ctx, C.byref(d)))
+        d.hip_stream = self._stream_handle(stream, queries.device)
+        check(entry(self._ctx, C.byref(d)))
         return res
+
+    def overlap_triangles(self, tris, kind="list", max_hits=8, cull_mask=0xFF, out=None, stream=None):
+        """The scene triangles that touch each query triangle (art_overlap_triangles; DESIGN.md 3.13 is the definition).  tris: a torch tensor on this context's device,
+        float32, shape (n, 12) -- q0.xyz, -, q1.xyz, -, q2.xyz, - (words 3, 7 and 11 are not read) -- contiguous and 16-byte aligned.  Every test is closed: touching
+        counts, also at one vertex; coplanar triangles apart from each other are apart.  A SURFACE test: a query wholly inside a closed mesh touches nothing
+        (points_inside on one vertex answers containment).  kind "list" returns (ids, count): (n, K, 2) int32 (primitive, triangle in the primitive) of the K = max_hits
+        overlapping triangles with the smallest global ids, in ascending order, (-1, -1) behind them, and (n,) int32 the number of ALL overlapping triangles of the query,
+        not capped by K (a uint32 on the device, handed out as int32, as overlap_boxes').  kind "any" returns hit: (n,) uint8, 1 where some triangle overlaps; max_hits is
+        not used.  A query with a non-finite coordinate overlaps nothing; a segment or a point (equal vertices) goes through the same formulas.  Alpha cutoffs are not
+        tested; primitive masks are, against cull_mask.  out: (ids, count) or hit to write instead of new ones, of at least n queries and exactly K records a query, not
+        overlapping the queries or each other.  Every tensor is checked before anything is enqueued.  Enqueued on `stream` (default: torch's current stream) without
+        host synchronisation, like cast_rays."""
+        return self._overlap(self._L.art_overlap_triangles, _lib.ArtTriQuery, "tris_dev", tris, "tris", 12, kind, max_hits, cull_mask, out, stream)
+
+    def collide_mesh(self, positions, indices, model_matrix=None, kind="any", max_hits=8, cull_mask=0xFF, stream=None):
+        """Does this mesh, where it stands, cut the scene's surfaces, and which triangles does it cut?  positions: (V, 3) float32 and indices: (T, 3) int32 or int64,
+        contiguous torch tensors on this context's device; model_matrix: a row-major 3x4 (12 floats, rows of x y z and the translation; None: the positions as they
+        are).  The (T, 12) query buffer is gathered on the device, on `stream`: vertex k of triangle t is positions[indices[t, k]], through the matrix as
+        ((p.x * m[r][0] + p.y * m[r][1]) + p.z * m[r][2]) + m[r][3] in float32 for each row r; a triangle with an index outside positions becomes a dead query (NaN
+        coordinates: it touches nothing).  The answer is overlap_triangles of that buffer and nothing else: kind "any" returns hit, (T,) uint8; kind "list" returns
+        (ids, count), (T, K, 2) int32 and (T,) int32 -- per triangle of the mesh, in the order of indices.  hit.any() is "the mesh collides".  No host synchronisation."""
+        import torch
+        _mask_value("cull_mask", cull_mask)
+        if kind not in ("list", "any"):
+            raise ValueError("kind must be 'list' or 'any'")
+        nv = self._dev_tensor(positions, "positions", "float32", (3,), 4).shape[0]
+        dev = positions.device
+        if not (isinstance(indices, torch.Tensor) and indices.device == dev and indices.dtype in (torch.int32, torch.int64) and indices.dim() == 2 and indices.shape[1] == 3
+                and indices.is_contiguous()):
+            raise ValueError(f"indices must be a contiguous int32 or int64 torch tensor on {dev} of shape (T, 3)")
+        nt = indices.shape[0]
+        if nt > _lib.ART_CAST_MAX_RAYS:
+            raise ValueError("indices: more than ART_CAST_MAX_RAYS triangles")
+        if nt and not nv:
+            raise ValueError("positions: empty, with triangles to gather")
+        mm = None
+        if model_matrix is not None:
+            mm = np.asarray(model_matrix.cpu() if isinstance(model_matrix, torch.Tensor) else model_matrix, np.float32).reshape(-1)
+            if mm.size != 12 or not np.isfinite(mm).all():
+                raise ValueError("model_matrix must be 12 finite floats, a row-major 3x4")
+            mm = [float(x) for x in mm]
+        stream = self._torch_stream(stream, dev)
+        with torch.cuda.stream(stream):
+            tris = torch.zeros((nt, 3, 4), dtype=torch.float32, device=dev)
+            if nt:
+                idx = indices.to(torch.int64)
+                p = positions[idx.clamp(0, nv - 1)]                                    # (T, 3, 3)
+                if mm is not None:
+                    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+                    p = torch.stack([((x * mm[4 * r] + y * mm[4 * r + 1]) + z * mm[4 * r + 2]) + mm[4 * r + 3] for r in range(3)], dim=-1)
+                outside = ((idx < 0) | (idx >= nv)).any(dim=1)
+                tris[..., 0:3] = torch.where(outside[:, None, None], torch.full_like(p, float("nan")), p)
+            return self.overlap_triangles(tris.reshape(nt, 12), kind, max_hits, cull_mask, stream=stream)
 
     def voxelize(self, origin, cell, dims, cull_mask=0xFF, stream=None):
         """An occupancy grid of the scene: a uint8 tensor [nx, ny, nz] on this context's device, 1 where some triangle touches the cell (overlap_boxes, kind "any").

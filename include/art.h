@@ -520,6 +520,46 @@ typedef struct ArtBoxQuery {
     uint32_t reserved;      /* must be 0 */
 } ArtBoxQuery;              /* 64 bytes */
 int32_t art_overlap_boxes(ArtContext *ctx, const ArtBoxQuery *q);
+/* The scene triangles that touch query triangles (which is the definition; new functionality: Embree's rtcCollide, PhysX's overlap with a triangle-mesh
+ * geometry, FCL's mesh-mesh test -- the reference has no call for it): does this mesh, where it now stands, cut the scene's surfaces, and which triangles does it cut --
+ * a robot link, a tool, a vehicle hull, a character's proxy; an oriented box is twelve triangles of this query.  A query is a triangle q0, q1, q2.
+ *  - Results: defined exactly and independent of the structure.  A triangle with global id g and record v0, e1, e2, tlo, thi (its own box) OVERLAPS the query iff (1) tlo.x <
+ *    3.0e38 (a primitive that left the structure by residency is nowhere and is never returned); (2) the boxes meet: with qlo, qhi the componentwise minimum and maximum
+ *    of the three vertices (two selects from the first), on every axis tlo <= qhi and qlo <= thi, comparisons only; (3) none of 17 axes separates: with a_m = q_m - v0,
+ *    f = (e1, e2 - e1, -e2), g = (a1 - a0, a2 - a1, a0 - a2), n = cross(e1, e2), m = cross(g0, g1), the axes are n, m, the nine cross(f_i, g_j), the three cross(n, f_i)
+ *    and the three cross(m, g_j); an axis x separates iff min(0, x.e1, x.e2) > max(x.a0, x.a1, x.a2) or max(0, x.e1, x.e2) < min(x.a0, x.a1, x.a2) -- DESIGN.md 3.13's
+ *    formulas in fp32 without fused operations, sums of three as (a + b) + c, minima and maxima by selects; a comparison with a NaN is false, so a zero axis or one
+ *    with a NaN separates nothing.  Every test is closed: touching counts, also at a single vertex.  Coplanar disjoint triangles are apart (the six in-plane axes).
+ *    Zero-area scene triangles and zero-area queries (a segment, a point) go through the same formulas: for a zero-area operand lying in the other's plane that can be
+ *    an overlap geometry would not call one.  The candidates are the overlapping triangles whose primitive's mask & cull_mask != 0 (cull_mask 0 sees nothing); alpha
+ *    cutoffs are NOT tested, for art_closest_points' reason.
+ *  - This is a SURFACE test: a query wholly inside a closed mesh touches nothing (Renderer.points_inside on one vertex answers containment).  Pruning is exact for
+ *    art_overlap_boxes' reason: a child is skipped only when its decoded box misses [qlo, qhi] by comparison, or its byte box is inverted.
+ *  - ART_OVERLAP_ANY: hit_dev[i] = 1 iff the query has a candidate, else 0; the walk ends at the first one.  ART_OVERLAP_LIST: count_dev[i] (optional) = the number of
+ *    candidates, all of them, not capped by max_hits; records 0 .. c-1 of the query, c = min(count, max_hits), are (primitive id, triangle in the primitive) of the
+ *    candidates in ascending g; records c .. max_hits-1 are (-1, -1).  A query with a non-finite coordinate among its nine is dead: hit 0, count 0, miss records, no
+ *    walk.  Words 3, 7 and 11 of a query are not read.  A query's answer depends on that query alone.
+ *  - Asynchrony and scene: art_overlap_boxes', with no path of its own -- stream, no allocation or synchronisation on the steady path, the scene as of the call, the
+ *    version held, a block of the casts' ring (ART_CAST_POOL), the same fences.  art_cast_counts counts it in neither casts nor rays (it traces no ray); a host wait it
+ *    causes counts in host_waits.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; flags or reserved other than 0; a kind that is neither; cull_mask above
+ *    0xFF; n above ART_CAST_MAX_RAYS; a null or misaligned tris_dev (16 bytes; with n = 0 null is fine); ANY: ids_dev or count_dev given, max_hits other than 0, a null
+ *    hit_dev; LIST: hit_dev given, max_hits 0 or above ART_CAST_MAX_HITS, a null or misaligned ids_dev (8 bytes), a misaligned count_dev (4 bytes).  ART_E_STATE: the
+ *    scene is not built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtTriQuery {
+    const void *tris_dev;   /* n x 12 floats: q0.xyz, -, q1.xyz, -, q2.xyz, - (words 3, 7 and 11 are not read); 16-byte aligned */
+    void *hit_dev;          /* ANY: n x uint8, 1 = some triangle overlaps the query.  LIST: must be NULL */
+    void *ids_dev;          /* LIST: n x max_hits x 2 int32 (primitive id, triangle in the primitive), query-major: query i's record j at i*max_hits + j; 8-byte aligned.  ANY: must be NULL */
+    void *count_dev;        /* LIST: n x uint32: ALL candidates of the query, not capped by max_hits; 4-byte aligned.  May be NULL.  ANY: must be NULL */
+    void *hip_stream;       /* as ArtRayCast */
+    uint32_t n;             /* 0 is legal: nothing is enqueued */
+    uint32_t kind;          /* ART_OVERLAP_ANY | ART_OVERLAP_LIST */
+    uint32_t max_hits;      /* LIST: K, 1..ART_CAST_MAX_HITS.  ANY: must be 0 */
+    uint32_t cull_mask;     /* 0..0xFF; 0 sees nothing */
+    uint32_t flags;         /* must be 0 */
+    uint32_t reserved;      /* must be 0 */
+} ArtTriQuery;              /* 64 bytes */
+int32_t art_overlap_triangles(ArtContext *ctx, const ArtTriQuery *q);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
