@@ -1,5 +1,5 @@
-// art_api.hip -- the C ABI of include/art.h: context, frame ring and frame orchestration, read-backs, host maths.  (The scene and the versions of the acceleration
-// structure: art_scene.hip; the wave plan: art_plan.hip; rays in device buffers: art_cast.hip; the state they share: art_context.h.)
+// art_api.hip -- the C ABI of include/art.h: context, frame ring and frame orchestration, read-backs, host maths.  (The scene: art_scene.hip; the versions of the acceleration
+// structure: art_versions.hip; the wave plan: art_plan.hip; rays in device buffers: art_cast.hip; the state they share: art_context.h.)
 // Product code; gfx950 only; there is no CPU fallback anywhere in this file.
 #include "art_context.h"
 #include <mutex>
@@ -47,7 +47,7 @@ void art::drop_graphs(ArtContext *c) {
 
 int32_t art::sync_all(ArtContext *c) {
     { int32_t r = cast_sync(c); if (r) return r; }   // (first: a cast may stand behind a refit below, never the other way round)
-    for (uint32_t i = 0; i < c->n_refit_streams; i++) HIPC(hipStreamSynchronize(c->refit_stream[i]));   // (a refit no frame has waited for yet)
+    { int32_t r = as_sync_streams(c); if (r) return r; }   // (a refit no frame has waited for yet)
     { int32_t r = plan_sync(c); if (r) return r; }
     for (uint32_t k = 0; k < c->F; k++) HIPC(hipStreamSynchronize(c->stream_of(k)));
     return ART_OK;
@@ -299,7 +299,7 @@ int32_t art_destroy(ArtContext *c) {
     for (uint32_t k = 0; k < c->F; k++) if (c->stream_of(k)) (void)hipStreamSynchronize(c->stream_of(k));
     drop_graphs(c);
     (void)cast_sync(c);   // (the casts on callers' streams too)
-    for (uint32_t i = 0; i < c->n_refit_streams; i++) (void)hipStreamSynchronize(c->refit_stream[i]);
+    (void)as_sync_streams(c);
     if (c->plan.plan_stream) (void)hipStreamSynchronize(c->plan.plan_stream);
     delete c;
     return ART_OK;
@@ -530,13 +530,13 @@ int32_t art_trace(ArtContext *c) {
     FrameSlot &S = c->slot[k];
     hipStream_t s = c->stream_of(k);
     if (S.wait_event) { HIPC(hipStreamWaitEvent(s, (hipEvent_t)S.wait_event, 0)); S.wait_event = nullptr; }
-    if (c->xform_dirty) { r = scene_refresh(c, k, s); if (r) return r; } // a model moved: the refit this frame is ordered behind (past the cost threshold: a rebuild)
+    if (as_pending(c)) { r = scene_refresh(c, k, s); if (r) return r; } // a model moved: the refit this frame is ordered behind (past the cost threshold: a rebuild)
     r = ensure_wide(c, c->kind_primary == 4 || c->kind_shadow == 4 || c->packet_wide); if (r) return r;
     r = ensure_binary(c, !c->packet_wide || c->kind_primary == 2 || c->kind_shadow == 2); if (r) return r;
     if (c->plan.enabled) { r = plan_poll(c); if (r) return r; }
-    const uint32_t ver = c->as_cur;
+    const uint32_t ver = as_current(c);
     r = as_wait_ready(c, ver, s, k); if (r) return r;   // the refit that wrote this version may still run on another ring slot's stream
-    if (!c->as.empty()) { c->as[ver].used[k] = c->frame_no + 1; c->as[ver].aux[k] = false; }
+    as_frame_reads(c, ver, k);
     S.as_version = ver;
     r = lights_upload(c, S, s); if (r) return r;
     FrameArgs a = make_frame_args(c, S, ver);
@@ -624,7 +624,7 @@ int32_t art_trace_ao(ArtContext *c, uint32_t spp, float radius) {
     r = ensure_binary(c, c->kind_ao == 2); if (r) return r;
     FrameArgs a = make_frame_args(c, S, S.as_version); // the structure the frame itself was traced in
     a.alpha = S.alpha; a.ray_masks = S.ray_masks;       // (and the cutoffs and masks of that version's table, and the cull masks that were current at the frame's art_trace)
-    if (!c->as.empty()) c->as[S.as_version].aux[c->last] = true;
+    as_aux_behind(c, S.as_version, c->last);
     HIPC(hipMemsetAsync(S.d_counters.p + 64 + 16 * 32, 0, 8 * 32 * 4, s)); // the AO launch's work cursors
     HIPC(hipEventRecord(S.ao_ev[0], s));
     if (a.n_local) launch_ao(a, spp, radius, S.d_occl.p, S.d_ao_pix.p, c->d_ao_tab.p, c->ao_entry, S.d_ao.p, lut, s);
@@ -919,8 +919,7 @@ int32_t art_get_stats(ArtContext *c, ArtStats *out) {
             }
         }
     }
-    c->stats.first_move_ms = c->first_move_ms; c->stats.versions_ms = c->versions_ms;
-    c->stats.refit_ms = c->last_refit_ms; c->stats.refit_cost_ratio = c->refit_cost_ratio; c->stats.refits = c->refits; c->stats.rebuilds = c->rebuilds;
+    as_fill_stats(c, &c->stats);
     *out = c->stats;
     return ART_OK;
 }

@@ -46,10 +46,10 @@ static int32_t cast_claim(ArtContext *c, hipStream_t user, RingSlot *q) {
     int32_t r = use_device(c); if (r) return r;
     r = cast_setup(c); if (r) return r;
     CastState &K = c->cast;
-    if (c->xform_dirty) { r = scene_refresh(c, ~0u, K.stream); if (r) return r; }   // the scene as of the call: the refit in front of the cast (past the cost threshold: a rebuild)
+    if (as_pending(c)) { r = scene_refresh(c, ~0u, K.stream); if (r) return r; }   // the scene as of the call: the refit in front of the cast (past the cost threshold: a rebuild)
     r = ensure_wide(c, true); if (r) return r;
     hipStream_t s = user ? user : K.stream.p;
-    const uint32_t ver = c->as_cur;
+    const uint32_t ver = as_current(c);
     r = as_wait_ready(c, ver, s, ~0u); if (r) return r;   // the refit that wrote this version may still run: an event wait on the cast's stream, nothing on the host
     const uint32_t bi = K.next % ART_CAST_POOL;
     CastBlock &B = K.block[bi];

@@ -1,6 +1,7 @@
-// art_context.h -- the host state behind include/art.h, shared by the host units (art_api.hip: context, frame ring, read-backs; art_scene.hip: scene tables and the ring
-// of acceleration-structure versions; art_plan.hip: the wave plan; art_cast.hip: rays in device buffers).  Private to those four: no kernel unit includes it, and
-// nothing here is exported from libart.so.  Each subsystem's state is written only in its own unit; the others call the functions declared at the end.
+// art_context.h -- the host state behind include/art.h, shared by the host units (art_api.hip: context, frame ring, read-backs; art_scene.hip: scene tables, setters and the
+// build; art_versions.hip: the ring of acceleration-structure versions and the refit; art_plan.hip: the wave plan; art_cast.hip: rays in device buffers).  Private to those
+// five: no kernel unit includes it, and nothing here is exported from libart.so.  Each subsystem's state is written only in its own unit; the others call the functions
+// declared at the end.
 #pragma once
 #include "art_internal.h"
 
@@ -92,7 +93,7 @@ struct WavePlan {
 // One version of what a frame reads of the acceleration structure.  A static scene has none (the build's arrays are read directly); the first
 // art_scene_set_model_matrix makes a small ring of them: a refit writes the NEXT version while frames in flight still read the older ones, like the
 // reference's per-frame TLAS (one VkTlasBuilder per FrameData, renderer.rs:300-318, :637-651).  Version 0 is the build's own arrays.
-// A version owns its event and nothing else: its arrays are views into the context's blocks (as_block, as_pinned, shade_block, stage_*) or, version 0's, into the tree.
+// A version owns its event and nothing else: its arrays are views into the ring's blocks (Versions::as_block, as_pinned, shade_block, stage_*) or, version 0's, into the tree.
 constexpr uint32_t kMaxAsVersions = 24;
 struct AsVersion {
     DevTri *tris = nullptr; DevNodeW *widef = nullptr; DevNode4 *wide = nullptr; DevPrim *prims = nullptr;
@@ -111,9 +112,31 @@ struct AsVersion {
     uint64_t epoch = 0;                  // which refit wrote it (0: the build)
     // Deformed meshes (art_scene_set_vertices): the version's own shading records (the build's array until the context first deforms a built primitive: version 0
     // keeps aliasing it, the others get copies), and its staging of the replaced vertices -- pinned, written by the host once the version's previous refit is over,
-    // and device memory, filled by one copy on the refit's stream that the regather in the refit's leaf stage reads (ArtContext::deform_off: where each primitive's are)
+    // and device memory, filled by one copy on the refit's stream that the regather in the refit's leaf stage reads (Versions::deform_off: where each primitive's are)
     DevShadeTri *shade = nullptr;
     ArtVertex *h_stage = nullptr; float *d_stage = nullptr;
+};
+
+// The ring of versions behind moving, deforming, masked and alpha-cut primitives (art_scene_set_model_matrix and its kin): its memory, what changed since the build, the
+// epochs and the cost rule, the refit streams.  Written only in art_versions.hip.  Members go in reverse order of declaration: the blocks before the versions that point into them.
+struct Versions {
+    DevBuf<char> as_block; Pinned<char> as_pinned;    // ONE device allocation and ONE pinned one behind all the versions (six + three per version before).  versions_ms is something else: the refit streams' creation (a
+                                                      // high-priority hardware queue each: 4-10 ms apiece) and the refit's work lists (host, 9 ms for config 2) -- ArtTuning.log bit 0 prints the parts
+    // Refits run on streams of their own, one per ring slot (up to four): the refit in front of frame n of slot k then overlaps frame n - F, which still runs on that slot's
+    // stream, instead of queueing behind it -- the slot's chain is frame, frame, frame with the refits beside it, and the frame waits for its refit's event.  (On the frame's
+    // own stream a slot's cycle was refit + frame: a model moving every frame cost the ring a third of its depth, profiles/README.md round 4.)
+    Stream refit_stream[4]; uint32_t n_refit_streams = 0;
+    std::vector<uint64_t> prim_moved;          // per primitive: the refit (as_epoch numbering) that first shows its latest move; 0: where the build put it
+    std::vector<uint64_t> prim_deformed;       // per primitive: the refit that first shows its latest vertices (art_scene_set_vertices); 0: the build's
+    std::vector<int64_t> deform_off;           // per primitive: first vertex of its slot in every version's staging (-1: never deformed since the build)
+    size_t deform_verts = 0;                   // vertices of a version's staging (the sum of the deformed primitives' counts)
+    DevBuf<char> shade_block;                  // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
+    DevBuf<char> stage_block; Pinned<char> stage_pinned;    // every version's staging of replaced vertices: device, pinned
+    std::vector<AsVersion> as; uint32_t as_cur = 0; bool xform_dirty = false;   // (views into the five blocks above)
+    int64_t masked_tris = 0;                   // triangles of primitives disabled since the build (still in the arrays, written "nowhere")
+    bool alpha_bits_stale = false;             // a built primitive got a cutoff > 0 since the bits (ArtContext::d_alpha_bits) were last made
+    uint64_t as_epoch = 0, binary_epoch = 0;   // refits so far; the refit the binary trees / node records reflect
+    double as_cost0 = 0.0; float refit_cost_ratio = 1.0f; uint32_t refits = 0, rebuilds = 0; float last_refit_ms = 0.f, first_move_ms = 0.f, versions_ms = 0.f;
 };
 
 // Rays in device buffers (art_cast_rays).  Every cast takes the next of a ring of ART_CAST_POOL blocks: the block's work cursors (zeroed on the cast's stream in
@@ -161,31 +184,14 @@ struct ArtContext {
     std::vector<uint8_t> uploaded;   // which primitives' vertices / indices / texels are on the device, at the offsets a build over exactly this set computes (empty: nothing): a
                               // build over the same set -- the rebuild behind the refit's cost rule, a change of tuning -- uploads only the primitive table
     uint32_t T = 0;
-    // moving models (art_scene_set_model_matrix): versions of the structure, the primitive table as the next refit will upload it
-    DevBuf<char> as_block; Pinned<char> as_pinned;    // ONE device allocation and ONE pinned one behind all the versions (six + three per version before).  versions_ms is something else: the refit streams' creation (a
-                                                      // high-priority hardware queue each: 4-10 ms apiece) and the refit's work lists (host, 9 ms for config 2) -- ArtTuning.log bit 0 prints the parts
-    // Refits run on streams of their own, one per ring slot (up to four): the refit in front of frame n of slot k then overlaps frame n - F, which still runs on that slot's
-    // stream, instead of queueing behind it -- the slot's chain is frame, frame, frame with the refits beside it, and the frame waits for its refit's event.  (On the frame's
-    // own stream a slot's cycle was refit + frame: a model moving every frame cost the ring a third of its depth, profiles/README.md round 4.)
-    Stream refit_stream[4]; uint32_t n_refit_streams = 0;
-    std::vector<DevPrim> h_dev_prims;          // host copy of d_prims (build order), matrices kept current
-    std::vector<uint64_t> prim_moved;          // per primitive: the refit (as_epoch numbering) that first shows its latest move; 0: where the build put it
-    std::vector<uint64_t> prim_deformed;       // per primitive: the refit that first shows its latest vertices (art_scene_set_vertices); 0: the build's
-    std::vector<int64_t> deform_off;           // per primitive: first vertex of its slot in every version's staging (-1: never deformed since the build)
-    size_t deform_verts = 0;                   // vertices of a version's staging (the sum of the deformed primitives' counts)
-    DevBuf<char> shade_block;                  // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
-    DevBuf<char> stage_block; Pinned<char> stage_pinned;    // every version's staging of replaced vertices: device, pinned
-    std::vector<AsVersion> as; uint32_t as_cur = 0; bool xform_dirty = false;   // (views into the five blocks above)
-    int64_t masked_tris = 0;                   // triangles of primitives disabled since the build (still in the arrays, written "nowhere")
+    Versions ver;                              // moving models: the ring of versions of the structure (art_versions.hip)
+    std::vector<DevPrim> h_dev_prims;          // host copy of d_prims (build order), matrices kept current: the primitive table as the next refit will upload it
     // alpha-masked primitives: the cutoffs travel in the versioned primitive table (DevPrim::cutoff), so a change is a refit over no batch, like a
     // primitive that is disabled; alpha_bits marks the leaves whose primitive may have a cutoff (made by the build, bits added in front of the refit that first shows a
     // new cutoff, never cleared until the next build: a superset is safe, the cutoff itself decides)
     DevBuf<uint32_t> d_alpha_bits;
     bool alpha_live = false;                   // some enabled primitive has a cutoff > 0 or a visibility mask other than 0xFF: frames and queries run the instances with the alpha test
     uint32_t ray_masks = kRayMasksAll;         // art_set_ray_masks: primary | shadow << 8 | ao << 16; per-launch state like the camera
-    bool alpha_bits_stale = false;             // a built primitive got a cutoff > 0 since the bits were last made
-    uint64_t as_epoch = 0, binary_epoch = 0;   // refits so far; the refit the binary trees / node records reflect
-    double as_cost0 = 0.0; float refit_cost_ratio = 1.0f; uint32_t refits = 0, rebuilds = 0; float last_refit_ms = 0.f, first_move_ms = 0.f, versions_ms = 0.f;
     ArtCamera camera{};
     uint32_t B = 1, read_b = 0;       // frames per launch of the fused frame (art_set_frames_per_launch); which of them the read / device-pointer calls refer to
     ArtCamera cam_more[kMaxBatch - 1] = {}; // cameras of frames 1.. of a launch (frame 0: camera)
@@ -234,17 +240,33 @@ int32_t use_device(ArtContext *c);
 void drop_graphs(ArtContext *c);
 int32_t sync_all(ArtContext *c);                           // every stream of the context, the casts on callers' streams included
 // ---- art_scene.hip ----
+int32_t ensure_wide(ArtContext *c, bool needed);
+int32_t ensure_binary(ArtContext *c, bool needed);
+void gid_to_ids(const ArtContext *c, uint32_t gid, int32_t *ids);
+// ---- art_versions.hip (every write of a Versions field is there) ----
 AsPtrs as_ptrs(const ArtContext *c, uint32_t v);
+uint32_t as_current(const ArtContext *c);                  // the version the next launch reads
+bool as_pending(const ArtContext *c);                      // a primitive changed since that version was written: scene_refresh in front of the next launch
 void as_release(ArtContext *c);                            // the versions go (the caller synchronised); the tree and its work lists stay
 // Launches on `stream` read version v: ordered behind the refit that wrote it, by an event wait while that refit may still run.  own_slot: the ring slot whose stream
 // `stream` is -- a refit recorded on that slot's stream orders the launch by itself -- or ~0u for a stream that no ring slot owns (casts; scene_refresh writes
 // ready_slot the same way).
 int32_t as_wait_ready(ArtContext *c, uint32_t v, hipStream_t stream, uint32_t own_slot);
+void as_frame_reads(ArtContext *c, uint32_t v, uint32_t k);   // ring slot k's frame about to be launched (frame_no) reads version v
+void as_aux_behind(ArtContext *c, uint32_t v, uint32_t k);    // art_trace_ao / art_present ran behind that frame on the slot's stream
 void harvest_cost(ArtContext *c);
 int32_t scene_refresh(ArtContext *c, uint32_t k, hipStream_t s);
-int32_t ensure_wide(ArtContext *c, bool needed);
-int32_t ensure_binary(ArtContext *c, bool needed);
-void gid_to_ids(const ArtContext *c, uint32_t gid, int32_t *ids);
+int32_t refresh_now(ArtContext *c);                        // the parity surface's: nothing in flight, the pending change applied
+int32_t as_sync_streams(ArtContext *c);                    // sync_all's and art_destroy's part: a refit no frame has waited for yet
+void as_fill_stats(const ArtContext *c, ArtStats *st);     // first_move_ms, versions_ms, refit_ms, refit_cost_ratio, refits, rebuilds
+void as_scene_reset(ArtContext *c);                        // art_scene_build's start (synchronised): the ring goes, the epochs and the cost rule start over, nothing is pending
+int32_t as_scene_built(ArtContext *c);                     // ... and its end: the per-primitive records of the new table; the ring at once under ART_FLAG_DYNAMIC_SCENE
+bool binary_is_current(const ArtContext *c);               // ensure_binary's: the binary trees reflect the current version
+void binary_mark(ArtContext *c, bool current);             // ... they do now / they have to be made again whatever the version
+// what the setters report about a primitive of the built structure.  shows: it is enabled, so the next launch has to refit first
+void as_prim_moved(ArtContext *c, uint32_t id, bool shows, int64_t masked_delta = 0);   // a matrix; masked_delta: triangles that left (+) or came back (-) with a residency change
+int32_t as_prim_deformed(ArtContext *c, uint32_t id, bool shows);   // new vertices: the ring if there is none, the versions' shading records and staging (one synchronisation the first time); fails with nothing changed
+void as_table_changed(ArtContext *c, bool new_alpha_bits); // a cutoff or a visibility mask: a refit over no batch; new_alpha_bits: the primitive's leaves need their bits first
 // ---- art_plan.hip (every write of a WavePlan field is there) ----
 int32_t plan_reset(ArtContext *c, const std::vector<uint32_t> &order);   // a new frame layout: the launch order of its 256-pixel blocks, the first table
 int32_t plan_poll(ArtContext *c);

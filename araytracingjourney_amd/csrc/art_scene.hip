@@ -1,9 +1,8 @@
-// art_scene.hip -- the scene behind include/art.h: the primitive table and its setters, art_scene_build, the ring of versions of the acceleration structure (refit,
-// deformation), the trees the non-default walks read on demand, and the tree read-outs of the parity surface.  Host code only; the kernels are art_build.hip's (LBVH), art_wide.hip's (4-wide collapse) and art_refit.hip's (refit).
+// art_scene.hip -- the scene behind include/art.h: the primitive table and its setters, art_scene_build, the trees the non-default walks read on demand, and the tree
+// read-outs of the parity surface.  What a setter changes in a built scene it reports to the ring of versions (art_versions.hip), which refits in front of the next launch.
+// Host code only; the kernels are art_build.hip's (LBVH) and art_wide.hip's (4-wide collapse).
 #include "art_context.h"
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 
 static void affine_inverse(const float *m, float *o) { // row-major 3x4
@@ -42,223 +41,14 @@ static void alpha_refresh_live(ArtContext *c) {
     c->alpha_live = any;
 }
 
-// ---- versions of the acceleration structure (moving models) ------------------------------------------------------------------------------
-AsPtrs art::as_ptrs(const ArtContext *c, uint32_t v) {
-    if (c->as.empty()) return AsPtrs{c->bvh.tris, c->bvh.widef, c->bvh.wide, c->d_prims.p, c->bvh.shade_tris};
-    const AsVersion &V = c->as[v];
-    return AsPtrs{V.tris, V.widef, V.wide, V.prims, V.shade};
-}
-static uint64_t as_epoch_of(const ArtContext *c, uint32_t v) { return c->as.empty() ? 0 : c->as[v].epoch; }
-// everything that reads them has finished (the caller synchronised)
-void art::as_release(ArtContext *c) {
-    c->as.clear(); c->as_cur = 0;   // (their events) -- then the blocks they pointed into: device arrays, staging memory, shading records, staging of replaced vertices
-    c->as_block.release(); c->as_pinned.release(); c->shade_block.release(); c->stage_block.release(); c->stage_pinned.release();
-    c->deform_verts = 0; std::fill(c->deform_off.begin(), c->deform_off.end(), (int64_t)-1);
-}
-// the first move of a built scene: the ring of versions (ArtTuning.as_versions; default 4: one more than the reference's frames in flight, renderer.rs:135 -- measured on
-// config 2 with a model of 164 k triangles moving every frame, 16 ring slots: 0.70 / 0.38 / 0.28 / 0.25 / 0.26 ms per frame with 1 / 2 / 3 / 4 / 8 versions), every one a copy of
-// the build's arrays -- the topology (child references, valid masks, sort axes) is never written again -- and the cost of the tree as built
-static int32_t as_create(ArtContext *c) {
-    int32_t r = ensure_wide(c, true); if (r) return r;
-    r = sync_all(c); if (r) return r;
-    const auto t_begin = std::chrono::steady_clock::now();
-    // (default: twice the frames in flight, 4 at least and 24 at most.  The host may issue the refit of frame n once the frames that read that version -- frame n - K -- are
-    //  over, so K sets how far it runs ahead of the GPU: with K = F + 1 a refit is issued when its ring slot's previous frame has all but finished and its latency -- 0.5 ms
-    //  among eight frames in flight -- stands in front of the slot's next frame; with K = 2 F it is a ring trip ahead.  Config 2, F = 8, a model of 164 k triangles moving
-    //  every frame: 0.252 / 0.229 / 0.213 / 0.210 / 0.205 / 0.205 ms a frame with 4 / 8 / 10 / 12 / 16 / 24 versions (profiles/README.md round 4d); a version is the tree's
-    //  arrays once more: 42 MB for config 2, 450 MB for config 4.)
-    const uint32_t K = c->tuning.as_versions ? std::min(c->tuning.as_versions, kMaxAsVersions) : std::min(std::max(2u * c->F, 4u), kMaxAsVersions);
-    const size_t np = c->h_dev_prims.size(), T = c->T, NW = c->bvh.n_wide;
-    c->as.clear(); c->as.resize(K);
-    hipStream_t s = c->main_stream();
-    double t_sec[6] = {0, 0, 0, 0, 0, 0};
-    auto lap = [&, last = std::chrono::steady_clock::now()](int i) mutable { const auto n = std::chrono::steady_clock::now(); t_sec[i] += std::chrono::duration<double, std::milli>(n - last).count(); last = n; };
-    auto body = [&]() -> int32_t {
-        const uint32_t want = c->tuning.refit_streams == 0xFFFFFFFFu ? 0u : (c->tuning.refit_streams ? std::min(c->tuning.refit_streams, 4u) : std::min(c->F, 4u));
-        while (c->n_refit_streams < want) {   // (kept for the life of the context)
-            int lo = 0, hi = 0; HIPC(hipDeviceGetStreamPriorityRange(&lo, &hi));   // hi: the numerically smallest = the most urgent: a refit is a handful of small launches a whole frame waits for
-            HIPC(c->refit_stream[c->n_refit_streams].create(hi)); c->n_refit_streams++;
-        }
-        while (c->n_refit_streams > want) c->refit_stream[--c->n_refit_streams].release();   // (waits for it first)
-        lap(0);
-        if (!c->bvh.sub_off) { // the parents in the 4-wide tree and the refit's work lists (a workgroup per batch of subtrees): all there or none (refit_lists_build)
-            hipError_t e = refit_lists_build(c->bvh, c->T, s);
-            if (e != hipSuccess) return hipfail(e, "refit_lists_build");
-        }
-        lap(1);
-        // one device block and one pinned block, carved per version (256-byte steps)
-        auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
-        const size_t nbat = c->bvh.sub_batches ? c->bvh.sub_batches : 1;
-        const size_t dev_owned = pad(T * sizeof(DevTri)) + pad(NW * sizeof(DevNodeW)) + pad(NW * sizeof(DevNode4)) + pad(np * sizeof(DevPrim)), dev_every = pad(NW * 4) + pad(32) + pad(nbat * 8);
-        const size_t pin_every = pad(np * sizeof(DevPrim)) + pad(np) + pad(32) + pad(nbat * 4);
-        HIPC(c->as_block.ensure((K - 1) * dev_owned + K * dev_every));
-        HIPC(c->as_pinned.ensure(K * pin_every));
-        lap(2);
-        char *dp = c->as_block.p, *hp = c->as_pinned.p, *dhp = c->as_pinned.d;
-        auto carve = [&](char *&p, size_t n) { char *q = p; p += pad(n); return q; };
-        for (uint32_t v = 0; v < K; v++) { // (everything on the context's first stream, asynchronously: one wait at the end)
-            AsVersion &V = c->as[v];
-            V.shade = c->bvh.shade_tris;   // (every version's own copy only once a built primitive is deformed: deform_prepare)
-            if (v == 0) { V.tris = c->bvh.tris; V.widef = c->bvh.widef; V.wide = c->bvh.wide; V.prims = c->d_prims.p; }
-            else {
-                V.owned = true;
-                V.tris = (DevTri *)carve(dp, T * sizeof(DevTri)); V.widef = (DevNodeW *)carve(dp, NW * sizeof(DevNodeW)); V.wide = (DevNode4 *)carve(dp, NW * sizeof(DevNode4)); V.prims = (DevPrim *)carve(dp, np * sizeof(DevPrim));
-                HIPC(hipMemcpyAsync(V.tris, c->bvh.tris, T * sizeof(DevTri), hipMemcpyDeviceToDevice, s)); HIPC(hipMemcpyAsync(V.widef, c->bvh.widef, NW * sizeof(DevNodeW), hipMemcpyDeviceToDevice, s));
-                HIPC(hipMemcpyAsync(V.wide, c->bvh.wide, NW * sizeof(DevNode4), hipMemcpyDeviceToDevice, s)); HIPC(hipMemcpyAsync(V.prims, c->d_prims.p, np * sizeof(DevPrim), hipMemcpyDeviceToDevice, s));
-            }
-            V.mark = (uint32_t *)carve(dp, NW * 4); V.acc = (double *)carve(dp, 32); V.batch_cost = (double *)carve(dp, nbat * 8);
-            HIPC(hipMemsetAsync(V.mark, 0, NW * 4, s)); HIPC(hipMemsetAsync(V.acc, 0, 32, s));
-            const size_t off = (size_t)(hp - c->as_pinned.p);
-            V.h_prims = (DevPrim *)carve(hp, np * sizeof(DevPrim)); V.h_touched = (uint8_t *)carve(hp, np); V.h_result = (double *)carve(hp, 32);
-            V.dh_prims = (DevPrim *)(dhp + off); V.dh_touched = (uint8_t *)(dhp + off + pad(np * sizeof(DevPrim))); V.dh_result = (double *)(dhp + off + pad(np * sizeof(DevPrim)) + pad(np));
-            V.h_dirty = (uint32_t *)carve(hp, nbat * 4); V.dh_dirty = (uint32_t *)(dhp + off + pad(np * sizeof(DevPrim)) + pad(np) + pad(32));
-            HIPC(V.ready.create(hipEventDisableTiming));
-        }
-        lap(3);
-        AsVersion &V0 = c->as[0];
-        launch_wide_cost(c->bvh.n_wide, V0.widef, nullptr, V0.acc, V0.dh_result, s);   // the cost of the tree as built
-        HIPC(hipGetLastError()); HIPC(hipStreamSynchronize(s));
-        c->as_cost0 = V0.h_result[0]; c->refit_cost_ratio = 1.0f;
-        lap(4);
-        if (c->tuning.log & 1u) std::fprintf(stderr, "[art] versions: %u of them; refit streams %.2f ms, parents + work lists %.2f, the two allocations %.2f, copies issued + events %.2f, the wait for them + the cost of the tree as built %.2f\n", K, t_sec[0], t_sec[1], t_sec[2], t_sec[3], t_sec[4]);
-        return ART_OK;
-    };
-    r = body();
-    if (r) as_release(c);
-    c->versions_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    return r;
-}
-// the surface-area cost of the latest refit travels to the host behind it; once it has arrived it is what ArtStats.refit_cost_ratio and the rebuild rule go by
-void art::harvest_cost(ArtContext *c) {
-    if (c->as.empty()) return;
-    AsVersion &L = c->as[c->as_cur];
-    if (!L.result_pending || hipEventQuery(L.ready) != hipSuccess) return;
-    L.result_pending = false; L.ready_known = true;
-    if (c->as_cost0 > 0.0) c->refit_cost_ratio = (float)(L.h_result[0] / c->as_cost0);
-    const unsigned long long *st = reinterpret_cast<const unsigned long long *>(L.h_result);
-    c->last_refit_ms = (float)((double)(st[3] - st[2]) * 1e-5);   // wall_clock64: 100 MHz
-}
-int32_t art::as_wait_ready(ArtContext *c, uint32_t v, hipStream_t stream, uint32_t own_slot) {
-    if (c->as.empty()) return ART_OK;
-    AsVersion &V = c->as[v];
-    if (V.ready_known) return ART_OK;
-    if (hipEventQuery(V.ready) == hipSuccess) { V.ready_known = true; return ART_OK; }
-    if (own_slot == ~0u) (void)hipGetLastError();    // (no launch check of a frame follows: the not-ready answer is not left behind)
-    else if (V.ready_slot == own_slot) return ART_OK;   // the refit is in front of the launch on this very stream
-    HIPC(hipStreamWaitEvent(stream, V.ready, 0));      // nothing on the host
-    return ART_OK;
-}
-// A model moved since the last launch: bring the NEXT version of the structure up to date on stream s, the stream of ring slot k whose frame is about to be
-// launched -- the frame is ordered behind the refit by the stream, frames on other streams by V.ready (art_trace).  Frames still reading the version about to be
-// written are waited for on the host, like the reference's per-frame fence (renderer.rs:451-466).
-// What the stream sees: three launches and one event record (round 3: two uploads, a launch per tree level, a clear, the cost's read-back and four event records --
-// twenty operations, 0.3 ms of issue in front of a 0.1 ms refit).
-// (k = ~0u: in front of a cast, s a stream of the context that no frame runs on: every ring slot's frames are waited for, every later launch waits for V.ready)
-int32_t art::scene_refresh(ArtContext *c, uint32_t k, hipStream_t s) {
-    if (!c->xform_dirty) return ART_OK;
-    int32_t r;
-    if (c->as.empty()) { // (a host that announced its moves with ART_FLAG_DYNAMIC_SCENE paid this in art_scene_build)
-        const auto t_begin = std::chrono::steady_clock::now();
-        r = as_create(c); if (r) return r;
-        c->first_move_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
-    {   // the cost of the latest refit, if it has arrived: past the threshold the tree is built again for where the models are now
-        harvest_cost(c);
-        const float thr = c->tuning.refit_rebuild_ratio > 0.0f ? c->tuning.refit_rebuild_ratio : (c->tuning.refit_rebuild_ratio < 0.0f ? INFINITY : 2.0f);
-        if (c->refit_cost_ratio > thr) {
-            if (c->tuning.log & 1u) std::fprintf(stderr, "[art] refit cost %.2f x the build's: building again\n", c->refit_cost_ratio);
-            r = art_scene_build(c); // (synchronises, uploads the primitives with their current matrices, drops the versions)
-            if (r == ART_OK) c->rebuilds++;
-            return r;
-        }
-    }
-    const uint32_t K = (uint32_t)c->as.size(), next = (c->as_cur + 1) % K;
-    AsVersion &V = c->as[next];
-    const bool beside = c->n_refit_streams != 0;   // the refit runs beside the slot's frames, on a stream of its own
-    if (beside) s = c->refit_stream[k % c->n_refit_streams];
-    for (uint32_t j = 0; j < c->F; j++) {
-        if (j != k || beside) { // (on the frame's own stream ring slot k's earlier work is ordered before the refit by that stream)
-            if (V.aux[j]) HIPC(hipStreamSynchronize(c->stream_of(j)));
-            else if (V.used[j]) {
-                const uint64_t f = V.used[j] - 1;
-                if (c->frame_no - f <= (uint64_t)ArtContext::kRing) HIPC(hipEventSynchronize(c->ev[f % ArtContext::kRing][4])); else HIPC(hipStreamSynchronize(c->stream_of(j)));
-            }
-        }
-        V.used[j] = 0; V.aux[j] = false;
-    }
-    r = cast_wait_version(c, next); if (r) return r;   // casts still reading it (art_cast_rays: a cast holds the version it was launched on): the same wait, counted
-    // the staging memory below is read by the kernels of the refit that wrote this version last: that refit has to be over before the host writes it again (it is, whenever the
-    // frames above were waited for -- they ran behind it -- but nothing else says so: a version no frame ever read, a ring slot that skipped its turn)
-    if (!V.ready_known) { HIPC(hipEventSynchronize(V.ready)); V.ready_known = true; }
-    V.result_pending = false;
-    if (c->graph_mode) drop_graphs(c); // a captured frame holds the old version's pointers
-    const size_t np = c->h_dev_prims.size();
-    std::memcpy(V.h_prims, c->h_dev_prims.data(), np * sizeof(DevPrim));
-    for (size_t p = 0; p < np; p++) V.h_touched[p] = (p < c->prim_moved.size() && c->prim_moved[p] > V.epoch) ? 1 : 0;   // what moved since THIS version was written (it may be several refits behind)
-    {   // what was deformed since this version was written: its current vertices into the version's staging (pinned, then ONE copy a run of slots on the refit's stream, in
-        // front of the refit that reads them from device memory), its table entry pointed there, and its shading records gathered again by the refit's leaf stage
-        size_t run_lo = 0, run_hi = 0;   // the run of staging slots the next copy covers (vertices)
-        auto flush = [&]() -> int32_t {
-            if (run_hi > run_lo) HIPC(hipMemcpyAsync(V.d_stage + run_lo * 12, V.h_stage + run_lo, (run_hi - run_lo) * sizeof(ArtVertex), hipMemcpyHostToDevice, s));
-            run_lo = run_hi = 0; return ART_OK;
-        };
-        for (size_t p = 0; p < np && p < c->prim_deformed.size(); p++) {
-            if (c->prim_deformed[p] <= V.epoch) continue;
-            const std::vector<ArtVertex> &vv = c->prims[p].verts;
-            const size_t off = (size_t)c->deform_off[p];
-            std::memcpy(V.h_stage + off, vv.data(), vv.size() * sizeof(ArtVertex));
-            V.h_prims[p].vertices = V.d_stage + off * 12;
-            V.h_touched[p] |= kTouchRegather;
-            if (off != run_hi) { r = flush(); if (r) return r; run_lo = off; }
-            run_hi = off + vv.size();
-        }
-        r = flush(); if (r) return r;
-    }
-    RefitArgs ra{};
-    ra.T = c->T; ra.n_wide = c->bvh.n_wide; ra.n_prims = (uint32_t)np; ra.shade = V.shade; ra.prims_host = V.dh_prims; ra.prims_dev = V.prims; ra.touched = V.dh_touched;
-    ra.sub_nodes = c->bvh.sub_nodes; ra.sub_leaves = c->bvh.sub_leaves; ra.sub_off = c->bvh.sub_off; ra.sub_batches = c->bvh.sub_batches; ra.sub_levels = c->bvh.sub_levels;
-    ra.leaf_parent = c->bvh.leaf_parent; ra.node_parent = c->bvh.node_parent; ra.mark = V.mark; ra.tris = V.tris; ra.wide = V.wide; ra.widef = V.widef; ra.acc = V.acc; ra.result = V.dh_result;
-    {   // the batches that hold a primitive that moved (since this version was written); the others keep their triangles, their boxes and -- in a large tree -- their
-        // cached share of the cost, which a version's first refit makes for all of them
-        const std::vector<uint32_t> &po = c->bvh.batch_prim_off, &pi = c->bvh.batch_prim_ids;
-        ra.fold = c->bvh.n_wide >= (c->tuning.refit_fold_nodes ? c->tuning.refit_fold_nodes : kFoldRequantNodes);
-        const bool all = po.size() != (size_t)c->bvh.sub_batches + 1 || (ra.fold && !V.cost_cached);
-        uint32_t nd = 0;
-        if (!all) for (uint32_t b = 0; b < c->bvh.sub_batches; b++) {
-            bool hit = false;
-            for (uint32_t i = po[b]; i < po[b + 1] && !hit; i++) hit = pi[i] < np && V.h_touched[pi[i]] != 0;
-            if (hit) V.h_dirty[nd++] = b;
-        }
-        ra.dirty = all ? nullptr : V.dh_dirty; ra.n_dirty = nd; ra.batch_cost = V.batch_cost;
-        if (all) V.cost_cached = true;
-    }
-    if (c->alpha_bits_stale) {   // a primitive got a cutoff: its leaves' bits, from this version's table, in front of the refit whose event the frames wait for
-        launch_alpha_bits(c->T, c->bvh.leaf_gid, c->bvh.tri_prim, V.dh_prims, c->d_alpha_bits.p, s);
-        c->alpha_bits_stale = false;
-    }
-    launch_refit(ra, s);
-    HIPC(hipEventRecord(V.ready, s)); V.ready_known = false; V.ready_slot = beside ? ~0u : k; V.result_pending = true;   // (~0: no frame stream is behind it by itself)
-    HIPC(hipGetLastError());
-    c->as_cur = next; V.epoch = ++c->as_epoch; c->xform_dirty = false; c->refits++;
-    return ART_OK;
-}
-// for the calls that read the structure outside a frame (queries, the parity surface): nothing in flight, the pending move applied
-static int32_t refresh_now(ArtContext *c) {
-    int32_t r = sync_all(c); if (r) return r;
-    if (!c->xform_dirty) return ART_OK;
-    r = scene_refresh(c, 0, c->stream_of(0)); if (r) return r;
-    r = sync_all(c); if (r) return r;   // (the refit may have run on a stream of its own)
-    if (!c->as.empty()) c->as[c->as_cur].ready_known = true;
-    return ART_OK;
-}
 // the binary trees and the 64-byte node records follow the versions on demand only (the non-default walks and the parity surface read them): they are
 // not versioned, so this waits for everything in flight
 int32_t art::ensure_binary(ArtContext *c, bool needed) {
-    if (!needed || c->binary_epoch == as_epoch_of(c, c->as_cur)) return ART_OK;
+    if (!needed || binary_is_current(c)) return ART_OK;
     int32_t r = sync_all(c); if (r) return r;
-    hipError_t e = binary_refit(c->bvh, c->T, as_ptrs(c, c->as_cur).tris, c->main_stream());
+    hipError_t e = binary_refit(c->bvh, c->T, as_ptrs(c, as_current(c)).tris, c->main_stream());
     if (e != hipSuccess) return hipfail(e, "binary_refit");
-    c->binary_epoch = as_epoch_of(c, c->as_cur);
+    binary_mark(c, true);
     drop_graphs(c);
     return ART_OK;
 }
@@ -321,10 +111,7 @@ int32_t art_scene_set_primitive_enabled(ArtContext *c, uint32_t id, int32_t enab
         // device arrays stay where they are until the next art_scene_build (288 GB of HBM: the way back is as cheap).
         DevPrim &d = c->h_dev_prims[id];
         d.masked = (d.masked & ~kPrimOut) | (p.enabled ? 0u : kPrimOut);   // (the visibility bits stay)
-        c->masked_tris += p.enabled ? -(int64_t)d.n_tri : (int64_t)d.n_tri;
-        c->prim_moved[id] = c->as_epoch + 1;
-        c->xform_dirty = true;
-        c->stats.num_triangles = (uint32_t)((int64_t)c->T - c->masked_tris);
+        as_prim_moved(c, id, true, p.enabled ? -(int64_t)d.n_tri : (int64_t)d.n_tri);   // (ArtStats.num_triangles follows)
         return ART_OK;
     }
     c->built = false;                                            // not part of the built structure: art_scene_build
@@ -347,8 +134,7 @@ int32_t art_scene_set_alpha_cutoff(ArtContext *c, uint32_t id, float cutoff) {
     DevPrim &d = c->h_dev_prims[id];
     d.cutoff = cutoff;
     if (d.n_tri == 0) return ART_OK;                                // no triangles in the structure (a build brings them, with the cutoff)
-    if (cutoff > 0.0f && !was_cut) c->alpha_bits_stale = true;      // its leaves get their bits in front of the refit
-    c->xform_dirty = true;                                          // the next art_trace (or query) writes the next version of the table
+    as_table_changed(c, cutoff > 0.0f && !was_cut);                 // the next art_trace (or query) writes the next version of the table; a new cutoff's leaves get their bits in front of the refit
     return ART_OK;
 }
 
@@ -366,8 +152,7 @@ int32_t art_scene_set_primitive_mask(ArtContext *c, uint32_t id, uint32_t mask) 
     DevPrim &d = c->h_dev_prims[id];
     d.masked = (d.masked & kPrimOut) | ((~mask & 0xFFu) << kPrimVisShift);
     if (d.n_tri == 0) return ART_OK;                                // no triangles in the structure (a build brings them, with the mask)
-    if (mask != 0xFFu) c->alpha_bits_stale = true;                  // its leaves get their bits in front of the refit (bits that are there already stay)
-    c->xform_dirty = true;                                          // the next art_trace (or query) writes the next version of the table
+    as_table_changed(c, mask != 0xFFu);                             // the next art_trace (or query) writes the next version of the table; its leaves get their bits in front of the refit (bits that are there already stay)
     return ART_OK;
 }
 
@@ -388,42 +173,7 @@ int32_t art_scene_set_model_matrix(ArtContext *c, uint32_t first, uint32_t n, co
         std::memcpy(p.o2w, model3x4, 48); std::memcpy(p.w2o, w2o, 48);
         if (!c->built || id >= c->h_dev_prims.size()) continue;  // takes effect with the build
         std::memcpy(c->h_dev_prims[id].o2w, model3x4, 48); std::memcpy(c->h_dev_prims[id].w2o, w2o, 48);
-        if (id < c->prim_moved.size()) c->prim_moved[id] = c->as_epoch + 1;   // the next refit is the first to show it
-        if (p.enabled) c->xform_dirty = true;                    // instanced: the next art_trace (or query) refits first
-    }
-    return ART_OK;
-}
-
-// The first deformation of a built primitive (art_scene_set_vertices): every version gets shading records of its own (a frame in flight must keep the normals it was
-// launched with), and the primitive a slot in every version's staging.  One synchronisation, here and never in front of a frame: an allocation that fails
-// comes back from the call that asked for it, with nothing changed.
-static int32_t deform_prepare(ArtContext *c, uint32_t id) {
-    const uint32_t K = (uint32_t)c->as.size();
-    const bool need_shade = K > 1 && !c->shade_block, need_stage = c->deform_off[id] < 0;
-    if (!need_shade && !need_stage) return ART_OK;   // (the steady state)
-    int32_t r = sync_all(c); if (r) return r;
-    auto pad = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    if (need_shade) {   // versions 1 .. K-1: copies of the build's records (nothing has written any version's yet); version 0 keeps aliasing them
-        const size_t each = pad((size_t)c->T * sizeof(DevShadeTri));
-        DevBuf<char> blk;   // (the context takes it once the copies are in it)
-        hipError_t e = blk.ensure((K - 1) * each);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(ART_E_NOMEM, std::string("art_scene_set_vertices: the versions' shading records: ") + hipGetErrorString(e)); }
-        hipStream_t s = c->main_stream();
-        for (uint32_t v = 1; v < K && e == hipSuccess; v++) e = hipMemcpyAsync(blk.p + (v - 1) * each, c->bvh.shade_tris, (size_t)c->T * sizeof(DevShadeTri), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hipfail(e, "art_scene_set_vertices: copies of the shading records");
-        c->shade_block = std::move(blk);
-        for (uint32_t v = 1; v < K; v++) c->as[v].shade = (DevShadeTri *)(c->shade_block.p + (v - 1) * each);
-    }
-    if (need_stage) {   // a larger staging for every version; what the old one held is not needed (a refit writes a version's staging in full for what it regathers)
-        const size_t nv = c->deform_verts + c->prims[id].verts.size(), each = pad(nv * sizeof(ArtVertex));
-        DevBuf<char> dblk; Pinned<char> hblk;   // (both or neither: the context keeps the old ones until then)
-        hipError_t e = dblk.ensure(K * each);
-        if (e == hipSuccess) e = hblk.ensure(K * each);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(ART_E_NOMEM, std::string("art_scene_set_vertices: staging of the vertices: ") + hipGetErrorString(e)); }
-        c->stage_block = std::move(dblk); c->stage_pinned = std::move(hblk);
-        for (uint32_t v = 0; v < K; v++) { c->as[v].d_stage = (float *)(c->stage_block.p + v * each); c->as[v].h_stage = (ArtVertex *)(c->stage_pinned.p + v * each); }
-        c->deform_off[id] = (int64_t)c->deform_verts; c->deform_verts = nv;
+        as_prim_moved(c, id, p.enabled);                         // the next refit is the first to show it; instanced: the next art_trace (or query) refits first
     }
     return ART_OK;
 }
@@ -436,19 +186,11 @@ int32_t art_scene_set_vertices(ArtContext *c, uint32_t id, const ArtVertex *vert
     const bool in_tree = c->built && id < c->h_dev_prims.size() && c->h_dev_prims[id].n_tri > 0;   // its triangles are in the built structure (masked or not)
     if (in_tree) {
         int32_t r = use_device(c); if (r) return r;
-        if (c->as.empty()) {   // (the ring of versions: art_scene_build made it already when the host announced ART_FLAG_DYNAMIC_SCENE)
-            const auto t_begin = std::chrono::steady_clock::now();
-            r = as_create(c); if (r) return r;
-            c->first_move_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        }
-        r = deform_prepare(c, id); if (r) return r;
+        r = as_prim_deformed(c, id, p.enabled); if (r) return r;     // the versions' memory for it (a failure changes nothing); the next refit is the first to show the vertices below
     }
     std::memcpy(p.verts.data(), verts, (size_t)n_verts * sizeof(ArtVertex));
     p.verts_stale = true;                                            // the device's build copy is behind (a rebuild over the same set uploads them again)
-    if (!in_tree) return ART_OK;                                     // takes effect with the build
-    c->prim_deformed[id] = c->as_epoch + 1;                          // the next refit is the first to show them
-    if (p.enabled) c->xform_dirty = true;                            // instanced: the next art_trace (or query) refits first; a masked one is regathered when it comes back
-    return ART_OK;
+    return ART_OK;                                                   // (not in the tree: takes effect with the build)
 }
 
 int32_t art_scene_build(ArtContext *c) {
@@ -456,7 +198,7 @@ int32_t art_scene_build(ArtContext *c) {
     if (c->prims.empty()) return fail(ART_E_STATE, "art_scene_build: no primitives");
     int32_t r = use_device(c); if (r) return r;
     r = sync_all(c); if (r) return r;
-    as_release(c); c->xform_dirty = false; c->as_epoch = 0; c->binary_epoch = 0; c->refit_cost_ratio = 1.0f; // the versions were copies of the tree that goes away
+    as_scene_reset(c); // the versions were copies of the tree that goes away
     c->bvh = Lbvh{}; c->bvh.arena = &c->arena; c->built = false; drop_graphs(c);
     // Only enabled primitives are uploaded and instanced (get_acceleration_structure_instance returns None unless the model is in
     // the Device state, vk_model.rs:360-372).  Ids keep their meaning: a disabled primitive stays in the table with zero triangles.
@@ -510,8 +252,7 @@ int32_t art_scene_build(ArtContext *c) {
     HIPC(hipMemcpy(c->d_first_tri.p, first.data(), first.size() * 4, hipMemcpyHostToDevice));
     c->uploaded = any ? now_set : std::vector<uint8_t>();
     c->h_first_tri = first;
-    c->h_dev_prims = dp; c->masked_tris = 0;
-    c->prim_moved.assign(dp.size(), 0); c->prim_deformed.assign(dp.size(), 0); c->deform_off.assign(dp.size(), -1);
+    c->h_dev_prims = dp;
     c->T = T;
     BuildInputs in{c->d_prims.p, (uint32_t)dp.size(), c->d_first_tri.p, T, c->cfg.morton_bits};
     Event e0, e1;
@@ -546,14 +287,11 @@ int32_t art_scene_build(ArtContext *c) {
         // the shadow-occluder hints are leaf positions of the tree that just went away: all empty (nothing is in flight -- sync_all above -- and the wait below is in front of every later frame)
         if (c->d_hints.p) HIPC(hipMemsetAsync(c->d_hints.p, 0xFF, c->d_hints.n * 4, c->main_stream()));
         HIPC(hipStreamSynchronize(c->main_stream()));
-        c->alpha_bits_stale = false;
         alpha_refresh_live(c);
     }
     c->built = true;
     plan_hint_built(c);
-    c->first_move_ms = 0.f; c->versions_ms = 0.f;
-    if (c->cfg.flags & ART_FLAG_DYNAMIC_SCENE) { r = as_create(c); if (r) return r; }   // the host said its models move: the ring of versions now, not in front of the first moved frame
-    return ART_OK;
+    return as_scene_built(c);   // the ring's records of the new table; the ring itself now if the host said its models move
 }
 
 int32_t art_get_lbvh(ArtContext *c, uint32_t *leaf_gid, uint64_t *keys, int32_t *child, float *node_lo, float *node_hi, float *leaf_lo, float *leaf_hi) {
@@ -561,7 +299,7 @@ int32_t art_get_lbvh(ArtContext *c, uint32_t *leaf_gid, uint64_t *keys, int32_t 
     if (!c->built) return fail(ART_E_STATE, "art_get_lbvh: scene not built");
     int32_t r = use_device(c); if (r) return r;
     r = refresh_now(c); if (r) return r;       // after a move: the boxes of where the models are now (the keys and the topology are the build's)
-    if (!c->bvh.canon_boxes) c->binary_epoch = ~0ull;   // the build left the canonical tree's boxes for now: have them made
+    if (!c->bvh.canon_boxes) binary_mark(c, false);     // the build left the canonical tree's boxes for now: have them made
     r = ensure_binary(c, true); if (r) return r;
     size_t T = c->T, NI = T > 1 ? T - 1 : 0;
     if (leaf_gid) HIPC(hipMemcpy(leaf_gid, c->bvh.leaf_gid, T * 4, hipMemcpyDeviceToHost));
@@ -599,7 +337,7 @@ int32_t art_get_wide_nodes(ArtContext *c, void *quantised, void *floats, size_t 
     r = ensure_wide(c, true); if (r) return r;
     *n_nodes = c->bvh.n_wide;
     if ((quantised || floats) && capacity_nodes < c->bvh.n_wide) return fail(ART_E_INVALID, "art_get_wide_nodes: buffers too small");
-    const AsPtrs as = as_ptrs(c, c->as_cur);   // the version the next frame would read
+    const AsPtrs as = as_ptrs(c, as_current(c));   // the version the next frame would read
     if (quantised) HIPC(hipMemcpy(quantised, as.wide, (size_t)c->bvh.n_wide * sizeof(DevNode4), hipMemcpyDeviceToHost));
     if (floats) HIPC(hipMemcpy(floats, as.widef, (size_t)c->bvh.n_wide * sizeof(DevNodeW), hipMemcpyDeviceToHost));
     return ART_OK;
