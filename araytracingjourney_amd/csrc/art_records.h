@@ -60,6 +60,7 @@ __device__ inline void wide_quantise(const float *const lo[4], const float *cons
         int e = ext > 0 ? ceil_log2(ext / 255.0) : -100;
         if (e < -100) e = -100;
         for (;;) { scale[k] = ldexpf(1.0f, e); if (fmaf(255.0f, scale[k], org[k]) >= top[k]) break; e++; }
+        while (e > -100 && fmaf(255.0f, ldexpf(1.0f, e - 1), org[k]) >= top[k]) { e--; scale[k] = ldexpf(1.0f, e); }   // (the fma may round half the scale's last plane UP onto the top: the smallest scale is the one the walks' own evaluation allows)
         ebits[k] = (uint32_t)(e + 127);
     }
     uint32_t mask = 0;
@@ -73,6 +74,10 @@ __device__ inline void wide_quantise(const float *const lo[4], const float *cons
             ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql); qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
             while (ql > 0 && fmaf((float)ql, scale[k], org[k]) > lo[i][k]) ql--;
             while (qh < 255 && fmaf((float)qh, scale[k], org[k]) < hi[i][k]) qh++;
+            // floor / ceil are of the exact quotient, but the fma may round the next plane inwards exactly ONTO the box: a tighter value that still contains it, so take it
+            // (only a value that differs: a flat box on a 2^-100 axis keeps lo plane <= hi plane -- an inverted pair means "absent")
+            for (float v; ql < 255 && (v = fmaf((float)(ql + 1), scale[k], org[k])) <= lo[i][k] && v > fmaf((float)ql, scale[k], org[k]);) ql++;
+            for (float v; qh > 0 && (v = fmaf((float)(qh - 1), scale[k], org[k])) >= hi[i][k] && v < fmaf((float)qh, scale[k], org[k]);) qh--;
             d.q[k] |= (uint32_t)ql << (8 * i);
             d.q[3 + k] |= (uint32_t)qh << (8 * i);
         }

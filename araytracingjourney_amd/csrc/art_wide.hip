@@ -80,6 +80,7 @@ static hipError_t wide_build_host(Lbvh &l, uint32_t T, hipStream_t s) {
             int e = ext > 0 ? ceil_log2(ext / 255.0) : -100;
             if (e < -100) e = -100;
             for (;;) { scale[k] = std::ldexp(1.0f, e); if (std::fmaf(255.0f, scale[k], org[k]) >= top[k]) break; e++; }
+            while (e > -100 && std::fmaf(255.0f, std::ldexp(1.0f, e - 1), org[k]) >= top[k]) { e--; scale[k] = std::ldexp(1.0f, e); }   // (... or down, where the fma rounds the last plane of half the scale up onto the top)
             ebits[k] = (uint32_t)(e + 127);
         }
         uint32_t mask = 0;
@@ -93,8 +94,11 @@ static hipError_t wide_build_host(Lbvh &l, uint32_t T, hipStream_t s) {
                 int ql = (int)std::floor(((double)b.lo[k] - (double)org[k]) / (double)scale[k]);
                 int qh = (int)std::ceil(((double)b.hi[k] - (double)org[k]) / (double)scale[k]);
                 ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql); qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-                while (ql > 0 && std::fmaf((float)ql, scale[k], org[k]) > b.lo[k]) ql--;   // never taken by construction; kept as a guard
+                while (ql > 0 && std::fmaf((float)ql, scale[k], org[k]) > b.lo[k]) ql--;   // taken only where the float64 difference above itself rounded (places more than 53 bits apart: tests/test_wide_tree.py, "exponent steps")
                 while (qh < 255 && std::fmaf((float)qh, scale[k], org[k]) < b.hi[k]) qh++;
+                // ... and inwards where the fma rounds the next plane exactly onto the box (a value that differs only: a flat box keeps lo plane <= hi plane)
+                while (ql < 255 && std::fmaf((float)(ql + 1), scale[k], org[k]) <= b.lo[k] && std::fmaf((float)(ql + 1), scale[k], org[k]) > std::fmaf((float)ql, scale[k], org[k])) ql++;
+                while (qh > 0 && std::fmaf((float)(qh - 1), scale[k], org[k]) >= b.hi[k] && std::fmaf((float)(qh - 1), scale[k], org[k]) < std::fmaf((float)qh, scale[k], org[k])) qh--;
                 d.q[k] |= (uint32_t)ql << (8 * i);
                 d.q[3 + k] |= (uint32_t)qh << (8 * i);
             }

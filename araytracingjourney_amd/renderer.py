@@ -1168,8 +1168,14 @@ class Renderer:
         check(self._L.art_query_any_masked(self._ctx, _ptr(rays), n, m, _ptr(hit)))   # (0xFF is art_query_any)
         return hit
 
+    def _leaf_count(self):
+        """the leaves of the built structure: the leaf references of the 4-wide records.  (Not ArtStats.num_triangles: that leaves out the triangles of primitives disabled
+        since the build, whose leaves stay -- nowhere -- in every array art_get_lbvh and art_get_traversal_tree fill.)"""
+        c = self.get_wide_nodes()[1][:, 24:28].view(np.int32)
+        return int(((c < 0) & (c != -2 ** 31)).sum())
+
     def get_lbvh(self):
-        T = self.stats()["num_triangles"]
+        T = self._leaf_count()
         NI = max(T - 1, 0)
         out = dict(leaf_gid=np.zeros(T, np.uint32), keys=np.zeros(T, np.uint64), child=np.zeros((NI, 2), np.int32), node_lo=np.zeros((NI, 3), np.float32),
                    node_hi=np.zeros((NI, 3), np.float32), leaf_lo=np.zeros((T, 3), np.float32), leaf_hi=np.zeros((T, 3), np.float32))
@@ -1178,7 +1184,7 @@ class Renderer:
 
     def get_traversal_tree(self):
         """the tree the walks use over get_lbvh()'s leaves (binned SAH by default)"""
-        NI = max(self.stats()["num_triangles"] - 1, 0)
+        NI = max(self._leaf_count() - 1, 0)
         out = dict(child=np.zeros((NI, 2), np.int32), node_lo=np.zeros((NI, 3), np.float32), node_hi=np.zeros((NI, 3), np.float32))
         check(self._L.art_get_traversal_tree(self._ctx, _ptr(out["child"]), _ptr(out["node_lo"]), _ptr(out["node_hi"])))
         return out
