@@ -24,6 +24,7 @@ struct HostPrim {
     float o2w[12], w2o[12];
     bool enabled = true; // instanced in the acceleration structure (the reference's Device state, vk_model.rs:334-345); else kept on the host only
     bool verts_stale = false; // art_scene_set_vertices replaced `verts` since they were uploaded: a build over the same set uploads them again
+    bool verts_behind = false; // art_scene_set_vertices_device wrote the primitive's slot of ArtContext::d_verts since: `verts` is behind it until someone needs it (verts_read_back)
     float cutoff = 0.0f;      // alpha cutoff (art_scene_set_alpha_cutoff; 0: opaque)
     uint32_t vis = 0xFFu;     // visibility mask (art_scene_set_primitive_mask; 0xFF: every ray sees it)
 };
@@ -119,6 +120,9 @@ struct AsVersion {
 
 // The ring of versions behind moving, deforming, masked and alpha-cut primitives (art_scene_set_model_matrix and its kin): its memory, what changed since the build, the
 // epochs and the cost rule, the refit streams.  Written only in art_versions.hip.  Members go in reverse order of declaration: the blocks before the versions that point into them.
+// art_scene_set_vertices_device's record of one built primitive: the event behind its latest ingest (the next refit's stream waits for it, so does the next ingest), and
+// which versions' latest refits gathered from its slot of ArtContext::d_verts -- the next ingest's stream waits for those that may still run before it overwrites the slot
+struct PrimIngest { Event done; bool open = false; uint32_t readers = 0; };   // open: recorded and not yet known to have fired; readers: a bit per version (kMaxAsVersions <= 32)
 struct Versions {
     DevBuf<char> as_block; Pinned<char> as_pinned;    // ONE device allocation and ONE pinned one behind all the versions (six + three per version before).  versions_ms is something else: the refit streams' creation (a
                                                       // high-priority hardware queue each: 4-10 ms apiece) and the refit's work lists (host, 9 ms for config 2) -- ArtTuning.log bit 0 prints the parts
@@ -128,6 +132,9 @@ struct Versions {
     Stream refit_stream[4]; uint32_t n_refit_streams = 0;
     std::vector<uint64_t> prim_moved;          // per primitive: the refit (as_epoch numbering) that first shows its latest move; 0: where the build put it
     std::vector<uint64_t> prim_deformed;       // per primitive: the refit that first shows its latest vertices (art_scene_set_vertices); 0: the build's
+    std::vector<PrimIngest> ingest;            // per primitive (art_scene_set_vertices_device); the events are made by a primitive's first ingest and go with the next build
+    std::vector<uint32_t> ingest_open;         // the primitives whose ingest event may not have fired yet (sync_all and art_destroy wait for them: the caller's streams are not the context's)
+    uint64_t ingests = 0, ingest_host_syncs = 0, ingest_readbacks = 0;   // art_vertex_update_counts
     std::vector<int64_t> deform_off;           // per primitive: first vertex of its slot in every version's staging (-1: never deformed since the build)
     size_t deform_verts = 0;                   // vertices of a version's staging (the sum of the deformed primitives' counts)
     DevBuf<char> shade_block;                  // ONE device allocation behind the shading records of versions 1 .. K-1 (made by the first deformation of a built primitive)
@@ -265,7 +272,13 @@ bool binary_is_current(const ArtContext *c);               // ensure_binary's: t
 void binary_mark(ArtContext *c, bool current);             // ... they do now / they have to be made again whatever the version
 // what the setters report about a primitive of the built structure.  shows: it is enabled, so the next launch has to refit first
 void as_prim_moved(ArtContext *c, uint32_t id, bool shows, int64_t masked_delta = 0);   // a matrix; masked_delta: triangles that left (+) or came back (-) with a residency change
-int32_t as_prim_deformed(ArtContext *c, uint32_t id, bool shows);   // new vertices: the ring if there is none, the versions' shading records and staging (one synchronisation the first time); fails with nothing changed
+int32_t as_prim_deformed(ArtContext *c, uint32_t id, bool shows, bool staged = true);   // new vertices: the ring if there is none, the versions' shading records and -- staged: the host form -- staging (one synchronisation the first time); fails with nothing changed
+// art_scene_set_vertices_device on a primitive of the built structure, after as_prim_deformed(.., false): k_ingest_verts into the primitive's slot on stream s, ordered on the
+// device behind the refits that still gather from the slot and behind the primitive's previous ingest.  bring_up: the host copy the slot is behind (a host-form call since
+// the build, in front of a POSITIONS update) is copied into it first, synchronously
+int32_t as_ingest(ArtContext *c, uint32_t id, const void *src, uint32_t stride_bytes, const ArtVertex *bring_up, hipStream_t s);
+int32_t as_ingest_wait(ArtContext *c, uint32_t id);        // the host waits for the primitive's latest ingest (a read-back of its slot follows)
+void as_ingest_counts(ArtContext *c, uint64_t host_syncs, uint64_t readbacks);   // what art_scene.hip adds to art_vertex_update_counts
 void as_table_changed(ArtContext *c, bool new_alpha_bits); // a cutoff or a visibility mask: a refit over no batch; new_alpha_bits: the primitive's leaves need their bits first
 // ---- art_plan.hip (every write of a WavePlan field is there) ----
 int32_t plan_reset(ArtContext *c, const std::vector<uint32_t> &order);   // a new frame layout: the launch order of its 256-pixel blocks, the first table

@@ -172,6 +172,9 @@ struct RefitArgs {
 constexpr uint8_t kTouchRegather = 2u;         // RefitArgs::touched: the primitive's vertices were replaced (bit 0: it moved)
 constexpr uint32_t kFoldRequantNodes = 400000;   // trees of this many 4-wide nodes and more: the refit's workgroups make the quantised records and the cost themselves (art_refit.hip launch_refit)
 void launch_refit(const RefitArgs &r, hipStream_t s);
+// art_scene_set_vertices_device's one kernel (k_ingest_verts): n_verts vertices from the caller's device buffer into the primitive's slot of the build's vertex array.
+// stride_bytes 0: whole 48-byte vertices, src 16-byte aligned; else three floats at src + i * stride_bytes (a multiple of 4) into words 0-2 of vertex i
+void launch_ingest_verts(const void *src, uint32_t stride_bytes, float *slot, uint32_t n_verts, hipStream_t s);
 void launch_wide_parents(uint32_t n_wide, const DevNodeW *widef, uint32_t *leaf_parent, uint32_t *node_parent, hipStream_t s);
 hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s);   // the parents (launch_wide_parents) and the work lists: all of them into l, or on a failure none (synchronises: a one-off of the scene's first version ring)
 void launch_wide_cost(uint32_t n_wide, const DevNodeW *widef, DevNode4 *wide /*null: cost only*/, double *acc, double *result, hipStream_t s);

@@ -302,6 +302,36 @@ hipError_t refit_lists_build(Lbvh &l, uint32_t T, hipStream_t s) {
 void launch_wide_cost(uint32_t n_wide, const DevNodeW *widef, DevNode4 *wide, double *acc, double *result, hipStream_t s) {
     k_wide_requant<<<(n_wide + 255) / 256, 256, 0, s>>>(n_wide, widef, wide, nullptr, acc, result);
 }
+// art_scene_set_vertices_device: a primitive's new vertices from the caller's device buffer into its own slot of the build's vertex array (48-byte records, the slot
+// 16-byte aligned), on the caller's stream -- the one read of that buffer.  A streaming copy: a grid-stride loop over at most kIngestBlocks workgroups (four of 256
+// threads a CU of 256), plain stores (the refit's gather reads the slot next, from whichever XCD).
+//   FULL      three 16-byte loads and stores a vertex, lane after lane: fully coalesced
+//   POSITIONS lane i reads three dwords at src + i * stride and writes words 0-2 of vertex i: one 12-byte load and one 12-byte store a lane (a 16-byte load for
+//             strides and pointers that allow it compiles to the same 12-byte one: the fourth word is dead).  Words 3-11 (uv, normal, tangent) are not touched.
+constexpr uint32_t kIngestBlocks = 1024;
+enum IngestForm { kIngestFull = 0, kIngestPositions = 1 };
+template <int FORM> __global__ __launch_bounds__(256) void k_ingest_verts(const float *__restrict__ src, uint32_t stride_words, float *__restrict__ dst, uint32_t n_verts) {
+    if (FORM == kIngestFull) {
+        const float4 *from = reinterpret_cast<const float4 *>(src); float4 *to = reinterpret_cast<float4 *>(dst);
+        const uint64_t n_quads = 3ull * n_verts;
+        for (uint64_t i = blockIdx.x * 256u + threadIdx.x; i < n_quads; i += gridDim.x * 256u) to[i] = from[i];
+        return;
+    }
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_verts; i += gridDim.x * 256u) {
+        const float *from = src + (size_t)i * stride_words;
+        const float x = from[0], y = from[1], z = from[2];
+        float *to = static_cast<float *>(__builtin_assume_aligned(dst + (size_t)i * 12, 16));
+        to[0] = x; to[1] = y; to[2] = z;
+    }
+}
+void launch_ingest_verts(const void *src, uint32_t stride_bytes /*0: whole 48-byte vertices*/, float *slot, uint32_t n_verts, hipStream_t s) {
+    if (n_verts == 0) return;
+    const uint64_t items = stride_bytes ? n_verts : 3ull * n_verts;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((items + 255) / 256, kIngestBlocks), sw = stride_bytes / 4;
+    const float *from = static_cast<const float *>(src);
+    if (!stride_bytes) k_ingest_verts<kIngestFull><<<grid, 256, 0, s>>>(from, 12u, slot, n_verts);
+    else k_ingest_verts<kIngestPositions><<<grid, 256, 0, s>>>(from, sw, slot, n_verts);
+}
 __global__ void k_refit_noop() {}
 void refit_prewarm(hipStream_t s) { k_refit_noop<<<1, 1, 0, s>>>(); }   // build_prewarm's empty launch from this unit
 

@@ -61,6 +61,18 @@ void art::gid_to_ids(const ArtContext *c, uint32_t gid, int32_t *ids) {
     ids[0] = (int32_t)lo; ids[1] = (int32_t)(gid - f[lo]);
 }
 
+// A primitive whose slot of the device's vertex array is ahead of its host copy (art_scene_set_vertices_device wrote it): the slot read back, once the ingest behind it
+// has finished.  Only where the library needs the host copy: a build that lays the arrays out again, art_scene_get_vertices, an update of a primitive that has left the tree
+static int32_t verts_read_back(ArtContext *c, uint32_t id) {
+    HostPrim &p = c->prims[id];
+    if (!p.verts_behind) return ART_OK;
+    int32_t r = as_ingest_wait(c, id); if (r) return r;
+    HIPC(hipMemcpy(p.verts.data(), c->h_dev_prims[id].vertices, p.verts.size() * sizeof(ArtVertex), hipMemcpyDeviceToHost));
+    p.verts_behind = false;
+    as_ingest_counts(c, 0, 1);
+    return ART_OK;
+}
+
 extern "C" {
 
 int32_t art_scene_add_primitive(ArtContext *c, const ArtVertex *verts, uint32_t n_verts, const void *indices, uint32_t n_indices,
@@ -92,6 +104,7 @@ int32_t art_scene_add_primitive(ArtContext *c, const ArtVertex *verts, uint32_t 
 int32_t art_scene_clear(ArtContext *c) {
     if (!c) return fail(ART_E_INVALID, "art_scene_clear: null context");
     int32_t r = cast_drain(c); if (r) return r;   // outstanding casts read the scene that goes away
+    if (!c->ver.ingest_open.empty()) { r = use_device(c); if (r) return r; r = as_sync_streams(c); if (r) return r; }   // (ingests on callers' streams write the slots of primitives that go away)
     c->prims.clear(); c->uploaded.clear(); c->built = false;
     return ART_OK;
 }
@@ -190,7 +203,69 @@ int32_t art_scene_set_vertices(ArtContext *c, uint32_t id, const ArtVertex *vert
     }
     std::memcpy(p.verts.data(), verts, (size_t)n_verts * sizeof(ArtVertex));
     p.verts_stale = true;                                            // the device's build copy is behind (a rebuild over the same set uploads them again)
+    p.verts_behind = false;                                          // (whatever art_scene_set_vertices_device left in the slot is replaced with it)
     return ART_OK;                                                   // (not in the tree: takes effect with the build)
+}
+
+// art_scene_set_vertices with the data in device memory ("Vertices from device buffers").  On a primitive of the built structure: one kernel on the caller's
+// stream into the primitive's slot of the build's vertex array, ordered on the device (as_ingest); the host copy falls behind (verts_behind) and nothing is staged.
+int32_t art_scene_set_vertices_device(ArtContext *c, const ArtVertexUpdate *u) {
+    if (!c || !u || !u->verts_dev) return fail(ART_E_INVALID, "art_scene_set_vertices_device: null argument");
+    if (u->flags != 0) return fail(ART_E_INVALID, "art_scene_set_vertices_device: flags: must be 0");
+    if (u->reserved != 0) return fail(ART_E_INVALID, "art_scene_set_vertices_device: reserved: must be 0");
+    if (u->layout != ART_VERTS_FULL && u->layout != ART_VERTS_POSITIONS) return fail(ART_E_INVALID, "art_scene_set_vertices_device: layout: neither ART_VERTS_FULL nor ART_VERTS_POSITIONS");
+    const bool full = u->layout == ART_VERTS_FULL;
+    if (full ? (u->stride_bytes != 0 && u->stride_bytes != 48) : (u->stride_bytes != 0 && (u->stride_bytes < 12 || u->stride_bytes % 4 != 0)))
+        return fail(ART_E_INVALID, full ? "art_scene_set_vertices_device: stride_bytes: 0 or 48 for ART_VERTS_FULL" : "art_scene_set_vertices_device: stride_bytes: 0, or at least 12 and a multiple of 4, for ART_VERTS_POSITIONS");
+    if ((uintptr_t)u->verts_dev % (full ? 16 : 4) != 0) return fail(ART_E_INVALID, full ? "art_scene_set_vertices_device: verts_dev: not 16-byte aligned" : "art_scene_set_vertices_device: verts_dev: not 4-byte aligned");
+    const uint32_t id = u->primitive_id;
+    if (id >= c->prims.size()) return fail(ART_E_INVALID, "art_scene_set_vertices_device: no such primitive");
+    HostPrim &p = c->prims[id];
+    if ((size_t)u->n_verts != p.verts.size()) return fail(ART_E_INVALID, "art_scene_set_vertices_device: the vertex count differs from the primitive's");
+    if (hipError_t e = hipSetDevice(c->device); e != hipSuccess) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { (void)hipGetLastError(); return fail(ART_E_NO_DEVICE, "art_scene_set_vertices_device: no HIP device to read verts_dev with"); }
+        return hipfail(e, "art_scene_set_vertices_device: hipSetDevice");
+    }
+    const uint32_t stride = full ? 0u : (u->stride_bytes ? u->stride_bytes : 12u);
+    hipStream_t s = u->hip_stream ? (hipStream_t)u->hip_stream : c->main_stream();
+    if (s == hipStreamLegacy) s = nullptr;   // the null stream by its own handle: an event is recorded there that the refit streams wait for, and the runtime takes the stream an event was recorded on for a pointer
+    const bool in_tree = c->built && id < c->h_dev_prims.size() && c->h_dev_prims[id].n_tri > 0;   // its triangles are in the built structure (masked or not): it has a slot
+    if (in_tree) {
+        int32_t r = as_prim_deformed(c, id, p.enabled, false); if (r) return r;   // the versions' shading records (a failure changes nothing); the next refit is the first to show the vertices
+        // POSITIONS keeps the CURRENT attributes: a slot that is behind the host copy (a host-form call since the build) gets that copy first
+        r = as_ingest(c, id, u->verts_dev, stride, !full && p.verts_stale ? p.verts.data() : nullptr, s); if (r) return r;
+        p.verts_stale = false; p.verts_behind = true;
+        return ART_OK;
+    }
+    // not in the tree (added since the build, disabled at the build, no built scene): no slot.  The host copy takes the vertices, synchronously; they show with the next build
+    int32_t r = verts_read_back(c, id); if (r) return r;   // (a slot from before the scene fell out of date may still be ahead: POSITIONS merges into the current attributes)
+    if (full) HIPC(hipMemcpyAsync(p.verts.data(), u->verts_dev, p.verts.size() * sizeof(ArtVertex), hipMemcpyDeviceToHost, s));
+    std::vector<float> pos(full ? 0 : p.verts.size() * 3);
+    if (!full) HIPC(hipMemcpy2DAsync(pos.data(), 12, u->verts_dev, stride, 12, p.verts.size(), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    as_ingest_counts(c, 1, 0);
+    for (size_t i = 0; i < pos.size() / 3; i++) std::memcpy(&p.verts[i], &pos[3 * i], 12);
+    p.verts_stale = true;
+    return ART_OK;
+}
+
+int32_t art_scene_get_vertices(ArtContext *c, uint32_t id, ArtVertex *dst, uint32_t n_verts) {
+    if (!c || !dst) return fail(ART_E_INVALID, "art_scene_get_vertices: null argument");
+    if (id >= c->prims.size()) return fail(ART_E_INVALID, "art_scene_get_vertices: no such primitive");
+    HostPrim &p = c->prims[id];
+    if ((size_t)n_verts != p.verts.size()) return fail(ART_E_INVALID, "art_scene_get_vertices: the vertex count differs from the primitive's");
+    if (p.verts_behind) { int32_t r = use_device(c); if (r) return r; r = verts_read_back(c, id); if (r) return r; }
+    std::memcpy(dst, p.verts.data(), (size_t)n_verts * sizeof(ArtVertex));
+    return ART_OK;
+}
+
+int32_t art_vertex_update_counts(ArtContext *c, uint64_t *ingests, uint64_t *host_syncs, uint64_t *readbacks) {
+    if (!c) return fail(ART_E_INVALID, "art_vertex_update_counts: null context");
+    if (ingests) *ingests = c->ver.ingests;
+    if (host_syncs) *host_syncs = c->ver.ingest_host_syncs;
+    if (readbacks) *readbacks = c->ver.ingest_readbacks;
+    return ART_OK;
 }
 
 int32_t art_scene_build(ArtContext *c) {
@@ -213,7 +288,10 @@ int32_t art_scene_build(ArtContext *c) {
     std::vector<uint8_t> now_set(c->prims.size());
     for (size_t k = 0; k < c->prims.size(); k++) now_set[k] = c->prims[k].enabled ? 1 : 0;
     const bool resident = any && now_set == c->uploaded;   // the same primitives as the last upload, nothing added since: their data is where this build would put it
-    if (!resident) c->uploaded.clear();   // (an upload that fails half way leaves nothing to rely on)
+    if (!resident) {   // the arrays are laid out again from the host copies: those that art_scene_set_vertices_device left behind their slots are read back first
+        for (size_t k = 0; k < c->prims.size() && k < c->h_dev_prims.size(); k++) { r = verts_read_back(c, (uint32_t)k); if (r) return r; }
+        c->uploaded.clear();   // (an upload that fails half way leaves nothing to rely on)
+    }
     HIPC(c->d_verts.ensure(nv * 12)); HIPC(c->d_indices.ensure(ib)); HIPC(c->d_tex.ensure(nt));
     std::vector<DevPrim> dp(c->prims.size() + (any ? 0 : 1));
     std::vector<uint32_t> first(dp.size());

@@ -35,7 +35,10 @@ void art::binary_mark(ArtContext *c, bool current) { c->ver.binary_epoch = curre
 void art::as_frame_reads(ArtContext *c, uint32_t v, uint32_t k) { if (!c->ver.as.empty()) { c->ver.as[v].used[k] = c->frame_no + 1; c->ver.as[v].aux[k] = false; } }
 void art::as_aux_behind(ArtContext *c, uint32_t v, uint32_t k) { if (!c->ver.as.empty()) c->ver.as[v].aux[k] = true; }
 int32_t art::as_sync_streams(ArtContext *c) {
-    for (uint32_t i = 0; i < c->ver.n_refit_streams; i++) HIPC(hipStreamSynchronize(c->ver.refit_stream[i]));
+    Versions &R = c->ver;
+    for (uint32_t id : R.ingest_open) if (id < R.ingest.size() && R.ingest[id].open) { HIPC(hipEventSynchronize(R.ingest[id].done)); R.ingest[id].open = false; }   // (ingests on callers' streams: a refit below may stand behind one)
+    R.ingest_open.clear();
+    for (uint32_t i = 0; i < R.n_refit_streams; i++) HIPC(hipStreamSynchronize(R.refit_stream[i]));
     return ART_OK;
 }
 void art::as_fill_stats(const ArtContext *c, ArtStats *st) {
@@ -150,12 +153,13 @@ static int32_t ring_ensure(ArtContext *c) {
 // ---- art_scene_build's two ends, and what the setters report ----------------------------------------------------------------------------
 void art::as_scene_reset(ArtContext *c) {   // (the caller synchronised) the versions were copies of the tree that goes away
     Versions &R = c->ver;
-    as_release(c); R.xform_dirty = false; R.as_epoch = 0; R.binary_epoch = 0; R.refit_cost_ratio = 1.0f;
+    as_release(c); R.ingest.clear(); R.ingest_open.clear();   // (the ingests' events: sync_all waited for them)
+    R.xform_dirty = false; R.as_epoch = 0; R.binary_epoch = 0; R.refit_cost_ratio = 1.0f;
 }
 int32_t art::as_scene_built(ArtContext *c) {
     Versions &R = c->ver;
     const size_t np = c->h_dev_prims.size();
-    R.masked_tris = 0; R.prim_moved.assign(np, 0); R.prim_deformed.assign(np, 0); R.deform_off.assign(np, -1);
+    R.masked_tris = 0; R.prim_moved.assign(np, 0); R.prim_deformed.assign(np, 0); R.deform_off.assign(np, -1); R.ingest.clear(); R.ingest.resize(np);
     R.alpha_bits_stale = false;   // (the build made the bits of every cutoff and mask there is)
     R.first_move_ms = 0.f; R.versions_ms = 0.f;
     if (c->cfg.flags & ART_FLAG_DYNAMIC_SCENE) return as_create(c);   // the host said its models move: the ring of versions now, not in front of the first moved frame
@@ -182,12 +186,13 @@ template <class T, class F> static size_t carve_slots(uint32_t first, uint32_t K
 // The first deformation of a built primitive (art_scene_set_vertices): every version gets shading records of its own (a frame in flight must keep the normals it was
 // launched with), and the primitive a slot in every version's staging.  One synchronisation, here and never in front of a frame: an allocation that fails
 // comes back from the call that asked for it, with nothing changed.
-static int32_t deform_prepare(ArtContext *c, uint32_t id) {
+static int32_t deform_prepare(ArtContext *c, uint32_t id, bool staged) {
     Versions &R = c->ver;
     const uint32_t K = (uint32_t)R.as.size();
-    const bool need_shade = K > 1 && !R.shade_block, need_stage = R.deform_off[id] < 0;
+    const bool need_shade = K > 1 && !R.shade_block, need_stage = staged && R.deform_off[id] < 0;   // (the device form reads the primitive's slot of the build's vertex array: no staging)
     if (!need_shade && !need_stage) return ART_OK;   // (the steady state)
     int32_t r = sync_all(c); if (r) return r;
+    if (!staged) R.ingest_host_syncs++;
     auto only_count = [](uint32_t, void *, char *) {};
     if (need_shade) {   // versions 1 .. K-1: copies of the build's records (nothing has written any version's yet); version 0 keeps aliasing them
         DevBuf<char> blk;   // (the context takes it once the copies are in it)
@@ -212,13 +217,48 @@ static int32_t deform_prepare(ArtContext *c, uint32_t id) {
     }
     return ART_OK;
 }
-int32_t art::as_prim_deformed(ArtContext *c, uint32_t id, bool shows) {
+int32_t art::as_prim_deformed(ArtContext *c, uint32_t id, bool shows, bool staged) {
+    const bool ring_made = !c->ver.as.empty(), shade_made = (bool)c->ver.shade_block;
     int32_t r = ring_ensure(c); if (r) return r;   // (art_scene_build made it already when the host announced ART_FLAG_DYNAMIC_SCENE)
-    r = deform_prepare(c, id); if (r) return r;
+    r = deform_prepare(c, id, staged); if (r) return r;
+    if (!staged && !ring_made && shade_made == (bool)c->ver.shade_block) c->ver.ingest_host_syncs++;   // (the ring's own wait, where deform_prepare's did not follow and count: one call, one count)
     c->ver.prim_deformed[id] = c->ver.as_epoch + 1;   // the next refit is the first to show the new vertices
     if (shows) c->ver.xform_dirty = true;             // instanced: the next art_trace (or query) refits first; a masked one is regathered when it comes back
     return ART_OK;
 }
+
+// ---- art_scene_set_vertices_device: the ingest and its ordering ("Vertices from device buffers") ---------------------------------
+int32_t art::as_ingest(ArtContext *c, uint32_t id, const void *src, uint32_t stride_bytes, const ArtVertex *bring_up, hipStream_t s) {
+    Versions &R = c->ver;
+    PrimIngest &I = R.ingest[id];
+    HIPC(I.done.create(hipEventDisableTiming));   // (once a primitive and build)
+    // a refit that still gathers from the slot finishes first: up to four refit streams, so there can be more than one
+    for (uint32_t v = 0; I.readers && v < (uint32_t)R.as.size(); v++) {
+        if (!(I.readers & (1u << v))) continue;
+        AsVersion &V = R.as[v];
+        if (!V.ready_known) { if (hipEventQuery(V.ready) == hipSuccess) V.ready_known = true; else { (void)hipGetLastError(); HIPC(hipStreamWaitEvent(s, V.ready, 0)); } }
+    }
+    I.readers = 0;
+    if (I.open) HIPC(hipStreamWaitEvent(s, I.done, 0));   // two ingests of one primitive run in call order, whichever streams they came on
+    float *slot = const_cast<float *>(c->h_dev_prims[id].vertices);
+    const uint32_t n = (uint32_t)c->prims[id].verts.size();
+    if (bring_up) {   // the transition from the host form: the slot gets the host copy's attributes first; synchronous (the copy reads pageable memory), never the steady state
+        HIPC(hipMemcpyAsync(slot, bring_up, (size_t)n * sizeof(ArtVertex), hipMemcpyHostToDevice, s));
+        HIPC(hipStreamSynchronize(s)); R.ingest_host_syncs++;
+    }
+    launch_ingest_verts(src, stride_bytes, slot, n, s);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(I.done, s));
+    if (!I.open) { I.open = true; R.ingest_open.push_back(id); }
+    R.ingests++;
+    return ART_OK;
+}
+int32_t art::as_ingest_wait(ArtContext *c, uint32_t id) {
+    Versions &R = c->ver;
+    if (id < R.ingest.size() && R.ingest[id].open) { HIPC(hipEventSynchronize(R.ingest[id].done)); R.ingest[id].open = false; R.ingest_host_syncs++; }   // (its entry in ingest_open goes with the next sync_all)
+    return ART_OK;
+}
+void art::as_ingest_counts(ArtContext *c, uint64_t host_syncs, uint64_t readbacks) { c->ver.ingest_host_syncs += host_syncs; c->ver.ingest_readbacks += readbacks; }
 
 // the surface-area cost of the latest refit travels to the host behind it; once it has arrived it is what ArtStats.refit_cost_ratio and the rebuild rule go by
 void art::harvest_cost(ArtContext *c) {
@@ -279,9 +319,11 @@ static void stage_table(ArtContext *c, AsVersion &V) {
     for (size_t p = 0; p < np; p++) V.h_touched[p] = (p < R.prim_moved.size() && R.prim_moved[p] > V.epoch) ? 1 : 0;
 }
 // 4. what was deformed since this version was written: its current vertices into the version's staging (pinned, then ONE copy a run of slots on the refit's stream, in
-// front of the refit that reads them from device memory), its table entry pointed there, and its shading records gathered again by the refit's leaf stage
-static int32_t stage_deformed(ArtContext *c, AsVersion &V, hipStream_t s) {
-    const Versions &R = c->ver;
+// front of the refit that reads them from device memory), its table entry pointed there, and its shading records gathered again by the refit's leaf stage.
+// A primitive whose slot of the build's vertex array holds its current vertices (art_scene_set_vertices_device wrote them there: the host copy is not ahead of it) is
+// gathered from the slot, where its table entry points anyway: the refit's stream waits for the ingest's event, and the next ingest for this refit's
+static int32_t stage_deformed(ArtContext *c, AsVersion &V, uint32_t v, hipStream_t s) {
+    Versions &R = c->ver;
     const size_t np = c->h_dev_prims.size();
     size_t run_lo = 0, run_hi = 0;   // the run of staging slots the next copy covers (vertices)
     auto flush = [&]() -> int32_t {
@@ -290,6 +332,13 @@ static int32_t stage_deformed(ArtContext *c, AsVersion &V, hipStream_t s) {
     };
     for (size_t p = 0; p < np && p < R.prim_deformed.size(); p++) {
         if (R.prim_deformed[p] <= V.epoch) continue;
+        if (!c->prims[p].verts_stale) {
+            PrimIngest &I = R.ingest[p];
+            if (I.open) HIPC(hipStreamWaitEvent(s, I.done, 0));   // nothing on the host
+            I.readers |= 1u << v;
+            V.h_touched[p] |= kTouchRegather;
+            continue;
+        }
         const std::vector<ArtVertex> &vv = c->prims[p].verts;
         const size_t off = (size_t)R.deform_off[p];
         std::memcpy(V.h_stage + off, vv.data(), vv.size() * sizeof(ArtVertex));
@@ -344,7 +393,7 @@ int32_t art::scene_refresh(ArtContext *c, uint32_t k, hipStream_t s) {
     r = wait_for_readers(c, V, next, k, beside); if (r) return r;
     if (c->graph_mode) drop_graphs(c); // a captured frame holds the old version's pointers
     stage_table(c, V);
-    r = stage_deformed(c, V, s); if (r) return r;
+    r = stage_deformed(c, V, next, s); if (r) return r;
     RefitArgs ra = refit_args(c, V);
     choose_batches(c, V, ra);
     if (R.alpha_bits_stale) {   // a primitive got a cutoff: its leaves' bits, from this version's table, in front of the refit whose event the frames wait for

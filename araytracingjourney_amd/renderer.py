@@ -253,6 +253,46 @@ class Model:
         m = self.model_matrix if self.model_matrix is not None else np.eye(3, 4, dtype=np.float32)
         self.model_bounding_sphere = self._object_sphere.transform(m)
 
+    def set_vertices_device(self, primitive_index, tensor, layout="full", stream=None):
+        """set_vertices with the vertices in a torch tensor on the device (art_scene_set_vertices_device): no trip through the host.  layout "full": float32 [n, 12],
+        contiguous and 16-byte aligned, all attributes replaced.  layout "positions": float32 [n, 3] with unit inner stride and any row stride >= 3 -- a column view of
+        a wider state tensor works -- positions replaced, uv / normal / tangent kept as they currently are (shading normals go stale: recomputing them is the caller's
+        business).  The library reads the tensor on `stream` (a torch stream or a raw hipStream_t; default: torch's current stream), behind whatever produced it there,
+        and the call returns without waiting: work enqueued on that stream afterwards may overwrite the tensor.  The model's bounding sphere is left as it is -- the
+        positions never reach the host -- so a caller that relies on the residency distances keeps it current itself."""
+        import torch
+        if layout not in ("full", "positions"):
+            raise ValueError("layout must be 'full' or 'positions'")
+        if self._renderer is None:
+            raise ValueError("the model belongs to no renderer")
+        dev = self._renderer._query_device()
+        if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.device.index == dev):
+            raise ValueError(f"tensor must be a torch tensor on cuda:{dev}")
+        if layout == "full":
+            if not (tensor.dtype == torch.float32 and tensor.dim() == 2 and tensor.shape[1] == 12 and tensor.is_contiguous() and tensor.data_ptr() % 16 == 0):
+                raise ValueError("tensor must be float32 of shape (n, 12), contiguous and 16-byte aligned")
+            code, stride = _lib.ART_VERTS_FULL, 0
+        else:
+            if not (tensor.dtype == torch.float32 and tensor.dim() == 2 and tensor.shape[1] == 3 and tensor.stride(1) == 1 and (tensor.stride(0) >= 3 or tensor.shape[0] <= 1)):
+                raise ValueError("tensor must be float32 of shape (n, 3) with unit inner stride and a row stride of at least 3")
+            code, stride = _lib.ART_VERTS_POSITIONS, 4 * (tensor.stride(0) if tensor.shape[0] > 1 else 3)
+        if not 0 <= primitive_index < len(self.primitive_ids):
+            raise IndexError("primitive_index out of range")
+        u = _lib.ArtVertexUpdate(verts_dev=tensor.data_ptr() or None, hip_stream=self._renderer._stream_handle(stream, tensor.device),
+                                 primitive_id=self.primitive_ids[primitive_index], n_verts=tensor.shape[0], layout=code, stride_bytes=stride, flags=0, reserved=0)
+        check(self._renderer._L.art_scene_set_vertices_device(self._renderer._ctx, C.byref(u)))
+
+    def vertices(self, primitive_index):
+        """the current 48-byte vertices of primitive `primitive_ids[primitive_index]`, whichever form set them last: float32 [n, 12] (art_scene_get_vertices; waits for
+        the primitive's latest set_vertices_device and reads the device copy back where that is ahead of the host's)"""
+        if not 0 <= primitive_index < len(self.primitive_ids):
+            raise IndexError("primitive_index out of range")
+        if self._renderer is None or self._positions is None:
+            raise ValueError("the model belongs to no renderer")
+        out = np.empty((self._positions[primitive_index].shape[0], 12), np.float32)
+        check(self._renderer._L.art_scene_get_vertices(self._renderer._ctx, self.primitive_ids[primitive_index], _ptr(out), out.shape[0]))
+        return out
+
     def set_alpha_cutoff(self, primitive_index, cutoff):
         """Alpha-masked primitive (glTF alphaMode MASK; Vulkan: non-opaque geometry whose any-hit shader ignores the intersection when alpha < cutoff; the
         reference marks all its geometry opaque, vk_model.rs:927): a hit on primitive `primitive_ids[primitive_index]` is discarded for every ray -- primary,
@@ -1144,6 +1184,13 @@ class Renderer:
     def cast_sync(self):
         """every cast enqueued so far has finished, on whichever stream (art_cast_sync)"""
         check(self._L.art_cast_sync(self._ctx))
+
+    def vertex_update_counts(self) -> dict:
+        """what Model.set_vertices_device has done in this context: kernels enqueued, host synchronisations it made itself, device copies read back into host
+        copies (art_vertex_update_counts)"""
+        a, b, w = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self._L.art_vertex_update_counts(self._ctx, C.byref(a), C.byref(b), C.byref(w)))
+        return dict(ingests=a.value, host_syncs=b.value, readbacks=w.value)
 
     def cast_counts(self) -> dict:
         """casts enqueued, their rays, and the host waits casts caused (art_cast_counts)"""

@@ -205,6 +205,40 @@ int32_t art_scene_set_model_matrix(ArtContext *ctx, uint32_t first_primitive, ui
  * one the built structure does not hold (added since, or disabled at the build) with the next art_scene_build.  Every rank of an
  * art_mgpu job must make the same calls. */
 int32_t art_scene_set_vertices(ArtContext *ctx, uint32_t primitive_id, const ArtVertex *verts, uint32_t n_verts);
+/* art_scene_set_vertices with the data in DEVICE memory (GPU skinning, cloth, a physics step, a learned deformation in torch): no trip through the host.
+ * MEANING: that of art_scene_set_vertices.  Frames, casts and queries called AFTER it are those of a fresh build over the new vertices, bit for bit; frames in
+ * flight keep theirs; moves and deformations between two frames make one refit; the rebuild rule, residency, masks and cutoffs behave as for the host form.
+ * LAYOUT: ART_VERTS_FULL replaces all 48 bytes of every vertex.  ART_VERTS_POSITIONS replaces the positions only -- three floats at verts_dev + i * stride_bytes for
+ * vertex i -- and keeps uv, normal and tangent as they CURRENTLY are: as of the latest host-form or FULL call, or as added.  Shading normals therefore go stale under a
+ * POSITIONS update; recomputing them is the caller's business.  Geometry (casts, crossings, nearest points, overlaps, depth) is exact.
+ * STREAM ORDER: the library reads verts_dev ON hip_stream: the call enqueues one kernel there (behind whatever the caller enqueued earlier, such as the kernel that
+ * produces the vertices) and returns.  Work enqueued on hip_stream afterwards may overwrite or free verts_dev; nothing else of the library ever reads it.  The refit in
+ * front of the next art_trace or query waits for that kernel on the device, and the kernel for the refits that still read the primitive's previous vertices: nothing
+ * waits on the host, and the steady state allocates nothing.  The first deformation of a built primitive in a context synchronises once and allocates the versions'
+ * shading records, as for the host form (ART_E_NOMEM if they do not fit); no staging memory is allocated for a primitive only ever updated this way.
+ * THE HOST COPY of the primitive falls behind; the library reads it back where it needs it (a build that lays the scene out again, art_scene_get_vertices).  A later
+ * art_scene_set_vertices simply replaces it.  A POSITIONS call right after a host-form call first brings the device copy up to date, synchronously.
+ * A primitive the built structure does not hold (added since the build, disabled at the build, no built scene) has no device copy: the call copies into the host
+ * copy, synchronises hip_stream, and the vertices show with the next art_scene_build.
+ * ERRORS change nothing and enqueue nothing: a null context, descriptor or verts_dev, an unknown id, another count, an unknown layout, a stride the layout does not
+ * allow, verts_dev not 16-byte (FULL) or 4-byte (POSITIONS) aligned, flags or reserved other than 0 are ART_E_INVALID; ART_E_NO_DEVICE without a device.
+ * Every rank of an art_mgpu job must make the same calls.  DESIGN.md 3.1. */
+#define ART_VERTS_FULL 0u       /* n_verts x ArtVertex (48 B), all attributes replaced */
+#define ART_VERTS_POSITIONS 1u  /* n_verts x 3 floats at stride_bytes: positions replaced, uv / normal / tangent kept as they are */
+typedef struct ArtVertexUpdate {
+    const void *verts_dev;   /* device memory (a torch tensor, any hipMalloc'ed memory) */
+    void *hip_stream;        /* the stream verts_dev is produced on; NULL = a stream the context owns */
+    uint32_t primitive_id;
+    uint32_t n_verts;        /* must equal the count the primitive was added with */
+    uint32_t layout;         /* ART_VERTS_* */
+    uint32_t stride_bytes;   /* FULL: 0 or 48.  POSITIONS: 0 (= 12) or >= 12 and a multiple of 4 */
+    uint32_t flags;          /* must be 0 */
+    uint32_t reserved;       /* must be 0 */
+} ArtVertexUpdate;           /* 40 bytes */
+int32_t art_scene_set_vertices_device(ArtContext *ctx, const ArtVertexUpdate *u);
+/* the primitive's current vertices (whichever form set them last), n_verts x 48 B into host memory; synchronises what it must (the latest device-form update of the
+ * primitive, whose device copy is then read back).  A null context or dst, an unknown id or another count is ART_E_INVALID. */
+int32_t art_scene_get_vertices(ArtContext *ctx, uint32_t primitive_id, ArtVertex *dst, uint32_t n_verts);
 /* VkBlasBuilder::build_blas_from_geometry (vk_blas_builder.rs:88-170) + VkTlasBuilder::recreate_tlas
  * (vk_tlas_builder.rs:38-233): device LBVH over the world-space triangle soup. */
 int32_t art_scene_build(ArtContext *ctx);

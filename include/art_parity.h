@@ -165,6 +165,10 @@ int32_t art_read_wave_plan(ArtContext *ctx, uint8_t *level, size_t n64, uint32_t
 /* what libart holds in this process right now: out[0] device allocations, [1] pinned allocations, [2] events,
  * [3] streams in use by contexts and ArtMgpu objects, [4] streams parked in the process-wide pool.  No context needed; never fails with out non-NULL. */
 int32_t art_parity_live_resources(uint64_t out[5]);
+/* what art_scene_set_vertices_device has done in this context so far: kernels enqueued (one per update of a primitive of the built structure), host synchronisations
+ * the device form made itself (the one of a context's first deformation counts; so do the synchronous paths: a primitive outside the structure, the transition
+ * from the host form, a read-back's wait), and device copies read back into host copies.  Any pointer but ctx may be NULL.  The steady state adds to the first only. */
+int32_t art_vertex_update_counts(ArtContext *ctx, uint64_t *ingests, uint64_t *host_syncs, uint64_t *readbacks);
 
 
 /* groups of launches of an ArtMgpu whose exchange has not been submitted yet (their frames may still run) and launches of the group that is still open.

@@ -2,26 +2,29 @@
 """Deformed meshes on config 2 (art_scene_set_vertices): ms per frame for four legs -- still, the 164 k-triangle model moving, the same model deforming, moving
 and deforming -- as a 20-frame burst and as 1 000 frames fenced at both ends, 8 ring slots.  Also: the refit's device time (ArtStats.refit_ms, the model alone),
 host time per art_scene_set_vertices call, the device memory the first deformation takes (versions' shading records + staging), and the register and spill counts
-of both k_refit_sub instances from the code object.  One JSON line.
-    python tools/deform_probe.py [--frames-in-flight 8] [--steps 1000] [--burst 20] [--no-regs]"""
+of both k_refit_sub instances and of k_ingest_verts from the code object.  --device: the deforming legs go through art_scene_set_vertices_device, the shapes being
+tensors on the device (no staging: first_deformation_device_bytes is the shading records alone).  Either way two more legs deform the model from a DEVICE tensor a
+kernel has just produced: "from device, through the host" (tensor -> .cpu() -> art_scene_set_vertices: what a caller had to do before the device form) and "from
+device" (art_scene_set_vertices_device).  One JSON line.
+    python tools/deform_probe.py [--frames-in-flight 8] [--steps 1000] [--burst 20] [--no-regs] [--device] [--priority-stream]"""
 import argparse, ctypes as C, json, math, os, re, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-try:
-    import torch  # noqa: F401
-except Exception:
-    pass
+import torch
 from araytracingjourney_amd import renderer, scenes
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames-in-flight", type=int, default=8); ap.add_argument("--steps", type=int, default=1000); ap.add_argument("--burst", type=int, default=20)
-ap.add_argument("--width", type=int, default=1920); ap.add_argument("--height", type=int, default=1080); ap.add_argument("--no-regs", action="store_true")
+ap.add_argument("--width", type=int, default=1920); ap.add_argument("--height", type=int, default=1080); ap.add_argument("--no-regs", action="store_true"); ap.add_argument("--device", action="store_true"); ap.add_argument("--priority-stream", action="store_true")
 a = ap.parse_args()
+if a.priority_stream:   # the torch work and the device form's kernel on a high-priority stream instead of the null stream
+    torch.cuda.set_stream(torch.cuda.Stream(priority=-1))
 
 
 def regs():
-    """VGPRs / SGPR and VGPR spills / waves per SIMD of k_refit_sub<true> and <false>, as the compiler reports them for the code object of art_refit.hip"""
+    """VGPRs / SGPR and VGPR spills / waves per SIMD of k_refit_sub<true> and <false> and of k_ingest_verts' two instances, as the compiler reports them for the code
+    object of art_refit.hip"""
     src = os.path.join(ROOT, "araytracingjourney_amd", "csrc", "art_refit.hip")
     out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17",
                           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull], capture_output=True, text=True, timeout=600).stderr
@@ -29,12 +32,13 @@ def regs():
     for line in out.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
-            cur = {"_ZN3art11k_refit_subILb1EEE": "fold", "_ZN3art11k_refit_subILb0EEE": "plain"}.get(next((k for k in ("_ZN3art11k_refit_subILb1EEE", "_ZN3art11k_refit_subILb0EEE") if m.group(1).startswith(k)), None))
+            names = {"_ZN3art11k_refit_subILb1EEE": "fold", "_ZN3art11k_refit_subILb0EEE": "plain", "_ZN3art14k_ingest_vertsILi0EEE": "ingest_full", "_ZN3art14k_ingest_vertsILi1EEE": "ingest_positions"}
+            cur = names.get(next((k for k in names if m.group(1).startswith(k)), None))
             if cur:
                 res[cur] = {}
             continue
         if cur:
-            for key, name in (("VGPRs:", "vgpr"), ("SGPRs Spill:", "sgpr_spill"), ("VGPRs Spill:", "vgpr_spill"), ("Occupancy [waves/SIMD]:", "waves")):
+            for key, name in (("VGPRs:", "vgpr"), ("SGPRs Spill:", "sgpr_spill"), ("VGPRs Spill:", "vgpr_spill"), ("Occupancy [waves/SIMD]:", "waves"), ("ScratchSize [bytes/lane]:", "scratch"), ("LDS Size [bytes/block]:", "lds")):
                 m = re.search(re.escape(key) + r" (\d+)", line)
                 if m:
                     res[cur][name] = int(m.group(1))
@@ -77,14 +81,25 @@ for i in range(8):   # a closed loop of poses and of shapes (positions breathing
     shapes.append(np.ascontiguousarray(v))
 L, ctx = r._L, r._ctx
 set_ns = []
+d_shapes = [torch.from_numpy(v).cuda() for v in shapes]   # the shapes where a skinning kernel would leave them
+d_made = torch.empty_like(d_shapes[0])
 
 
-def set_shape(k):
-    v = shapes[k % len(shapes)]
+def set_shape(k, how=None):
+    """how: None = the form --device chooses, from ready-made vertices; "via host" / "device": the vertices are first made on the device (a kernel writes d_made)"""
+    v, dv = shapes[k % len(shapes)], d_shapes[k % len(shapes)]
     t0 = time.perf_counter_ns()
-    rc = L.art_scene_set_vertices(ctx, pid, v.ctypes.data_as(C.c_void_p), v.shape[0])
+    if how is not None:
+        torch.mul(dv, 1.0, out=d_made)   # the producer
+        dv = d_made
+        if how == "via host":
+            v = d_made.cpu().numpy()
+    if how == "device" or (how is None and a.device):
+        model.set_vertices_device(0, dv)
+    else:
+        rc = L.art_scene_set_vertices(ctx, pid, v.ctypes.data_as(C.c_void_p), v.shape[0])
+        assert rc == 0, rc
     set_ns.append(time.perf_counter_ns() - t0)
-    assert rc == 0, rc
 
 
 def set_pose(k):
@@ -97,6 +112,8 @@ def frame(leg, k):
         set_pose(k)
     if leg in ("deforming", "moving+deforming"):
         set_shape(k)
+    if leg.startswith("from device"):
+        set_shape(k, "via host" if leg.endswith("through the host") else "device")
     r.trace()
 
 
@@ -108,9 +125,9 @@ set_shape(1); set_ns.clear()
 r.sync()
 first_deform_bytes = free0 - free_bytes()
 out = {"what": "deform_probe", "scene": "sponza_like 1.0 (config 2)", "extent": [a.width, a.height], "frames_in_flight": F, "model_triangles": int(p.n_tris),
-       "model_vertices": int(p.verts.shape[0]), "legs": {}}
+       "model_vertices": int(p.verts.shape[0]), "form": "device" if a.device else "host", "priority_stream": bool(a.priority_stream), "legs": {}}
 k = 0
-for leg in ("still", "moving", "deforming", "moving+deforming"):
+for leg in ("still", "moving", "deforming", "moving+deforming", "from device, through the host", "from device"):
     for _ in range(3 * F):   # settle
         frame(leg, k); k += 1
     r.sync()
@@ -144,7 +161,10 @@ out["refit_device_ms_alone"] = refit_alone
 out["first_deformation_device_bytes"] = int(first_deform_bytes)
 out["shade_copies_bytes_formula"] = 144 * T * (min(max(2 * F, 4), 24) - 1)
 out["refits"], out["rebuilds"] = st["refits"], st["rebuilds"]
+out["vertex_update_counts"] = r.vertex_update_counts()
 if not a.no_regs:
-    out["k_refit_sub"] = regs()
+    kr = regs()
+    out["k_refit_sub"] = {k: kr[k] for k in ("fold", "plain") if k in kr}
+    out["k_ingest_verts"] = {k[7:]: kr[k] for k in ("ingest_full", "ingest_positions") if k in kr}
 r.close()
 print(json.dumps(out))
