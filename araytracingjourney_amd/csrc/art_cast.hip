@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings, art_overlap_triangles; DESIGN.md 3.5 .. 3.13) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings, art_overlap_triangles, art_closest_triangles; DESIGN.md 3.5 .. 3.14) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
 // entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -255,6 +255,23 @@ int32_t art_overlap_triangles(ArtContext *c, const ArtTriQuery *d) {
     r = overlap_begin(c, d, a, &q); if (r) return r;
     a.qtris = (const float4 *)d->tris_dev;
     launch_tri_overlap(a, q.stream);
+    return cast_commit(c, q, 0);
+}
+
+// ---- the distance from a triangle to the scene (include/art.h: art_closest_triangles) -----------------------------------------------------------------
+// art_closest_points' path with triangles for points and a second point a record: a block of the ring, counted as no cast.
+int32_t art_closest_triangles(ArtContext *c, const ArtTriDistance *d) {
+    const char *who = "art_closest_triangles"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
+    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
+    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "tris_dev", d->tris_dev, 16, d->n)) || (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) ||
+        (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true)) || (r = check_buffer(who, "qpoint_dev", d->qpoint_dev, 16, d->n, true))) return r;
+    if (!c->built) return fail(ART_E_STATE, "art_closest_triangles: scene not built, or changed since the build (art_scene_build)");
+    if (d->n == 0u) return ART_OK;
+    TriDistanceArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
+    a.qtris = (const float4 *)d->tris_dev; a.point = (float4 *)d->point_dev; a.qpoint = (float4 *)d->qpoint_dev;
+    launch_tri_distance(a, q.stream);
     return cast_commit(c, q, 0);
 }
 

@@ -330,6 +330,10 @@ void launch_overlap(const OverlapArgs &c, hipStream_t s);
 // The triangles that touch a triangle (art_overlap_triangles): qtris[3i .. 3i+2] = q0.xyz,- | q1.xyz,- | q2.xyz,-; the outputs are OverlapArgs' (boxes is not used)
 struct TriOverlapArgs : OverlapArgs { const float4 *qtris; };
 void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s);
+// The distance from a triangle to the scene (art_closest_triangles): qtris as TriOverlapArgs', the radius in word 3; tuv / ids / point are ClosestArgs' (points
+// is not used); qpoint (optional) = the witness point on the query, w = 1 (a miss: zeros)
+struct TriDistanceArgs : ClosestArgs { const float4 *qtris; float4 *qpoint; };
+void launch_tri_distance(const TriDistanceArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
 struct ResolveArgs {

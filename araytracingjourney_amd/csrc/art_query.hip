@@ -293,6 +293,10 @@ template <bool FILTER> struct TravPoint {
         return step_leaf_take(a, lds, ovf, [this](float de, float u, float v, uint32_t pos, uint32_t gid) { limit = de; bu = u; bv = v; bpos = pos; bgid = gid; });
     }
     __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
+        return step_internal_by(wide, lds, ovf, [this](float lx, float ly, float lz, float hx, float hy, float hz) { return box_d2(p, lx, ly, lz, hx, hy, hz); });
+    }
+    // the node step for any query that has a squared distance to a box (dist: the point's box_d2 here, the query box's in TravTriDist)
+    template <class DIST> __device__ __forceinline__ bool step_internal_by(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf, const DIST &dist) {
         const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, cur);
         float d2[4]; bool h[4];
 #pragma unroll
@@ -301,7 +305,7 @@ template <bool FILTER> struct TravPoint {
             const float lx = fmaf((float)lxq, sx, ox), hx = fmaf((float)hxq, sx, ox);
             const float ly = fmaf((float)((b.y >> (8 * i)) & 255u), sy, oy), hy = fmaf((float)((c.x >> (8 * i)) & 255u), sy, oy);
             const float lz = fmaf((float)((b.z >> (8 * i)) & 255u), sz, oz), hz = fmaf((float)((c.y >> (8 * i)) & 255u), sz, oz);
-            d2[i] = box_d2(p, lx, ly, lz, hx, hy, hz);
+            d2[i] = dist(lx, ly, lz, hx, hy, hz);
             h[i] = (lxq <= hxq) & !(d2[i] > limit);   // an inverted box (255 / 0): an absent child or a masked subtree -- a distance to it means nothing, so it is asked
         }
         // on with the nearest child within the limit; the others wait with their distances, the farthest at the bottom: what is popped next is the nearest of them, and
@@ -798,22 +802,30 @@ template <bool ANY, bool FILTER> struct TravTri : TravBox<ANY, FILTER> {
         return this->pop(lds, ovf);
     }
 };
+// a query triangle into a walk that has q0, q1, q2, lo, hi: three 16-byte loads, the vertices and their box [qlo, qhi]; w3: word 3 as given (art_closest_triangles'
+// radius; the overlap query does not read it).  False: a dead query (a non-finite coordinate among the nine), whose walk state is left as it was
+template <class TRAV> __device__ __forceinline__ bool read_tri(const float4 *qtris, uint32_t sidx, TRAV &tr, float &w3) {
+    const float4 r0 = qtris[3 * (size_t)sidx], r1 = qtris[3 * (size_t)sidx + 1], r2 = qtris[3 * (size_t)sidx + 2];
+    const float z = (((0.0f * r0.x + 0.0f * r0.y) + 0.0f * r0.z) + ((0.0f * r1.x + 0.0f * r1.y) + 0.0f * r1.z)) + ((0.0f * r2.x + 0.0f * r2.y) + 0.0f * r2.z);   // 0 for nine finite coordinates, NaN otherwise
+    w3 = r0.w;
+    if (z == 0.0f) {
+        V3 mn = mk(r0.x, r0.y, r0.z), mx = mn;   // qlo, qhi: two selects an axis from the first vertex
+        mn.x = r1.x < mn.x ? r1.x : mn.x; mn.y = r1.y < mn.y ? r1.y : mn.y; mn.z = r1.z < mn.z ? r1.z : mn.z;
+        mx.x = r1.x > mx.x ? r1.x : mx.x; mx.y = r1.y > mx.y ? r1.y : mx.y; mx.z = r1.z > mx.z ? r1.z : mx.z;
+        mn.x = r2.x < mn.x ? r2.x : mn.x; mn.y = r2.y < mn.y ? r2.y : mn.y; mn.z = r2.z < mn.z ? r2.z : mn.z;
+        mx.x = r2.x > mx.x ? r2.x : mx.x; mx.y = r2.y > mx.y ? r2.y : mx.y; mx.z = r2.z > mx.z ? r2.z : mx.z;
+        tr.q0 = mk(r0.x, r0.y, r0.z); tr.q1 = mk(r1.x, r1.y, r1.z); tr.q2 = mk(r2.x, r2.y, r2.z);
+        tr.lo = mn; tr.hi = mx;
+        return true;
+    }
+    return false;
+}
 // OverlapSink with the fetch of a triangle: init and finish are the box query's
 template <bool ANY, int KMAX> struct TriSink : OverlapSink<ANY, KMAX> {
     const float4 *qtris;
     template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &) const {
-        const float4 r0 = qtris[3 * (size_t)sidx], r1 = qtris[3 * (size_t)sidx + 1], r2 = qtris[3 * (size_t)sidx + 2];
-        const float z = (((0.0f * r0.x + 0.0f * r0.y) + 0.0f * r0.z) + ((0.0f * r1.x + 0.0f * r1.y) + 0.0f * r1.z)) + ((0.0f * r2.x + 0.0f * r2.y) + 0.0f * r2.z);   // 0 for nine finite coordinates, NaN otherwise
-        if (z == 0.0f) {
-            V3 mn = mk(r0.x, r0.y, r0.z), mx = mn;   // qlo, qhi: two selects an axis from the first vertex
-            mn.x = r1.x < mn.x ? r1.x : mn.x; mn.y = r1.y < mn.y ? r1.y : mn.y; mn.z = r1.z < mn.z ? r1.z : mn.z;
-            mx.x = r1.x > mx.x ? r1.x : mx.x; mx.y = r1.y > mx.y ? r1.y : mx.y; mx.z = r1.z > mx.z ? r1.z : mx.z;
-            mn.x = r2.x < mn.x ? r2.x : mn.x; mn.y = r2.y < mn.y ? r2.y : mn.y; mn.z = r2.z < mn.z ? r2.z : mn.z;
-            mx.x = r2.x > mx.x ? r2.x : mx.x; mx.y = r2.y > mx.y ? r2.y : mx.y; mx.z = r2.z > mx.z ? r2.z : mx.z;
-            tr.q0 = mk(r0.x, r0.y, r0.z); tr.q1 = mk(r1.x, r1.y, r1.z); tr.q2 = mk(r2.x, r2.y, r2.z);
-            tr.lo = mn; tr.hi = mx; tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
-            return true;
-        }
+        float w3;
+        if (read_tri(qtris, sidx, tr, w3)) { tr.cnt = 0u; tr.cur = 0; tr.sp = 0; return true; }
         const OverlapK &a = this->a;
         if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate): its answer, without a walk
         else {
@@ -831,6 +843,145 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(ANY
     __shared__ int stack[kOverlapLds * kTraceBlock];
     __shared__ uint32_t gids[(ANY ? 1 : KMAX) * kTraceBlock];
     point_trace<TravTri<ANY, FILTER>>(a, stack, TriSink<ANY, KMAX>{{a, gids}, a.qtris});
+}
+
+// ---- the distance from a triangle to the scene (art_closest_triangles) ----------------------------------------------------------------------------------
+// A query is art_overlap_triangles' triangle with a radius in word 3, and the answer art_closest_points' record for a triangle in place of a point: the walk is TravPoint's
+// -- its stack of (reference, distance) pairs, push, pop, the five-comparator child order (step_internal_by) and the hook of its leaf step's tie rule -- with the
+// squared distance between the query's box [qlo, qhi] and a box where the point's box_d2 stood.  What is this query's own: that distance (boxes_d2), the clamped
+// segment pair (seg_seg) and the fifteen features of a pair of triangles (tri_tri_closest); tri_closest, tri_tri_overlap and the fetch (read_tri) are the one copy above.
+// No fmaf in anything that decides a record: tests/np_tri_distance.py restates every operation in numpy float32.
+// [lo, hi] against [tlo, thi]: per axis max(max(tlo - hi, lo - thi), 0) by selects, summed (x^2 + y^2) + z^2
+__device__ __forceinline__ float boxes_d2(V3 lo, V3 hi, float lx, float ly, float lz, float hx, float hy, float hz) {
+    const float ax = lx - hi.x, bx = lo.x - hx, ay = ly - hi.y, by = lo.y - hy, az = lz - hi.z, bz = lo.z - hz;
+    float ex = bx > ax ? bx : ax, ey = by > ay ? by : ay, ez = bz > az ? bz : az;
+    ex = ex > 0.0f ? ex : 0.0f; ey = ey > 0.0f ? ey : 0.0f; ez = ez > 0.0f ? ez : 0.0f;
+    return (ex * ex + ey * ey) + ez * ez;
+}
+__device__ __forceinline__ float clamp01(float x) { x = x > 0.0f ? x : 0.0f; return x < 1.0f ? x : 1.0f; }   // (two selects: a NaN becomes 0, seg_param's rule)
+// the nearest points of the segments {p1 + s d1} and {p2 + t d2}, 0 <= s, t <= 1 (Ericson 5.1.9, every divisor guarded as seg_param's): r = p1 - p2.  -> their squared distance
+__device__ __forceinline__ float seg_seg(V3 p1, V3 d1, V3 p2, V3 d2, float &s, float &t) {
+    const V3 r = p1 - p2;
+    const float a = dotp(d1, d1), e = dotp(d2, d2), f = dotp(d2, r), c = dotp(d1, r), b = dotp(d1, d2);
+    const float den = a * e - b * b, qa = a > 0.0f ? a : 1.0f;
+    s = clamp01((b * f - c * e) / (den > 0.0f ? den : 1.0f));
+    s = den > 0.0f ? s : 0.0f;
+    s = a > 0.0f ? s : 0.0f;
+    t = (b * s + f) / (e > 0.0f ? e : 1.0f);
+    t = e > 0.0f ? t : 0.0f;
+    const float s0 = clamp01(-c / qa), s1 = clamp01((b - c) / qa);
+    s = t < 0.0f ? s0 : s; s = t > 1.0f ? s1 : s;
+    s = a > 0.0f ? s : 0.0f;
+    t = clamp01(t);
+    const float dx = (p1.x + s * d1.x) - (p2.x + t * d2.x), dy = (p1.y + s * d1.y) - (p2.y + t * d2.y), dz = (p1.z + s * d1.z) - (p2.z + t * d2.z);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// The features of DESIGN.md 3.14 for the scene triangle v0 e1 e2 and the query q0 q1 q2 in their order, the first of the smallest winning: the query's vertices against
+// the triangle, the triangle's vertices against the query, the nine edge pairs, scene edge outermost.  u, v: the scene side's barycentrics of the winning pair of
+// points; s, t: the query side's.  +inf: no feature gave a number
+__device__ __forceinline__ float tri_tri_closest(V3 v0, V3 e1, V3 e2, V3 q0, V3 q1, V3 q2, float &u, float &v, float &s, float &t) {
+    float best = INFINITY, cu, cv; u = 0.0f; v = 0.0f; s = 0.0f; t = 0.0f;
+    const V3 g1 = q1 - q0, g2 = q2 - q0;
+    float d = tri_closest(q0 - v0, e1, e2, cu, cv);
+    if (d < best) { best = d; u = cu; v = cv; s = 0.0f; t = 0.0f; }
+    d = tri_closest(q1 - v0, e1, e2, cu, cv);
+    if (d < best) { best = d; u = cu; v = cv; s = 1.0f; t = 0.0f; }
+    d = tri_closest(q2 - v0, e1, e2, cu, cv);
+    if (d < best) { best = d; u = cu; v = cv; s = 0.0f; t = 1.0f; }
+    const V3 v1 = mk(v0.x + e1.x, v0.y + e1.y, v0.z + e1.z), v2 = mk(v0.x + e2.x, v0.y + e2.y, v0.z + e2.z);
+    d = tri_closest(v0 - q0, g1, g2, cu, cv);
+    if (d < best) { best = d; u = 0.0f; v = 0.0f; s = cu; t = cv; }
+    d = tri_closest(v1 - q0, g1, g2, cu, cv);
+    if (d < best) { best = d; u = 1.0f; v = 0.0f; s = cu; t = cv; }
+    d = tri_closest(v2 - q0, g1, g2, cu, cv);
+    if (d < best) { best = d; u = 0.0f; v = 1.0f; s = cu; t = cv; }
+    const V3 sp[3] = {v0, v0, v1}, sd[3] = {e1, e2, e2 - e1}, qp[3] = {q0, q0, mk(q0.x + g1.x, q0.y + g1.y, q0.z + g1.z)}, qd[3] = {g1, g2, g2 - g1};
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            d = seg_seg(sp[i], sd[i], qp[j], qd[j], cu, cv);
+            if (d < best) {   // the parameters as barycentrics: edge 0 is (x, 0), edge 1 (0, x), edge 2 (1 - x, x)
+                best = d;
+                u = i == 0 ? cu : (i == 1 ? 0.0f : 1.0f - cu); v = i == 0 ? 0.0f : cu;
+                s = j == 0 ? cv : (j == 1 ? 0.0f : 1.0f - cv); t = j == 0 ? 0.0f : cv;
+            }
+        }
+    }
+    return best;
+}
+// d2_tri of DESIGN.md 3.14: 0 where the 17 axes say the two touch or cut (asked only while the features are above 0: the result is the same), else the winning feature's
+// distance; the witnesses are the winning feature's either way.  Where no feature gave a number (a non-finite triangle, which no axis separates either) it stays +inf
+__device__ __forceinline__ float tri_tri_d2(V3 v0, V3 e1, V3 e2, V3 q0, V3 q1, V3 q2, float &u, float &v, float &s, float &t) {
+    const float d = tri_tri_closest(v0, e1, e2, q0, q1, q2, u, v, s, t);
+    return (d > 0.0f && d < INFINITY && tri_tri_overlap(v0, e1, e2, q0, q1, q2)) ? 0.0f : d;
+}
+struct TriDistanceK : ClosestK { const float4 *qtris; float4 *qpoint; };   // points: not used; qpoint: may be null
+// TravPoint with the query's vertices and box where its point stood: push, pop and the child order are TravPoint's; the node step asks boxes_d2, and the leaf step is its own
+template <bool FILTER> struct TravTriDist : TravPoint<FILTER> {
+    V3 q0, q1, q2, lo, hi;   // (TravPoint's p is not used here, and its step_internal and step_leaf are shadowed by the two below)
+    float bs, bt;   // the best candidate's barycentrics on the query
+    __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
+        return this->step_internal_by(wide, lds, ovf, [this](float lx, float ly, float lz, float hx, float hy, float hz) { return boxes_d2(lo, hi, lx, ly, lz, hx, hy, hz); });
+    }
+    // the triangle in `cur`: its own box first (box_d2 > limit: d2_eff is at least that, nothing to take), then the features and the 17 axes, then TravPoint's tie rule and the masks
+    __device__ __forceinline__ bool step_leaf(const TriDistanceK &a, int2 *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const float bd = boxes_d2(lo, hi, tc.y, tc.z, tc.w, td.x, td.y, td.z);
+        if ((tc.y < 3.0e38f) & !(bd > this->limit)) {
+            float u, v, s, t;
+            const float dt = tri_tri_d2(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), q0, q1, q2, u, v, s, t);
+            if ((dt < INFINITY) & (bd < INFINITY)) {   // the parts, not the maximum (TravPoint::step_leaf_take)
+                const float de = bd > dt ? bd : dt;
+                const uint32_t gid = __float_as_uint(td.w);
+                if ((de < this->limit || (de == this->limit && gid < this->bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
+                    this->limit = de; this->bu = u; this->bv = v; this->bpos = pos; this->bgid = gid; bs = s; bt = t;
+                }
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+};
+// The walk carries the query side's (s, t) of its best candidate (bs, bt) beside limit, u, v, pos and gid: 123 VGPRs.  A finish that evaluates the winning pair once more
+// for them instead holds the fifteen features a second time and comes out at 133 (DESIGN.md 3.14's table has both figures)
+struct TriDistanceSink {
+    const TriDistanceK &a;
+    template <class I> __device__ __forceinline__ void miss(I at, float r) const {
+        write_point_miss(a, at, r);
+        if (a.qpoint) a.qpoint[at] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &) const { return 1u; }
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t, float &radius) const {
+        float r;
+        if (read_tri(a.qtris, sidx, tr, r) && r == r && !(r < 0.0f)) {   // a NaN or negative radius: read_point's rule
+            tr.limit = r * r; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
+            radius = r;
+            return true;
+        }
+        miss(sidx, r);
+        return false;
+    }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t, float radius) const {
+        if (tr.bgid != kNoHit) {
+            write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
+            if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
+            if (a.qpoint) {
+                const float s = tr.bs, t = tr.bt;
+                const V3 g1 = tr.q1 - tr.q0, g2 = tr.q2 - tr.q0;
+                a.qpoint[slot] = make_float4(tr.q0.x + (s * g1.x + t * g2.x), tr.q0.y + (s * g1.y + t * g2.y), tr.q0.z + (s * g1.z + t * g2.z), 1.0f);
+            }
+        } else miss(slot, radius);
+    }
+};
+// (waves_per_eu 4: the fifteen features and the 17 axes hold 123 VGPRs without a spill; at 5 waves (96) the compiler spills 85 of them to scratch -- DESIGN.md
+// 3.14's table)
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_closest_tris(TriDistanceK a) {
+    __shared__ int2 stack[kClosestLds * kTraceBlock];
+    point_trace<TravTriDist<FILTER>>(a, stack, TriDistanceSink{a});
 }
 
 // The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
@@ -892,6 +1043,10 @@ void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s) {   // launch_ov
     a.qtris = c.qtris; a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
     if (c.any) launch_query(c.filter ? k_overlap_tris<true, 0, true> : k_overlap_tris<true, 0, false>, a, c, s);
     else launch_query(c.filter ? k_overlap_tris<false, 8, true> : k_overlap_tris<false, 8, false>, a, c, s);
+}
+void launch_tri_distance(const TriDistanceArgs &c, hipStream_t s) {
+    TriDistanceK a = closest_fill<TriDistanceK>(c); a.qtris = c.qtris; a.qpoint = c.qpoint;
+    launch_query(c.filter ? k_closest_tris<true> : k_closest_tris<false>, a, c, s);
 }
 
 } // namespace art

@@ -324,6 +324,16 @@ public:
     static_assert(sizeof(ArtTriQuery) == 64, "ArtTriQuery is part of the ABI");
     static void overlap_triangles(ArtContext *ctx, const ArtTriQuery &d) { check(art_overlap_triangles(ctx, &d)); }
     void overlap_triangles(const ArtTriQuery &d) { overlap_triangles(ctx_, d); }
+    // the distance from each of n query triangles (q0.xyz, r, q1.xyz, -, q2.xyz, -) in device memory to the scene: records of art_closest_points' kind and (optionally)
+    // n x float4 witness points on the scene triangle and on the query (art_closest_triangles)
+    static ArtTriDistance tri_distance(const void *tris_dev, uint32_t n, void *duv_dev, void *ids_dev, void *point_dev = nullptr, void *qpoint_dev = nullptr, void *hip_stream = nullptr,
+                                       uint32_t cull_mask = 0xFFu) {
+        ArtTriDistance d{}; d.tris_dev = tris_dev; d.duv_dev = duv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.qpoint_dev = qpoint_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtTriDistance) == 64, "ArtTriDistance is part of the ABI");
+    static void closest_triangles(ArtContext *ctx, const ArtTriDistance &d) { check(art_closest_triangles(ctx, &d)); }
+    void closest_triangles(const ArtTriDistance &d) { closest_triangles(ctx_, d); }
     // where a ball of `radius` along each of n rays in device memory first touches the scene: records as a closest cast's and (optionally) n x float4 contact points (art_cast_spheres)
     static ArtSphereCast sphere_cast(const void *rays_dev, uint32_t n, float radius, void *tuv_dev, void *ids_dev, void *point_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
         ArtSphereCast d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask; d.radius = radius;

@@ -986,10 +986,65 @@ class Renderer:
         ((p.x * m[r][0] + p.y * m[r][1]) + p.z * m[r][2]) + m[r][3] in float32 for each row r; a triangle with an index outside positions becomes a dead query (NaN
         coordinates: it touches nothing).  The answer is overlap_triangles of that buffer and nothing else: kind "any" returns hit, (T,) uint8; kind "list" returns
         (ids, count), (T, K, 2) int32 and (T,) int32 -- per triangle of the mesh, in the order of indices.  hit.any() is "the mesh collides".  No host synchronisation."""
-        import torch
         _mask_value("cull_mask", cull_mask)
         if kind not in ("list", "any"):
             raise ValueError("kind must be 'list' or 'any'")
+        import torch
+        tris, stream = self._mesh_tris(positions, indices, model_matrix, stream)
+        with torch.cuda.stream(stream):   # (the outputs are torch's allocations on the stream that writes them)
+            return self.overlap_triangles(tris, kind, max_hits, cull_mask, stream=stream)
+
+    def closest_triangles(self, tris, cull_mask=0xFF, out=None, stream=None):
+        """The distance from each query triangle to the scene, and where (art_closest_triangles; DESIGN.md 3.14 is the definition).  tris: a torch tensor on this context's
+        device, float32, shape (n, 12) -- q0.xyz, r, q1.xyz, -, q2.xyz, - (word 3 is the query's search radius, inf: unbounded; words 7 and 11 are not read) --
+        contiguous and 16-byte aligned: a buffer of overlap_triangles' queries with the radius written into column 3.  Returns (duv, ids, point, qpoint): (n, 4) float32
+        d,u,v,0 -- the distance and the barycentrics of vertices 1 and 2 of the witness point on the scene triangle -- (n, 2) int32 (primitive, triangle in the
+        primitive), (n, 4) float32 that point, w = 1, and (n, 4) float32 the witness point on the query triangle, w = 1.  A pair that touches or cuts has d = 0; its two
+        points are the nearest features' and need not coincide (overlap_triangles says which triangles cut, this says the clearance is 0).  Nothing within r (or a
+        non-finite coordinate, a NaN or negative r) is the miss record: (r, 0, 0, 0), (-1, -1) and points of zeros.  Alpha cutoffs are not tested; primitive masks are,
+        against cull_mask.  out: (duv, ids, point, qpoint) to write instead of new ones, of at least n records, not overlapping the queries or each other.  Every tensor
+        is checked before anything is enqueued.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        m = _mask_value("cull_mask", cull_mask)
+        n = self._dev_tensor(tris, "tris", "float32", (12,), 16).shape[0]
+        duv, ids, point, qpoint = self._outputs(out, n, tris.device, (("duv", "float32", (4,), 16), self._RECORDS[1], self._POINT, ("qpoint", "float32", (4,), 16)))
+        d = _lib.ArtTriDistance(tris_dev=tris.data_ptr() or None, duv_dev=duv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
+                                qpoint_dev=qpoint.data_ptr() or None, n=n, cull_mask=m, flags=0, reserved=0, hip_stream=self._stream_handle(stream, tris.device))
+        check(self._L.art_closest_triangles(self._ctx, C.byref(d)))
+        return duv, ids, point, qpoint
+
+    def mesh_clearance(self, positions, indices, model_matrix=None, radius=float("inf"), cull_mask=0xFF, stream=None):
+        """How far is this mesh, where it stands, from the scene's surfaces, and where?  positions, indices, model_matrix: collide_mesh's, gathered the same way on the
+        device -- one closest_triangles query per triangle of the mesh, each with the search radius `radius` (a float >= 0, inf: unbounded; a triangle with an index outside
+        positions is a dead query).  Returns (records, nearest): records = closest_triangles' (duv, ids, point, qpoint) per triangle, in the order of indices; nearest = a
+        dict of tensors reduced on the device from them -- distance () float32, the smallest d of the triangles that have an answer; index () int64, the mesh triangle it
+        belongs to, the lowest among equals; ids (2,) int32; point (4,) and qpoint (4,) float32, that record's.  Nothing within radius of any triangle (or no triangle):
+        distance = radius, index = -1, ids (-1, -1), points of zeros.  distance == 0 is "the mesh touches or cuts the scene".  No host synchronisation."""
+        import torch
+        _mask_value("cull_mask", cull_mask)
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a float >= 0 (inf: unbounded)")
+        tris, stream = self._mesh_tris(positions, indices, model_matrix, stream)
+        with torch.cuda.stream(stream):
+            tris[:, 3] = radius
+            duv, ids, point, qpoint = records = self.closest_triangles(tris, cull_mask, stream=stream)
+            nt, dev = tris.shape[0], tris.device
+            if nt == 0:
+                return records, dict(distance=torch.full((), radius, dtype=torch.float32, device=dev), index=torch.full((), -1, dtype=torch.int64, device=dev),
+                                     ids=torch.full((2,), -1, dtype=torch.int32, device=dev), point=torch.zeros(4, device=dev), qpoint=torch.zeros(4, device=dev))
+            has = ids[:, 0] >= 0
+            key = torch.where(has, duv[:, 0], torch.full_like(duv[:, 0], float("inf")))
+            at = torch.where(key == key.min(), torch.arange(nt, device=dev), nt).min()   # the lowest index among equals
+            any_ = has.any()
+            at = torch.where(any_, at, torch.zeros_like(at))   # (no answer at all: record 0 is a miss record, which is what is handed out)
+            row = at.reshape(1)   # (index_select: a 0-dim tensor as a plain index would be read back by the host)
+            pick = lambda t: t.index_select(0, row)[0]   # noqa: E731
+            return records, dict(distance=pick(duv)[0], index=torch.where(any_, at, torch.full_like(at, -1)), ids=pick(ids), point=pick(point), qpoint=pick(qpoint))
+
+    def _mesh_tris(self, positions, indices, model_matrix, stream):
+        """collide_mesh's and mesh_clearance's gather behind their docstrings: the checks, then the (T, 12) query buffer made on the device on `stream` (words 3, 7 and 11
+        are 0) -> (tris, the torch stream it was made on)"""
+        import torch
         nv = self._dev_tensor(positions, "positions", "float32", (3,), 4).shape[0]
         dev = positions.device
         if not (isinstance(indices, torch.Tensor) and indices.device == dev and indices.dtype in (torch.int32, torch.int64) and indices.dim() == 2 and indices.shape[1] == 3
@@ -1017,7 +1072,7 @@ class Renderer:
                     p = torch.stack([((x * mm[4 * r] + y * mm[4 * r + 1]) + z * mm[4 * r + 2]) + mm[4 * r + 3] for r in range(3)], dim=-1)
                 outside = ((idx < 0) | (idx >= nv)).any(dim=1)
                 tris[..., 0:3] = torch.where(outside[:, None, None], torch.full_like(p, float("nan")), p)
-            return self.overlap_triangles(tris.reshape(nt, 12), kind, max_hits, cull_mask, stream=stream)
+        return tris.reshape(nt, 12), stream
 
     def voxelize(self, origin, cell, dims, cull_mask=0xFF, stream=None):
         """An occupancy grid of the scene: a uint8 tensor [nx, ny, nz] on this context's device, 1 where some triangle touches the cell (overlap_boxes, kind "any").

@@ -594,6 +594,40 @@ typedef struct ArtTriQuery {
     uint32_t reserved;      /* must be 0 */
 } ArtTriQuery;              /* 64 bytes */
 int32_t art_overlap_triangles(ArtContext *ctx, const ArtTriQuery *q);
+/* The distance from query triangles to the scene, and where (which is the definition; new functionality: FCL's distance, PhysX's computeDistance, PQP's
+ * TriDist -- the reference has no call for it): the clearance of a mesh that art_overlap_triangles says cuts nothing -- a robot link 2 mm from a wall and one 2 m from it
+ * -- which bundles of art_closest_points on sampled points miss where two edges cross.  A query is a triangle q0, q1, q2 and a search radius r in word 3.
+ *  - Results: defined exactly and independent of the structure, in fp32 without fused operations, sums of three as (a + b) + c, minima and maxima by selects, every divisor
+ *    guarded.  For a triangle with global id g and record v0, e1, e2, tlo, thi, with g1 = q1 - q0, g2 = q2 - q0: the FEATURES are, in this order, the first of the smallest
+ *    winning, art_closest_points' d2_tri of q0, q1, q2 against the triangle; of v0, v0 + e1, v0 + e2 against the query (q0, g1, g2); and the nine pairs of scene edge
+ *    (v0,e1), (v0,e2), (v0+e1,e2-e1) against query edge (q0,g1), (q0,g2), (q0+g1,g2-g1), scene edge outermost, by DESIGN.md 3.14's clamped segment formula.  d2_tri = 0 if
+ *    art_overlap_triangles' condition 3 (the 17 axes) says the two touch or cut, else the winning feature's distance (+inf, the axes not asked, where no feature gives a
+ *    number: a non-finite triangle); box_d2 = the squared distance between the query's box [qlo, qhi] and [tlo, thi]; d2_eff = max(d2_tri, box_d2).  The candidates are the
+ *    triangles with tlo.x < 3.0e38 (a primitive that left the structure by residency is nowhere), whose primitive's mask & cull_mask != 0, with d2_tri and box_d2 finite
+ *    and d2_eff <= r*r; the answer is the argmin of (d2_eff, g).  duv_dev[i] = (sqrtf(d2_eff), u, v, 0), u, v the barycentrics of vertices 1 and 2 of the witness point on
+ *    the scene triangle (a record art_resolve_hits takes); ids_dev[i] as a closest cast's; point_dev[i] (optional) = (v0 + (u*e1 + v*e2), 1); qpoint_dev[i] (optional) =
+ *    (q0 + (s*g1 + t*g2), 1), the witness on the query.  The witnesses are the winning feature's in both cases: for a cutting pair the two points are NOT a point of the
+ *    intersection and need not coincide -- art_overlap_triangles says which triangles cut, this query says the clearance is 0.  Zero-area operands (a segment, a point) go
+ *    through the same formulas.
+ *  - A miss -- nothing within r -- is (r as given, 0, 0, 0), (-1, -1) and points of zeros.  A query with a non-finite coordinate among its nine, a NaN r or r < 0 is dead:
+ *    its miss record, no walk.  r = +inf and -0.0 are legal.  Words 7 and 11 of a query are not read.  A record depends on its query alone.
+ *  - Alpha cutoffs are NOT tested, for art_closest_points' reason.  Visibility masks apply as for casts: cull_mask 0 sees nothing.  Penetration depth is not computed.
+ *  - Asynchrony and scene: art_closest_points', with no path of its own -- stream, no allocation or synchronisation on the steady path, the scene as of the call, the
+ *    version held, a block of the casts' ring (ART_CAST_POOL), the same fences.  art_cast_counts counts it in neither casts nor rays (it traces no ray); a host wait it
+ *    causes counts in host_waits.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; flags or reserved other than 0; cull_mask above 0xFF; n above
+ *    ART_CAST_MAX_RAYS; a null or misaligned tris_dev / duv_dev (16 bytes) / ids_dev (8 bytes) -- with n = 0 null is fine; a misaligned point_dev or qpoint_dev.
+ *    ART_E_STATE: the scene is not built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtTriDistance {
+    const void *tris_dev;   /* n x 12 floats: q0.xyz, r | q1.xyz, - | q2.xyz, - ; 16-byte aligned.  Word 3 is the query's radius; words 7 and 11 are not read */
+    void *duv_dev;          /* n x 4 floats d,u,v,0 -- a miss is (r as given,0,0,0); 16-byte aligned */
+    void *ids_dev;          /* n x 2 int32 (primitive id, triangle in the primitive), -1,-1 for a miss; 8-byte aligned */
+    void *point_dev;        /* n x float4: the witness point on the SCENE triangle, w = 1; a miss is zeros.  16-byte aligned.  May be NULL */
+    void *qpoint_dev;       /* n x float4: the witness point on the QUERY triangle, w = 1; a miss is zeros.  16-byte aligned.  May be NULL */
+    void *hip_stream;       /* as ArtRayCast: NULL = the context's cast stream */
+    uint32_t n, cull_mask, flags, reserved;   /* n = 0 is legal: nothing is enqueued; cull_mask 0..0xFF; flags, reserved: must be 0 */
+} ArtTriDistance;           /* 64 bytes */
+int32_t art_closest_triangles(ArtContext *ctx, const ArtTriDistance *q);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
