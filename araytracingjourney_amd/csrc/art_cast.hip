@@ -1,6 +1,6 @@
 // art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings, art_overlap_triangles, art_closest_triangles; DESIGN.md 3.5 .. 3.14) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
-// entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query.hip's and art_resolve.hip's.
+// entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query_rays.hip's, art_query_points.hip's and art_resolve.hip's.
 #include "art_context.h"
 
 // the first cast of a context: its stream (counted against the budget beside kMaxFrameSlots), the cursor blocks and their events
@@ -100,6 +100,7 @@ static int32_t check_null(const char *who, const void *c, const void *d) { retur
 static int32_t check_flags(const char *who, uint32_t flags) { return flags != 0u ? invalid(who, "flags: must be 0") : ART_OK; }
 static int32_t check_cull(const char *who, uint32_t cull_mask) { return cull_mask > 0xFFu ? invalid(who, "cull_mask: above 0xFF") : ART_OK; }
 static int32_t check_n(const char *who, uint32_t n) { return n > ART_CAST_MAX_RAYS ? invalid(who, "n: above ART_CAST_MAX_RAYS") : ART_OK; }
+static int32_t check_built(const char *who, const ArtContext *c, bool changed = true) { return c->built ? ART_OK : fail(ART_E_STATE, std::string(who) + ": scene not built" + (changed ? ", or changed since the build" : "") + " (art_scene_build)"); }
 static int32_t check_buffer(const char *who, const char *name, const void *p, size_t align, uint32_t n, bool optional = false) {
     if (!misaligned(p, align) && (optional || p || !n)) return ART_OK;
     std::string what = optional ? "" : "null";
@@ -135,8 +136,7 @@ template <class D> static int32_t overlap_check(const char *who, ArtContext *c, 
         if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
         if ((r = check_buffer(who, "ids_dev", d->ids_dev, 8, d->n)) || (r = check_buffer(who, "count_dev", d->count_dev, 4, d->n, true))) return r;
     }
-    if (!c->built) return fail(ART_E_STATE, std::string(who) + ": scene not built, or changed since the build (art_scene_build)");
-    return ART_OK;
+    return check_built(who, c);
 }
 // a block of the ring for a checked descriptor of n > 0 queries, and the outputs both kinds of query share
 template <class D> static int32_t overlap_begin(ArtContext *c, const D *d, OverlapArgs &a, RingSlot *q) {
@@ -160,7 +160,7 @@ int32_t art_cast_rays(ArtContext *c, const ArtRayCast *d) {
         if (d->hit_dev) return invalid(who, "hit_dev: must be NULL for ART_CAST_CLOSEST");
         if ((r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n))) return r;
     }
-    if (!c->built) return fail(ART_E_STATE, "art_cast_rays: scene not built (art_scene_build)");
+    if ((r = check_built(who, c, false))) return r;
     if (d->n == 0u) return ART_OK;
     return cast_enqueue(c, d->rays_dev, d->n, any, d->cull_mask, d->tuv_dev, d->ids_dev, d->hit_dev, (hipStream_t)d->hip_stream, nullptr);
 }
@@ -170,7 +170,7 @@ int32_t art_cast_rays_multi(ArtContext *c, const ArtRayCastMulti *d) {
     if ((r = check_null(who, c, d))) return r;
     if (d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS) return invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS");
     if ((r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev)) || (r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n))) return r;
-    if (!c->built) return fail(ART_E_STATE, "art_cast_rays_multi: scene not built (art_scene_build)");
+    if ((r = check_built(who, c, false))) return r;
     if (d->n == 0u) return ART_OK;
     CastArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
@@ -189,7 +189,7 @@ int32_t art_resolve_hits(ArtContext *c, const ArtHitResolve *d) {
         return invalid(who, "pos_dev / ng_dev / ns_dev / albedo_dev / orm_dev: not 16-byte aligned");
     if ((r = check_buffer(who, "uv_dev", d->uv_dev, 8, d->n, true))) return r;
     if (d->n != 0u && !d->pos_dev && !d->ng_dev && !d->ns_dev && !d->uv_dev && !d->albedo_dev && !d->orm_dev) return invalid(who, "no output buffer given");
-    if (!c->built) return fail(ART_E_STATE, "art_resolve_hits: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_built(who, c))) return r;
     if (d->n == 0u) return ART_OK;
     RingSlot q;
     r = cast_claim(c, (hipStream_t)d->hip_stream, &q); if (r) return r;
@@ -209,7 +209,7 @@ int32_t art_closest_points(ArtContext *c, const ArtPointQuery *d) {
     const char *who = "art_closest_points"; int32_t r;
     if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
     if ((r = d->reserved != 0u ? invalid(who, "reserved: must be 0") : point_check(who, d))) return r;
-    if (!c->built) return fail(ART_E_STATE, "art_closest_points: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_built(who, c))) return r;
     if (d->n == 0u) return ART_OK;
     ClosestArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
@@ -224,7 +224,7 @@ int32_t art_closest_points_multi(ArtContext *c, const ArtPointQueryMulti *d) {
     const char *who = "art_closest_points_multi"; int32_t r;
     if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
     if ((r = d->max_hits == 0u || d->max_hits > ART_CAST_MAX_HITS ? invalid(who, "max_hits: 1 .. ART_CAST_MAX_HITS") : point_check(who, d))) return r;
-    if (!c->built) return fail(ART_E_STATE, "art_closest_points_multi: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_built(who, c))) return r;
     if (d->n == 0u) return ART_OK;
     ClosestMultiArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
@@ -266,7 +266,7 @@ int32_t art_closest_triangles(ArtContext *c, const ArtTriDistance *d) {
     if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
     if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "tris_dev", d->tris_dev, 16, d->n)) || (r = check_records(who, "duv_dev", d->duv_dev, d->ids_dev, d->n)) ||
         (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true)) || (r = check_buffer(who, "qpoint_dev", d->qpoint_dev, 16, d->n, true))) return r;
-    if (!c->built) return fail(ART_E_STATE, "art_closest_triangles: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_built(who, c))) return r;
     if (d->n == 0u) return ART_OK;
     TriDistanceArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->duv_dev, d->ids_dev, a, &q); if (r) return r;
@@ -282,7 +282,7 @@ int32_t art_cast_spheres(ArtContext *c, const ArtSphereCast *d) {
     if ((r = check_null(who, c, d)) || (r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev))) return r;
     if (!(d->radius >= 0.0f) || d->radius == INFINITY) return invalid(who, "radius: NaN, negative or infinite");
     if ((r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n)) || (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true))) return r;
-    if (!c->built) return fail(ART_E_STATE, "art_cast_spheres: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_built(who, c))) return r;
     if (d->n == 0u) return ART_OK;
     CastArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
@@ -298,7 +298,7 @@ int32_t art_cast_crossings(ArtContext *c, const ArtRayCrossings *d) {
     if ((r = check_null(who, c, d)) || (r = cast_check(who, d->flags, d->cull_mask, d->n, d->rays_dev))) return r;
     if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
     if ((r = check_buffer(who, "cross_dev", d->cross_dev, 8, d->n))) return r;
-    if (!c->built) return fail(ART_E_STATE, "art_cast_crossings: scene not built, or changed since the build (art_scene_build)");
+    if ((r = check_built(who, c))) return r;
     if (d->n == 0u) return ART_OK;
     CastArgs a{}; RingSlot q;
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, nullptr, nullptr, a, &q); if (r) return r;

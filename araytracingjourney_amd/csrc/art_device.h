@@ -1,5 +1,5 @@
 // art_device.h -- the device helpers that more than one unit of libart compiles: vectors, the exact-math cores, the sampler, the alpha test, Ray / slab / Moller-Trumbore,
-// the launch constants and the tracers' presets.  Included by art_walk.h and art_shade.h (and through them by art_trace.hip, art_frame.hip, art_query.hip and art_sweeps.hip),
+// the launch constants and the tracers' presets.  Included by art_walk.h and art_shade.h (and through them by art_trace.hip, art_frame.hip, art_query_rays.hip, art_query_points.hip and art_sweeps.hip),
 // by art_resolve.hip and by art_present.hip.  A device function that is not forceinline is `inline` (sample_tex; the lights and Burley's diffuse term in art_shade.h), in every header of this directory.
 //
 // Built with -ffp-contract=off: every fused multiply-add below is an explicit fmaf, so the geometry stages

@@ -81,7 +81,7 @@ constexpr uint32_t kTileRingMax = 8;    // caller-owned compact tile buffers per
 int32_t ring_rewind(ArtContext *ctx);   // art_api.hip: waits for every frame in flight, then the next art_trace is launch 0 again (ring slot 0, first tile buffer)
 void set_last_error(const char *msg);   // art_api.hip: the thread's art_last_error() string, for entry points that live in other files
 
-// ---- launch wrappers (art_build.hip, art_wide.hip, art_refit.hip / art_trace.hip, art_frame.hip, art_query.hip, art_sweeps.hip, art_present.hip) ----------------------------
+// ---- launch wrappers (art_build.hip, art_wide.hip, art_refit.hip / art_trace.hip, art_frame.hip, art_query_rays.hip, art_query_points.hip, art_sweeps.hip, art_present.hip) ----------------------------
 #define HIPQ(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)   // the builders' early return of a hipError_t
 struct BuildInputs {
     const DevPrim *prims; uint32_t n_prims; const uint32_t *prim_first_tri; // device

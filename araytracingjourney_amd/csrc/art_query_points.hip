@@ -1,203 +1,9 @@
-// art_query.hip -- the device side of the queries on device buffers (gfx950): ray casts (k_cast), the first K hits (k_cast_multi), the crossings of each ray (k_cross), nearest surface points (k_closest), the K nearest
-// triangles (k_closest_multi), swept spheres (k_sweep), the triangles that touch a box (k_overlap) and those that touch a triangle (k_overlap_tris).  The casts and the sweep
-// are Sources and candidate policies of art_walk.h's pooled loop; the point, box and triangle queries, which have no ray to pool, are Sinks and walks of one loop of their own (point_trace).  What the queries share stands
-// once: at the top the ray read, the hit and miss records, the contact point, the mask test and the 4-wide node's decode (load_node4); the sorted list of both K-walks
-// (KList), which a walk fills through its leaf step's hook for a candidate's fate (step_leaf_take: one leaf step a walk); at the bottom the arguments' common fields and
-// the launch.  (The list, the leaf steps and the loop were copies once, kept apart so that no other kernel's code would move.  Compared instruction for instruction --
-// tools/kernel_diff.py -- what moves is in profiles/README.md, "one list, one hook" and "one point loop".)  art_cast.hip is their host side.
-#include "art_walk.h"
+// art_query_points.hip -- the device side of the point, box and triangle queries on device buffers (gfx950): nearest surface points (k_closest), the K nearest triangles (k_closest_multi), the triangles that
+// touch a box (k_overlap) and those that touch a triangle (k_overlap_tris), the distance from a triangle to the scene (k_closest_tris).  They have no ray to pool, so they are Sinks and walks of one loop of
+// their own (point_trace); the casts and the sweep run art_walk.h's pooled loop in art_query_rays.hip.  What the two units share stands once, in art_query.h.  art_cast.hip is their host side.
+#include "art_query.h"
 
 namespace art {
-
-// ---- what the queries share -----------------------------------------------------------------------------------------------------------------------------------
-// One ray of a cast's buffer: two 16-byte loads a lane (2 KB a wave in one piece), o.xyz tmin | d.xyz tmax.  False: a dead ray (non-finite origin or direction, NaN
-// tmax: TravBase::start's rule), which accepts nothing -- its source writes the miss record there and then, with tmax as given, and the ray never enters the pool.
-__device__ __forceinline__ bool read_ray(const float4 *rays, uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) {
-    const float4 r0 = rays[2 * (size_t)sidx], r1 = rays[2 * (size_t)sidx + 1];
-    o = mk(r0.x, r0.y, r0.z); d = mk(r1.x, r1.y, r1.z); e0 = r0.w; e1 = r1.w;
-    return ray_finite(o, d) && r1.w == r1.w;
-}
-// A record, on the device: t,u,v,0 and (primitive, triangle in the primitive) -- tri_prim names the gid's primitive (k_soup's table) and first_tri that primitive's first
-// gid; no triangle record, no host.  A miss: (x,0,0,0) and (-1,-1), x the range's end as the caller gave it.  K: anything with tuv, ids, tri_prim, first_tri.
-// (I: the index in its caller's own type, uint32_t or size_t: with a size_t parameter the compiler assigns the registers of k_cast, k_sweep and k_closest otherwise, and
-// k_cast gains an instruction)
-template <class K, class I> __device__ __forceinline__ void write_hit(const K &a, I at, uint32_t gid, float t, float u, float v) {
-    const uint32_t prim = a.tri_prim[gid];
-    a.tuv[at] = make_float4(t, u, v, 0.f);
-    a.ids[at] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
-}
-template <class K, class I> __device__ __forceinline__ void write_miss(const K &a, I at, float x) { a.tuv[at] = make_float4(x, 0.f, 0.f, 0.f); a.ids[at] = make_int2(-1, -1); }
-// the point u, v of the triangle at leaf position pos, from its record (v0 e1 e2), w = 1: what the point queries and k_sweep report beside a hit; a miss: zeros (point: may be null)
-__device__ __forceinline__ float4 contact_point(const DevTri *tris, uint32_t pos, float u, float v) {
-    const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
-    const float4 ta = tq[0], tb = tq[1], tc = tq[2];
-    return make_float4(ta.x + (u * ta.w + v * tb.z), ta.y + (u * tb.x + v * tb.w), ta.z + (u * tb.y + v * tc.x), 1.0f);
-}
-template <class K, class I> __device__ __forceinline__ void write_point_miss(const K &a, I at, float x) {
-    write_miss(a, at, x);
-    if (a.point) a.point[at] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-// does a query with this cull mask see the triangle at leaf position pos?  The masks only -- no cutoff: the test of the walks that have no alpha_cut
-__device__ __forceinline__ bool leaf_visible(const uint32_t *bits, const DevShadeTri *shade, const DevPrim *prims, uint32_t cull, uint32_t pos) {
-    if (cull == 0u) return false;
-    if (!((bits[pos >> 5] >> (pos & 31u)) & 1u)) return true;   // a leaf without the bit: mask 0xFF
-    const uint32_t prim = __float_as_uint(reinterpret_cast<const float4 *>(shade + pos)[8].z);
-    return (prim_vis(prims[prim].masked) & cull) != 0u;
-}
-// A 4-wide node as the queries' own walks (TravPoint, TravSweep, TravBox) take it apart: four bytes a plane, child i's in bits 8i.. of b (lo.x lo.y lo.z hi.x) and c
-// (hi.y hi.z); the origin and the power-of-two scales that decode them (plane = byte * s + o); the four references.  It is Trav4::step_internal's decode, which stays
-// with the kernels of the frame.  What a walk makes of a child's box is its own.  (c: the two words in use, not the uint4 -- handed on whole, k_sweep loads all four)
-struct Node4 { uint4 b; uint2 c; float ox, oy, oz, sx, sy, sz; int refs[4]; };
-__device__ __forceinline__ Node4 load_node4(const DevNode4 *__restrict__ wide, int cur) {
-    const uint4 *nq = reinterpret_cast<const uint4 *>(wide + cur);
-    uint4 a = nq[0], b = nq[1], c = nq[2], d = nq[3];
-    asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));   // the references arrive with the boxes (Trav4::step_internal)
-    return {b, make_uint2(c.x, c.y), __uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z),
-            __uint_as_float((a.w & 255u) << 23), __uint_as_float(((a.w >> 8) & 255u) << 23), __uint_as_float(((a.w >> 16) & 255u) << 23), {(int)d.x, (int)d.y, (int)d.z, (int)d.w}};
-}
-
-// Rays the CALLER made, in a device buffer (art_cast_rays, DESIGN.md 3.5: the application's own traceRayEXT), are READ.  One walk for every context, whatever ArtTuning
-// says.  Closest hits leave as records of the walk's best candidate; any-hit answers are bytes.  The order of the rays in the buffer cannot matter: a ray's record
-// depends on the ray alone.
-struct CastK {
-    const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
-    const float4 *rays; float4 *tuv; int2 *ids; uint8_t *hit;
-    uint32_t total, chunk, refill, leaf_batch;
-    uint32_t *cursors;        // 8 per-XCD chunk cursors, kCursorStride words apart (zeroed in front of the launch)
-    AlphaView alpha;          // the instances with the mask / alpha test only
-};
-static_assert(kCastCursorWords == 8u * kCursorStride, "a cast's cursor block");
-constexpr int kCastLds = 8;           // per-lane stack entries in LDS
-template <bool ANY> struct CastSource {
-    static constexpr int kFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
-    const CastK &a;
-    template <class TRAV> __device__ __forceinline__ void init(TRAV &) const {}
-    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
-        if (!has) { if (ANY) a.hit[sidx] = 0; else write_miss(a, sidx, e1); }   // a dead ray: its miss record, without a walk
-        return has;
-    }
-    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
-    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
-        if (ANY) a.hit[slot] = tr.bpos != kNoHit ? 1 : 0;
-        else if (tr.bgid != kNoHit) write_hit(a, slot, tr.bgid, tr.tbest, tr.bu, tr.bv);
-        else write_miss(a, slot, tr.r.tmax);
-    }
-};
-template <bool ANY, bool ALPHA>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cast(CastK a) { pooled_trace<kCastLds, ANY, ALPHA>(a, CastSource<ANY>{a}); }
-
-// A lane's K best candidates, which both multi walks keep (TravMulti below, TravPointMulti): up to K entries (key, u, v, gid) in ascending (key, gid), the key a t_eff or a
-// d2_eff -- in LDS, [entry][lane] like the walk stack, 16 bytes an entry, so the insertion runs on ds_read / ds_write_b128 with the entry index in a register and nothing
-// goes to scratch.  A walk's best pair (tbest | limit, bgid) is its LIMIT: (the range's end, none) until the list is full, the K-th entry's pair from then on -- boxes and
-// leaves cull against it as they cull against the best candidate of a closest walk, and a candidate enters iff it is below the limit in the total order, which is that
-// walk's comparison (its step_leaf_take makes it: K = 1 IS the closest walk).  Every triangle sits in one leaf and a walk visits a leaf at most once: no entry can arrive
-// twice, nothing is checked.  Only a candidate that would enter is put to the mask / alpha test.
-struct KList {
-    uint32_t K, cnt;   // K: 1..KMAX, wave-uniform; cnt: entries held, 0..K
-    uint4 *list;       // this lane's entry 0; entry j at list[j * kTraceBlock]
-    // hits: the kernel's __shared__ uint4[kmax * kTraceBlock].  (It is declared where each kernel had it, not in here: with one array in here for both walks, k_closest_multi's
-    // instances with a list of 4 came out five and six instructions longer and 0.4 % slower on two legs of their probe -- profiles/README.md, "one list, one hook")
-    __device__ __forceinline__ void bind(uint4 *hits, uint32_t k, uint32_t kmax) {
-        K = min(max(k, 1u), kmax); cnt = 0u; list = &hits[threadIdx.x];   // (the host launches KMAX >= K: the clamp keeps every index inside the array whatever it is handed)
-    }
-    // a candidate below the limit enters; limit / limit_gid: the walk's pair
-    __device__ __forceinline__ void enter(float key, float u, float v, uint32_t gid, float &limit, uint32_t &limit_gid) {
-        uint32_t j = min(cnt, K - 1u);   // the slot that is free: behind the last entry, or the K-th entry's, which leaves
-        while (j > 0u) {                 // entries above the candidate move up one
-            const uint4 p = list[(j - 1u) * kTraceBlock];
-            const float pk = __uint_as_float(p.x);
-            if (pk < key || (pk == key && p.w < gid)) break;
-            list[j * kTraceBlock] = p; j--;
-        }
-        list[j * kTraceBlock] = make_uint4(__float_as_uint(key), __float_as_uint(u), __float_as_uint(v), gid);
-        cnt = min(cnt + 1u, K);
-        if (cnt == K) { const uint4 e = list[(K - 1u) * kTraceBlock]; limit = __uint_as_float(e.x); limit_gid = e.w; }   // full: the K-th entry is the limit
-    }
-};
-// The first K hits of each ray, in order (art_cast_rays_multi): the third candidate policy.  The closest walk keeps ONE best candidate; this one hands it to
-// the list, through the hook TravBase::step_leaf_take has for a candidate's fate -- the leaf step, its slab cull and the box tests of Trav4 are the closest walk's own.
-template <int KMAX, int LDSN, bool ALPHA> struct TravMulti : Trav4<false, LDSN, ALPHA>, KList {
-    __device__ __forceinline__ void bind(uint32_t k) {
-        __shared__ uint4 hits[KMAX * kTraceBlock];
-        KList::bind(hits, k, KMAX);
-    }
-    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
-        return this->step_leaf_take(tris, lds, ovf, av, [this](float teff, float u, float v, uint32_t, uint32_t gid) { enter(teff, u, v, gid, this->tbest, this->bgid); });
-    }
-};
-struct CastMultiK : CastK { uint8_t *count; uint32_t max_hits; };   // tuv / ids: max_hits records a ray, ray-major; count: a byte a ray, or null
-template <int KMAX> struct CastMultiSource {
-    static constexpr int kFields = 12;   // CastSource's
-    const CastMultiK &a;
-    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.bind(a.max_hits); }
-    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
-        if (!has) {                // a dead ray: K miss records, no walk
-            const size_t base = (size_t)sidx * a.max_hits;
-            for (uint32_t j = 0; j < a.max_hits; j++) write_miss(a, base + j, e1);
-            if (a.count) a.count[sidx] = 0;
-        }
-        return has;
-    }
-    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; tr.cnt = 0u; }
-    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
-        const size_t base = (size_t)slot * tr.K;
-        for (uint32_t j = 0; j < tr.K; j++) {
-            if (j < tr.cnt) {
-                const uint4 e = tr.list[j * kTraceBlock];
-                write_hit(a, base + j, e.w, __uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z));
-            } else write_miss(a, base + j, tr.r.tmax);
-        }
-        if (a.count) a.count[slot] = (uint8_t)tr.cnt;
-    }
-};
-// KMAX 4 | 8: the list is KMAX KB of LDS a wave on top of the 5 KB of stack and pool, and LDS is what bounds the waves a CU holds -- small K keeps more resident.
-// (waves_per_eu: LDS allows four waves a SIMD with KMAX 4 and three with KMAX 8, so the registers of that many are the kernel's to use)
-template <int KMAX, bool ALPHA>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMAX > 4 ? 3 : 4, 4))) void k_cast_multi(CastMultiK a) {
-    pooled_trace<kCastLds, false, ALPHA, CastMultiK, CastMultiSource<KMAX>, TravMulti<KMAX, kCastLds, ALPHA>>(a, CastMultiSource<KMAX>{a});
-}
-
-// The surfaces each ray enters and leaves (art_cast_crossings): the fourth candidate policy.  Nothing orders or shrinks: tbest stays the range's end for
-// the whole walk, so Trav4's box tests and the triangle's slab cull against [tmin, tmax] alone and every triangle accept() takes is met once.  Two counters a lane, no list:
-// LDS is the walk stack and the pool, as k_cast's.  The leaf step is a sibling of TravBase::step_leaf_take -- that one's hook has no det -- around moller_trumbore_det,
-// whose det is the one that accepted the candidate.  EVERY candidate is put to the mask / alpha test (each one counts; there is no "would win").
-template <int LDSN, bool ALPHA> struct TravCross : Trav4<false, LDSN, ALPHA> {
-    uint32_t n_in, n_out;   // det > 0: against the winding normal, an entry; det < 0: along it, an exit
-    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
-        const uint32_t pos = (uint32_t)~this->cur;
-        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
-        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
-        float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
-        asm volatile("" : "+v"(td.x), "+v"(td.y), "+v"(td.z), "+v"(td.w), "+v"(tc.y), "+v"(tc.z), "+v"(tc.w));   // the box arrives with the vertices (TravBase::step_leaf_take)
-        float te, t, u, v, det;
-        if (moller_trumbore_det(this->r, mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), t, u, v, det)) {
-            if (slab(this->r, tc.y, tc.z, tc.w, td.x, td.y, td.z, this->tbest, te)) {
-                if (!ALPHA || !alpha_cut(av, pos, u, v)) { if (det > 0.0f) n_in++; else n_out++; }   // (alpha_cut: the masks first, then the cutoff)
-            }
-        }
-        return this->pop(lds, ovf);
-    }
-};
-struct CrossK : CastK { uint2 *cross; };   // cross: (entries, exits) a ray; tuv / ids / hit are not used
-struct CrossSource {
-    static constexpr int kFields = 12;   // CastSource's
-    const CrossK &a;
-    template <class TRAV> __device__ __forceinline__ void init(TRAV &) const {}
-    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
-        if (!has) a.cross[sidx] = make_uint2(0u, 0u);   // a dead ray crosses nothing: its record, without a walk
-        return has;
-    }
-    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; tr.n_in = 0u; tr.n_out = 0u; }
-    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const { a.cross[slot] = make_uint2(tr.n_in, tr.n_out); }
-};
-// (waves_per_eu 8: k_cast's walk with two counters for the best candidate's five fields -- DESIGN.md 3.12's table has the compiler's figures)
-template <bool ALPHA>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cross(CrossK a) {
-    pooled_trace<kCastLds, false, ALPHA, CrossK, CrossSource, TravCross<kCastLds, ALPHA>>(a, CrossSource{a});
-}
 
 // ---- nearest surface points (art_closest_points) ------------------------------------------------------------------------------------------------
 // A query is a point and a radius, not a ray: the pooled loop's ray fields (inv, ood, tmin / tmax, the slab of every policy) have no meaning for it, and a query is ONE
@@ -206,44 +12,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
 // only ever falls, and an entry whose box has fallen behind it by the time it is popped is dropped without a fetch.  Eight pairs a lane in LDS (4 KB a wave: 40 waves
 // fit a CU's 160 KB, more than its 32 slots); deeper entries spill to scratch as references alone.
 // No fmaf in anything that decides a record: d2_tri, box_d2 of a triangle and the point are restated by numpy float32 bit for bit (tests/np_closest.py).
-__device__ __forceinline__ float dotp(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 crossp(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-// |w - (u e1 + v e2)|^2: the one distance every feature is measured by, and the point art_closest_points reports
-__device__ __forceinline__ float tri_uv_d2(V3 w, V3 e1, V3 e2, float u, float v) {
-    const float dx = w.x - (u * e1.x + v * e2.x), dy = w.y - (u * e1.y + v * e2.y), dz = w.z - (u * e1.z + v * e2.z);
-    return (dx * dx + dy * dy) + dz * dz;
-}
-// the parameter of the point of segment {s e, 0 <= s <= 1} nearest to w; a segment of no length is its first end point
-__device__ __forceinline__ float seg_param(V3 w, V3 e) {
-    const float den = dotp(e, e);
-    float s = dotp(w, e) / (den > 0.0f ? den : 1.0f);
-    s = den > 0.0f ? s : 0.0f;
-    s = s > 0.0f ? s : 0.0f;   // (selects, not fmaxf / fminf: a NaN becomes 0 here and in numpy.where alike)
-    return s < 1.0f ? s : 1.0f;
-}
-// d2_tri of DESIGN.md 3.8: the face where the projection falls inside it, then the edges v0v1, v0v2, v1v2 clamped; the first of the smallest wins.  +inf: no feature gave
-// a number (a triangle nowhere, a non-finite one).  u, v: barycentrics of vertices 1 and 2 of the winning point.
-__device__ __forceinline__ float tri_closest(V3 w, V3 e1, V3 e2, float &u, float &v) {
-    float best = INFINITY; u = 0.0f; v = 0.0f;
-    const V3 n = crossp(e1, e2);
-    const float nn = dotp(n, n), den = nn > 0.0f ? nn : 1.0f;
-    const float fu = dotp(crossp(w, e2), n) / den, fv = dotp(crossp(e1, w), n) / den;
-    if ((nn > 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f)) {
-        const float d = tri_uv_d2(w, e1, e2, fu, fv);
-        if (d < best) { best = d; u = fu; v = fv; }
-    }
-    const float sa = seg_param(w, e1), da = tri_uv_d2(w, e1, e2, sa, 0.0f);
-    if (da < best) { best = da; u = sa; v = 0.0f; }
-    const float sb = seg_param(w, e2), db = tri_uv_d2(w, e1, e2, 0.0f, sb);
-    if (db < best) { best = db; u = 0.0f; v = sb; }
-    const float sc = seg_param(w - e1, e2 - e1), uc = 1.0f - sc, dc = tri_uv_d2(w, e1, e2, uc, sc);
-    if (dc < best) { best = dc; u = uc; v = sc; }
-    return best;
-}
-__device__ __forceinline__ float box_d2(V3 p, float lx, float ly, float lz, float hx, float hy, float hz) {
-    const float ex = fmaxf(fmaxf(lx - p.x, p.x - hx), 0.0f), ey = fmaxf(fmaxf(ly - p.y, p.y - hy), 0.0f), ez = fmaxf(fmaxf(lz - p.z, p.z - hz), 0.0f);
-    return (ex * ex + ey * ey) + ez * ez;
-}
 struct ClosestK {
     const DevNode4 *wide; const DevTri *tris; const uint32_t *tri_prim, *first_tri;
     const float4 *points; float4 *tuv; int2 *ids; float4 *point;   // tuv: d,u,v,0; point: may be null
@@ -296,6 +64,7 @@ template <bool FILTER> struct TravPoint {
         return step_internal_by(wide, lds, ovf, [this](float lx, float ly, float lz, float hx, float hy, float hz) { return box_d2(p, lx, ly, lz, hx, hy, hz); });
     }
     // the node step for any query that has a squared distance to a box (dist: the point's box_d2 here, the query box's in TravTriDist)
+    // (the decode of a child's six planes stands here and in TravBox::step_internal: one copy, as a struct returned or as out-parameters, moves k_closest* and k_overlap* -- profiles/README.md, "two query units")
     template <class DIST> __device__ __forceinline__ bool step_internal_by(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf, const DIST &dist) {
         const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, cur);
         float d2[4]; bool h[4];
@@ -379,30 +148,29 @@ __device__ __forceinline__ void point_trace(const ARGS &a, STACK *stack, const S
         if (done) { active = false; sink.finish(tr, slot, K, radius); }
     }
 }
+__device__ __forceinline__ float zero3(const float4 &q) { return (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z; }   // 0 for three finite coordinates, NaN otherwise: a fetch sums one a vertex, in its own association
 // a point query: xyz and the radius in w.  False: a dead one (a non-finite point, a NaN or negative radius), which gets its miss records without a walk
 __device__ __forceinline__ bool read_point(const float4 *points, uint32_t sidx, float4 &q) {
     q = points[sidx];
-    const float z = (0.0f * q.x + 0.0f * q.y) + 0.0f * q.z;   // 0 for a finite point, NaN otherwise
-    return z == 0.0f && q.w == q.w && !(q.w < 0.0f);
+    return zero3(q) == 0.0f && q.w == q.w && !(q.w < 0.0f);
+}
+// the two walks that keep ONE best candidate (TravPoint, TravTriDist): the start state for radius r, and the finished query's hit record with its optional point
+template <class TRAV> __device__ __forceinline__ void best_start(TRAV &tr, float r) { tr.limit = r * r; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0; }
+template <class K, class TRAV> __device__ __forceinline__ void best_write(const K &a, const TRAV &tr, uint32_t slot) {
+    write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
+    if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
 }
 struct ClosestSink {
     const ClosestK &a;
     template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &) const { return 1u; }
     template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t, float &radius) const {
         float4 q;
-        if (read_point(a.points, sidx, q)) {
-            tr.p = mk(q.x, q.y, q.z); tr.limit = q.w * q.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
-            radius = q.w;
-            return true;
-        }
+        if (read_point(a.points, sidx, q)) { tr.p = mk(q.x, q.y, q.z); best_start(tr, q.w); radius = q.w; return true; }
         write_point_miss(a, sidx, q.w);
         return false;
     }
     template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t, float radius) const {
-        if (tr.bgid != kNoHit) {
-            write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
-            if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
-        } else write_point_miss(a, slot, radius);
+        if (tr.bgid != kNoHit) best_write(a, tr, slot); else write_point_miss(a, slot, radius);
     }
 };
 template <bool FILTER>
@@ -460,135 +228,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(KMA
     __shared__ int2 stack[kClosestLds * kTraceBlock];
     __shared__ uint4 hits[KMAX * kTraceBlock];
     point_trace<TravPointMulti<FILTER>>(a, stack, ClosestMultiSink<KMAX>{a, hits});
-}
-
-// ---- a ball along a ray (art_cast_spheres) --------------------------------------------------------------------------------------------------------
-// The rays are the casts' -- 32 bytes a ray, everything ray_init makes of them -- so the loop is pooled_trace with a fourth candidate policy.  The ball's radius is the
-// same for every ray of a launch: boxes grow by it (one subtraction / addition a plane, before the slab), and a triangle answers with the first time the ball's centre is
-// within it of the triangle: at tmin already (S), or where it enters the slab round the face, a cylinder round an edge or a sphere round a vertex.
-// No fmaf in anything that decides a record but the slab's: tests/np_sweep.py restates every operation in numpy float32.
-struct SweepK : CastK { float4 *point; float radius; };   // point: may be null
-// the ENTRY root of A t^2 + 2 B t + Cq = 0
-__device__ __forceinline__ bool sweep_root(float A, float B, float Cq, float &t) {
-    const float disc = B * B - A * Cq;
-    t = (-B - sqrtf(disc >= 0.0f ? disc : 0.0f)) / (A > 0.0f ? A : 1.0f);
-    return (A > 0.0f) & (disc >= 0.0f);
-}
-// the cylinder of radius sqrt(rr) round the line {m + s e}: the direction of the edge is projected out of m and d before the quadratic (second order in lengths)
-__device__ __forceinline__ bool sweep_edge(V3 m, V3 e, V3 d, float rr, float &t, float &s) {
-    const float ee = dotp(e, e), q = ee > 0.0f ? ee : 1.0f, qm = dotp(m, e) / q, qd = dotp(d, e) / q;
-    const V3 mp = mk(m.x - qm * e.x, m.y - qm * e.y, m.z - qm * e.z), dp = mk(d.x - qd * e.x, d.y - qd * e.y, d.z - qd * e.z);
-    const bool ok = sweep_root(dotp(dp, dp), dotp(mp, dp), dotp(mp, mp) - rr, t);
-    s = qm + t * qd;
-    return (ee > 0.0f) & ok & (s >= 0.0f) & (s <= 1.0f);
-}
-__device__ __forceinline__ void sweep_take(bool ok, float t, float u, float v, float tmin, float tmax, float &bt, float &bu, float &bv) {
-    if (ok & (t >= tmin) & (t < tmax) & (t < bt)) { bt = t; bu = u; bv = v; }   // (a NaN never wins)
-}
-// t_tri of DESIGN.md 3.9 for w0 = o - v0: the smallest t in [tmin, tmax) among S, F, E01, E02, E12, V0, V1, V2, the first of equals; +inf: none.  u, v: its barycentrics
-__device__ __forceinline__ float tri_sweep(V3 w0, V3 d, V3 e1, V3 e2, float rho, float tmin, float tmax, float &u, float &v) {
-    float bt = INFINITY, t, s; u = 0.0f; v = 0.0f;
-    const float rr = rho * rho, dd = dotp(d, d);
-    {   // S: the ball touches the triangle where it starts
-        float su, sv;
-        const float d2 = tri_closest(mk(w0.x + tmin * d.x, w0.y + tmin * d.y, w0.z + tmin * d.z), e1, e2, su, sv);
-        sweep_take(d2 <= rr, tmin, su, sv, tmin, tmax, bt, u, v);
-    }
-    {   // F: the centre reaches the plane at distance rho on its own side, above the face
-        const V3 n = crossp(e1, e2);
-        const float nn = dotp(n, n), h = dotp(n, w0), nd = dotp(n, d);
-        float off = rho * sqrtf(nn); off = h >= 0.0f ? off : -off;
-        t = (off - h) / (nd != 0.0f ? nd : 1.0f);
-        const V3 w = mk(w0.x + t * d.x, w0.y + t * d.y, w0.z + t * d.z);
-        const float den = nn > 0.0f ? nn : 1.0f, fu = dotp(crossp(w, e2), n) / den, fv = dotp(crossp(e1, w), n) / den;
-        sweep_take((nn > 0.0f) & (nd != 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f), t, fu, fv, tmin, tmax, bt, u, v);
-    }
-    const V3 w1 = w0 - e1, w2 = w0 - e2;
-    bool ok = sweep_edge(w0, e1, d, rr, t, s); sweep_take(ok, t, s, 0.0f, tmin, tmax, bt, u, v);
-    ok = sweep_edge(w0, e2, d, rr, t, s); sweep_take(ok, t, 0.0f, s, tmin, tmax, bt, u, v);
-    ok = sweep_edge(w1, e2 - e1, d, rr, t, s); sweep_take(ok, t, 1.0f - s, s, tmin, tmax, bt, u, v);
-    ok = sweep_root(dd, dotp(w0, d), dotp(w0, w0) - rr, t); sweep_take(ok, t, 0.0f, 0.0f, tmin, tmax, bt, u, v);
-    ok = sweep_root(dd, dotp(w1, d), dotp(w1, w1) - rr, t); sweep_take(ok, t, 1.0f, 0.0f, tmin, tmax, bt, u, v);
-    ok = sweep_root(dd, dotp(w2, d), dotp(w2, w2) - rr, t); sweep_take(ok, t, 0.0f, 1.0f, tmin, tmax, bt, u, v);
-    return bt;
-}
-// The candidate policy: TravBase's state, stack and tie rule; boxes inflated by rho.  FILTER: the visibility masks (leaf_visible; alpha cutoffs are not tested)
-template <int LDSN, bool FILTER> struct TravSweep : TravBase<false, kOvfStack4 + (kLdsStack - LDSN), LDSN, false> {
-    using Nodes = const DevNode4 *;
-    float rho;
-    // the triangle's own box, inflated, against tbest first -- an exact cull: a candidate's t_eff is at least its box's entry and at least tmin -- then the eight features
-    __device__ __forceinline__ bool step_leaf(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av) {
-        const uint32_t pos = (uint32_t)~this->cur;
-        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf)
-        const float4 *tq = reinterpret_cast<const float4 *>(tris + pos);
-        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
-        const Ray &r = this->r;
-        float te;
-        if (slab(r, tc.y - rho, tc.z - rho, tc.w - rho, td.x + rho, td.y + rho, td.z + rho, this->tbest, te)) {
-            float u, v;
-            const float tt = tri_sweep(r.o - mk(ta.x, ta.y, ta.z), r.d, mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), rho, r.tmin, r.tmax, u, v);
-            if (tt < INFINITY) {
-                const float teff = fmaxf(tt, te);
-                const uint32_t gid = __float_as_uint(td.w);
-                if ((teff < this->tbest || (teff == this->tbest && gid < this->bgid)) && (!FILTER || leaf_visible(av.bits, av.shade, av.prims, av.cull, pos))) { this->tbest = teff; this->bu = u; this->bv = v; this->bpos = pos; this->bgid = gid; }
-            }
-        }
-        return this->pop(lds, ovf);
-    }
-    // Trav4's sign-selected slab with each child's near plane moved out and its far plane moved out by rho.  An absent child or a masked subtree carries an inverted byte box
-    // (255 / 0): "left before it is entered" no longer holds once the planes have moved, so it is skipped by TravPoint's explicit test
-    __device__ __forceinline__ bool step_internal(Nodes wide, int *lds, int *ovf) {
-        const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, this->cur);
-        float te[4]; bool h[4];
-        const Ray &r = this->r;
-        const bool ngx = r.inv.x < 0.0f, ngy = r.inv.y < 0.0f, ngz = r.inv.z < 0.0f;
-        const uint32_t nxw = ngx ? b.w : b.x, fxw = ngx ? b.x : b.w, nyw = ngy ? c.x : b.y, fyw = ngy ? b.y : c.x, nzw = ngz ? c.y : b.z, fzw = ngz ? b.z : c.y;
-        const float px = ngx ? rho : -rho, py = ngy ? rho : -rho, pz = ngz ? rho : -rho;   // what the near plane moves by (lo - rho is lo + (-rho), bit for bit); the far plane by the opposite
-        const float lim = this->tbest;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float tnx = fmaf(fmaf((float)((nxw >> (8 * i)) & 255u), sx, ox) + px, r.inv.x, -r.ood.x), tfx = fmaf(fmaf((float)((fxw >> (8 * i)) & 255u), sx, ox) - px, r.inv.x, -r.ood.x);
-            const float tny = fmaf(fmaf((float)((nyw >> (8 * i)) & 255u), sy, oy) + py, r.inv.y, -r.ood.y), tfy = fmaf(fmaf((float)((fyw >> (8 * i)) & 255u), sy, oy) - py, r.inv.y, -r.ood.y);
-            const float tnz = fmaf(fmaf((float)((nzw >> (8 * i)) & 255u), sz, oz) + pz, r.inv.z, -r.ood.z), tfz = fmaf(fmaf((float)((fzw >> (8 * i)) & 255u), sz, oz) - pz, r.inv.z, -r.ood.z);
-            const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
-            te[i] = tn;
-            h[i] = (((b.x >> (8 * i)) & 255u) <= ((b.w >> (8 * i)) & 255u)) & (fmaxf(tn, r.tmin) <= fminf(tf, lim));
-        }
-        float tn = 3.0e38f; int ni = -1;   // on with the nearest child, the others wait: the order is speed only
-#pragma unroll
-        for (int i = 0; i < 4; i++) if (h[i] && te[i] < tn) { tn = te[i]; ni = i; }
-        if (ni < 0) {   // (a child entered at 3e38 or beyond -- a structure nowhere -- is still a child: the first of them)
-#pragma unroll
-            for (int i = 3; i >= 0; i--) if (h[i]) ni = i;
-            if (ni < 0) return this->pop(lds, ovf);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) if (h[i] && i != ni) this->push(refs[i], lds, ovf);
-        this->cur = ni == 0 ? refs[0] : (ni == 1 ? refs[1] : (ni == 2 ? refs[2] : refs[3]));
-        return false;
-    }
-};
-struct SweepSource {
-    static constexpr int kFields = 12;   // o.xyz d.xyz inv.xyz tmin tmax slot
-    const SweepK &a;
-    template <class TRAV> __device__ __forceinline__ void init(TRAV &tr) const { tr.rho = a.radius; }   // the same for every ray
-    __device__ __forceinline__ bool fetch(uint32_t sidx, V3 &o, V3 &d, float &e0, float &e1) const {
-        const bool has = read_ray(a.rays, sidx, o, d, e0, e1);
-        if (!has) write_point_miss(a, sidx, e1);   // a dead ray: its miss record, without a walk
-        return has;
-    }
-    template <class TRAV> __device__ __forceinline__ void begin(TRAV &tr, float e0, float e1) const { tr.r.tmin = e0; tr.r.tmax = e1; tr.cur = 0; }
-    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot) const {
-        if (tr.bgid != kNoHit) {
-            write_hit(a, slot, tr.bgid, tr.tbest, tr.bu, tr.bv);
-            if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
-        } else write_point_miss(a, slot, tr.r.tmax);
-    }
-};
-// 6 waves a SIMD: the eight-feature test holds 79 VGPRs without a spill; at 8 waves (64) the compiler spills two dozen of them to scratch, at 4 it uses no more than at 6
-template <bool FILTER>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_sweep(SweepK a) {
-    pooled_trace<kCastLds, false, FILTER, SweepK, SweepSource, TravSweep<kCastLds, FILTER>>(a, SweepSource{a});
 }
 
 // ---- the triangles that touch a box (art_overlap_boxes) -----------------------------------------------------------------------------------------------
@@ -661,14 +300,15 @@ template <bool ANY, bool FILTER> struct TravBox {
         }
         list[j * kTraceBlock] = gid;
     }
-    // the triangle in `cur`: conditions 1 and 2 on its own box, then the separating axes, then the masks; ANY is finished by its first candidate
-    __device__ __forceinline__ bool step_leaf(const OverlapK &a, int *lds, int *ovf) {
+    // the triangle in `cur`: conditions 1 and 2 on its own box, then the separating axes -- touch(v0, e1, e2): the query's own pair test -- then the masks; ANY is finished by its first candidate
+    // (the load of the leaf's record, ta tb tc td, stands in every leaf step of this unit: a helper for it moves k_overlap* and k_closest_tris -- profiles/README.md, "two query units")
+    template <class TOUCH> __device__ __forceinline__ bool step_leaf_if(const OverlapK &a, int *lds, int *ovf, const TOUCH &touch) {
         const uint32_t pos = (uint32_t)~cur;
         if (pos == 0x7FFFFFFFu) return pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
         const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
         const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
         const bool meets = (tc.y < 3.0e38f) & (tc.y <= hi.x) & (lo.x <= td.x) & (tc.z <= hi.y) & (lo.y <= td.y) & (tc.w <= hi.z) & (lo.z <= td.z);
-        if (meets && tri_box_overlap(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), lo, hi) &&
+        if (meets && touch(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x)) &&
             (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
             if (ANY) { cnt = 1u; return true; }
             enter(__float_as_uint(td.w));
@@ -676,13 +316,14 @@ template <bool ANY, bool FILTER> struct TravBox {
         }
         return pop(lds, ovf);
     }
+    __device__ __forceinline__ bool step_leaf(const OverlapK &a, int *lds, int *ovf) { return step_leaf_if(a, lds, ovf, [this](V3 v0, V3 e1, V3 e2) { return tri_box_overlap(v0, e1, e2, lo, hi); }); }
     // Four box-against-box tests.  A child is skipped iff a comparison says its box misses the query's, or its box is inverted
     // (255 / 0: absent or masked); on with the first that stays, the others wait.  (The order is speed only: nothing here shrinks)
     __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int *lds, int *ovf) {
         const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, cur);
         bool h[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < 4; i++) {   // (the decode is TravPoint::step_internal_by's, and a copy of it: see there)
             const uint32_t lxq = (b.x >> (8 * i)) & 255u, hxq = (b.w >> (8 * i)) & 255u;
             const float lx = fmaf((float)lxq, sx, ox), hx = fmaf((float)hxq, sx, ox);
             const float ly = fmaf((float)((b.y >> (8 * i)) & 255u), sy, oy), hy = fmaf((float)((c.x >> (8 * i)) & 255u), sy, oy);
@@ -708,19 +349,22 @@ template <bool ANY, int KMAX> struct OverlapSink {
         tr.list = &gids[threadIdx.x];
         return tr.K;
     }
-    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &) const {
-        const float4 q0 = a.boxes[2 * (size_t)sidx], q1 = a.boxes[2 * (size_t)sidx + 1];
-        const float z = ((0.0f * q0.x + 0.0f * q0.y) + 0.0f * q0.z) + ((0.0f * q1.x + 0.0f * q1.y) + 0.0f * q1.z);   // 0 for six finite coordinates, NaN otherwise
-        if (z == 0.0f && q0.x <= q1.x && q0.y <= q1.y && q0.z <= q1.z) {
-            tr.lo = mk(q0.x, q0.y, q0.z); tr.hi = mk(q1.x, q1.y, q1.z); tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
-            return true;
-        }
-        if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate, lo > hi on an axis): its answer, without a walk
+    __device__ __forceinline__ void dead(uint32_t sidx, uint32_t K) const {   // a dead query's answer, without a walk: the ANY byte, or K (-1, -1) records and the count
+        if (ANY) a.hit[sidx] = 0;
         else {
             const size_t base = (size_t)sidx * K;
             for (uint32_t j = 0; j < K; j++) a.ids[base + j] = make_int2(-1, -1);
             if (a.count) a.count[sidx] = 0u;
         }
+    }
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &) const {
+        const float4 q0 = a.boxes[2 * (size_t)sidx], q1 = a.boxes[2 * (size_t)sidx + 1];
+        const float z = zero3(q0) + zero3(q1);   // 0 for six finite coordinates, NaN otherwise
+        if (z == 0.0f && q0.x <= q1.x && q0.y <= q1.y && q0.z <= q1.z) {
+            tr.lo = mk(q0.x, q0.y, q0.z); tr.hi = mk(q1.x, q1.y, q1.z); tr.cnt = 0u; tr.cur = 0; tr.sp = 0;
+            return true;
+        }
+        dead(sidx, K);   // a non-finite coordinate, lo > hi on an axis
         return false;
     }
     template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t K, float) const {
@@ -728,7 +372,7 @@ template <bool ANY, int KMAX> struct OverlapSink {
         else {
             const size_t base = (size_t)slot * K;
             for (uint32_t j = 0; j < K; j++) {
-                if (j < tr.cnt) {
+                if (j < tr.cnt) {   // (write_hit's gid -> (primitive, triangle), and a copy of it: one helper for both moves instructions in sixteen instances -- profiles/README.md, "two query units")
                     const uint32_t gid = tr.list[j * kTraceBlock], prim = a.tri_prim[gid];
                     a.ids[base + j] = make_int2((int)prim, (int)(gid - a.first_tri[prim]));
                 } else a.ids[base + j] = make_int2(-1, -1);
@@ -782,31 +426,16 @@ __device__ __forceinline__ bool tri_tri_overlap(V3 v0, V3 e1, V3 e2, V3 q0, V3 q
     for (int j = 0; j < 3; j++) s |= tri_axis_separates(crossp(m, g[j]), e1, e2, a0, a1, a2);
     return !s;
 }
-// TravBox with the query's vertices beside its box (lo, hi: qlo, qhi) and a leaf step of its own; push, pop, enter and step_internal are TravBox's
+// TravBox with the query's vertices beside its box (lo, hi: qlo, qhi) and a pair test of its own in the leaf step; push, pop, enter and step_internal are TravBox's
 template <bool ANY, bool FILTER> struct TravTri : TravBox<ANY, FILTER> {
     V3 q0, q1, q2;
-    // the triangle in `cur`: conditions 1 and 2 on its own box, then the separating axes, then the masks; ANY is finished by its first candidate
-    __device__ __forceinline__ bool step_leaf(const TriOverlapK &a, int *lds, int *ovf) {
-        const uint32_t pos = (uint32_t)~this->cur;
-        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
-        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
-        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
-        const V3 &lo = this->lo, &hi = this->hi;
-        const bool meets = (tc.y < 3.0e38f) & (tc.y <= hi.x) & (lo.x <= td.x) & (tc.z <= hi.y) & (lo.y <= td.y) & (tc.w <= hi.z) & (lo.z <= td.z);
-        if (meets && tri_tri_overlap(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), q0, q1, q2) &&
-            (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
-            if (ANY) { this->cnt = 1u; return true; }
-            this->enter(__float_as_uint(td.w));
-            this->cnt++;
-        }
-        return this->pop(lds, ovf);
-    }
+    __device__ __forceinline__ bool step_leaf(const TriOverlapK &a, int *lds, int *ovf) { return this->step_leaf_if(a, lds, ovf, [this](V3 v0, V3 e1, V3 e2) { return tri_tri_overlap(v0, e1, e2, q0, q1, q2); }); }
 };
 // a query triangle into a walk that has q0, q1, q2, lo, hi: three 16-byte loads, the vertices and their box [qlo, qhi]; w3: word 3 as given (art_closest_triangles'
 // radius; the overlap query does not read it).  False: a dead query (a non-finite coordinate among the nine), whose walk state is left as it was
 template <class TRAV> __device__ __forceinline__ bool read_tri(const float4 *qtris, uint32_t sidx, TRAV &tr, float &w3) {
     const float4 r0 = qtris[3 * (size_t)sidx], r1 = qtris[3 * (size_t)sidx + 1], r2 = qtris[3 * (size_t)sidx + 2];
-    const float z = (((0.0f * r0.x + 0.0f * r0.y) + 0.0f * r0.z) + ((0.0f * r1.x + 0.0f * r1.y) + 0.0f * r1.z)) + ((0.0f * r2.x + 0.0f * r2.y) + 0.0f * r2.z);   // 0 for nine finite coordinates, NaN otherwise
+    const float z = (zero3(r0) + zero3(r1)) + zero3(r2);   // 0 for nine finite coordinates, NaN otherwise
     w3 = r0.w;
     if (z == 0.0f) {
         V3 mn = mk(r0.x, r0.y, r0.z), mx = mn;   // qlo, qhi: two selects an axis from the first vertex
@@ -820,19 +449,13 @@ template <class TRAV> __device__ __forceinline__ bool read_tri(const float4 *qtr
     }
     return false;
 }
-// OverlapSink with the fetch of a triangle: init and finish are the box query's
+// OverlapSink with the fetch of a triangle: init, finish and a dead query's answer are the box query's
 template <bool ANY, int KMAX> struct TriSink : OverlapSink<ANY, KMAX> {
     const float4 *qtris;
     template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t K, float &) const {
         float w3;
         if (read_tri(qtris, sidx, tr, w3)) { tr.cnt = 0u; tr.cur = 0; tr.sp = 0; return true; }
-        const OverlapK &a = this->a;
-        if (ANY) a.hit[sidx] = 0;   // a dead query (a non-finite coordinate): its answer, without a walk
-        else {
-            const size_t base = (size_t)sidx * K;
-            for (uint32_t j = 0; j < K; j++) a.ids[base + j] = make_int2(-1, -1);
-            if (a.count) a.count[sidx] = 0u;
-        }
+        this->dead(sidx, K);   // a non-finite coordinate
         return false;
     }
 };
@@ -956,18 +579,13 @@ struct TriDistanceSink {
     template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &) const { return 1u; }
     template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t, float &radius) const {
         float r;
-        if (read_tri(a.qtris, sidx, tr, r) && r == r && !(r < 0.0f)) {   // a NaN or negative radius: read_point's rule
-            tr.limit = r * r; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
-            radius = r;
-            return true;
-        }
+        if (read_tri(a.qtris, sidx, tr, r) && r == r && !(r < 0.0f)) { best_start(tr, r); radius = r; return true; }   // a NaN or negative radius: read_point's rule
         miss(sidx, r);
         return false;
     }
     template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t, float radius) const {
         if (tr.bgid != kNoHit) {
-            write_hit(a, slot, tr.bgid, sqrtf(tr.limit), tr.bu, tr.bv);
-            if (a.point) a.point[slot] = contact_point(a.tris, tr.bpos, tr.bu, tr.bv);
+            best_write(a, tr, slot);
             if (a.qpoint) {
                 const float s = tr.bs, t = tr.bt;
                 const V3 g1 = tr.q1 - tr.q0, g2 = tr.q2 - tr.q0;
@@ -984,45 +602,16 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(4, 
     point_trace<TravTriDist<FILTER>>(a, stack, TriDistanceSink{a});
 }
 
-// The launch shape of every query: {chunk, refill, blocks, leaf_batch} as for the AO launch, whose shape the kernels have -- a query is throughput-bound like it -- with
-// the context's ArtTuning overrides.  query_fill: the fields every kernel's arguments share (cast_fill, closest_fill: with those of the casts, of the point queries);
-// launch_query: one instance, chosen by its caller, on that shape.
-static Tune query_tune(const QueryArgs &c) { return tune_over(Tune{256, kPoolTake, 2048, 8}, c.tune); }
-template <class K> static K query_fill(const QueryArgs &c) {
-    const Tune t = query_tune(c);
-    K a{};
-    a.wide = c.wide; a.tris = c.tris; a.tri_prim = c.tri_prim; a.first_tri = c.first_tri; a.tuv = c.tuv; a.ids = c.ids;
-    a.total = c.n; a.chunk = t.chunk; a.refill = t.refill; a.leaf_batch = t.leaf_batch; a.cursors = c.cursors;
-    return a;
-}
-template <class K> static K cast_fill(const CastArgs &c) {
-    K a = query_fill<K>(c);
-    a.rays = c.rays; a.alpha = AlphaView{c.alpha_bits, c.shade, c.prims, c.tex_pool, c.cull};
-    return a;
-}
+template <class K> static void mask_fill(K &a, const QueryArgs &c) { a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull; }   // the four fields of every FILTER instance
 template <class K> static K closest_fill(const ClosestArgs &c) {
     K a = query_fill<K>(c);
-    a.points = c.points; a.point = c.point; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    a.points = c.points; a.point = c.point; mask_fill(a, c);
     return a;
 }
-template <class K> static void launch_query(void (*kernel)(K), const K &a, const QueryArgs &c, hipStream_t s) {
-    if (c.n) kernel<<<persistent_blocks(c.n, query_tune(c)), kTraceBlock, 0, s>>>(a);
-}
-
-void launch_cast(const CastArgs &c, hipStream_t s) {
-    if (c.kind == CastKind::Sweep) {          // the filtered instance tests masks, never a cutoff
-        SweepK a = cast_fill<SweepK>(c); a.point = c.point; a.radius = c.radius;
-        launch_query(c.filter ? k_sweep<true> : k_sweep<false>, a, c, s);
-    } else if (c.kind == CastKind::Crossings) {
-        CrossK a = cast_fill<CrossK>(c); a.cross = c.cross;
-        launch_query(c.filter ? k_cross<true> : k_cross<false>, a, c, s);
-    } else if (c.kind == CastKind::Multi) {   // the instance with the smallest list that holds K
-        CastMultiK a = cast_fill<CastMultiK>(c); a.count = c.count; a.max_hits = c.max_hits;
-        launch_query(c.max_hits <= 4u ? (c.filter ? k_cast_multi<4, true> : k_cast_multi<4, false>) : (c.filter ? k_cast_multi<8, true> : k_cast_multi<8, false>), a, c, s);
-    } else {
-        CastK a = cast_fill<CastK>(c); a.hit = c.hit;
-        launch_query(c.kind == CastKind::Any ? (c.filter ? k_cast<true, true> : k_cast<true, false>) : (c.filter ? k_cast<false, true> : k_cast<false, false>), a, c, s);
-    }
+template <class K> static K overlap_fill(const OverlapArgs &c) {
+    K a = query_fill<K>(c);
+    a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; mask_fill(a, c);
+    return a;
 }
 void launch_closest(const ClosestArgs &c, hipStream_t s) {
     launch_query(c.filter ? k_closest<true> : k_closest<false>, closest_fill<ClosestK>(c), c, s);
@@ -1033,14 +622,12 @@ void launch_closest_multi(const ClosestMultiArgs &c, hipStream_t s) {   // the i
 }
 void launch_overlap(const OverlapArgs &c, hipStream_t s) {   // one list size: ART_CAST_MAX_HITS gids a lane are 2 KB of LDS a wave, which bounds nothing
     static_assert(ART_CAST_MAX_HITS == 8u, "k_overlap's list");
-    OverlapK a = query_fill<OverlapK>(c);
-    a.boxes = c.boxes; a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    OverlapK a = overlap_fill<OverlapK>(c); a.boxes = c.boxes;
     if (c.any) launch_query(c.filter ? k_overlap<true, 0, true> : k_overlap<true, 0, false>, a, c, s);
     else launch_query(c.filter ? k_overlap<false, 8, true> : k_overlap<false, 8, false>, a, c, s);
 }
 void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s) {   // launch_overlap's instances and list size
-    TriOverlapK a = query_fill<TriOverlapK>(c);
-    a.qtris = c.qtris; a.hit = c.hit; a.count = c.count; a.max_hits = c.max_hits; a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull;
+    TriOverlapK a = overlap_fill<TriOverlapK>(c); a.qtris = c.qtris;
     if (c.any) launch_query(c.filter ? k_overlap_tris<true, 0, true> : k_overlap_tris<true, 0, false>, a, c, s);
     else launch_query(c.filter ? k_overlap_tris<false, 8, true> : k_overlap_tris<false, 8, false>, a, c, s);
 }

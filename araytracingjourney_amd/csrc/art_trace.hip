@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void k_ao_pixels(FrameArgs a, const DevNode
 }
 
 // what a persistent tracing wave reads its rays from and writes its results to
-enum { MODE_PRIMARY = 0, MODE_SHADOW = 1, MODE_AO = 4 };   // (2 and 3 were the queries': rays in device buffers have a tracer of their own, k_cast in art_query.hip.  Not renumbered: tools and profiles name k_trace<4, ..>)
+enum { MODE_PRIMARY = 0, MODE_SHADOW = 1, MODE_AO = 4 };   // (2 and 3 were the queries': rays in device buffers have a tracer of their own, k_cast in art_query_rays.hip.  Not renumbered: tools and profiles name k_trace<4, ..>)
 struct TraceArgs {
     const DevNode *nodes; const DevNode4 *wide; const DevTri *tris;
     uint32_t total;          // candidate slots

@@ -1,6 +1,6 @@
 // art_walk.h -- the per-ray walk: a lane's traversal state over the binary and the 4-wide quantised nodes (TravBase / Trav / Trav4), the per-XCD chunk cursors
-// (pop_chunk) and the pooled persistent-wave loop (pooled_trace).  Included by art_trace.hip (k_trace, k_trace_ao) and art_query.hip (the casts, the point queries, k_sweep).
-// TravBase has ONE leaf step, step_leaf_take, with a hook for what becomes of a closest candidate: step_leaf keeps it as the best, art_query.hip's TravMulti lists it.
+// (pop_chunk) and the pooled persistent-wave loop (pooled_trace).  Included by art_trace.hip (k_trace, k_trace_ao) and, through art_query.h, art_query_rays.hip (the casts, k_sweep) and art_query_points.hip (the point queries).
+// TravBase has ONE leaf step, step_leaf_take, with a hook for what becomes of a closest candidate: step_leaf keeps it as the best, art_query_rays.hip's TravMulti lists it.
 #pragma once
 #include "art_device.h"
 
@@ -35,7 +35,7 @@ template <bool ANY, int OVF, int LDSN = kLdsStack, bool ALPHA = false> struct Tr
         return false;
     }
     // accept() of DESIGN.md 1.1 for the triangle in `cur`: exact triangle-AABB slab, then Moeller-Trumbore (and with ALPHA the alpha test of DESIGN.md 3.2).  What becomes of a
-    // closest candidate that is below (tbest, bgid) is the caller's: take(t_eff, u, v, pos, gid) -- step_leaf keeps it as the best, TravMulti (art_query.hip) enters it in its list
+    // closest candidate that is below (tbest, bgid) is the caller's: take(t_eff, u, v, pos, gid) -- step_leaf keeps it as the best, TravMulti (art_query_rays.hip) enters it in its list
     template <class TAKE> __device__ __forceinline__ bool step_leaf_take(const DevTri *__restrict__ tris, int *lds, int *ovf, const AlphaView &av, const TAKE &take) {
         uint32_t pos = (uint32_t)~cur;
         // the reference of an ABSENT child of a 4-wide node (kAbsentChild: no leaf sits at position 2^31 - 1).  Its inverted box is left before it is entered by every

@@ -28,7 +28,7 @@ from helpers import _dead_rays, _layout_is_the_headers, R, _tex_flat as _tex, to
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATTERN = tm.PATTERN      # tests/test_cast.py's: what oversized output buffers are filled with
 N = tm.N                  # 4096
-LDS_DEPTH = tq.LDS_DEPTH  # kCastLds of art_query.hip
+LDS_DEPTH = tq.LDS_DEPTH  # kCastLds of art_query_rays.hip
 WHO = b"art_cast_crossings: "
 
 

@@ -46,7 +46,7 @@ PATTERN = -0x5A5A5A5B   # tests/test_cast.py's: what oversized output buffers ar
 RHO = 0.05
 RADII = (RHO, 0.0)
 KS = (1, 4, 8)
-LDS_DEPTH = 8           # kCastLds and kClosestLds of art_query.hip: stack entries a lane keeps in LDS; deeper ones spill
+LDS_DEPTH = 8           # kCastLds of art_query_rays.hip and kClosestLds of art_query_points.hip: stack entries a lane keeps in LDS; deeper ones spill
 OUTPUTS = ("pos", "ng", "ns", "uv", "albedo", "orm")
 SIZES = (0, 1, 63, 64, 65, 127, 511, 513, 4097)
 
@@ -353,7 +353,7 @@ def test_knobs_change_the_schedule_never_the_records(R, torch, orc, get_scene, k
     """2: ArtTuning.trace_chunk 64 / 65536, trace_refill 1 / 64, trace_blocks 1 / 16384 and trace_leaf_batch 1 / 64 (test_walk_edges.KNOBS' eight tracer settings) on
     sponza_like at detail 0.05 with the shared 4096-input references: the three kinds give the references' bits, and the presets' bits word for word.
 
-    Why trace_leaf_batch = 64 and trace_refill = 64 cannot hang k_closest's own loop (read against art_query.hip and art_walk.h): its step block is pooled_trace's.  Triangle tests run
+    Why trace_leaf_batch = 64 and trace_refill = 64 cannot hang k_closest's own loop (read against art_query_points.hip and art_walk.h): its step block is pooled_trace's.  Triangle tests run
     once leaf_batch lanes wait on one OR no active lane stands on an internal node, and a lane on an internal node always moves -- step_internal goes on with a child or
     pops -- so a wave whose waiting lanes can never number 64 still tests them as soon as nobody else can move: every iteration does a node step or a leaf step, and a
     walk has finitely many.  The refill block is entered when at least trace_refill lanes are idle; 64 idle lanes is always at least that, so a wave that has finished

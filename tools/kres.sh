@@ -1,6 +1,6 @@
 #!/bin/bash
 # Registers, scratch, spills, occupancy and LDS of every kernel of one translation unit of libart (the compiler's own resource remarks):
-#   tools/kres.sh araytracingjourney_amd/csrc/art_frame.hip [extra hipcc flags]      (art_trace.hip: the AO tracer; art_query.hip: the queries)
+#   tools/kres.sh araytracingjourney_amd/csrc/art_frame.hip [extra hipcc flags]      (art_trace.hip: the AO tracer; art_query_rays.hip, art_query_points.hip: the queries)
 # The fused frame and the AO tracer live at the 64-register edge (8 waves per SIMD): run this after touching them.
 f=$1; shift
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -std=c++17 "$@" -Rpass-analysis=kernel-resource-usage -c "$f" -o /dev/null 2>&1 | awk '
