@@ -1013,6 +1013,29 @@ int32_t art_parity_math_sweep(ArtContext *c, uint32_t which, uint32_t first_bits
     return ART_OK;
 }
 
+// the short forms of the once-per-wave divisions (rcp_core, div_core: art_device.h), swept by art_sweeps.hip against the divisions themselves (include/art_parity.h)
+int32_t art_parity_div_sweep(ArtContext *c, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint32_t numerator_bits, uint64_t *mismatches, uint32_t first_bad[2],
+                             uint64_t *short_lanes, uint64_t *lanes, float guard[4]) {
+    if (!c || !mismatches || !first_bad || !short_lanes || !lanes || !guard) return fail(ART_E_INVALID, "art_parity_div_sweep: null argument");
+    if (which > 4 || count > (1ull << 32)) return fail(ART_E_INVALID, "art_parity_div_sweep: which 0..4, at most 2^32 patterns");
+    int32_t r = use_device(c); if (r) return r;
+    r = sync_all(c); if (r) return r;
+    div_sweep_guard(guard);
+    unsigned long long h[4] = {0ull, ~0ull, 0ull, 0ull};
+    DevBuf<unsigned long long> d;
+    HIPC(d.ensure(4));
+    HIPC(hipMemcpy(d.p, h, sizeof h, hipMemcpyHostToDevice));
+    launch_div_sweep(which, first_bits, count, stride, numerator_bits, d.p, nullptr); HIPC(hipGetLastError());
+    HIPC(hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost));
+    *mismatches = h[0]; *short_lanes = h[2]; *lanes = h[3];
+    if (h[0]) {
+        const uint32_t j = first_bits + (uint32_t)h[1] * stride;
+        first_bad[0] = numerator_bits; first_bad[1] = j;   // which 0 (the numerator is 1), 1, 2: the pattern itself
+        if (which >= 3) div_sweep_pair(which, j, numerator_bits, first_bad[0], first_bad[1]);
+    }
+    return ART_OK;
+}
+
 // the radiance-only helpers (pow22_texel, art_shade.h; quotient_rcp, art_sweeps.hip) against the expressions they stand for: a distance in ulps and the result classes (include/art_parity.h)
 int32_t art_parity_radiance_sweep(ArtContext *c, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numerator, uint32_t *max_ulps, uint32_t *worst_bits,
                                   uint64_t *class_mismatches, uint32_t *first_class_bits) {

@@ -47,14 +47,38 @@ __device__ __forceinline__ float rcp_core(float d) {   // 1.0f / d: the quotient
     float q = fmaf(fmaf(-d, r, 1.0f), r, r);
     return fmaf(fmaf(-d, q, 1.0f), r, q);
 }
+// The shorter form of 1.0f / sqrtf(x): v_rsq_f32, a Markstein step to the root, v_rcp_f32 and one Newton step -- 10 vector instructions instead of the core's 16.  Not the
+// compiler's instructions, so nothing says by construction that it rounds alike: art_parity_math_sweep (which = 3) finds 0 mismatches against the plain expression over the
+// whole of [kExactLo, kExactHi], in whole and in mixed waves.  The k_frame instances that keep their pinned registers with it run it (kFrameShort, art_frame.hip).
+__device__ __forceinline__ float inv_sqrt_short(float x) {
+    float y = __builtin_amdgcn_rsqf(x);
+    float s = x * y, h = 0.5f * y;
+    s = fmaf(s, fmaf(-h, s, 0.5f), s);
+    s = fmaf(fmaf(-s, s, x), h, s);
+    float q = __builtin_amdgcn_rcpf(s);
+    return fmaf(fmaf(-s, q, 1.0f), q, q);
+}
+// a / b as hipcc compiles it once v_div_scale_f32 scales nothing and v_div_fmas_f32 / v_div_fixup_f32 pass their operand on: v_rcp_f32, one refinement, q = a r, two residual
+// corrections -- the same instructions in the same order, 9 instead of 12.  The scaling does nothing where a and b are normal, |a| >= 2^-103, |b| <= 2^126, the quotient is
+// normal and the exponents are less than 96 apart; div_core_domain is a box well inside that, and art_parity_div_sweep proves the bits over it (tests/test_short_math.py).
+// rcp_core above is div_core(1.0f, d); the sweep proves it too, against 1.0f / safe_dir(x) (a ray's reciprocal direction), over [kExactLo, kExactHi].
+constexpr float kDivLo = 0x1p-47f, kDivHi = 0x1p47f;
+__device__ __forceinline__ float div_core(float a, float b) {
+    float r = __builtin_amdgcn_rcpf(b);
+    r = fmaf(fmaf(-b, r, 1.0f), r, r);
+    float q = a * r;
+    q = fmaf(fmaf(-b, q, a), r, q);
+    return fmaf(fmaf(-b, q, a), r, q);
+}
+__device__ __forceinline__ bool div_core_domain(float a, float b) { return fabsf(a) >= kDivLo && fabsf(a) <= kDivHi && fabsf(b) >= kDivLo && fabsf(b) <= kDivHi; }
 // plain: wave-uniform, forces the plain expression (ArtTuning.plain_math); fast: whether this wave took the core (the sweep counts it); FAST = false: the plain expression
 // and nothing else, for the k_frame instances whose register allocation the guard's branches would move (kFrameFastMath)
 __device__ __forceinline__ bool exact_in_range(float x, bool plain) {
     return !plain && __builtin_amdgcn_ballot_w64(!(x >= kExactLo && x <= kExactHi)) == 0ull;
 }
-template <bool FAST = true> __device__ __forceinline__ float inv_sqrt_exact(float x, bool plain, bool &fast) {
+template <bool FAST = true, bool SHORT = false> __device__ __forceinline__ float inv_sqrt_exact(float x, bool plain, bool &fast) {   // SHORT: inv_sqrt_short for the core
     fast = FAST && exact_in_range(x, plain);
-    if (fast) return rcp_core(sqrt_core(x));
+    if (fast) return SHORT ? inv_sqrt_short(x) : rcp_core(sqrt_core(x));
     return 1.0f / sqrtf(x);
 }
 template <bool FAST = true> __device__ __forceinline__ float sqrt_exact(float x, bool plain, bool &fast) {
@@ -67,11 +91,11 @@ template <bool FAST = true> __device__ __forceinline__ float sqrt_exact(float x,
 __device__ __forceinline__ void exact_note(float x, uint32_t &far) { far = max(far, __float_as_uint(x) - __float_as_uint(kExactLo)); }
 __device__ __forceinline__ bool exact_noted_in_range(uint32_t far) { return __builtin_amdgcn_ballot_w64(far > __float_as_uint(kExactHi) - __float_as_uint(kExactLo)) == 0ull; }
 template <bool FAST = true> __device__ __forceinline__ float len3(V3 a, bool plain = false) { bool f; return sqrt_exact<FAST>(dot3(a, a), plain, f); }
-template <bool FAST = true> __device__ __forceinline__ V3 nrm3(V3 a, bool plain = false) { bool f; float inv = inv_sqrt_exact<FAST>(dot3(a, a), plain, f); return a * inv; }
-__device__ __forceinline__ float inv_sqrt_noting(float x, uint32_t &far) { exact_note(x, far); return rcp_core(sqrt_core(x)); }   // the core, unguarded, and its note
-template <bool CORE> __device__ __forceinline__ V3 nrm3_noting(V3 a, uint32_t &far) {   // CORE: that | the plain expression
+template <bool FAST = true, bool SHORT = false> __device__ __forceinline__ V3 nrm3(V3 a, bool plain = false) { bool f; float inv = inv_sqrt_exact<FAST, SHORT>(dot3(a, a), plain, f); return a * inv; }
+template <bool SHORT = false> __device__ __forceinline__ float inv_sqrt_noting(float x, uint32_t &far) { exact_note(x, far); return SHORT ? inv_sqrt_short(x) : rcp_core(sqrt_core(x)); }   // the core, unguarded, and its note
+template <bool CORE, bool SHORT = false> __device__ __forceinline__ V3 nrm3_noting(V3 a, uint32_t &far) {   // CORE: that | the plain expression
     float x = dot3(a, a);
-    return a * (CORE ? inv_sqrt_noting(x, far) : 1.0f / sqrtf(x));
+    return a * (CORE ? inv_sqrt_noting<SHORT>(x, far) : 1.0f / sqrtf(x));
 }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 __device__ __forceinline__ float mixf(float x, float y, float a) { return x * (1.0f - a) + y * a; }
@@ -92,16 +116,18 @@ __device__ __forceinline__ V3 xform_vec(const float *m, V3 p) {
 // ------------------------------------------------------------------------------------------------ textures
 // sampler2DArray, linear / REPEAT, LOD 0 (no derivatives in a raygen stage): vk_rt_descriptor_set.rs:42-56
 __device__ __forceinline__ int wrapi(int i, int n) { int m = i % n; return m < 0 ? m + n : m; }
+// wrapi(i + 1, n) for an i that is wrapped already, 0 <= i < n: SEL = a compare and a select instead of the signed remainder -- the same value for every such i
+template <bool SEL> __device__ __forceinline__ int wrap_next(int i, int n) { return SEL ? (i + 1 == n ? 0 : i + 1) : wrapi(i + 1, n); }
 // the four taps of a bilinear sample and its weights (texture_offset, tw, th: the primitive's texture in the pool) -- sample_tex's first lines, restated for the alpha
 // test: shared by a call, the default k_frame instances' register allocation moved (k_frame<true, true, false, false> 63 -> 64 VGPRs)
-__device__ __forceinline__ void tex_taps(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw_, uint32_t th_, int layer, float u, float v,
+template <bool SEL = false> __device__ __forceinline__ void tex_taps(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw_, uint32_t th_, int layer, float u, float v,
                                          uint32_t &t00, uint32_t &t10, uint32_t &t01, uint32_t &t11, float &fx, float &fy) {
     int tw = (int)tw_, th = (int)th_;
     float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
     float x0f = floorf(x), y0f = floorf(y);
     fx = x - x0f; fy = y - y0f;
     int x0 = wrapi((int)x0f, tw), y0 = wrapi((int)y0f, th);
-    int x1 = wrapi(x0 + 1, tw), y1 = wrapi(y0 + 1, th);
+    int x1 = wrap_next<SEL>(x0, tw), y1 = wrap_next<SEL>(y0, th);
     const uint32_t *base = pool + texture_offset + (size_t)layer * tw * th;
     t00 = base[(size_t)y0 * tw + x0]; t10 = base[(size_t)y0 * tw + x1]; t01 = base[(size_t)y1 * tw + x0]; t11 = base[(size_t)y1 * tw + x1];
 }
@@ -113,13 +139,13 @@ __device__ __forceinline__ float tex_channel(uint32_t t00, uint32_t t10, uint32_
     float top = A * (1.0f - fx) + B * fx, bot = Cc * (1.0f - fx) + D * fx;
     return top * (1.0f - fy) + bot * fy;
 }
-__device__ inline float4 sample_tex(const uint32_t *__restrict__ pool, const DevPrim &P, int layer, float u, float v) {
+template <bool SEL = false> __device__ inline float4 sample_tex(const uint32_t *__restrict__ pool, const DevPrim &P, int layer, float u, float v) {
     int tw = (int)P.tw, th = (int)P.th;
     float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
     float x0f = floorf(x), y0f = floorf(y);
     float fx = x - x0f, fy = y - y0f;
     int x0 = wrapi((int)x0f, tw), y0 = wrapi((int)y0f, th);
-    int x1 = wrapi(x0 + 1, tw), y1 = wrapi(y0 + 1, th);
+    int x1 = wrap_next<SEL>(x0, tw), y1 = wrap_next<SEL>(y0, th);
     const uint32_t *base = pool + P.texture_offset + (size_t)layer * tw * th;
     uint32_t t00 = base[(size_t)y0 * tw + x0], t10 = base[(size_t)y0 * tw + x1], t01 = base[(size_t)y1 * tw + x0], t11 = base[(size_t)y1 * tw + x1];
     float o[4];
@@ -141,11 +167,11 @@ struct AlphaView {
     uint32_t cull;               // ray visibility masks: the cull mask of this launch's rays
 };
 // the alpha of the candidate (pos, u, v) of primitive prim_tex = {texture_offset, tw, th}; uv0..uv2 of its shading record
-__device__ __forceinline__ float alpha_at(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw, uint32_t th, float4 s2, float4 s3, float u, float v) {
+template <bool SEL = false> __device__ __forceinline__ float alpha_at(const uint32_t *__restrict__ pool, uint32_t texture_offset, uint32_t tw, uint32_t th, float4 s2, float4 s3, float u, float v) {
     float bx = 1.0f - u - v, by = u, bz = v;
     float tu = (s2.y * bx + s2.w * by) + s3.y * bz, tv = (s2.z * bx + s3.x * by) + s3.z * bz;   // shade_surface's tu / tv
     uint32_t t00, t10, t01, t11; float fx, fy;
-    tex_taps(pool, texture_offset, tw, th, 0, tu, tv, t00, t10, t01, t11, fx, fy);
+    tex_taps<SEL>(pool, texture_offset, tw, th, 0, tu, tv, t00, t10, t01, t11, fx, fy);
     return tex_channel(t00, t10, t01, t11, fx, fy, 3);
 }
 // per-ray walks: true = the candidate at leaf position pos is cut (its lane fetches the record, the cutoff and four texels only if the leaf's bit is set)

@@ -86,7 +86,7 @@ __device__ __forceinline__ PacketHints hints_seed(int *stk, uint32_t w0, uint32_
 // then compile to more instructions than the parent commit's (7 224 -> 7 278 in k_frame<true, true, true, true, true>).
 struct StepUpdate { uint64_t m = 0ull; float t, u, v; uint32_t pos, gid; };
 struct NoUpdate {};
-template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false, bool HINTS = false, class ON>   // HINTS: an any-hit walk that takes and leaves hints
+template <bool ANY, bool WIDE, int OCT, bool COUNT = false, bool ALPHA = false, bool HINTS = false, bool TSEL = false, class ON>   // HINTS: an any-hit walk that takes and leaves hints; TSEL: the alpha test's second taps wrap by a select (tex_taps)
 __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, ON &on, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
     constexpr bool MASKS = std::is_same<ON, uint64_t>::value;
     int cur = HINTS ? h.cur : 0, sp = HINTS ? h.sp : 0; // wave-uniform
@@ -201,7 +201,7 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, ON
                         if (!(c > 0.0f)) return cand;
                         const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
                         bool keep = __builtin_amdgcn_inverse_ballot_w64(cand);
-                        if (keep) keep = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
+                        if (keep) keep = !(alpha_at<TSEL>(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
                         return cand & ballot64(keep);
                     };
                     // the ray state itself changes behind the step (below): here only who changes, and to what
@@ -235,7 +235,7 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, ON
                         const float c = __uint_as_float(P[offsetof(DevPrim, cutoff) / 4]);
                         if (!(c > 0.0f)) return cand;
                         const uint32_t toff = P[offsetof(DevPrim, texture_offset) / 4], tw = P[offsetof(DevPrim, tw) / 4], th = P[offsetof(DevPrim, th) / 4];
-                        if (cand) cand = !(alpha_at(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
+                        if (cand) cand = !(alpha_at<TSEL>(a.tex_pool, toff, tw, th, s2, s3, u, v) < c);
                         return cand;
                     };
                     // the ray state changes through selects, outside the divergent branches (no register copies around them)
@@ -286,7 +286,7 @@ __device__ __forceinline__ void packet_walk(const FrameArgs &a, const Ray &r, ON
 }
 
 // one packet through the walk that fits its rays' direction signs
-template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false, bool HINTS = false, bool MASKS = true>   // MASKS: the walk in its mask form (packet_walk's ON)
+template <bool ANY, bool WIDE, bool COUNT = false, bool ALPHA = false, bool HINTS = false, bool MASKS = true, bool TSEL = false>   // MASKS: the walk in its mask form (packet_walk's ON)
 __device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, bool alive, int *stk, float &tbest, float &bu, float &bv, uint32_t &bpos, uint32_t &bgid, uint32_t &steps, PacketHints &h) {
     typename std::conditional<MASKS, uint64_t, bool>::type on;
     int oct;
@@ -307,15 +307,15 @@ __device__ __forceinline__ void walk_dispatch(const FrameArgs &a, const Ray &r, 
         oct = !uniform ? 8 : (nx ? 1 : 0) | (ny ? 2 : 0) | (nz ? 4 : 0);
     }
     switch (oct) {
-    case 0: packet_walk<ANY, WIDE, 0, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 1: packet_walk<ANY, WIDE, 1, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 2: packet_walk<ANY, WIDE, 2, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 3: packet_walk<ANY, WIDE, 3, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 4: packet_walk<ANY, WIDE, 4, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 5: packet_walk<ANY, WIDE, 5, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 6: packet_walk<ANY, WIDE, 6, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    case 7: packet_walk<ANY, WIDE, 7, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
-    default: packet_walk<ANY, WIDE, 8, COUNT, ALPHA, HINTS>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 0: packet_walk<ANY, WIDE, 0, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 1: packet_walk<ANY, WIDE, 1, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 2: packet_walk<ANY, WIDE, 2, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 3: packet_walk<ANY, WIDE, 3, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 4: packet_walk<ANY, WIDE, 4, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 5: packet_walk<ANY, WIDE, 5, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 6: packet_walk<ANY, WIDE, 6, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    case 7: packet_walk<ANY, WIDE, 7, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
+    default: packet_walk<ANY, WIDE, 8, COUNT, ALPHA, HINTS, TSEL>(a, r, on, stk, tbest, bu, bv, bpos, bgid, steps, h); break;
     }
 }
 
@@ -377,6 +377,22 @@ template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constex
 #else
 template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr uint32_t kFrameMoves = kFrameMovesTable[WIDE << 4 | ONE_LIGHT << 3 | COUNT << 2 | BATCH << 1 | ALPHA];
 #endif
+// Which of the short exact forms an instance of k_frame takes (profiles/README.md "short math").  Bits 0-8: the surface block's nine normalisations, in the
+// block's order, as inv_sqrt_short; 9: the camera ray's; 10: the light's (L and H); 11: the camera ray's fx / W and fy / H as div_core; 12: the second taps of the
+// surface's texture samples wrapped by a select; 13: those of the alpha test.  Bits 0-10 hang on the guards of kFrameFastMath and mean nothing in an instance without
+// them; bit 13 means nothing without the alpha test.  Every form computes the same bits
+// (tests/test_short_math.py, tests/test_short_math_frames.py), so any subset is the same frame; the rule is kFrameMoves': an instance takes a subset that reproduces its
+// pinned resource line with no more vector instructions and no more lane accesses than the parent, the one with the fewest vector instructions, and 0 -- the parent's
+// code, instruction for instruction -- where there is none.  tools/short_math_sweep.py compiles the candidates (-DART_SHORT_FORCE=n) and prints this table.
+// Indexed like kFrameMovesTable.
+constexpr uint16_t kFrameShortTable[32] = {0x1800, 0x3800, 0x1800, 0x1800, 0x1800, 0x3800, 0x1800, 0x3800, 0x1ffb, 0x2800, 0x0800, 0x2800, 0x1e00, 0x2800, 0x0800, 0x2800, 0x1800, 0x3800, 0x1800, 0x3800, 0x1800, 0x3800, 0x1800, 0x3800, 0x1ffb, 0x2800, 0x0800, 0x2800, 0x1ffb, 0x2800, 0x0800, 0x2800};
+#ifdef ART_SHORT_FORCE
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr uint32_t kFrameShortRaw = ART_SHORT_FORCE;   // (the sweep that made the table)
+#else
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr uint32_t kFrameShortRaw = kFrameShortTable[WIDE << 4 | ONE_LIGHT << 3 | COUNT << 2 | BATCH << 1 | ALPHA];
+#endif
+template <bool WIDE, bool ONE_LIGHT, bool COUNT, bool BATCH, bool ALPHA> constexpr uint32_t kFrameShort =
+    kFrameShortRaw<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA> & ((kFrameFastMath<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA> ? 0x7FFu : 0u) | 0x1800u | (ALPHA ? 0x2000u : 0u));
 // The kernel's arguments, looked at again: k_frame's phases -- the camera ray, the surface, every light, the outputs -- each read what they need of FrameArgs from the
 // kernel-argument segment where they need it, through the constant address space (scalar loads that hit the scalar cache and stay scalar behind the frame's stores, like
 // ConstQuads), instead of through `a`, whose fields the compiler loads once at the top and then parks across the walks in the lanes of a vector register (v_writelane /
@@ -398,6 +414,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     constexpr bool HINTS = kFrameHints<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     constexpr bool FASTM = kFrameFastMath<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     constexpr uint32_t MV = kFrameMoves<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
+    constexpr uint32_t SH = kFrameShort<WIDE, ONE_LIGHT, COUNT, BATCH, ALPHA>;
     int *stk = wstack;
     const uint32_t wid = blockIdx.x;
     if (wid >= a_.n_wave_items) return;
@@ -416,9 +433,10 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         uint32_t p, x, y; bool mine;
         in = frame_pixel(a_, wid, p, x, y, mine);
         float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
-        float dx = (fx / (float)a_.W) * 2.0f - 1.0f, dy = (fy / (float)a_.H) * 2.0f - 1.0f;
+        // fx / W: 0.5 <= fx < 16384 + 32 (a block's lanes past the frame's edge compute too) and 1 <= W <= 16384 (art_resize): inside div_core's domain, and every such pair is swept
+        float dx = ((SH & 0x800u) ? div_core(fx, (float)a_.W) : fx / (float)a_.W) * 2.0f - 1.0f, dy = ((SH & 0x800u) ? div_core(fy, (float)a_.H) : fy / (float)a_.H) * 2.0f - 1.0f;
         V3 org = mat4_mul(cam0.view_inv, 0.f, 0.f, 0.f, 1.f);
-        V3 tgt = nrm3<FASTM>(mat4_mul(cam0.proj_inv, dx, dy, 1.f, 1.f), a_.plain_math);
+        V3 tgt = nrm3<FASTM, (SH & 0x200u) != 0u>(mat4_mul(cam0.proj_inv, dx, dy, 1.f, 1.f), a_.plain_math);
         V3 dir = mat4_mul(cam0.view_inv, tgt.x, tgt.y, tgt.z, 0.f);
         ray_init(r, org, dir, 0.001f, 10000.0f);
     }
@@ -426,7 +444,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     PHASE(0, r.inv.x)
     float tbest = on ? r.tmax : -1.0f, bu = 0.f, bv = 0.f;
     uint32_t bpos = kNoHit, bgid = kNoHit;
-    { PacketHints none{0, 0, 0u}; walk_dispatch<false, WIDE, COUNT, ALPHA, false, (MV & 1u) != 0u>(a_, r, on, stk, tbest, bu, bv, bpos, bgid, steps, none); }   // (closest-hit walks take no hints)
+    { PacketHints none{0, 0, 0u}; walk_dispatch<false, WIDE, COUNT, ALPHA, false, (MV & 1u) != 0u, (SH & 0x2000u) != 0u>(a_, r, on, stk, tbest, bu, bv, bpos, bgid, steps, none); }   // (closest-hit walks take no hints)
     PHASE(1, tbest)
     const FrameArgs &a = (MV & 2u) ? frame_args_again(a_) : a_;   // the hit record, the depth and normal outputs
     const FrameArgs &as = (MV & 4u) ? a : a_;                      // the surface
@@ -440,7 +458,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
     Surface S;
     S.world_pos = mk(0.f, 0.f, 0.f); S.N = mk(0.f, 0.f, 1.f); S.Vv = mk(0.f, 0.f, 1.f); S.albedo = mk(0.f, 0.f, 0.f);
     S.metallic = 0.f; S.alpha = 0.f; S.nc_NdotV = 0.f; S.NdotV = 0.f;
-    if (hit) shade_surface<FASTM, ONE_LIGHT && !BATCH && ALPHA>(as, cam, bpos, bu, bv, S, out_depth, out_normal);
+    if (hit) shade_surface<FASTM, ONE_LIGHT && !BATCH && ALPHA, SH & 0x1FFu, (SH & 0x1000u) != 0u>(as, cam, bpos, bu, bv, S, out_depth, out_normal);
     if (in) {
         const size_t pix = frame_px + (size_t)y * a.W + x;
         st_nt(&a.depth[pix], out_depth);
@@ -464,7 +482,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f), ro = make_float4(0.f, 0.f, 0.f, 1.0f), rd = make_float4(0.f, 0.f, 1.f, 0.f);
         bool want = false;
         const ArtLight L = ONE_LIGHT ? b.lights[0] : frame_light(b, i);
-        if (hit) want = shade_light<FASTM>(L, S, b.plain_math, c4, ro, rd);
+        if (hit) want = shade_light<FASTM, (SH & 0x400u) != 0u>(L, S, b.plain_math, c4, ro, rd);
         if (want) { if (i < 16u) sbits |= 1u << (16u + i); else more++; }   // (lights 16.. have no bits of their own: their shadow rays are counted)
         Ray sr;
         if (L.type == 2u) ray_init_inv(sr, mk(ro.x, ro.y, ro.z), ld3(L.area_pos2), ld3(L.area_pos3), 0.01f, L.penumbra_angle); // (wave-uniform branch)
@@ -474,7 +492,7 @@ __global__ __launch_bounds__(kFrameBlock) __attribute__((amdgpu_waves_per_eu(8, 
         float st = son ? sr.tmax : -1.0f, su = 0.f, sv = 0.f;
         uint32_t spos = kNoHit, sgid = kNoHit;
         const uint64_t traced = HINTS ? ballot64(son) : 0ull;
-        walk_dispatch<true, WIDE, COUNT, ALPHA, HINTS, (MV & 1u) != 0u>(b, sr, son, stk, st, su, sv, spos, sgid, steps, hn);
+        walk_dispatch<true, WIDE, COUNT, ALPHA, HINTS, (MV & 1u) != 0u, (SH & 0x2000u) != 0u>(b, sr, son, stk, st, su, sv, spos, sgid, steps, hn);
         const FrameArgs &c = (MV & 16u) ? frame_args_again(a_) : a_;   // where the walk's hints go
         if (HINTS && c.hints && traced != 0ull) { // (no shadow ray: the entry is left alone -- the idle wave of a split block shares the entry of the block's working parts)
             // the walk's occluders, the most recent first; the entry's address and what it holds now are looked up again (launder: like the pixel, nothing of this is carried

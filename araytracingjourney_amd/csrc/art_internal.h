@@ -276,6 +276,11 @@ void launch_frame_stats(const FrameArgs &a, uint32_t *out, hipStream_t s); // ou
 // art_parity_math_sweep (include/art_parity.h): out = three device words, [0] += mismatches, [1] = min(index of a mismatch), [2] += lanes on the fast path; guard = the fast path's range
 void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, unsigned long long *out, hipStream_t s);
 void math_sweep_guard(float guard[2]);
+// art_parity_div_sweep: out = four device words, [0] += mismatches, [1] = min(index of a mismatch), [2] += lanes on the short form, [3] += lanes of the set; guard = {kExactLo, kExactHi, kDivLo, kDivHi};
+// div_sweep_pair: the operands of pair j of the sets made from an index (which 3, 4), false past the set
+void launch_div_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint32_t numer_bits, unsigned long long *out, hipStream_t s);
+void div_sweep_guard(float guard[4]);
+bool div_sweep_pair(uint32_t which, uint32_t j, uint32_t seed, uint32_t &a, uint32_t &b);
 // art_parity_radiance_sweep: out = three device words, [0] = max(distance in ulps << 32 | index of that input), [1] += inputs whose result class differs, [2] = min(index of one)
 void launch_radiance_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, float numer, unsigned long long *out, hipStream_t s);
 // The wave plan of the fused frame, made ON THE DEVICE behind a sampled frame (k_plan, art_frame.hip): from the steps every wave of that launch counted, every 8x8 block's level

@@ -102,7 +102,8 @@ __device__ __forceinline__ float pow22_texel(float x) {
 struct Surface { V3 world_pos, N, Vv, albedo; float metallic, alpha, nc_NdotV, NdotV; };
 
 // rgen:107-150: the hit triangle's attributes, normal mapping, material; also the frame's depth / view-space normal outputs
-template <bool CORE, bool HOLD = false> __device__ __forceinline__ void shade_surface_body(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal, uint32_t &far) {
+// SITES: bit k = the block's k-th normalisation in its ten-instruction form (inv_sqrt_short) where CORE; SEL: the second taps' wrap as a compare and a select (wrap_next)
+template <bool CORE, bool HOLD = false, uint32_t SITES = 0u, bool SEL = false> __device__ __forceinline__ void shade_surface_body(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal, uint32_t &far) {
     // one dependent fetch: the shading record holds what get_indices + three vertex reads would return (rgen:107-114)
     const float4 *sq = reinterpret_cast<const float4 *>(a.shade_tris + pos);
     float4 s0 = sq[0], s1 = sq[1], s2 = sq[2], s3 = sq[3], s4 = sq[4], s5 = sq[5], s6 = sq[6], s7 = sq[7], s8 = sq[8];
@@ -111,22 +112,22 @@ template <bool CORE, bool HOLD = false> __device__ __forceinline__ void shade_su
     V3 posv = (mk(s0.x, s0.y, s0.z) * bx + mk(s0.w, s1.x, s1.y) * by) + mk(s1.z, s1.w, s2.x) * bz;
     V3 world_pos = xform_point(P.o2w, posv);
     float tu = (s2.y * bx + s2.w * by) + s3.y * bz, tv = (s2.z * bx + s3.x * by) + s3.z * bz;
-    V3 nrm = nrm3_noting<CORE>((mk(s3.w, s4.x, s4.y) * bx + mk(s4.z, s4.w, s5.x) * by) + mk(s5.y, s5.z, s5.w) * bz, far);
+    V3 nrm = nrm3_noting<CORE, (SITES >> 0 & 1u) != 0u>((mk(s3.w, s4.x, s4.y) * bx + mk(s4.z, s4.w, s5.x) * by) + mk(s5.y, s5.z, s5.w) * bz, far);
     const float *Wm = P.w2o;
-    V3 world_normal = nrm3_noting<CORE>(mk(dot3(nrm, mk(Wm[0], Wm[4], Wm[8])), dot3(nrm, mk(Wm[1], Wm[5], Wm[9])), dot3(nrm, mk(Wm[2], Wm[6], Wm[10]))), far);
-    V3 tan = nrm3_noting<CORE>((mk(s6.x, s6.y, s6.z) * bx + mk(s6.w, s7.x, s7.y) * by) + mk(s7.z, s7.w, s8.x) * bz, far);
-    V3 world_tangent = nrm3_noting<CORE>(xform_vec(P.o2w, tan), far);
-    world_tangent = nrm3_noting<CORE>(world_tangent - world_normal * dot3(world_tangent, world_normal), far);
+    V3 world_normal = nrm3_noting<CORE, (SITES >> 1 & 1u) != 0u>(mk(dot3(nrm, mk(Wm[0], Wm[4], Wm[8])), dot3(nrm, mk(Wm[1], Wm[5], Wm[9])), dot3(nrm, mk(Wm[2], Wm[6], Wm[10]))), far);
+    V3 tan = nrm3_noting<CORE, (SITES >> 2 & 1u) != 0u>((mk(s6.x, s6.y, s6.z) * bx + mk(s6.w, s7.x, s7.y) * by) + mk(s7.z, s7.w, s8.x) * bz, far);
+    V3 world_tangent = nrm3_noting<CORE, (SITES >> 3 & 1u) != 0u>(xform_vec(P.o2w, tan), far);
+    world_tangent = nrm3_noting<CORE, (SITES >> 4 & 1u) != 0u>(world_tangent - world_normal * dot3(world_tangent, world_normal), far);
     V3 world_binormal = cross3(world_normal, world_tangent) * s8.y;
-    float4 tx = sample_tex(a.tex_pool, P, 2, tu, tv);
-    V3 N = nrm3_noting<CORE>(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f), far);
-    N = nrm3_noting<CORE>((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z, far);
-    tx = sample_tex(a.tex_pool, P, 0, tu, tv);
+    float4 tx = sample_tex<SEL>(a.tex_pool, P, 2, tu, tv);
+    V3 N = nrm3_noting<CORE, (SITES >> 5 & 1u) != 0u>(mk(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f), far);
+    N = nrm3_noting<CORE, (SITES >> 6 & 1u) != 0u>((world_tangent * N.x + world_binormal * N.y) + world_normal * N.z, far);
+    tx = sample_tex<SEL>(a.tex_pool, P, 0, tu, tv);
     V3 albedo = mk(pow22_texel(tx.x), pow22_texel(tx.y), pow22_texel(tx.z)); // radiance-only from here: pow22_texel is within 8 ulp of libm's pow (the BRDF's __fdividef is the IEEE division on this toolchain)
-    tx = sample_tex(a.tex_pool, P, 1, tu, tv);
+    tx = sample_tex<SEL>(a.tex_pool, P, 1, tu, tv);
     float roughness = tx.y, metallic = tx.z;
     S.world_pos = world_pos; S.N = N; S.albedo = albedo; S.metallic = metallic;
-    S.Vv = nrm3_noting<CORE>(ld3(cam.camera_pos) - world_pos, far); // exact: V + L cancels at grazing angles and would amplify a 1-ulp rsq
+    S.Vv = nrm3_noting<CORE, (SITES >> 7 & 1u) != 0u>(ld3(cam.camera_pos) - world_pos, far); // exact: V + L cancels at grazing angles and would amplify a 1-ulp rsq
     S.alpha = roughness * roughness;
     S.nc_NdotV = dot3(N, S.Vv);
     S.NdotV = clampf(S.nc_NdotV, 1e-5f, 1.0f);
@@ -135,7 +136,7 @@ template <bool CORE, bool HOLD = false> __device__ __forceinline__ void shade_su
     const float *VI = cam.view_inv;
     V3 on = mk((VI[0] * N.x + VI[1] * N.y) + VI[2] * N.z, (VI[4] * N.x + VI[5] * N.y) + VI[6] * N.z, (VI[8] * N.x + VI[9] * N.y) + VI[10] * N.z);
     on.y = -on.y; on.z = -on.z;
-    on = nrm3_noting<CORE>(on, far);
+    on = nrm3_noting<CORE, (SITES >> 8 & 1u) != 0u>(on, far);
     out_normal = mk(on.x * 0.5f + 0.5f, on.y * 0.5f + 0.5f, on.z * 0.5f + 0.5f);
     // HOLD (the four k_frame instances <*, true, *, false, true>: one light, one frame per launch, alpha test): libm's pow was what took those instances to 61 VGPRs; without
     // it they need 58, and the figure is pinned to the register (tests/test_ray_masks.py).  The block's last result passes through v60 -- a move there and back -- so they claim 61.
@@ -146,18 +147,19 @@ template <bool CORE, bool HOLD = false> __device__ __forceinline__ void shade_su
 // allocation of every k_frame instance; here the block runs the core straight through, notes the range of what it was given, and a wave in which any lane's note is out
 // of range runs the block again with the plain expressions (a normal of length zero, a NaN vertex: nothing a frame has many of).  What the first pass computed from such a
 // value is discarded whole: no address depends on a normalised vector, so it is arithmetic on garbage and nothing else.
-template <bool FAST, bool HOLD = false> __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal) {
+template <bool FAST, bool HOLD = false, uint32_t SITES = 0u, bool SEL = false> __device__ __forceinline__ void shade_surface(const FrameArgs &a, const CameraArg &cam, uint32_t pos, float hu, float hv, Surface &S, float &out_depth, V3 &out_normal) {
     uint32_t far = 0u;
-    if (FAST) { if (!a.plain_math) { shade_surface_body<true>(a, cam, pos, hu, hv, S, out_depth, out_normal, far); if (exact_noted_in_range(far)) return; } }
-    shade_surface_body<false, HOLD>(a, cam, pos, hu, hv, S, out_depth, out_normal, far);
+    if (FAST) { if (!a.plain_math) { shade_surface_body<true, false, SITES, SEL>(a, cam, pos, hu, hv, S, out_depth, out_normal, far); if (exact_noted_in_range(far)) return; } }
+    shade_surface_body<false, HOLD, 0u, SEL>(a, cam, pos, hu, hv, S, out_depth, out_normal, far);
 }
 // rgen:152-185 up to the shadow ray: c = (rho_s + rho_d) * radiance, c.w = NdotL; the shadow ray (origin, tmax | direction) if one is due
-template <bool FAST> __device__ __forceinline__ bool shade_light(const ArtLight &l, const Surface &S, bool plain, float4 &c4, float4 &ro, float4 &rd) {
+// SHORT: L's and H's normalisations in their ten-instruction form behind their guards
+template <bool FAST, bool SHORT = false> __device__ __forceinline__ bool shade_light(const ArtLight &l, const Surface &S, bool plain, float4 &c4, float4 &ro, float4 &rd) {
     // a directional light's L and |nn_L| do not depend on the pixel: the host made them (art_api.hip directional_constants, the same operations)
     const bool directional = l.type == 2u;
     V3 nn_L = directional ? mk(0.f, 0.f, 0.f) : get_unnormalized_L_vec(l, S.world_pos);
-    V3 L = directional ? ld3(l.area_pos2) : nrm3<FAST>(nn_L, plain);
-    V3 Hh = nrm3<FAST>(S.Vv + L, plain);
+    V3 L = directional ? ld3(l.area_pos2) : nrm3<FAST, SHORT>(nn_L, plain);
+    V3 Hh = nrm3<FAST, SHORT>(S.Vv + L, plain);
     float nc_NdotL = dot3(S.N, L);
     float NdotL = clampf(nc_NdotL, 0.0f, 1.0f);
     float NdotH = clampf(dot3(S.N, Hh), 0.0f, 1.0f);

@@ -1,23 +1,12 @@
-// art_sweeps.hip -- the parity sweeps (include/art_parity.h): the exact-math helpers of art_device.h and the radiance-only helpers of art_shade.h against the expressions
+// art_sweeps.hip -- the parity sweeps (include/art_parity.h): the exact-math helpers of art_device.h (square roots, divisions) and the radiance-only helpers of art_shade.h against the expressions
 // they stand for, over any set of bit patterns.  No frame and no query needs anything here.
 #include "art_shade.h"
 
 namespace art {
 
-// ---- art_parity_math_sweep: inv_sqrt_exact / sqrt_exact against the plain expressions, any set of the 2^32 inputs (tests/test_exact_math.py) ----
+// ---- art_parity_math_sweep: inv_sqrt_exact / sqrt_exact / inv_sqrt_short (art_device.h) against the plain expressions, any set of the 2^32 inputs (tests/test_exact_math.py) ----
 __device__ __attribute__((noinline)) float plain_inv_sqrt(float x) { return 1.0f / sqrtf(x); }
 __device__ __attribute__((noinline)) float plain_sqrt(float x) { return sqrtf(x); }
-// The shorter candidate: v_rsq_f32, a Markstein step to the root, v_rcp_f32 and one Newton step -- 10 vector instructions instead of 16.  The sweep finds it exact over
-// the whole guard range too (profiles/README.md, "exact 1/sqrt"), but no placement of it left the default k_frame instance its 63 registers (61 or 64: the figure is
-// pinned), so the frame kernels run the compiler's core; kept here so that the sweep keeps proving it for the day the allocation has room.
-__device__ __forceinline__ float inv_sqrt_short(float x) {
-    float y = __builtin_amdgcn_rsqf(x);
-    float s = x * y, h = 0.5f * y;
-    s = fmaf(s, fmaf(-h, s, 0.5f), s);
-    s = fmaf(fmaf(-s, s, x), h, s);
-    float q = __builtin_amdgcn_rcpf(s);
-    return fmaf(fmaf(-s, q, 1.0f), q, q);
-}
 constexpr uint32_t kSweepBlocks = 4096;
 template <int WHICH> __global__ __launch_bounds__(kBlock) void k_math_sweep(uint32_t first_bits, uint64_t count, uint32_t stride, unsigned long long *__restrict__ out) {
     unsigned long long bad = 0, fast_n = 0, bad_at = ~0ull;
@@ -62,6 +51,75 @@ void launch_math_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint
     else k_math_sweep<4><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, out);
 }
 void math_sweep_guard(float guard[2]) { guard[0] = kExactLo; guard[1] = kExactHi; }
+
+// ---- art_parity_div_sweep: rcp_core / div_core against the divisions they stand for (tests/test_short_math.py) ----
+__device__ __attribute__((noinline)) float plain_rcp_dir(float x) { return 1.0f / safe_dir(x); }
+__device__ __attribute__((noinline)) float plain_div(float a, float b) { return a / b; }
+// pair j of the sets whose pairs are made from an index (host and device: the host names a mismatch by its pair).  false: j is past the set.
+// set 3 -- every pair of biased exponents 1..254 with 64 mantissa pairs each: sixteen from the edges {0, 1, 2^22, 2^23 - 1}^2, 48 hashed from (j, seed) with hashed signs
+// set 4 -- the camera ray's fx / W: W = 1..16384 (art_resize's limit), x = every column of the 32-pixel tiles that cover W (lanes past the edge divide too), a = x + 0.5
+constexpr uint32_t kDivPairSet = 254u * 254u * 64u, kDivCamMaxW = 16384u, kDivCamCols = kDivCamMaxW + 32u;
+__host__ __device__ inline uint32_t div_hash(uint32_t v) { v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16; return v; }
+__host__ __device__ inline bool div_pair(uint32_t which, uint32_t j, uint32_t seed, uint32_t &a, uint32_t &b) {
+    if (which == 3u) {
+        if (j >= kDivPairSet) return false;
+        const uint32_t k = j & 63u, e = j >> 6, ea = e / 254u + 1u, eb = e % 254u + 1u;
+        const uint32_t edge[4] = {0u, 1u, 0x400000u, 0x7FFFFFu};
+        uint32_t ma, mb, sa = 0u, sb = 0u;
+        if (k < 16u) { ma = edge[k >> 2]; mb = edge[k & 3u]; }
+        else { const uint32_t h0 = div_hash(2u * j + seed), h1 = div_hash(2u * j + 1u + seed * 0x9E3779B1u); ma = h0 & 0x7FFFFFu; mb = h1 & 0x7FFFFFu; sa = h0 >> 31; sb = h1 >> 31; }
+        a = sa << 31 | ea << 23 | ma; b = sb << 31 | eb << 23 | mb;
+        return true;
+    }
+    const uint32_t W = j / kDivCamCols + 1u, x = j % kDivCamCols;
+    if (W > kDivCamMaxW || x >= ((W + 31u) & ~31u)) return false;
+    const float fa = (float)x + 0.5f, fb = (float)W;
+    __builtin_memcpy(&a, &fa, 4); __builtin_memcpy(&b, &fb, 4);
+    return true;
+}
+// WHICH 0: rcp_core(safe_dir(x)) | 1: div_core(numer, x) | 2: the control, numer * v_rcp_f32(x) | 3, 4: div_core over the pair sets above.  A lane inside the form's proven
+// domain takes the short form, any other lane the plain expression (the kernels have no guard of their own here: they show their operands inside the domain).
+template <int WHICH> __global__ __launch_bounds__(kBlock) void k_div_sweep(uint32_t first_bits, uint64_t count, uint32_t stride, uint32_t numer_bits, unsigned long long *__restrict__ out) {
+    unsigned long long bad = 0, short_n = 0, lanes = 0, bad_at = ~0ull;
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += step) {
+        const uint32_t j = first_bits + (uint32_t)i * stride;
+        float got, ref; bool in;
+        if (WHICH == 0) {
+            const float x = __uint_as_float(j), d = fabsf(safe_dir(x));
+            in = d >= kExactLo && d <= kExactHi;
+            got = in ? rcp_core(safe_dir(x)) : 1.0f / safe_dir(x); ref = plain_rcp_dir(x);
+        } else {
+            uint32_t ab = numer_bits, bb = j;
+            if (WHICH >= 3 && !div_pair((uint32_t)WHICH, j, numer_bits, ab, bb)) continue;
+            const float a = __uint_as_float(ab), b = __uint_as_float(bb);
+            in = div_core_domain(a, b);
+            got = in ? (WHICH == 2 ? a * __builtin_amdgcn_rcpf(b) : div_core(a, b)) : a / b; ref = plain_div(a, b);
+        }
+        if (__float_as_uint(got) != __float_as_uint(ref)) { bad++; if (i < bad_at) bad_at = i; }
+        short_n += in ? 1u : 0u; lanes++;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        bad += __shfl_xor(bad, off); short_n += __shfl_xor(short_n, off); lanes += __shfl_xor(lanes, off);
+        const unsigned long long o = __shfl_xor(bad_at, off); bad_at = o < bad_at ? o : bad_at;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], bad_at); }
+        if (short_n) atomicAdd(&out[2], short_n);
+        if (lanes) atomicAdd(&out[3], lanes);
+    }
+}
+void launch_div_sweep(uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint32_t numer_bits, unsigned long long *out, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kSweepBlocks, (count + kBlock - 1) / kBlock);
+    if (!blocks) return;
+    if (which == 0) k_div_sweep<0><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer_bits, out);
+    else if (which == 1) k_div_sweep<1><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer_bits, out);
+    else if (which == 2) k_div_sweep<2><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer_bits, out);
+    else if (which == 3) k_div_sweep<3><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer_bits, out);
+    else k_div_sweep<4><<<blocks, kBlock, 0, s>>>(first_bits, count, stride, numer_bits, out);
+}
+void div_sweep_guard(float guard[4]) { guard[0] = kExactLo; guard[1] = kExactHi; guard[2] = kDivLo; guard[3] = kDivHi; }
+bool div_sweep_pair(uint32_t which, uint32_t j, uint32_t seed, uint32_t &a, uint32_t &b) { return div_pair(which, j, seed, a, b); }
 
 // ---- art_parity_radiance_sweep: the radiance-only helpers against the expressions they replace, which are NOT bit-equal -- a distance, not a mismatch count (tests/test_fast_radiance.py) ----
 __device__ __attribute__((noinline)) float plain_pow22(float x) { return __ocml_pow_f32(x, 2.2f); }

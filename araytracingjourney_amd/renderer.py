@@ -703,6 +703,14 @@ class Renderer:
         check(self._L.art_parity_math_sweep(self._ctx, which, first_bits, count, stride, C.byref(bad), C.byref(first), C.byref(fast), guard))
         return dict(mismatches=bad.value, first_bad_bits=first.value if bad.value else None, fast_lanes=fast.value, guard=(guard[0], guard[1]))
 
+    def div_sweep(self, which, first_bits=0, count=1 << 32, stride=1, numerator_bits=0x3F800000):
+        """art_parity_div_sweep: the short forms of the frame kernels' once-per-wave divisions against the divisions (which 0: rcp_core(safe_dir(x)); 1: div_core(numerator, x);
+        2: the control that must fail; 3: div_core over the exponent-pair set, numerator_bits the seed; 4: over the camera ray's operands)
+        -> dict(mismatches, first_bad=(a bits, b bits) (None without a mismatch), short_lanes, lanes, guard=(lo, hi) of the unary form, domain=(lo, hi) of div_core's operands)"""
+        bad, short, lanes, first, guard = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), (C.c_uint32 * 2)(), (C.c_float * 4)()
+        check(self._L.art_parity_div_sweep(self._ctx, which, first_bits, count, stride, numerator_bits, C.byref(bad), first, C.byref(short), C.byref(lanes), guard))
+        return dict(mismatches=bad.value, first_bad=(first[0], first[1]) if bad.value else None, short_lanes=short.value, lanes=lanes.value, guard=(guard[0], guard[1]), domain=(guard[2], guard[3]))
+
     def radiance_sweep(self, which, first_bits=0, count=1 << 32, stride=1, numerator=1.0):
         """art_parity_radiance_sweep: the albedo's x^2.2 helper against libm's powf (which 0) or numerator * rcp(x) against numerator / x (1) on the bit patterns
         first_bits + i * stride, i < count -> dict(max_ulps, worst_bits (None at distance 0), class_mismatches, first_class_bits (None without one))"""

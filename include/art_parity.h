@@ -83,10 +83,21 @@ int32_t art_get_wide_nodes(ArtContext *ctx, void *quantised, void *floats, size_
  * patterns first_bits + i * stride (mod 2^32), i < count, lane l of a wave taking i = 64 k + l, to the helper the frame kernels call and to a non-inlined copy of the plain
  * expression in the same translation unit, and compares the two results as uint32.  *mismatches = patterns that differ, *first_bad_bits = the pattern of the lowest such i
  * (untouched when there is none), *fast_lanes = patterns whose wave took the fast path (a wave takes it only when all its lanes are inside guard[0] <= x <= guard[1]).
- * which = 3: the shorter v_rsq_f32-based candidate for 1.0f / sqrtf(x) that the frame kernels do not run yet (profiles/README.md, "exact 1/sqrt"), under the same guard;
+ * which = 3: the shorter v_rsq_f32-based form of 1.0f / sqrtf(x) (inv_sqrt_short: what the k_frame instances of kFrameShort run for the core), under the same guard;
  * which = 4: v_rsq_f32 alone under that guard -- a 1-ulp approximation, the sweep's own control: it must report mismatches.  Synchronises. */
 int32_t art_parity_math_sweep(ArtContext *ctx, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint64_t *mismatches, uint32_t *first_bad_bits,
                               uint64_t *fast_lanes, float guard[2]);
+/* proof that the short forms of the frame kernels' once-per-wave divisions return the division's bits.  which = 0: rcp_core(safe_dir(x)) against
+ * 1.0f / safe_dir(x) (a ray's reciprocal direction), x = the bit patterns first_bits + i * stride (mod 2^32), i < count; 1: div_core(a, x) against a / x for the numerator
+ * a = numerator_bits, x likewise; 2: a * v_rcp_f32(x) in div_core's place, the sweep's own control: it must report mismatches; 3: div_core over pair j = first_bits + i * stride of
+ * a set of 254 * 254 * 64 pairs -- every pair of normal exponents with 16 mantissa pairs from the edges and 48 hashed from (j, numerator_bits as the seed); 4: div_core over the
+ * camera ray's own operands, pair j = (W - 1) * 16416 + x: a = x + 0.5, b = W for W = 1..16384 and every x below W rounded up to 32.  An index past a set is skipped.
+ * A lane whose operands lie inside the form's proven domain -- guard[0] <= |safe_dir(x)| <= guard[1] for which 0, guard[2] <= |a|, |b| <= guard[3] otherwise -- takes the
+ * short form, any other lane the plain expression; the reference is a non-inlined copy of the plain expression in the same translation unit, compared as uint32.
+ * *mismatches = lanes that differ, first_bad = the operands (a, b) of the lowest such i (untouched when there is none), *short_lanes = lanes that took the short form,
+ * *lanes = lanes of the set.  Synchronises. */
+int32_t art_parity_div_sweep(ArtContext *ctx, uint32_t which, uint32_t first_bits, uint64_t count, uint32_t stride, uint32_t numerator_bits, uint64_t *mismatches,
+                             uint32_t first_bad[2], uint64_t *short_lanes, uint64_t *lanes, float guard[4]);
 /* how far the radiance-only helpers of the shading kernels are from the expressions they stand for (they are NOT bit-equal: DESIGN.md 1 keeps radiance to 1e-4 relative).
  * which = 0: the albedo's x^2.2 (pow22_texel: frexp, one hardware log2, one exp2, ldexp) against libm's powf(x, 2.2f), the frame kernels' form; which = 1: numerator * rcp(x),
  * the candidate for the BRDF's quotients, against the IEEE numerator / x (the kernels still run the division).  x = the bit patterns first_bits + i * stride (mod 2^32),
