@@ -1,4 +1,4 @@
-// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings, art_overlap_triangles, art_closest_triangles; DESIGN.md 3.5 .. 3.14) and the queries of include/art_parity.h
+// art_cast.hip -- rays and points in device buffers (include/art.h: art_cast_rays, art_cast_rays_multi, art_resolve_hits, art_closest_points, art_cast_spheres, art_closest_points_multi, art_overlap_boxes, art_cast_crossings, art_overlap_triangles, art_closest_triangles, art_cast_triangles; DESIGN.md 3.5 .. 3.15) and the queries of include/art_parity.h
 // over them: the host side of the ring of cast blocks (CastState, art_context.h) -- one claim / commit, one query_begin and one set of descriptor checks, which every
 // entry point goes through.  Every use of a CastState / CastBlock field is in this file; the kernels are art_query_rays.hip's, art_query_points.hip's and art_resolve.hip's.
 #include "art_context.h"
@@ -288,6 +288,23 @@ int32_t art_cast_spheres(ArtContext *c, const ArtSphereCast *d) {
     r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
     a.rays = (const float4 *)d->rays_dev; a.kind = CastKind::Sweep; a.radius = d->radius + 0.0f; a.point = (float4 *)d->point_dev;   // (-0.0 + 0.0 is +0.0)
     launch_cast(a, q.stream);
+    return cast_commit(c, q, d->n);
+}
+
+// ---- a triangle along each ray (include/art.h: art_cast_triangles) ------------------------------------------------------------------------------------
+// A cast like the others, counted in casts and rays, on the point queries' loop: query_begin, a launch, cast_commit.
+int32_t art_cast_triangles(ArtContext *c, const ArtTriCast *d) {
+    const char *who = "art_cast_triangles"; int32_t r;
+    if ((r = check_null(who, c, d)) || (r = check_flags(who, d->flags))) return r;
+    if (d->reserved != 0u) return invalid(who, "reserved: must be 0");
+    if ((r = check_cull(who, d->cull_mask)) || (r = check_n(who, d->n)) || (r = check_buffer(who, "sweeps_dev", d->sweeps_dev, 16, d->n)) || (r = check_records(who, "tuv_dev", d->tuv_dev, d->ids_dev, d->n)) ||
+        (r = check_buffer(who, "point_dev", d->point_dev, 16, d->n, true)) || (r = check_buffer(who, "qpoint_dev", d->qpoint_dev, 16, d->n, true))) return r;
+    if ((r = check_built(who, c))) return r;
+    if (d->n == 0u) return ART_OK;
+    TriCastArgs a{}; RingSlot q;
+    r = query_begin(c, (hipStream_t)d->hip_stream, d->n, d->cull_mask, d->tuv_dev, d->ids_dev, a, &q); if (r) return r;
+    a.sweeps = (const float4 *)d->sweeps_dev; a.point = (float4 *)d->point_dev; a.qpoint = (float4 *)d->qpoint_dev;
+    launch_tri_cast(a, q.stream);
     return cast_commit(c, q, d->n);
 }
 

@@ -339,6 +339,10 @@ void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s);
 // is not used); qpoint (optional) = the witness point on the query, w = 1 (a miss: zeros)
 struct TriDistanceArgs : ClosestArgs { const float4 *qtris; float4 *qpoint; };
 void launch_tri_distance(const TriDistanceArgs &c, hipStream_t s);
+// A triangle along a ray (art_cast_triangles): sweeps[4i .. 4i+3] = q0.xyz,tmin | q1.xyz,tmax | q2.xyz,- | d.xyz,-; tuv / ids / point are ClosestArgs' with
+// t_eff where the distance stood (points is not used; a miss record's x is tmax); qpoint (optional) = the witness point on the query in its rest pose, w = 1 (a miss: zeros)
+struct TriCastArgs : ClosestArgs { const float4 *sweeps; float4 *qpoint; };
+void launch_tri_cast(const TriCastArgs &c, hipStream_t s);
 // One resolve of hit records (art_resolve_hits; art_resolve.hip): tuv / ids as a cast wrote them, n records; the version's shading records and primitive
 // table, the structure's gid -> leaf table and the texture pool; the outputs wanted (null: not written).
 struct ResolveArgs {

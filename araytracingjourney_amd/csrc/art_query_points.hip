@@ -1,5 +1,5 @@
 // art_query_points.hip -- the device side of the point, box and triangle queries on device buffers (gfx950): nearest surface points (k_closest), the K nearest triangles (k_closest_multi), the triangles that
-// touch a box (k_overlap) and those that touch a triangle (k_overlap_tris), the distance from a triangle to the scene (k_closest_tris).  They have no ray to pool, so they are Sinks and walks of one loop of
+// touch a box (k_overlap) and those that touch a triangle (k_overlap_tris), the distance from a triangle to the scene (k_closest_tris), a triangle along a ray (k_cast_tris).  They have no ray to pool, so they are Sinks and walks of one loop of
 // their own (point_trace); the casts and the sweep run art_walk.h's pooled loop in art_query_rays.hip.  What the two units share stands once, in art_query.h.  art_cast.hip is their host side.
 #include "art_query.h"
 
@@ -602,6 +602,178 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(4, 
     point_trace<TravTriDist<FILTER>>(a, stack, TriDistanceSink{a});
 }
 
+// ---- a triangle along a ray (art_cast_triangles) ---------------------------------------------------------------------------------------------------------
+// A query is art_overlap_triangles' triangle with a displacement: q0.xyz, tmin | q1.xyz, tmax | q2.xyz, - | d.xyz, - -- four 16-byte loads a lane and more state than
+// pooled_trace's twelve pool fields hold, so the loop is point_trace and the stack TravPoint's pairs, (reference, the child's entry time): tbest (`limit`) only ever falls,
+// and an entry whose box is entered behind it by the time it is popped is dropped without a fetch.  The node step is TravSweep's sign-selected slab of the ray (0, d) with
+// each child's low planes moved by -qhi and its high planes by -qlo (the box of scene point minus query point); the leaf step runs that slab on the triangle's own box
+// against tbest, then the fifteen moving features -- three query vertices against the scene face, three scene vertices against the query face, nine edge pairs -- and the 17
+// axes at pose tmin (S).  S is first in 3.15's order and nothing is earlier than tmin: asked last, it replaces whatever the features found, which is the same answer.
+// Its witnesses (3.14's tri_tri_closest at pose tmin) are made once, at the finish, for a winner flagged S (bit 31 of bpos: no leaf sits there).
+// No fmaf in anything that decides a record: tests/np_tri_sweep.py restates every operation in numpy float32 (the slab's fmaf has a zero addend here: a product).
+struct TriCastK : ClosestK { const float4 *sweeps; float4 *qpoint; };   // points: not used; qpoint: may be null
+constexpr uint32_t kStartFlag = 0x80000000u;
+__device__ __forceinline__ void cast_take(bool ok, float t, float cu, float cv, float cs, float ct, float tmin, float tmax, float &bt, float &u, float &v, float &s, float &tt) {
+    if (ok & (t >= tmin) & (t < tmax) & (t < bt)) { bt = t; u = cu; v = cv; s = cs; tt = ct; }   // (a NaN never wins)
+}
+// a vertex against a face: the ray (w0 + face origin, d) against the triangle (0, e1, e2) with the normal n, nn = n.n; fu, fv: 3.9's face barycentrics of where it meets the plane
+__device__ __forceinline__ bool cast_vertex_face(V3 w0, V3 d, V3 e1, V3 e2, V3 n, float nn, float nd, float &t, float &fu, float &fv) {
+    t = -dotp(n, w0) / (nd != 0.0f ? nd : 1.0f);
+    const V3 w = mk(w0.x + t * d.x, w0.y + t * d.y, w0.z + t * d.z);
+    const float den = nn > 0.0f ? nn : 1.0f;
+    fu = dotp(crossp(w, e2), n) / den; fv = dotp(crossp(e1, w), n) / den;
+    return (nn > 0.0f) & (nd != 0.0f) & (fu >= 0.0f) & (fv >= 0.0f) & (fu + fv <= 1.0f);
+}
+// t_tri of DESIGN.md 3.15 without S, for the scene triangle v0 e1 e2 and the query q0 q1 q2 moving by d: the smallest t in [tmin, tmax) among QV0..2, SV0..2 and the nine
+// edge pairs, scene edge outermost, the first of equals; +inf: none.  u, v: its barycentrics on the scene triangle; s, tt: on the query
+__device__ __forceinline__ float tri_tri_cast(V3 v0, V3 e1, V3 e2, V3 q0, V3 q1, V3 q2, V3 d, float tmin, float tmax, float &u, float &v, float &s, float &tt) {
+    float bt = INFINITY, t, fu, fv; u = 0.0f; v = 0.0f; s = 0.0f; tt = 0.0f;
+    const V3 g1 = q1 - q0, g2 = q2 - q0;
+    {
+        const V3 n = crossp(e1, e2);
+        const float nn = dotp(n, n), nd = dotp(n, d);
+        bool ok = cast_vertex_face(q0 - v0, d, e1, e2, n, nn, nd, t, fu, fv); cast_take(ok, t, fu, fv, 0.0f, 0.0f, tmin, tmax, bt, u, v, s, tt);
+        ok = cast_vertex_face(q1 - v0, d, e1, e2, n, nn, nd, t, fu, fv); cast_take(ok, t, fu, fv, 1.0f, 0.0f, tmin, tmax, bt, u, v, s, tt);
+        ok = cast_vertex_face(q2 - v0, d, e1, e2, n, nn, nd, t, fu, fv); cast_take(ok, t, fu, fv, 0.0f, 1.0f, tmin, tmax, bt, u, v, s, tt);
+    }
+    const V3 v1 = mk(v0.x + e1.x, v0.y + e1.y, v0.z + e1.z), v2 = mk(v0.x + e2.x, v0.y + e2.y, v0.z + e2.z);
+    {
+        const V3 n = crossp(g1, g2), nd_ = mk(-d.x, -d.y, -d.z);
+        const float nn = dotp(n, n), nd = dotp(n, nd_);
+        bool ok = cast_vertex_face(v0 - q0, nd_, g1, g2, n, nn, nd, t, fu, fv); cast_take(ok, t, 0.0f, 0.0f, fu, fv, tmin, tmax, bt, u, v, s, tt);
+        ok = cast_vertex_face(v1 - q0, nd_, g1, g2, n, nn, nd, t, fu, fv); cast_take(ok, t, 1.0f, 0.0f, fu, fv, tmin, tmax, bt, u, v, s, tt);
+        ok = cast_vertex_face(v2 - q0, nd_, g1, g2, n, nn, nd, t, fu, fv); cast_take(ok, t, 0.0f, 1.0f, fu, fv, tmin, tmax, bt, u, v, s, tt);
+    }
+    const V3 sp[3] = {v0, v0, v1}, sd[3] = {e1, e2, e2 - e1}, qp[3] = {q0, q0, mk(q0.x + g1.x, q0.y + g1.y, q0.z + g1.z)}, qd[3] = {g1, g2, g2 - g1};
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const V3 n = crossp(sd[i], qd[j]), r0 = sp[i] - qp[j];
+            const float nn = dotp(n, n), nd = dotp(n, d), den = nn > 0.0f ? nn : 1.0f;
+            t = dotp(n, r0) / (nd != 0.0f ? nd : 1.0f);
+            const V3 m = mk(r0.x - t * d.x, r0.y - t * d.y, r0.z - t * d.z);
+            const float se = -dotp(crossp(m, qd[j]), n) / den, sq = -dotp(crossp(m, sd[i]), n) / den;
+            const bool ok = (nn > 0.0f) & (nd != 0.0f) & (se >= 0.0f) & (se <= 1.0f) & (sq >= 0.0f) & (sq <= 1.0f);
+            // the parameters as barycentrics (tri_tri_closest): edge 0 is (x, 0), edge 1 (0, x), edge 2 (1 - x, x)
+            cast_take(ok, t, i == 0 ? se : (i == 1 ? 0.0f : 1.0f - se), i == 0 ? 0.0f : se, j == 0 ? sq : (j == 1 ? 0.0f : 1.0f - sq), j == 0 ? 0.0f : sq, tmin, tmax, bt, u, v, s, tt);
+        }
+    }
+    return bt;
+}
+// TravPoint's stack of pairs and its tie rule with a swept triangle where its point stood: limit is tbest, the pairs' second word a box's entry time
+template <bool FILTER> struct TravTriCast : TravPoint<FILTER> {
+    V3 q0, q1, q2, lo, hi, d, inv;   // (TravPoint's p is not used here, and its step_internal and step_leaf are shadowed by the two below)
+    float tmin, tmax, bs, bt;        // bs, bt: the best candidate's barycentrics on the query
+    // the triangle in `cur`: its own box, shifted, against tbest first -- an exact cull: a candidate's t_eff is at least its box's entry and at least tmin -- then the features
+    __device__ __forceinline__ bool step_leaf(const TriCastK &a, int2 *lds, int *ovf) {
+        const uint32_t pos = (uint32_t)~this->cur;
+        if (pos == 0x7FFFFFFFu) return this->pop(lds, ovf);   // kAbsentChild: nothing (TravBase::step_leaf_take)
+        const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+        const float4 ta = tq[0], tb = tq[1], tc = tq[2], td = tq[3];   // v0 e1 e2 lo hi gid
+        const float t0x = (tc.y - hi.x) * inv.x, t1x = (td.x - lo.x) * inv.x, t0y = (tc.z - hi.y) * inv.y, t1y = (td.y - lo.y) * inv.y, t0z = (tc.w - hi.z) * inv.z, t1z = (td.z - lo.z) * inv.z;
+        const float te = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)), tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
+        if ((tc.y < 3.0e38f) & (fmaxf(te, tmin) <= fminf(tf, this->limit))) {
+            const V3 v0 = mk(ta.x, ta.y, ta.z), e1 = mk(ta.w, tb.x, tb.y), e2 = mk(tb.z, tb.w, tc.x);
+            float u, v, s, t;
+            float tt = tri_tri_cast(v0, e1, e2, q0, q1, q2, d, tmin, tmax, u, v, s, t);
+            bool start = false;
+            if ((tmin < tmax) && tri_tri_overlap(v0, e1, e2, mk(q0.x + tmin * d.x, q0.y + tmin * d.y, q0.z + tmin * d.z), mk(q1.x + tmin * d.x, q1.y + tmin * d.y, q1.z + tmin * d.z),
+                                                 mk(q2.x + tmin * d.x, q2.y + tmin * d.y, q2.z + tmin * d.z))) { tt = tmin; start = true; }
+            if (tt < INFINITY) {
+                const float teff = fmaxf(tt, te);
+                const uint32_t gid = __float_as_uint(td.w);
+                if ((teff < this->limit || (teff == this->limit && gid < this->bgid)) && (!FILTER || leaf_visible(a.bits, a.shade, a.prims, a.cull, pos))) {
+                    this->limit = teff; this->bu = u; this->bv = v; this->bpos = start ? pos | kStartFlag : pos; this->bgid = gid; bs = s; bt = t;
+                }
+            }
+        }
+        return this->pop(lds, ovf);
+    }
+    // TravSweep's sign-selected slab, o = 0, with each child's near and far planes shifted by the query's box.  An absent child or a masked subtree carries an inverted byte
+    // box (255 / 0): "left before it is entered" does not hold once the planes have moved, so it is skipped by TravPoint's explicit test.  A child is skipped iff
+    // max(tn, tmin) > min(tf, tbest); on with the one entered first, the others wait with their entry times, the last at the bottom (TravPoint's order; speed only)
+    __device__ __forceinline__ bool step_internal(const DevNode4 *__restrict__ wide, int2 *lds, int *ovf) {
+        const auto [b, c, ox, oy, oz, sx, sy, sz, refs] = load_node4(wide, this->cur);
+        const bool ngx = inv.x < 0.0f, ngy = inv.y < 0.0f, ngz = inv.z < 0.0f;
+        const uint32_t nxw = ngx ? b.w : b.x, fxw = ngx ? b.x : b.w, nyw = ngy ? c.x : b.y, fyw = ngy ? b.y : c.x, nzw = ngz ? c.y : b.z, fzw = ngz ? b.z : c.y;
+        const float pnx = ngx ? lo.x : hi.x, pfx = ngx ? hi.x : lo.x, pny = ngy ? lo.y : hi.y, pfy = ngy ? hi.y : lo.y, pnz = ngz ? lo.z : hi.z, pfz = ngz ? hi.z : lo.z;   // what the near and the far plane move by
+        const float lim = this->limit;
+        float k[4]; int rf[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float tnx = (fmaf((float)((nxw >> (8 * i)) & 255u), sx, ox) - pnx) * inv.x, tfx = (fmaf((float)((fxw >> (8 * i)) & 255u), sx, ox) - pfx) * inv.x;
+            const float tny = (fmaf((float)((nyw >> (8 * i)) & 255u), sy, oy) - pny) * inv.y, tfy = (fmaf((float)((fyw >> (8 * i)) & 255u), sy, oy) - pfy) * inv.y;
+            const float tnz = (fmaf((float)((nzw >> (8 * i)) & 255u), sz, oz) - pnz) * inv.z, tfz = (fmaf((float)((fzw >> (8 * i)) & 255u), sz, oz) - pfz) * inv.z;
+            const float tn = fmaxf(fmaxf(tnx, tny), tnz), tf = fminf(fminf(tfx, tfy), tfz);
+            const bool h = (((b.x >> (8 * i)) & 255u) <= ((b.w >> (8 * i)) & 255u)) & (fmaxf(tn, tmin) <= fminf(tf, lim));
+            k[i] = h ? tn : INFINITY; rf[i] = h ? refs[i] : kAbsentChild;
+        }
+        // (TravPoint::step_internal_by's five comparators, and a copy of them: a child that is out sorts as +inf with the absent reference, which is pushed nowhere)
+#define ART_CSWAP(x, y) { const bool sw = k[y] < k[x]; const float tk = sw ? k[x] : k[y]; k[x] = sw ? k[y] : k[x]; k[y] = tk; const int tr_ = sw ? rf[x] : rf[y]; rf[x] = sw ? rf[y] : rf[x]; rf[y] = tr_; }
+        ART_CSWAP(0, 1) ART_CSWAP(2, 3) ART_CSWAP(0, 2) ART_CSWAP(1, 3) ART_CSWAP(1, 2)
+#undef ART_CSWAP
+#pragma unroll
+        for (int i = 3; i >= 1; i--) if (rf[i] != kAbsentChild) this->push(rf[i], k[i], lds, ovf);
+        if (rf[0] == kAbsentChild) return this->pop(lds, ovf);   // (a child entered at +inf -- a structure nowhere -- sorts among the absent ones: it was pushed, and comes back here)
+        this->cur = rf[0];
+        return false;
+    }
+};
+struct TriCastSink {
+    const TriCastK &a;
+    template <class I> __device__ __forceinline__ void miss(I at, float x) const {
+        write_point_miss(a, at, x);
+        if (a.qpoint) a.qpoint[at] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    template <class TRAV> __device__ __forceinline__ uint32_t init(TRAV &) const { return 1u; }
+    // `radius`, the loop's one float for the finish, carries nothing here: the walk keeps tmax
+    template <class TRAV> __device__ __forceinline__ bool begin(TRAV &tr, uint32_t sidx, uint32_t, float &) const {
+        const float4 r0 = a.sweeps[4 * (size_t)sidx], r1 = a.sweeps[4 * (size_t)sidx + 1], r2 = a.sweeps[4 * (size_t)sidx + 2], r3 = a.sweeps[4 * (size_t)sidx + 3];
+        const float z = ((zero3(r0) + zero3(r1)) + zero3(r2)) + zero3(r3);   // 0 for twelve finite values, NaN otherwise
+        if (z == 0.0f && r1.w == r1.w) {
+            V3 mn = mk(r0.x, r0.y, r0.z), mx = mn;   // qlo, qhi: read_tri's selects
+            mn.x = r1.x < mn.x ? r1.x : mn.x; mn.y = r1.y < mn.y ? r1.y : mn.y; mn.z = r1.z < mn.z ? r1.z : mn.z;
+            mx.x = r1.x > mx.x ? r1.x : mx.x; mx.y = r1.y > mx.y ? r1.y : mx.y; mx.z = r1.z > mx.z ? r1.z : mx.z;
+            mn.x = r2.x < mn.x ? r2.x : mn.x; mn.y = r2.y < mn.y ? r2.y : mn.y; mn.z = r2.z < mn.z ? r2.z : mn.z;
+            mx.x = r2.x > mx.x ? r2.x : mx.x; mx.y = r2.y > mx.y ? r2.y : mx.y; mx.z = r2.z > mx.z ? r2.z : mx.z;
+            tr.q0 = mk(r0.x, r0.y, r0.z); tr.q1 = mk(r1.x, r1.y, r1.z); tr.q2 = mk(r2.x, r2.y, r2.z); tr.lo = mn; tr.hi = mx;
+            tr.d = mk(r3.x, r3.y, r3.z); tr.inv = mk(1.0f / safe_dir(r3.x), 1.0f / safe_dir(r3.y), 1.0f / safe_dir(r3.z));   // ray_init's operations
+            tr.tmin = r0.w; tr.tmax = r1.w;
+            tr.limit = r1.w; tr.bu = 0.f; tr.bv = 0.f; tr.bpos = kNoHit; tr.bgid = kNoHit; tr.cur = 0; tr.sp = 0;
+            return true;
+        }
+        miss(sidx, r1.w);   // a dead query: its miss record, without a walk
+        return false;
+    }
+    template <class TRAV> __device__ __forceinline__ void finish(const TRAV &tr, uint32_t slot, uint32_t, float) const {
+        if (tr.bgid != kNoHit) {
+            const uint32_t pos = tr.bpos & ~kStartFlag;
+            float u = tr.bu, v = tr.bv, s = tr.bs, t = tr.bt;
+            if (tr.bpos & kStartFlag) {   // S: the witnesses of the pose at tmin
+                const float4 *tq = reinterpret_cast<const float4 *>(a.tris + pos);
+                const float4 ta = tq[0], tb = tq[1], tc = tq[2];
+                const float tm = tr.tmin;
+                (void)tri_tri_closest(mk(ta.x, ta.y, ta.z), mk(ta.w, tb.x, tb.y), mk(tb.z, tb.w, tc.x), mk(tr.q0.x + tm * tr.d.x, tr.q0.y + tm * tr.d.y, tr.q0.z + tm * tr.d.z),
+                                      mk(tr.q1.x + tm * tr.d.x, tr.q1.y + tm * tr.d.y, tr.q1.z + tm * tr.d.z), mk(tr.q2.x + tm * tr.d.x, tr.q2.y + tm * tr.d.y, tr.q2.z + tm * tr.d.z), u, v, s, t);
+            }
+            write_hit(a, slot, tr.bgid, tr.limit, u, v);
+            if (a.point) a.point[slot] = contact_point(a.tris, pos, u, v);
+            if (a.qpoint) {
+                const V3 g1 = tr.q1 - tr.q0, g2 = tr.q2 - tr.q0;
+                a.qpoint[slot] = make_float4(tr.q0.x + (s * g1.x + t * g2.x), tr.q0.y + (s * g1.y + t * g2.y), tr.q0.z + (s * g1.z + t * g2.z), 1.0f);
+            }
+        } else miss(slot, tr.tmax);
+    }
+};
+// (waves_per_eu 4: the fifteen moving features and the 17 axes hold 118 VGPRs without a spill; at 5 waves (96) the compiler spills 33 of them to scratch, at 6 (80) 56; at 3
+// it uses no more than at 4 -- DESIGN.md 3.15's table)
+template <bool FILTER>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_cast_tris(TriCastK a) {
+    __shared__ int2 stack[kClosestLds * kTraceBlock];
+    point_trace<TravTriCast<FILTER>>(a, stack, TriCastSink{a});
+}
+
 template <class K> static void mask_fill(K &a, const QueryArgs &c) { a.bits = c.alpha_bits; a.shade = c.shade; a.prims = c.prims; a.cull = c.cull; }   // the four fields of every FILTER instance
 template <class K> static K closest_fill(const ClosestArgs &c) {
     K a = query_fill<K>(c);
@@ -634,6 +806,10 @@ void launch_tri_overlap(const TriOverlapArgs &c, hipStream_t s) {   // launch_ov
 void launch_tri_distance(const TriDistanceArgs &c, hipStream_t s) {
     TriDistanceK a = closest_fill<TriDistanceK>(c); a.qtris = c.qtris; a.qpoint = c.qpoint;
     launch_query(c.filter ? k_closest_tris<true> : k_closest_tris<false>, a, c, s);
+}
+void launch_tri_cast(const TriCastArgs &c, hipStream_t s) {
+    TriCastK a = closest_fill<TriCastK>(c); a.sweeps = c.sweeps; a.qpoint = c.qpoint;
+    launch_query(c.filter ? k_cast_tris<true> : k_cast_tris<false>, a, c, s);
 }
 
 } // namespace art

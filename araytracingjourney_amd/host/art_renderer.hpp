@@ -334,6 +334,16 @@ public:
     static_assert(sizeof(ArtTriDistance) == 64, "ArtTriDistance is part of the ABI");
     static void closest_triangles(ArtContext *ctx, const ArtTriDistance &d) { check(art_closest_triangles(ctx, &d)); }
     void closest_triangles(const ArtTriDistance &d) { closest_triangles(ctx_, d); }
+    // where each of n query triangles (q0.xyz, tmin, q1.xyz, tmax, q2.xyz, -, d.xyz, -) in device memory, moved along its d, first touches the scene: records as a closest
+    // cast's and (optionally) n x float4 contact points on the scene triangle and witness points on the query in its rest pose (art_cast_triangles)
+    static ArtTriCast tri_cast(const void *sweeps_dev, uint32_t n, void *tuv_dev, void *ids_dev, void *point_dev = nullptr, void *qpoint_dev = nullptr, void *hip_stream = nullptr,
+                               uint32_t cull_mask = 0xFFu) {
+        ArtTriCast d{}; d.sweeps_dev = sweeps_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.qpoint_dev = qpoint_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask;
+        return d;
+    }
+    static_assert(sizeof(ArtTriCast) == 64, "ArtTriCast is part of the ABI");
+    static void cast_triangles(ArtContext *ctx, const ArtTriCast &d) { check(art_cast_triangles(ctx, &d)); }
+    void cast_triangles(const ArtTriCast &d) { cast_triangles(ctx_, d); }
     // where a ball of `radius` along each of n rays in device memory first touches the scene: records as a closest cast's and (optionally) n x float4 contact points (art_cast_spheres)
     static ArtSphereCast sphere_cast(const void *rays_dev, uint32_t n, float radius, void *tuv_dev, void *ids_dev, void *point_dev = nullptr, void *hip_stream = nullptr, uint32_t cull_mask = 0xFFu) {
         ArtSphereCast d{}; d.rays_dev = rays_dev; d.tuv_dev = tuv_dev; d.ids_dev = ids_dev; d.point_dev = point_dev; d.hip_stream = hip_stream; d.n = n; d.cull_mask = cull_mask; d.radius = radius;

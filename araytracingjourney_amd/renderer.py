@@ -1049,8 +1049,63 @@ class Renderer:
             pick = lambda t: t.index_select(0, row)[0]   # noqa: E731
             return records, dict(distance=pick(duv)[0], index=torch.where(any_, at, torch.full_like(at, -1)), ids=pick(ids), point=pick(point), qpoint=pick(qpoint))
 
+    def cast_triangles(self, sweeps, cull_mask=0xFF, out=None, stream=None):
+        """Where each query triangle, moved along its displacement, first touches the scene (art_cast_triangles; DESIGN.md 3.15 is the definition).  sweeps: a torch tensor
+        on this context's device, float32, shape (n, 16) -- q0.xyz, tmin, q1.xyz, tmax, q2.xyz, -, d.xyz, - (words 11 and 15 are not read) -- contiguous and 16-byte
+        aligned.  The triangle at time t is q_m + t*d (d need not be unit); the answer is the first t with tmin <= t < tmax at which it touches a scene triangle, tmin
+        itself where it touches or cuts one as it starts.  Returns (tuv, ids, point, qpoint): (n, 4) float32 t,u,v,0 -- u, v the barycentrics of vertices 1 and 2 of the
+        contact on the scene triangle, a record resolve_hits takes -- (n, 2) int32 (primitive, triangle in the primitive), (n, 4) float32 that point, w = 1, and (n, 4)
+        float32 the witness point on the query triangle in its REST pose, w = 1 (add t*d for the contact).  No contact (or a non-finite coordinate or displacement, a NaN
+        tmax) is the miss record: (tmax, 0, 0, 0), (-1, -1) and points of zeros.  d = 0 is legal: only a triangle that touches as it stands answers.  Two coplanar
+        triangles that slide within their common plane are seen only where they touch at tmin.  Alpha cutoffs are not tested; primitive masks are, against cull_mask.
+        out: (tuv, ids, point, qpoint) to write instead of new ones, of at least n records, not overlapping the queries or each other.  Every tensor is checked before
+        anything is enqueued.  Enqueued on `stream` (default: torch's current stream) without host synchronisation, like cast_rays."""
+        m = _mask_value("cull_mask", cull_mask)
+        n = self._dev_tensor(sweeps, "sweeps", "float32", (16,), 16).shape[0]
+        tuv, ids, point, qpoint = self._outputs(out, n, sweeps.device, (self._RECORDS[0], self._RECORDS[1], self._POINT, ("qpoint", "float32", (4,), 16)))
+        d = _lib.ArtTriCast(sweeps_dev=sweeps.data_ptr() or None, tuv_dev=tuv.data_ptr() or None, ids_dev=ids.data_ptr() or None, point_dev=point.data_ptr() or None,
+                            qpoint_dev=qpoint.data_ptr() or None, n=n, cull_mask=m, flags=0, reserved=0, hip_stream=self._stream_handle(stream, sweeps.device))
+        check(self._L.art_cast_triangles(self._ctx, C.byref(d)))
+        return tuv, ids, point, qpoint
+
+    def sweep_mesh(self, positions, indices, direction, model_matrix=None, tmin=0.0, tmax=1.0, cull_mask=0xFF, stream=None):
+        """How far can this mesh move along `direction` before it touches the scene's surfaces, and where?  positions, indices, model_matrix: collide_mesh's, gathered the
+        same way on the device -- one cast_triangles query per triangle of the mesh, each with the displacement `direction` (3 finite floats, world space, not through
+        the matrix; need not be unit) and the limits tmin, tmax (floats; tmax inf: unbounded; a triangle with an index outside positions is a dead query).  Returns
+        (records, first): records = cast_triangles' (tuv, ids, point, qpoint) per triangle, in the order of indices; first = a dict of tensors reduced on the device from
+        them -- t () float32, the smallest t of the triangles that have an answer: the mesh is free to move by t*direction; index () int64, the mesh triangle it belongs
+        to, the lowest among equals; ids (2,) int32; point (4,) and qpoint (4,) float32, that record's.  No contact of any triangle (or no triangle): t = tmax,
+        index = -1, ids (-1, -1), points of zeros.  No host synchronisation."""
+        import torch
+        _mask_value("cull_mask", cull_mask)
+        dirn = np.asarray(direction.cpu() if isinstance(direction, torch.Tensor) else direction, np.float32).reshape(-1)
+        if dirn.size != 3 or not np.isfinite(dirn).all():
+            raise ValueError("direction must be 3 finite floats")
+        tmin, tmax = float(tmin), float(tmax)
+        if tmax != tmax:
+            raise ValueError("tmax must not be NaN")
+        tris, stream = self._mesh_tris(positions, indices, model_matrix, stream)
+        with torch.cuda.stream(stream):
+            nt, dev = tris.shape[0], tris.device
+            sweeps = torch.zeros((nt, 16), dtype=torch.float32, device=dev)
+            sweeps[:, 0:12] = tris
+            sweeps[:, 3], sweeps[:, 7] = tmin, tmax
+            sweeps[:, 12], sweeps[:, 13], sweeps[:, 14] = float(dirn[0]), float(dirn[1]), float(dirn[2])
+            tuv, ids, point, qpoint = records = self.cast_triangles(sweeps, cull_mask, stream=stream)
+            if nt == 0:
+                return records, dict(t=torch.full((), tmax, dtype=torch.float32, device=dev), index=torch.full((), -1, dtype=torch.int64, device=dev),
+                                     ids=torch.full((2,), -1, dtype=torch.int32, device=dev), point=torch.zeros(4, device=dev), qpoint=torch.zeros(4, device=dev))
+            has = ids[:, 0] >= 0
+            key = torch.where(has, tuv[:, 0], torch.full_like(tuv[:, 0], float("inf")))
+            at = torch.where(key == key.min(), torch.arange(nt, device=dev), nt).min()   # the lowest index among equals (mesh_clearance's reduction)
+            any_ = has.any()
+            at = torch.where(any_, at, torch.zeros_like(at))   # (no answer at all: record 0 is a miss record, which is what is handed out)
+            row = at.reshape(1)
+            pick = lambda t: t.index_select(0, row)[0]   # noqa: E731
+            return records, dict(t=pick(tuv)[0], index=torch.where(any_, at, torch.full_like(at, -1)), ids=pick(ids), point=pick(point), qpoint=pick(qpoint))
+
     def _mesh_tris(self, positions, indices, model_matrix, stream):
-        """collide_mesh's and mesh_clearance's gather behind their docstrings: the checks, then the (T, 12) query buffer made on the device on `stream` (words 3, 7 and 11
+        """collide_mesh's, mesh_clearance's and sweep_mesh's gather behind their docstrings: the checks, then the (T, 12) query buffer made on the device on `stream` (words 3, 7 and 11
         are 0) -> (tris, the torch stream it was made on)"""
         import torch
         nv = self._dev_tensor(positions, "positions", "float32", (3,), 4).shape[0]

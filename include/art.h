@@ -628,6 +628,40 @@ typedef struct ArtTriDistance {
     uint32_t n, cull_mask, flags, reserved;   /* n = 0 is legal: nothing is enqueued; cull_mask 0..0xFF; flags, reserved: must be 0 */
 } ArtTriDistance;           /* 64 bytes */
 int32_t art_closest_triangles(ArtContext *ctx, const ArtTriDistance *q);
+/* The first contact of translating query triangles with the scene (which is the definition; new functionality: PhysX's sweep with a mesh geometry,
+ * Bullet's convex sweep, FCL's continuous collision -- the reference has no call for it): how far a body of triangles can move along a displacement before it touches the
+ * scene, and where.  A query is 16 floats: q0.xyz, tmin | q1.xyz, tmax | q2.xyz, - | d.xyz, -.  The query triangle at time t is q_m + t*d (d need not be unit); the
+ * answer is the first t with tmin <= t < tmax at which it touches a scene triangle.
+ *  - Results: defined exactly and independent of the structure, in fp32 with nothing fused, sums of three as (a + b) + c, minima and maxima by selects, every divisor
+ *    guarded.  For a triangle with global id g and record v0, e1, e2, tlo, thi, with g1 = q1 - q0, g2 = q2 - q0, the FEATURES are, in this order, the first of the
+ *    smallest t in [tmin, tmax) winning: S, the start -- art_overlap_triangles' condition 3 holds for the query posed at tmin (q_m + tmin*d), t = tmin, witnesses
+ *    art_closest_triangles' of that pose; each query vertex against the scene face and each scene vertex against the query face (the plane's t, then art_cast_spheres'
+ *    face barycentrics, closed); the nine pairs of scene edge (v0,e1), (v0,e2), (v0+e1,e2-e1) and query edge (q0,g1), (q0,g2), (q0+g1,g2-g1), scene edge outermost
+ *    (the t at which the two lines meet, both parameters in [0, 1]).  DESIGN.md 3.15 has every formula.  t_eff = fmaxf(t_tri, tn), tn the entry of the ray (0, d) into
+ *    the box [tlo - qhi, thi - qlo] by art_cast_rays' slab with tmax for its limit ([qlo, qhi]: the box of the three vertices).  The candidates are the triangles with
+ *    tlo.x < 3.0e38 (residency), whose primitive's mask & cull_mask != 0, with t_tri < inf, whose slab passes; the answer is the argmin of (t_eff, g).
+ *    tuv_dev[i] = (t_eff, u, v, 0), u, v on the scene triangle (a record art_resolve_hits takes); ids_dev[i] as a closest cast's; point_dev[i] (optional) =
+ *    (v0 + (u*e1 + v*e2), 1); qpoint_dev[i] (optional) = (q0 + (s*g1 + t*g2), 1), the witness on the query in its REST pose: add t_eff*d for the contact.
+ *  - A miss is (tmax as given, 0, 0, 0), (-1, -1) and points of zeros.  A query with a non-finite value among its nine coordinates or in d, or a NaN tmax, is dead: its
+ *    miss record, no walk.  d = 0 is legal: only S can answer.  Words 11 and 15 of a query are not read.  A record depends on its query alone.
+ *  - LIMITATION: two coplanar triangles that slide within their common plane have a zero denominator in every moving feature; S alone sees them, so a contact that
+ *    begins after tmin in that configuration is not reported.  Zero-area operands (a segment, a point) go through the same formulas.  No rotation during the sweep.
+ *  - Alpha cutoffs are NOT tested, for art_closest_points' reason.  Visibility masks apply as for casts: cull_mask 0 sees nothing.
+ *  - Asynchrony and scene: art_cast_rays', with no path of its own -- stream, no allocation or synchronisation on the steady path, the scene as of the call, the
+ *    version held, a block of the casts' ring (ART_CAST_POOL), the same fences.  art_cast_counts counts it in casts and rays.
+ *  - Errors change nothing and enqueue nothing.  ART_E_INVALID: a null context or descriptor; flags or reserved other than 0; cull_mask above 0xFF; n above
+ *    ART_CAST_MAX_RAYS; a null or misaligned sweeps_dev / tuv_dev (16 bytes) / ids_dev (8 bytes) -- with n = 0 null is fine; a misaligned point_dev or qpoint_dev.
+ *    ART_E_STATE: the scene is not built, or art_scene_needs_build.  Overlap between buffers is the caller's contract.  (Not through art_mgpu_*.) */
+typedef struct ArtTriCast {
+    const void *sweeps_dev; /* n x 16 floats: q0.xyz, tmin | q1.xyz, tmax | q2.xyz, - | d.xyz, - ; 16-byte aligned.  Words 11 and 15 are not read */
+    void *tuv_dev;          /* n x 4 floats t,u,v,0 -- a miss is (tmax as given,0,0,0); 16-byte aligned */
+    void *ids_dev;          /* n x 2 int32 (primitive id, triangle in the primitive), -1,-1 for a miss; 8-byte aligned */
+    void *point_dev;        /* n x float4: the contact point on the SCENE triangle, w = 1; a miss is zeros.  16-byte aligned.  May be NULL */
+    void *qpoint_dev;       /* n x float4: the witness point on the QUERY triangle in its rest pose, w = 1; a miss is zeros.  16-byte aligned.  May be NULL */
+    void *hip_stream;       /* as ArtRayCast: NULL = the context's cast stream */
+    uint32_t n, cull_mask, flags, reserved;   /* n = 0 is legal: nothing is enqueued; cull_mask 0..0xFF; flags, reserved: must be 0 */
+} ArtTriCast;               /* 64 bytes */
+int32_t art_cast_triangles(ArtContext *ctx, const ArtTriCast *c);
 
 /* get_color_output_image / get_output_depth_image / get_output_normal_image (vk_rt_lightning_shadows.rs:161-183):
  * fp32 RGBA colour (the value passed to imageStore, before the reference's lossy image formats), fp32 depth,
